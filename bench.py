@@ -1,20 +1,26 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's metric on MI355X: GKeys/s of the uint32 OneSweep sort.
 
-  python bench.py --gpus 1 --steps K --warmup W
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one complete sort of one batch of synthetic keys already resident
 in HBM: N=1 sorts BASELINE configs[1] (2^28 uniform uint32 keys, keys-only,
 reference protocol GPUSortingCUDA/GPUSortingCUDA.cu:22 — InitRandom seed 10+i,
 entropy preset 1); N>1 sorts configs[3]'s shape at 2^28 keys PER GPU (weak
 scaling): MSD split + RCCL all-to-all-v + per-GPU OneSweep.  Every step gets
-its own freshly generated input buffer (generated before the timed region:
-288 GB of HBM holds them all), so no step ever re-sorts sorted data.
+its own freshly generated input buffer (generated before the timed region;
+more steps than HBM holds buffers run in rounds, each generated before it),
+so no step ever re-sorts sorted data.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel =
-digit_binning_kernel, HIP events on the sort's stream) and `cpu_baseline`
-(the oracle's std::sort on this box's cores, bounded sample).
+A plain run sets up, warms up, times the K steps, checks the last step's
+output is sorted and prints ONE JSON line (rank 0): value = GKeys/s,
+ms_per_step = milliseconds per timed step.  --dump-outputs DIR first writes
+the last timed step's sorted keys (and values) as .npy files.  --full then
+also measures `roofline` (dominant kernel = digit_binning_kernel, HIP events
+on the sort's stream), the box floor, the `more` block and `cpu_baseline`
+(the oracle's std::sort on this box's cores, bounded sample), prints them on
+'# bench_full' lines and adds them to the JSON line.
 """
 from __future__ import annotations
 
@@ -49,7 +55,43 @@ def parse():
     ap.add_argument("--strong", action="store_true", help="N > 1: strong scaling — 2^log2-keys keys IN TOTAL, split evenly over the GPUs "
                     "(SURVEY.md 8d cfg 4; default: weak scaling, 2^log2-keys per GPU)")
     ap.add_argument("--cpu-log2", type=int, default=28, help="keys of the host-sort baseline sample (default: the workload itself)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything the result line's value does not "
+                    "need: per-kernel profile + roofline, box floor, the 'more' block (other configurations, entropy / size sweeps, the "
+                    "rocPRIM comparator), the host-sort baseline, and for N > 1 the other exchange call and the phase times")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed to DIR/<name>.npy "
+                    "(float64; above %d elements a fixed sample)" % DUMP_SAMPLE)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE = 1 << 21  # elements per dumped array: at most 3 x 16 MiB of float64 in all (keys + two value words), split over the ranks
+
+
+def dump_outputs(dirname, out_k, out_v, out_n, world=1, rank=0):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files (exact for every 32-bit word): `keys` = the
+    sorted keys' uint32 bit patterns and, for pairs, `values` (8-byte values as two uint32 columns, low word first); N > 1: each rank
+    its own bucket, `keys_rank<r>` / `values_rank<r>`.  Above DUMP_SAMPLE / world elements a fixed sample of positions: one from each
+    of that many equal strata of the output, picked by a fixed integer hash of the stratum index (no RNG whose stream could change)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    s = max(DUMP_SAMPLE // world, 1)
+    if out_n <= s:
+        idx = np.arange(out_n, dtype=np.int64)
+    else:
+        edges = np.arange(s + 1, dtype=np.int64) * out_n // s
+        h = (np.arange(s, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+        h ^= h >> np.uint64(29)
+        idx = edges[:-1] + (h % (edges[1:] - edges[:-1]).astype(np.uint64)).astype(np.int64)
+    it = torch.from_numpy(idx).to(out_k.device)
+    arrays = {"keys": out_k[:out_n].index_select(0, it).cpu().numpy().view(np.uint32)}
+    if out_v is not None:
+        v = out_v[:out_n].index_select(0, it).cpu().numpy()
+        arrays["values"] = v.view(np.uint32).reshape(idx.size, -1) if v.dtype.itemsize == 8 else v.view(np.uint32)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a.astype(np.float64))
 
 
 def baseline_metric() -> str:
@@ -513,7 +555,13 @@ def headline_line(out: dict) -> str:
     """The ONE JSON line the driver parses, from the full record: the contract's fields, `roofline` (dominant kernel, with the counter
     traffic) and `cpu_baseline`, plus a numbers-only digest of the `more` block — <= HEADLINE_MAX_BYTES, printed LAST.  Everything else
     (per-kernel tables, box floor, entropy / size sweeps, the rocPRIM comparator) goes to gpurun_out/bench_full.json and to '# bench_full'
-    lines printed BEFORE this one."""
+    lines printed BEFORE this one.  A plain run's record (no --full) has none of these blocks: its line is the contract's fields + config."""
+    cfg = out["config"]
+    line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                                "dtype", "data")}
+    line["config"] = {k: cfg[k] for k in ("workload", "keys_per_gpu", "entropy_preset", "generator", "tile_keys", "verified_sorted") if k in cfg}
+    if "roofline" not in out:
+        return json.dumps(line)
     rf = out["roofline"]
     ws = rf.get("whole_sort", {})
     prov = rf.get("traffic_provenance") or {}
@@ -530,10 +578,6 @@ def headline_line(out: dict) -> str:
     }
     if "frac_of_box_floor" in rf:
         roof["frac_of_box_tile_copy"] = _r(rf["frac_of_box_floor"]["pass"])
-    cfg = out["config"]
-    line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-                                "dtype", "data")}
-    line["config"] = {k: cfg[k] for k in ("workload", "keys_per_gpu", "entropy_preset", "generator", "tile_keys", "verified_sorted") if k in cfg}
     line["roofline"] = roof
     cb = out.get("cpu_baseline")
     line["cpu_baseline"] = None if not cb else {
@@ -628,14 +672,20 @@ def main():
     vdt = torch.int32 if args.pairs == 4 else torch.int64
     mode = g.MODE_PAIRS if pairs else g.MODE_KEYS_ONLY
 
-    # ---- inputs resident in HBM before the timed region: one buffer per step ----
-    nbuf = max(K, W, 1)
+    # ---- inputs resident in HBM before the timed region: one buffer per step.  More steps than buffers fit in HBM (beside the
+    # sorter's own, the alternates and the N > 1 pipeline's: `reserve`) run in rounds of `nbuf` steps, each round's inputs generated
+    # before it, outside the timed region; step i always sorts the keys of seed base + i ----
+    per_buf = n * (4 + args.pairs)
+    reserve = 8 * per_buf + (4 << 30)
+    fit = (torch.cuda.mem_get_info()[0] // (world if dry else 1) - reserve) // per_buf
+    nbuf = max(1, min(max(K, W), fit))
     bufs = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(nbuf)]
     vbufs = [torch.empty(n, dtype=vdt, device="cuda") for _ in range(nbuf)] if pairs else [None] * nbuf
 
-    def regenerate(base_seed):
-        for i in range(nbuf):
-            g.init_random(bufs[i], base_seed + i + 1000 * rank, args.entropy, vbufs[i])
+    def regenerate(base_seed, first=0):
+        """buffer i <- the keys of step first + i"""
+        for i in range(min(nbuf, max(K, W) - first)):
+            g.init_random(bufs[i], base_seed + first + i + 1000 * rank, args.entropy, vbufs[i])
         torch.cuda.synchronize()
 
     if world == 1:
@@ -681,20 +731,26 @@ def main():
             torch.cuda.synchronize()
 
     # ---- warmup (untimed) ----
-    regenerate(5000)
-    for i in range(W):
-        step(i)
+    for r0 in range(0, max(W, 1), nbuf):
+        regenerate(5000, r0)
+        for i in range(min(W - r0, nbuf)):
+            step(i)
     fence()
 
-    # ---- timed: exactly K steps ----
-    regenerate(10)  # reference seeds: 10 + i
-    fence()
-    t0 = time.perf_counter()
+    # ---- timed: exactly K steps (one round unless the steps outnumber the buffers) ----
+    elapsed = 0.0
     last = None
-    for i in range(K):
-        last = step(i)
-    fence()
-    elapsed = time.perf_counter() - t0
+    for r0 in range(0, K, nbuf):
+        regenerate(10, r0)  # reference seeds: 10 + i
+        fence()
+        t0 = time.perf_counter()
+        for i in range(min(K - r0, nbuf)):
+            last = step(i)
+        fence()
+        elapsed += time.perf_counter() - t0
+    sorter.check()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *last, world, rank)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -703,7 +759,7 @@ def main():
     # ---- N > 1, C-ABI pipeline over RCCL: the same steps with the OTHER bucket-exchange call, timed the same way, so that one run
     # records both (north_star names ncclAllToAllv; the default is grouped ncclSend / ncclRecv) ----
     exchange_ab = None
-    if dist is not None and not dry and sharded._ctx and "FALLBACK" not in pipeline:
+    if args.full and dist is not None and not dry and sharded._ctx and "FALLBACK" not in pipeline:
         try:
             reps = min(K, 5)
             sharded.set_alltoallv(True)
@@ -744,7 +800,7 @@ def main():
     # ---- multi-GPU: phase times of the last step on every rank (HIP events inside gs_onesweep_sort_sharded),
     # bytes exchanged, and the exchange rate per xGMI link against its peak ----
     mgpu = None
-    if dist is not None:
+    if args.full and dist is not None:
         p = sharded.profile() if sharded._ctx else {"split_ms": 0.0, "exchange_ms": 0.0, "local_sort_ms": 0.0, "total_ms": 0.0,
                                                     "bytes_sent": 0, "bytes_received": 0}
         mine = torch.tensor([p["split_ms"], p["exchange_ms"], p["local_sort_ms"], p["total_ms"], float(p["bytes_sent"]),
@@ -778,7 +834,7 @@ def main():
     prof_sorter = sorter
     prof = None
     two_level = False
-    if rank == 0:
+    if args.full and rank == 0:
         prof_sorter.set_profiling(True)
         acc = {}
         reps = min(K, 10)
@@ -807,7 +863,7 @@ def main():
         return
 
     floor = None
-    if world == 1 and not args.no_more:
+    if args.full and world == 1 and not args.no_more:
         bufs.clear()      # (the calibration buffers need room)
         vbufs.clear()
         last = out_k = out_v = None
@@ -833,13 +889,14 @@ def main():
             "keys_per_gpu": n, "entropy_preset": args.entropy + 1, "generator": "InitRandom seed 10+i (+1000*rank)",
             "tile_keys": sorter.partition_size, "verified_sorted": bool(sorted_ok and total_ok),
         },
-        "roofline": roofline_block(n, args.pairs, prof, args.log2_keys, args.entropy, args.shape, sorter.partition_size, sorter.rank_mode, floor, two_level),
     }
+    if prof is not None:
+        out["roofline"] = roofline_block(n, args.pairs, prof, args.log2_keys, args.entropy, args.shape, sorter.partition_size, sorter.rank_mode, floor, two_level)
     if floor is not None:
         out["box_floor"] = floor
     if mgpu is not None:
         out["multi_gpu"] = mgpu
-    if world == 1 and not args.pairs and not args.entropy and not args.shape and not args.no_more:
+    if args.full and world == 1 and not args.pairs and not args.entropy and not args.shape and not args.no_more:
         # free the headline's buffers first: the block allocates its own
         bufs.clear()
         vbufs.clear()
@@ -848,11 +905,11 @@ def main():
         torch.cuda.empty_cache()
         out["more"] = more_block(g, n, args.log2_keys, args.more_steps)
         out["more"]["comparator"] = comparator_block()
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(args.cpu_log2)
+    if args.full:
+        out["cpu_baseline"] = cpu_baseline(args.cpu_log2) if world == 1 and not args.no_cpu_baseline else None
+        emit(out)
     else:
-        out["cpu_baseline"] = None
-    emit(out)
+        print(headline_line(out))
     if dist is not None:
         dist.destroy_process_group()
     if not (sorted_ok and total_ok):

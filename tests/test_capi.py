@@ -237,6 +237,36 @@ def test_bench_headline_line_is_small_and_complete():
     # the counters file the line borrows `traffic` from exists and names the sources it was measured on
     path = bench.pmc_traffic_file()
     assert path and "kernel_sources_sha256" in json.load(open(path))
+    # a plain run (no --full) measures none of the blocks: its line is the contract's fields + config, nothing borrowed
+    plain = {k: v for k, v in full.items() if k not in ("roofline", "box_floor", "more", "cpu_baseline", "full_record")}
+    d3 = json.loads(bench.headline_line(plain))
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert d3[k] == d[k], k
+    assert not {"roofline", "cpu_baseline", "more_digest", "full_record"} & set(d3)
+
+
+def test_bench_dump_outputs_is_a_fixed_exact_sample(tmp_path):
+    """bench.py --dump-outputs on (CPU) tensors standing in for the last step's output: float64, exact for every 32-bit word (u64 values
+    as two uint32 columns), the same positions every time, in order, within 64 MB for the largest output the bench can produce."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = bench.DUMP_SAMPLE * 3 + 12345
+    keys = np.sort(np.random.default_rng(1).integers(0, 1 << 32, n, dtype=np.uint64)).astype(np.uint32)
+    kt = torch.from_numpy(keys.view(np.int32))
+    vt = torch.from_numpy((keys.astype(np.int64) << 32) | 5)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), kt, vt, n)
+    k, v = np.load(tmp_path / "a" / "keys.npy"), np.load(tmp_path / "a" / "values.npy")
+    assert k.dtype == v.dtype == np.float64 and k.shape == (bench.DUMP_SAMPLE,) and v.shape == (bench.DUMP_SAMPLE, 2)
+    assert np.array_equal(k, np.load(tmp_path / "b" / "keys.npy")) and np.array_equal(v, np.load(tmp_path / "b" / "values.npy"))
+    assert np.all(np.diff(k) >= 0) and np.isin(k, keys).all() and k[0] >= keys[0] and k[-1] <= keys[-1]
+    assert np.array_equal(v[:, 1], k) and (v[:, 0] == 5).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64e6
+    bench.dump_outputs(str(tmp_path / "small"), kt, None, 1000)   # below the sample size: the whole output
+    assert np.array_equal(np.load(tmp_path / "small" / "keys.npy"), keys[:1000].astype(np.float64))
 
 
 @pytest.mark.parametrize("world,bin_major", [(2, 1), (3, 1), (8, 1), (8, 0), (5, 1)])

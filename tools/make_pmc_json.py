@@ -33,7 +33,7 @@ def main():
     d, commit = sys.argv[1], sys.argv[2]
     res = {"round": 6, "commit": commit, "kernel_sources_sha256": bench.kernel_sources_sha256(), "kernel_sources": list(bench.KERNEL_SOURCES),
            "collected_by": "tools/rocprof_collect.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE in separate passes of `python bench.py --steps 3 "
-                           "--warmup 1 --no-cpu-baseline --no-more [--pairs N]`, 2^28 elements, summaries under profiles/r06_rocprof/",
+                           "--warmup 1 --full --no-cpu-baseline --no-more [--pairs N]`, 2^28 elements, summaries under profiles/r06_rocprof/",
            "correction": "FETCH_SIZE x 2 on gfx950 (128-byte requests tallied at 64 B); KiB per dispatch; mean over the WORKING dispatches of a kernel "
                          "(a sort also enqueues launches that exit on their flag word)"}
     for cfg, vb in (("keys", 0), ("pairs4", 4), ("pairs8", 8)):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Evidence run (round 6 layout) (GPU box): for keys-only, (u32,u32) and (u32,u64) pairs at 2^28 — rocprofv3 --kernel-trace --stats, then FETCH_SIZE and WRITE_SIZE
 # in runs of their own (counters never together with a trace domain other than --kernel-trace) — of `python bench.py --steps 3 --warmup 1
-# --no-cpu-baseline --no-more [--pairs N]`.  usage: tools/rocprof_collect.sh OUT_DIR   -> OUT_DIR/{keys,pairs4,pairs8}_{stats,fetch,write}.txt
+# --full --no-cpu-baseline --no-more [--pairs N]`.  usage: tools/rocprof_collect.sh OUT_DIR   -> OUT_DIR/{keys,pairs4,pairs8}_{stats,fetch,write}.txt
 set -u
 out=${1:-gpurun_out/r06_rocprof}
 repo=$(pwd)
@@ -9,7 +9,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for cfg in keys pairs4 pairs8; do
   case $cfg in keys) extra="";; pairs4) extra="--pairs 4";; pairs8) extra="--pairs 8";; esac
-  args="--steps 3 --warmup 1 --no-cpu-baseline --no-more $extra"
+  args="--steps 3 --warmup 1 --full --no-cpu-baseline --no-more $extra"
   rm -rf /tmp/p_stats /tmp/p_fetch /tmp/p_write
   rocprofv3 --kernel-trace --stats -d /tmp/p_stats -- python $repo/bench.py $args > /tmp/p_stats.log 2>&1
   if [ -z "${ONLY_STATS:-}" ]; then
