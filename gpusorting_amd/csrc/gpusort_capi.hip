@@ -16,11 +16,13 @@
 #include "mid_kernels.hpp"
 #include "hybrid_kernels.hpp"
 
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <utility>
 
 namespace {
 
@@ -35,13 +37,15 @@ thread_local int g_last_hip_error = 0;
         }                                              \
     } while (0)
 
-// ---- tile-shape table -------------------------------------------------------
-// One launcher per (shape, value bytes, key type).  Shape 0 is the default; the
-// others exist for on-device tuning sweeps (u32 keys only).
+// ---- launchers: one per kernel family, instantiated by the kernel registry below and nowhere else ------------------
+struct Shape { int threads, kpt; };  // a workgroup's threads x keys per thread
+
 using BinLauncher = void (*)(hipStream_t, uint32_t grid, uint32_t*, uint32_t*, void*, void*,
                              uint32_t* desc, uint32_t* counters, const uint32_t* info, uint32_t* hsub, uint32_t* status,
                              uint32_t n, uint32_t shift, uint32_t mode);
 
+// VR 2: the two-round form of the 8-byte-value pass (two workgroups per CU), launched beside the one-round form in full sorts;
+// the pass's PF_SKEW flag decides on the device which of the two works
 template <int THREADS, int KPT, int VB, int KT, int RANK, int VR = 1>
 void launch_bin(hipStream_t s, uint32_t grid, uint32_t* ka, uint32_t* kb, void* va, void* vb, uint32_t* desc,
                 uint32_t* counters, const uint32_t* info, uint32_t* hsub, uint32_t* status, uint32_t n, uint32_t shift,
@@ -49,20 +53,9 @@ void launch_bin(hipStream_t s, uint32_t grid, uint32_t* ka, uint32_t* kb, void* 
     hipLaunchKernelGGL((gs::digit_binning_kernel<THREADS, KPT, VB, KT, RANK, VR>), dim3(grid), dim3(THREADS), 0, s, ka, kb,
                        va, vb, desc, counters, info, hsub, status, n, shift, mode);
 }
-// the two-round form of the 8-byte-value pass (two workgroups per CU), launched beside the one-round form in full
-// sorts; the pass's PF_SKEW flag decides on the device which of the two works.  [rank mode][key type]
-#if defined(GS_MINIMAL) && defined(GS_MIN_PAIRS)
-const BinLauncher g_vr2[2][3] = {{nullptr, nullptr, nullptr}, {launch_bin<512, 32, 8, 0, 1, 2>, nullptr, nullptr}};
-#elif defined(GS_MINIMAL)  // experiment builds (tools/): u32 keys-only kernels of the three product shapes, nothing else — a 10 s compile
-const BinLauncher g_vr2[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-#else
-const BinLauncher g_vr2[2][3] = {{launch_bin<512, 32, 8, 0, 0, 2>, launch_bin<512, 32, 8, 1, 0, 2>, launch_bin<512, 32, 8, 2, 0, 2>},
-                                 {launch_bin<512, 32, 8, 0, 1, 2>, launch_bin<512, 32, 8, 1, 1, 2>, launch_bin<512, 32, 8, 2, 1, 2>}};
-#endif
 
 // keys-only sorts of 32-bit keys on the default tile that the Scan kernel may plan on position chains (PF_POS, skewed keys): one
 // launch per pass of the dual kernel — persistent workgroups that run the plain or the position-chain form, as planned.
-// [last pass][key type]
 // tile of the counting position-chain passes, as the Scan kernel takes it (bit 31: the plan's last pass runs on it as well).
 // Keys-only: the full tile, counters packed 2 x 16 bit; pairs: 512 x 24 with 32-bit counters — and for 8-byte values in the last
 // pass too (its two staging rounds run 9 % faster on the smaller tile, profiles/r04_pos_packed_counters.txt)
@@ -76,116 +69,32 @@ void launch_dual(hipStream_t s, uint32_t grid, uint32_t* ka, uint32_t* kb, void*
     hipLaunchKernelGGL((gs::digit_binning_dual_kernel<KT, LAST>), dim3(grid), dim3(512), 0, s, ka, kb, va, vb, desc, counters, info,
                        hsub, status, n, shift, mode);
 }
+// pairs: the position-chain form of the pass, launched beside the plain form(s)
 template <int VB, int KT, bool LAST>
 void launch_posv(hipStream_t s, uint32_t grid, uint32_t* ka, uint32_t* kb, void* va, void* vb, uint32_t* desc, uint32_t* counters,
                  const uint32_t* info, uint32_t* hsub, uint32_t* status, uint32_t n, uint32_t shift, uint32_t mode) {
     hipLaunchKernelGGL((gs::digit_binning_posv_kernel<VB, KT, LAST>), dim3(grid), dim3(512), 0, s, ka, kb, va, vb, desc, counters, info,
                        hsub, status, n, shift, mode);
 }
-// pairs on the two-level plan: the plain form of the pass as persistent workgroups [8-byte values][key type]; rank mode 1 only
+// pairs on the two-level plan: the plain form of the pass as persistent workgroups; rank mode 1 only
 template <int T, int K, int VB, int KT>
 void launch_persist(hipStream_t s, uint32_t grid, uint32_t* ka, uint32_t* kb, void* va, void* vb, uint32_t* desc, uint32_t* counters,
                     const uint32_t* info, uint32_t* hsub, uint32_t* status, uint32_t n, uint32_t shift, uint32_t mode) {
     hipLaunchKernelGGL((gs::digit_binning_persist_kernel<T, K, VB, KT, 1>), dim3(grid), dim3(T), 0, s, ka, kb, va, vb, desc, counters, info, hsub,
                        status, n, shift, mode);
 }
-#ifdef GS_MINIMAL
-const BinLauncher g_dual[2][3] = {{launch_dual<0, false>, nullptr, nullptr}, {launch_dual<0, true>, nullptr, nullptr}};
-#ifdef GS_MIN_PAIRS
-const BinLauncher g_posv[2][2][3] = {{{launch_posv<4, 0, false>, nullptr, nullptr}, {launch_posv<4, 0, true>, nullptr, nullptr}},
-                                     {{launch_posv<8, 0, false>, nullptr, nullptr}, {launch_posv<8, 0, true>, nullptr, nullptr}}};
-const BinLauncher g_persist[2][3] = {{launch_persist<1024, 16, 4, 0>, nullptr, nullptr}, {launch_persist<512, 32, 8, 0>, nullptr, nullptr}};
-#else
-const BinLauncher g_posv[2][2][3] = {{{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}, {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}};
-const BinLauncher g_persist[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-#endif
-#else
-const BinLauncher g_persist[2][3] = {{launch_persist<1024, 16, 4, 0>, launch_persist<1024, 16, 4, 1>, launch_persist<1024, 16, 4, 2>},
-                                     {launch_persist<512, 32, 8, 0>, launch_persist<512, 32, 8, 1>, launch_persist<512, 32, 8, 2>}};
-// pairs: the position-chain form of the pass, launched beside the plain form(s) [4- / 8-byte values][last pass][key type]
-const BinLauncher g_posv[2][2][3] = {{{launch_posv<4, 0, false>, launch_posv<4, 1, false>, launch_posv<4, 2, false>},
-                                      {launch_posv<4, 0, true>, launch_posv<4, 1, true>, launch_posv<4, 2, true>}},
-                                     {{launch_posv<8, 0, false>, launch_posv<8, 1, false>, launch_posv<8, 2, false>},
-                                      {launch_posv<8, 0, true>, launch_posv<8, 1, true>, launch_posv<8, 2, true>}}};
-const BinLauncher g_dual[2][3] = {{launch_dual<0, false>, launch_dual<1, false>, launch_dual<2, false>},
-                                  {launch_dual<0, true>, launch_dual<1, true>, launch_dual<2, true>}};
-#endif
 
-struct Shape {
-    int threads, kpt;
-    BinLauncher fn[2][3][6];  // [rank mode][vb index 0/4/8][key type: 3 x 32-bit, 3 x 64-bit]; nullptr = not compiled
-};
-
-#define GS_ROWS(T, K, R)                                                                             \
-    {                                                                                                \
-        {launch_bin<T, K, 0, 0, R>, launch_bin<T, K, 0, 1, R>, launch_bin<T, K, 0, 2, R>},           \
-            {launch_bin<T, K, 4, 0, R>, launch_bin<T, K, 4, 1, R>, launch_bin<T, K, 4, 2, R>},       \
-            {launch_bin<T, K, 8, 0, R>, launch_bin<T, K, 8, 1, R>, launch_bin<T, K, 8, 2, R>},       \
-    }
-#define GS_ROWS_U32(T, K, R)                                                                         \
-    {                                                                                                \
-        {launch_bin<T, K, 0, 0, R>, nullptr, nullptr}, {launch_bin<T, K, 4, 0, R>, nullptr, nullptr}, \
-            {launch_bin<T, K, 8, 0, R>, nullptr, nullptr},                                           \
-    }
-// every key type, 64-bit keys included (8-byte stage slots: tiles up to 8192 keys)
-#define GS_ROWS64(T, K, R)                                                                                                   \
-    {                                                                                                                        \
-        {launch_bin<T, K, 0, 0, R>, launch_bin<T, K, 0, 1, R>, launch_bin<T, K, 0, 2, R>, launch_bin<T, K, 0, 3, R>,         \
-         launch_bin<T, K, 0, 4, R>, launch_bin<T, K, 0, 5, R>},                                                              \
-            {launch_bin<T, K, 4, 0, R>, launch_bin<T, K, 4, 1, R>, launch_bin<T, K, 4, 2, R>, launch_bin<T, K, 4, 3, R>,     \
-             launch_bin<T, K, 4, 4, R>, launch_bin<T, K, 4, 5, R>},                                                          \
-            {launch_bin<T, K, 8, 0, R>, launch_bin<T, K, 8, 1, R>, launch_bin<T, K, 8, 2, R>, launch_bin<T, K, 8, 3, R>,     \
-             launch_bin<T, K, 8, 4, R>, launch_bin<T, K, 8, 5, R>},                                                          \
-    }
-#define GS_FULL64(T, K) {T, K, {GS_ROWS64(T, K, 0), GS_ROWS64(T, K, 1)}}
-#define GS_ROWS_KEYS(T, K, R) {{launch_bin<T, K, 0, 0, R>, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}
-#define GS_KEYSONLY(T, K) {T, K, {GS_ROWS_KEYS(T, K, 0), GS_ROWS_KEYS(T, K, 1)}}
-#define GS_FULL(T, K) {T, K, {GS_ROWS(T, K, 0), GS_ROWS(T, K, 1)}}
-#define GS_U32ONLY(T, K) {T, K, {GS_ROWS_U32(T, K, 0), GS_ROWS_U32(T, K, 1)}}
-
-#ifdef GS_MINIMAL
-#ifdef GS_MIN_PAIRS  // (tuning flavour with the uint32-key pairs kernels as well: the two-level plan for pairs, tools/)
-#define GS_ROWS_KEYS64(T, K, R) {{launch_bin<T, K, 0, 0, R>, nullptr, nullptr, nullptr, nullptr, nullptr}, {launch_bin<T, K, 4, 0, R>, nullptr, nullptr, nullptr, nullptr, nullptr}, {launch_bin<T, K, 8, 0, R>, nullptr, nullptr, nullptr, nullptr, nullptr}}
-#else
-#define GS_ROWS_KEYS64(T, K, R) {{launch_bin<T, K, 0, 0, R>, nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}}
-#endif
-#define GS_KEYSONLY64(T, K) {T, K, {GS_ROWS_KEYS64(T, K, 0), GS_ROWS_KEYS64(T, K, 1)}}
-const Shape g_shapes[] = {GS_KEYSONLY64(512, 32), GS_KEYSONLY64(1024, 16), GS_KEYSONLY64(512, 16),
-#ifdef GS_TUNING
-                          GS_KEYSONLY64(256, 32), GS_KEYSONLY64(256, 16), GS_KEYSONLY64(512, 20),
-#endif
-};
-#else
-const Shape g_shapes[] = {
-    GS_FULL(512, 32),   // default for keys-only and 8-byte values: 16384-key tiles, 2 workgroups per CU
-    GS_FULL(1024, 16),  // default for 4-byte values (measured best, profiles/r01_sweep_v16_*)
-    GS_FULL64(512, 16), // mid sizes (n <= mid_keys): 8192-key tiles, shorter per-tile latency, more workgroups;
-                        // and the shape of 64-bit keys at every size (8-byte stage slots: 64 KiB per tile)
-#ifdef GS_TUNING  // tuning build only (libgpusort_tuning.so)
-    GS_U32ONLY(256, 32), GS_U32ONLY(256, 16),
-    GS_U32ONLY(512, 20),  // 10 240-key tiles: 52 KiB of LDS, three workgroups per CU
-#endif
-};
-#endif
-constexpr int g_num_shapes = sizeof(g_shapes) / sizeof(g_shapes[0]);
-
-inline int vb_index(uint32_t vb) { return vb == 0 ? 0 : vb == 4 ? 1 : 2; }
-inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
-
-using gs::SLAB_COUNTERS;
-using gs::SLAB_DESC;
-using gs::SLAB_HIST;
-using gs::SLAB_INFO;
-using gs::SLAB_STATUS;
-
-constexpr uint32_t MIN_TILE = 4096;  // smallest tile of any compiled shape (sizing of the slab)
-constexpr uint32_t KEY64_TILE = 8192;  // tile of every sort of 64-bit keys (MID_SHAPE: 8-byte stage slots, 64 KiB)
-constexpr int MID_SHAPE = 2;         // g_shapes index used for n <= mid_keys(vb) unless the caller picked a shape
-// profiles/r02_shape_by_size.txt (general path, back-to-back sorts): the 8192-key tile wins up to 2^25 keys for keys-only
-// sorts (180 vs 194 us at 2^24, 293 vs 302 at 2^25, loses at 2^26) and for 8-byte values (whose big tile leaves one
-// workgroup per CU), up to 2^23 with 4-byte values (1024 x 16 wins from 2^24)
-inline uint32_t mid_keys(uint32_t vb) { return vb == 4 ? (1u << 23) : (1u << 25); }
-
+using HistLauncher = void (*)(hipStream_t, uint32_t, const uint32_t*, uint32_t*, size_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
+                              uint32_t*);
+template <int KT>
+void launch_hist(hipStream_t s, uint32_t blocks, const uint32_t* keys, uint32_t* slab, size_t used_words, uint32_t n,
+                 uint32_t seg_len0, uint32_t p0, uint32_t np, uint32_t word, uint32_t allow_pos, uint32_t* partials) {
+    hipLaunchKernelGGL((gs::global_histogram_kernel<KT>), dim3(blocks), dim3(gs::GHIST_THREADS), 0, s, keys, slab,
+                       used_words, n, seg_len0, p0, np, word, allow_pos, partials);
+    // the workgroups' tables -> the HIST region (one thread per bin)
+    hipLaunchKernelGGL(gs::hist_reduce_kernel, dim3(np * gs::NCH * gs::RADIX / 64u), dim3(256), 0, s, partials, blocks,
+                       np * gs::NCH * gs::RADIX, slab + gs::SLAB_HIST);
+}
 
 // ---- two-level plan (hybrid_kernels.hpp) ----
 using HyHistLauncher = void (*)(hipStream_t, uint32_t grid, const uint32_t* keys, uint32_t* slab, size_t used_words, uint32_t n, uint32_t seg_len0,
@@ -201,41 +110,220 @@ template <int KT, int T, int K>
 void launch_hy_local(hipStream_t s, uint32_t grid, uint32_t* keys, const uint32_t* tab, uint32_t* slab, uint32_t n, uint32_t descending) {
     hipLaunchKernelGGL((gs::hy_local_sort_kernel<KT, T, K>), dim3(grid), dim3(T), 0, s, keys, tab, slab, n, descending);
 }
-// the local sort's workgroup by the mean bucket n / 65 536: it holds 1.5 x the mean at the top of its class (uniform keys stay within
-// a few per cent of the mean; what does not fit sends the sort to the LSD passes).  [class][key type]
-struct HyLocalClass { uint32_t max_n, cap; };
-constexpr HyLocalClass g_hy_class[4] = {{1u << 27, 256 * 12}, {1u << 28, 512 * 12}, {1u << 29, 1024 * 12}, {GS_MAX_KEYS, 1024 * 24}};
-#ifdef GS_MINIMAL
-const HyHistLauncher g_hy_hist[3] = {launch_hy_hist<0>, nullptr, nullptr};
-const HyLocalLauncher g_hy_local[4][3] = {{launch_hy_local<0, 256, 12>, nullptr, nullptr}, {launch_hy_local<0, 512, 12>, nullptr, nullptr},
-                                          {launch_hy_local<0, 1024, 12>, nullptr, nullptr}, {launch_hy_local<0, 1024, 24>, nullptr, nullptr}};
-#else
-const HyHistLauncher g_hy_hist[3] = {launch_hy_hist<0>, launch_hy_hist<1>, launch_hy_hist<2>};
-const HyLocalLauncher g_hy_local[4][3] = {{launch_hy_local<0, 256, 12>, launch_hy_local<1, 256, 12>, launch_hy_local<2, 256, 12>},
-                                          {launch_hy_local<0, 512, 12>, launch_hy_local<1, 512, 12>, launch_hy_local<2, 512, 12>},
-                                          {launch_hy_local<0, 1024, 12>, launch_hy_local<1, 1024, 12>, launch_hy_local<2, 1024, 12>},
-                                          {launch_hy_local<0, 1024, 24>, launch_hy_local<1, 1024, 24>, launch_hy_local<2, 1024, 24>}};
-#endif
 using HyLocalPairsLauncher = void (*)(hipStream_t, uint32_t* keys, void* vals, const uint32_t* tab, const uint32_t* slab, uint32_t n, uint32_t descending);
 template <int KT, int VB, int T, int K>
 void launch_hy_local_pairs(hipStream_t s, uint32_t* keys, void* vals, const uint32_t* tab, const uint32_t* slab, uint32_t n, uint32_t descending) {
     hipLaunchKernelGGL((gs::hy_local_sort_pairs_kernel<KT, VB, T, K>), dim3(gs::HY_BINS), dim3(T), 0, s, keys, vals, tab, slab, n, descending);
 }
-// [8-byte values][class][key type]; the 24 576-pair class with 8-byte values does not fit a workgroup's LDS (nullptr: LSD passes)
-#define GS_HYP_ROW(VB, T, K) {launch_hy_local_pairs<0, VB, T, K>, launch_hy_local_pairs<1, VB, T, K>, launch_hy_local_pairs<2, VB, T, K>}
-#define GS_HYP_ROW0(VB, T, K) {launch_hy_local_pairs<0, VB, T, K>, nullptr, nullptr}
-#if defined(GS_MINIMAL) && defined(GS_MIN_PAIRS)
-const HyLocalPairsLauncher g_hy_local_pairs[2][4][3] = {{GS_HYP_ROW0(4, 256, 12), GS_HYP_ROW0(4, 512, 12), GS_HYP_ROW0(4, 1024, 12), GS_HYP_ROW0(4, 1024, 24)},
-                                                        {GS_HYP_ROW0(8, 256, 12), GS_HYP_ROW0(8, 512, 12), GS_HYP_ROW0(8, 1024, 12), {nullptr, nullptr, nullptr}}};
-#elif defined(GS_MINIMAL)
-const HyLocalPairsLauncher g_hy_local_pairs[2][4][3] = {};
-#else
-const HyLocalPairsLauncher g_hy_local_pairs[2][4][3] = {{GS_HYP_ROW(4, 256, 12), GS_HYP_ROW(4, 512, 12), GS_HYP_ROW(4, 1024, 12), GS_HYP_ROW(4, 1024, 24)},
-                                                        {GS_HYP_ROW(8, 256, 12), GS_HYP_ROW(8, 512, 12), GS_HYP_ROW(8, 1024, 12), {nullptr, nullptr, nullptr}}};
-#endif
+// the local sort's workgroup by the mean bucket n / 65 536: it holds 1.5 x the mean at the top of its class (uniform keys stay within
+// a few per cent of the mean; what does not fit sends the sort to the LSD passes)
+struct HyLocalClass {
+    uint32_t max_n;
+    int threads, kpt;
+    constexpr uint32_t cap() const { return (uint32_t)threads * kpt; }
+};
+constexpr HyLocalClass g_hy_class[4] = {{1u << 27, 256, 12}, {1u << 28, 512, 12}, {1u << 29, 1024, 12}, {GS_MAX_KEYS, 1024, 24}};
 inline int hy_class(uint32_t n) { return n <= g_hy_class[0].max_n ? 0 : n <= g_hy_class[1].max_n ? 1 : n <= g_hy_class[2].max_n ? 2 : 3; }
 constexpr uint32_t HY_MIN_PAIRS_DEFAULT = (1u << 25) + 1u;  // pairs: from where the position-chain plan (its fall-back) starts — at 2^25 pairs the two-level plan already wins (61.6 against 58.8, 44.6 against 40.4 GKeys/s with 4- / 8-byte values), at 2^24 it loses
 constexpr uint32_t HY_MIN_KEYS_DEFAULT = 3u << 24;  // 50 M keys: measured, the LSD passes win at 2^25 (121 against 102 GKeys/s), the two-level plan at 2^26 (139 against 122): below, its 65 536 buckets are a few hundred keys each and a workgroup per bucket is mostly launch (profiles/r05_two_level_threshold.txt)
+
+// ---- single-tile fast path: one launch, no scan state ----
+using SmallLauncher = void (*)(hipStream_t, uint32_t*, void*, uint32_t, uint32_t, uint32_t*);
+template <int T, int K, int VB, int KT, int RANK>
+void launch_small(hipStream_t s, uint32_t* keys, void* vals, uint32_t n, uint32_t descending, uint32_t* status) {
+    hipLaunchKernelGGL((gs::small_sort_kernel<T, K, VB, KT, RANK>), dim3(1), dim3(T), 0, s, keys, vals, n, descending, status);
+}
+// size classes by slots: 8192 slots (every mode), 16384 (keys-only and 4-byte values), 32768 (keys-only) — what fits 160 KiB of LDS;
+// 64-bit keys: the classes up to 8192 slots.  The two smallest classes (256 x 4 and 256 x 8 slots) exist because a sort of 2^10 keys
+// in the 8192-slot shape pays for 8192 slots in every pass: 10.5 us against 8.1 (profiles/r04_small_shapes.txt; the reference's size
+// sweep starts there, GPUSortingD3D12/Tests.h:392-393,415-416)
+constexpr Shape g_small_class[5] = {{256, 4}, {256, 8}, {512, 16}, {1024, 16}, {1024, 32}};
+inline int small_class(uint32_t n) { return n <= 1024 ? 0 : n <= 2048 ? 1 : n <= 8192 ? 2 : n <= 16384 ? 3 : n <= 32768 ? 4 : 5; }
+
+// ---- mid sizes: two launches (mid_kernels.hpp) ----
+using MidLauncher = void (*)(hipStream_t, uint32_t n_tiles, uint32_t* keys, uint32_t* alt, void* vals, void* valt, uint32_t* scratch,
+                             uint32_t* status, uint32_t n, uint32_t descending);
+template <int VB, int KT, int RANK, int T, int K, int T2, int K2>
+void launch_mid(hipStream_t s, uint32_t tiles, uint32_t* keys, uint32_t* alt, void* vals, void* valt, uint32_t* scratch, uint32_t* status,
+                uint32_t n, uint32_t descending) {
+    hipLaunchKernelGGL((gs::mid_msd_kernel<VB, KT, RANK, T, K, T2 * K2>), dim3(tiles), dim3(T), 0, s, keys, alt, vals, valt, scratch, status,
+                       n, descending);
+    hipLaunchKernelGGL((gs::bucket_sort_kernel<VB, KT, RANK, T2, K2>), dim3(gs::RADIX), dim3(T2), 0, s, keys, alt, vals, valt, scratch,
+                       status, n, descending);
+}
+// Classes by the bucket K2 can hold: 8192 keys (n <= 2^20, every value width; K1: <= 128 tiles of 8192), 16 384 (n <= 2^21, keys-only
+// and 4-byte values; K1: <= 128 tiles of 16 384), 32 768 (n <= 2^22, keys-only; K1: <= 256 tiles of 16 384 — the 32 768-key tile
+// spilled there and kept half the CUs idle, 44 us of a 67 us sort, profiles/r03_mid_size_timeline.txt).
+// Round 5: class 3 — keys-only up to 2^23 (K1: 256 tiles of 32 768, one per CU; K2 holds 34 816 keys: 6 % above the mean bucket) — and
+// class 4 — 4-byte values up to 2^22 pairs (K1: 256 tiles of 16 384; K2 holds 17 408 pairs): 74.6 -> 102 GKeys/s at 2^23 keys,
+// profiles/r05_mid_classes.txt.  K1's tiles: never more than fit the chip at once (512 tiles of 16 384 keys for 2^23 keys left half of
+// them to be adopted one by one — 1.7 ms).
+struct MidClass {
+    int threads, kpt;    // K1 (mid_msd_kernel): its tile
+    int threads2, kpt2;  // K2 (bucket_sort_kernel): the bucket it holds
+    uint32_t max_tiles;  // K1's tiles at most (<= MID_MAX_TILES)
+    constexpr uint32_t tile() const { return (uint32_t)threads * kpt; }
+};
+constexpr MidClass g_mid_class[5] = {{512, 16, 512, 16, 128}, {512, 32, 512, 32, 128}, {512, 32, 1024, 32, 256}, {1024, 32, 1024, 34, 256},
+                                     {512, 32, 512, 34, 256}};
+static_assert(g_mid_class[3].max_tiles <= gs::MID_MAX_TILES && g_mid_class[4].max_tiles <= gs::MID_MAX_TILES, "mid-size classes");
+// class of a mid-size sort, -1: the general pipeline
+inline int mid_class(uint32_t n, uint32_t vb) {
+    auto fits = [n](int c) { return n <= g_mid_class[c].max_tiles * g_mid_class[c].tile(); };
+    if (fits(0)) return 0;
+    if (fits(1) && vb != 8) return 1;
+    if (fits(2) && vb == 0) return 2;
+    if (fits(3) && vb == 0) return 3;
+    if (fits(4) && vb == 4) return 4;
+    return -1;
+}
+
+// ---- kernel registry ------------------------------------------------------------------------------------------------
+// Which kernel instantiations this build compiles: one predicate per family — the only place that reads the build flavour — and
+// one lookup per family, which returns the launcher for run-time parameters or nullptr if that combination is not built (left out
+// of this build flavour, or not existing by design: 64-bit keys on tiles above 8192 keys, the 24 576-pair local sort with 8-byte
+// values, single-tile and mid-size classes that do not fit LDS).  Nothing the predicates reject is instantiated.
+//   GS_MINIMAL (experiment builds, libgpusort_tuning.so): u32 keys-only kernels, plus the histogram of every key type — a 10 s compile;
+//   GS_TUNING: three more tile shapes for on-device tuning sweeps (u32 keys only).
+#ifdef GS_MINIMAL
+constexpr bool FULL = false;
+#else
+constexpr bool FULL = true;
+#endif
+// tile shapes of the binning passes; shape 0 is the default
+constexpr Shape g_shapes[] = {
+    {512, 32},   // default for keys-only and 8-byte values: 16384-key tiles, 2 workgroups per CU
+    {1024, 16},  // default for 4-byte values (measured best, profiles/r01_sweep_v16_*)
+    {512, 16},   // mid sizes (n <= mid_keys): 8192-key tiles, shorter per-tile latency, more workgroups;
+                 // and the shape of 64-bit keys at every size (8-byte stage slots: 64 KiB per tile)
+#ifdef GS_TUNING  // tuning build only (libgpusort_tuning.so)
+    {256, 32}, {256, 16},
+    {512, 20},  // 10 240-key tiles: 52 KiB of LDS, three workgroups per CU
+#endif
+};
+constexpr int g_num_shapes = sizeof(g_shapes) / sizeof(g_shapes[0]);
+constexpr int MID_SHAPE = 2;  // g_shapes index used for n <= mid_keys(vb) unless the caller picked a shape
+constexpr int NKT = 6;               // key types: 3 x 32-bit, 3 x 64-bit
+constexpr int VB_OF[3] = {0, 4, 8};  // value bytes by vb index
+constexpr bool key32(int kt) { return FULL ? kt < 3 : kt == 0; }  // 32-bit key types of the keys-only kernels
+
+// digit_binning_kernel (vr 1: every shape and rank mode; vr 2: the two-round form of 8-byte values on the default tile)
+constexpr bool bin_built(int shape, int vb, int kt, int vr) {
+    if (vr == 2) return FULL && shape == 0 && vb == 8 && kt < 3;
+    if (!FULL) return vb == 0 && kt == 0;
+    return shape == MID_SHAPE || (shape < 3 ? kt < 3 : kt == 0);  // 64-bit keys on 512 x 16 only; the tuning shapes: u32 keys
+}
+// the position-chain forms, last pass or not: digit_binning_dual_kernel (keys-only) and digit_binning_posv_kernel (pairs)
+constexpr bool pos_built(int vb, int kt) { return vb == 0 ? key32(kt) : FULL && kt < 3; }
+// digit_binning_persist_kernel (pairs on the two-level plan; 4-byte values on 1024 x 16, 8-byte values on 512 x 32);
+// hy_local_sort_pairs_kernel (all four classes with 4-byte values, the first three with 8-byte values)
+constexpr bool persist_built(int kt) { return FULL && kt < 3; }
+constexpr bool hy_pairs_built(int vb, int cls, int kt) { return FULL && kt < 3 && !(vb == 8 && cls == 3); }
+// hy_histogram_kernel and hy_local_sort_kernel: key32(kt); global_histogram_kernel: every key type
+// small_sort_kernel: classes 0-2 take every value width and key type, class 3 keys-only and 4-byte values, class 4 keys-only
+constexpr bool small_built(int cls, int vb, int kt) { return FULL && (cls < 3 || (kt < 3 && (cls == 3 ? vb != 8 : vb == 0))); }
+// mid_msd_kernel + bucket_sort_kernel: the value widths of mid_class
+constexpr bool mid_built(int cls, int vb, int kt) {
+    return FULL && kt < 3 && (cls == 0 || (cls == 1 ? vb != 8 : cls == 4 ? vb == 4 : vb == 0));
+}
+
+// A launcher table over D0 x D1 x ... (row-major): entry = f(c0, c1, ...), every coordinate a std::integral_constant, so that
+// f instantiates nothing but what it returns.
+template <int... D>
+struct Table {
+    template <class F> static constexpr auto make(F f) { return make_(f, std::make_integer_sequence<int, (D * ...)>{}); }
+    static constexpr int index(std::array<int, sizeof...(D)> c) {
+        int i = 0, k = 0;
+        for (int d : {D...}) i = i * d + c[k++];
+        return i;
+    }
+  private:
+    static constexpr int coord(int i, int k) {
+        const int d[] = {D...};
+        for (int j = (int)sizeof...(D) - 1; j > k; --j) i /= d[j];
+        return i % d[k];
+    }
+    template <int I, class F, size_t... K>
+    static constexpr auto entry(F f, std::index_sequence<K...>) { return f(std::integral_constant<int, coord(I, K)>{}...); }
+    template <class F, int... I>
+    static constexpr auto make_(F f, std::integer_sequence<int, I...>) { return std::array{entry<I>(f, std::make_index_sequence<sizeof...(D)>{})...}; }
+};
+
+using BinTable = Table<2, g_num_shapes, 2, 3, NKT>;  // [vr - 1][shape][rank mode][vb index][key type]
+constexpr auto g_bin = BinTable::make([](auto vr1, auto s, auto r, auto v, auto kt) -> BinLauncher {
+    if constexpr (bin_built(s, VB_OF[v], kt, vr1 + 1)) return launch_bin<g_shapes[s].threads, g_shapes[s].kpt, VB_OF[v], kt, r, vr1 + 1>;
+    else return nullptr;
+});
+using PosTable = Table<3, 2, NKT>;  // [vb index][last pass][key type]
+constexpr auto g_pos = PosTable::make([](auto v, auto last, auto kt) -> BinLauncher {
+    if constexpr (!pos_built(VB_OF[v], kt)) return nullptr;
+    else if constexpr (v == 0) return launch_dual<kt, last == 1>;
+    else return launch_posv<VB_OF[v], kt, last == 1>;
+});
+using PersistTable = Table<2, NKT>;  // [8-byte values][key type]
+constexpr auto g_persist = PersistTable::make([](auto v8, auto kt) -> BinLauncher {
+    if constexpr (!persist_built(kt)) return nullptr;
+    else if constexpr (v8 == 0) return launch_persist<1024, 16, 4, kt>;
+    else return launch_persist<512, 32, 8, kt>;
+});
+constexpr auto g_hist = Table<NKT>::make([](auto kt) -> HistLauncher { return launch_hist<kt>; });
+constexpr auto g_hy_hist = Table<NKT>::make([](auto kt) -> HyHistLauncher {
+    if constexpr (key32(kt)) return launch_hy_hist<kt>;
+    else return nullptr;
+});
+using HyTable = Table<4, NKT>;  // [class][key type]
+constexpr auto g_hy_local = HyTable::make([](auto c, auto kt) -> HyLocalLauncher {
+    if constexpr (key32(kt)) return launch_hy_local<kt, g_hy_class[c].threads, g_hy_class[c].kpt>;
+    else return nullptr;
+});
+using HyPairsTable = Table<2, 4, NKT>;  // [8-byte values][class][key type]
+constexpr auto g_hy_local_pairs = HyPairsTable::make([](auto v8, auto c, auto kt) -> HyLocalPairsLauncher {
+    if constexpr (hy_pairs_built(v8 ? 8 : 4, c, kt)) return launch_hy_local_pairs<kt, v8 ? 8 : 4, g_hy_class[c].threads, g_hy_class[c].kpt>;
+    else return nullptr;
+});
+using SmallTable = Table<5, 2, 3, NKT>;  // [class][rank mode][vb index][key type]
+constexpr auto g_small = SmallTable::make([](auto c, auto r, auto v, auto kt) -> SmallLauncher {
+    if constexpr (small_built(c, VB_OF[v], kt)) return launch_small<g_small_class[c].threads, g_small_class[c].kpt, VB_OF[v], kt, r>;
+    else return nullptr;
+});
+using MidTable = Table<5, 2, 3, NKT>;  // [class][rank mode][vb index][key type]
+constexpr auto g_mid = MidTable::make([](auto c, auto r, auto v, auto kt) -> MidLauncher {
+    constexpr MidClass m = g_mid_class[c];
+    if constexpr (mid_built(c, VB_OF[v], kt)) return launch_mid<VB_OF[v], kt, r, m.threads, m.kpt, m.threads2, m.kpt2>;
+    else return nullptr;
+});
+
+inline int vb_index(uint32_t vb) { return vb == 0 ? 0 : vb == 4 ? 1 : 2; }
+BinLauncher bin_launcher(int shape, int rank, uint32_t vb, int kt, int vr = 1) {
+    return g_bin[BinTable::index({vr - 1, shape, rank, vb_index(vb), kt})];
+}
+BinLauncher pos_launcher(uint32_t vb, bool last, int kt) { return g_pos[PosTable::index({vb_index(vb), last ? 1 : 0, kt})]; }
+BinLauncher persist_launcher(uint32_t vb, int kt) { return g_persist[PersistTable::index({vb == 8 ? 1 : 0, kt})]; }
+HistLauncher hist_launcher(int kt) { return g_hist[kt]; }
+HyHistLauncher hy_hist_launcher(int kt) { return g_hy_hist[kt]; }
+HyLocalLauncher hy_local_launcher(uint32_t n, int kt) { return g_hy_local[HyTable::index({hy_class(n), kt})]; }
+HyLocalPairsLauncher hy_pairs_launcher(uint32_t vb, uint32_t n, int kt) { return g_hy_local_pairs[HyPairsTable::index({vb == 8 ? 1 : 0, hy_class(n), kt})]; }
+SmallLauncher small_launcher(uint32_t n, int rank, uint32_t vb, int kt) {
+    const int c = small_class(n);
+    return c < 5 ? g_small[SmallTable::index({c, rank, vb_index(vb), kt})] : nullptr;  // nullptr: no single-tile kernel for this case
+}
+MidLauncher mid_launcher(int cls, int rank, uint32_t vb, int kt) { return g_mid[MidTable::index({cls, rank, vb_index(vb), kt})]; }
+// ---- end of the kernel registry -------------------------------------------------------------------------------------
+
+inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+
+using gs::SLAB_COUNTERS;
+using gs::SLAB_DESC;
+using gs::SLAB_HIST;
+using gs::SLAB_INFO;
+using gs::SLAB_STATUS;
+
+constexpr uint32_t MIN_TILE = 4096;  // smallest tile of any compiled shape (sizing of the slab)
+constexpr uint32_t KEY64_TILE = 8192;  // tile of every sort of 64-bit keys (MID_SHAPE: 8-byte stage slots, 64 KiB)
+// profiles/r02_shape_by_size.txt (general path, back-to-back sorts): the 8192-key tile wins up to 2^25 keys for keys-only
+// sorts (180 vs 194 us at 2^24, 293 vs 302 at 2^25, loses at 2^26) and for 8-byte values (whose big tile leaves one
+// workgroup per CU), up to 2^23 with 4-byte values (1024 x 16 wins from 2^24)
+inline uint32_t mid_keys(uint32_t vb) { return vb == 4 ? (1u << 23) : (1u << 25); }
 
 }  // namespace
 
@@ -244,7 +332,7 @@ struct gs_onesweep {
     gs_mode mode;
     uint32_t value_bytes;
     int shape;
-    int shape_auto;  // 1 = the library picks (mid sizes use MID_SHAPE); 0 after gs_onesweep_set_shape / gs_onesweep_options::shape_*
+    int shape_auto = 1;  // 1 = the library picks (mid sizes use MID_SHAPE); 0 after gs_onesweep_set_shape / gs_onesweep_options::shape_*
     int small_path; // 1 = single-tile kernel for n <= SMALL_TILE (default), 0 = always the tiled path
     int mid_path;    // 1 = two-launch MSD + bucket sort for single-tile limit < n <= 2^20 (default), 0 = the six-launch path
     int skip_passes; // 1 = identity passes (one digit value for all keys) are dropped in pairs (default)
@@ -252,31 +340,31 @@ struct gs_onesweep {
     int key64_sweeps;       // 64-bit keys: 1 = one GlobalHistogram + Scan for all eight passes (default), 2 = one per word (gs_onesweep_options::key64_sweeps; A/B, tests)
     uint32_t pos_min_keys;  // ... from this many keys up (default 2^25 + 1: where the big tile shape takes over; gs_onesweep_options::position_chains_min_log2)
     int rank_mode;  // 0 ballot multi-split, 1 returning LDS atomic (needs the lane-order probe to pass)
-    uint32_t* slab;
+    uint32_t* slab = nullptr;
     size_t slab_words;
-    uint32_t* partials;  // the histogram workgroups' tables: hist_blocks(max_keys) x HIST_TABLE_WORDS, summed by hist_reduce_kernel
+    uint32_t* partials = nullptr;  // the histogram workgroups' tables: hist_blocks(max_keys) x HIST_TABLE_WORDS, summed by hist_reduce_kernel
     size_t partials_words;
-    int profiling;
+    int profiling = 0;
     hipEvent_t ev[GS_PROFILE_SLOTS + 1];
-    bool ev_valid;
-    bool profile_pending;
-    void* trace_buf;   // experiment builds only (GS_EXP & 2): per-tile phase timestamps
-    const void* msd_keys;  // shard whose top-byte histogram + scan currently sit in the slab (msd_prepare)
-    uint32_t msd_n, msd_grid;
-    gs_key_type msd_kt;
-    uint32_t* pinned;  // 1024 + 8 words of pinned host memory for read-backs
+    bool ev_valid = false;
+    bool profile_pending = false;
+    void* trace_buf = nullptr;   // experiment builds only (GS_EXP & 2): per-tile phase timestamps
+    const void* msd_keys = nullptr;  // shard whose top-byte histogram + scan currently sit in the slab (msd_prepare)
+    uint32_t msd_n = 0, msd_grid = 0;
+    gs_key_type msd_kt = GS_KEY_UINT32;
+    uint32_t* pinned = nullptr;  // 1024 + 8 words of pinned host memory for read-backs
     // geometry of the last tiled call, for gs_debug_check_state (tile 0 = the last call left no scan state)
-    uint32_t last_n, last_tile, last_tile0, last_p0, last_np, last_dyn, last_desc_stride, last_pos_tile = 0;
-    bool hist_dirty;   // a call failed between the histogram launch and the kernel that hands HIST back zeroed
+    uint32_t last_n = 0, last_tile = 0, last_tile0 = 0, last_p0 = 0, last_np = 0, last_dyn = 0, last_desc_stride = 0, last_pos_tile = 0;
+    bool hist_dirty = false;   // a call failed between the histogram launch and the kernel that hands HIST back zeroed
     uint32_t hist_blocks_opt;  // gs_onesweep_options::hist_blocks (0 = the library picks)
     int first_pass_big;        // gs_onesweep_options::first_pass_big
-    uint32_t debug_flags;      // gs_onesweep_options::debug_flags
+    uint32_t debug_flags = 0;  // gs_onesweep_options::debug_flags
     int plan;              // gs_onesweep_options::plan / gs_onesweep_set_plan: 0 the library picks, 1 LSD passes only, 2 two-level plan wherever it can run
-    uint32_t hy_min_keys;  // plan 0: the two-level plan from this many keys up
-    uint32_t* hy_tab;      // the two-level plan's tables (gs::HYT_WORDS), nullptr: the handle cannot run it (pairs, 64-bit keys only ...)
+    uint32_t hy_min_keys = HY_MIN_KEYS_DEFAULT;  // plan 0: the two-level plan from this many keys up
+    uint32_t* hy_tab = nullptr;  // the two-level plan's tables (gs::HYT_WORDS), nullptr: the handle cannot run it (pairs, 64-bit keys only ...)
     uint32_t hy_grid;      // workgroups of its histogram kernel (a multiple of NCH)
-    int last_hy;           // the last sort was enqueued with the two-level plan's launches (whether it RAN on it is the device's decision: gs_onesweep_last_plan)
-    bool exp_keep_desc;  // experiment builds (GS_EXP & 1024): the histogram kernel leaves the descriptor rows alone
+    int last_hy = 0;       // the last sort was enqueued with the two-level plan's launches (whether it RAN on it is the device's decision: gs_onesweep_last_plan)
+    bool exp_keep_desc = false;  // experiment builds (GS_EXP & 1024): the histogram kernel leaves the descriptor rows alone
 };
 
 namespace {
@@ -290,22 +378,31 @@ size_t slab_words_for(uint32_t max_keys) {
     return SLAB_DESC + (rows4 > rows8 ? rows4 : rows8) * (size_t)gs::RADIX;
 }
 
-using HistLauncher = void (*)(hipStream_t, uint32_t, const uint32_t*, uint32_t*, size_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
-                              uint32_t*);
-template <int KT>
-void launch_hist(hipStream_t s, uint32_t blocks, const uint32_t* keys, uint32_t* slab, size_t used_words, uint32_t n,
-                 uint32_t seg_len0, uint32_t p0, uint32_t np, uint32_t word, uint32_t allow_pos, uint32_t* partials) {
-    hipLaunchKernelGGL((gs::global_histogram_kernel<KT>), dim3(blocks), dim3(gs::GHIST_THREADS), 0, s, keys, slab,
-                       used_words, n, seg_len0, p0, np, word, allow_pos, partials);
-    // the workgroups' tables -> the HIST region (one thread per bin)
-    hipLaunchKernelGGL(gs::hist_reduce_kernel, dim3(np * gs::NCH * gs::RADIX / 64u), dim3(256), 0, s, partials, blocks,
-                       np * gs::NCH * gs::RADIX, slab + SLAB_HIST);
+// HIST (four joint tables + what the keys look like as a whole) is zero between calls: hist_reduce_kernel OVERWRITES only the
+// tables it sums, the histogram kernel adds the HX words with atomics.  The first pass launched after the Scan hands it back zeroed
+// (BM_ZERO_HIST); a call that launches none does it here.  hist_dirty records a call that failed in between: prologue zeroes it then.
+gs_status hand_back_hist(gs_onesweep* h, hipStream_t s) {
+    GS_HIP(hipMemsetAsync(h->slab + SLAB_HIST, 0, gs::HIST_WORDS * sizeof(uint32_t), s));
+    h->hist_dirty = false;
+    return GS_OK;
 }
-inline hipError_t zero_hist(gs_onesweep* h, hipStream_t s) {  // the HIST region: four joint tables + what the keys look like as a whole
-    return hipMemsetAsync(h->slab + SLAB_HIST, 0, gs::HIST_WORDS * sizeof(uint32_t), s);
-}
-const HistLauncher g_hist[6] = {launch_hist<0>, launch_hist<1>, launch_hist<2>, launch_hist<3>, launch_hist<4>, launch_hist<5>};
 inline bool is_key64(gs_key_type kt) { return (int)kt >= 3; }
+
+// the tile shape of a binning pass of this handle: `shape` if it has a kernel for the key type, else MID_SHAPE — 64-bit keys
+// (8-byte stage slots) fit 8192-key tiles only
+int bin_shape(const gs_onesweep* h, gs_key_type kt, uint32_t vb, int shape) {
+    return (is_key64(kt) && !bin_launcher(shape, h->rank_mode, vb, kt)) ? MID_SHAPE : shape;
+}
+
+// compute units of the device (read once per process; 256 if it cannot be read)
+uint32_t cu_count() {
+    static const uint32_t cus = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        return (uint32_t)v;
+    }();
+    return cus;
+}
 
 uint32_t hist_blocks(uint32_t n, uint32_t forced = 0) {
     // one chunk per workgroup at mid sizes (measured: 4/8/16 chunks per workgroup — fewer closing global atomics,
@@ -315,11 +412,7 @@ uint32_t hist_blocks(uint32_t n, uint32_t forced = 0) {
     // of it at 2^28.  512 -> 256 workgroups: 30 -> 21 us at 2^21, 59 -> 51 us at 2^25, 179 -> 156 us at 2^27,
     // 300 -> 282 us at 2^28; counts that do not divide the CUs evenly (320, 384, 448) lose 10-35 %
     // (profiles/r02_hist_blocks_mid_sizes.txt).
-    static const uint32_t cus = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return (uint32_t)v;
-    }();
+    const uint32_t cus = cu_count();
     const uint32_t want = div_up(n, gs::HIST_CHUNK);
     const uint32_t cap = n <= (1u << 22) ? (cus + 1) / 2 : cus;
     if (forced > 0) return forced < want ? forced : want;  // gs_onesweep_options::hist_blocks (tuning aid)
@@ -327,18 +420,11 @@ uint32_t hist_blocks(uint32_t n, uint32_t forced = 0) {
 }
 
 // persistent workgroups of the position-chain pass: two per CU (76 KiB of LDS each)
-uint32_t pos_grid() {
-    static const uint32_t cus = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return (uint32_t)v;
-    }();
-    return 2u * cus;
-}
+uint32_t pos_grid() { return 2u * cu_count(); }
 
 // workgroups of the two-level plan's histogram kernel: one per CU, a multiple of NCH (position segments get equal numbers of them)
 uint32_t hy_grid_for_device() {
-    const uint32_t cus = pos_grid() / 2u;
+    const uint32_t cus = cu_count();
     return cus >= gs::NCH ? cus / gs::NCH * gs::NCH : gs::NCH;
 }
 
@@ -351,6 +437,19 @@ uint32_t hist_blocks_cap(uint32_t max_keys, uint32_t forced = 0) {
 }
 
 bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+// the value buffers of a pairs call: a pairs handle, both buffers, aligned
+gs_status check_vals(const gs_onesweep* h, const void* a, const void* b) {
+    if (h->mode != GS_MODE_PAIRS) return GS_ERR_MODE;
+    return (!a || !b || misaligned(a) || misaligned(b)) ? GS_ERR_ARG : GS_OK;
+}
+
+// one launch of a binning pass with pass p's scan state (descriptor region, counters, info block) and the shared words
+void launch_pass(const gs_onesweep* h, BinLauncher f, hipStream_t s, uint32_t grid, uint32_t p, uint32_t desc_stride, const void* keys_in,
+                 void* keys_out, const void* vals_in, void* vals_out, uint32_t n, uint32_t shift, uint32_t mode) {
+    f(s, grid, const_cast<uint32_t*>(static_cast<const uint32_t*>(keys_in)), static_cast<uint32_t*>(keys_out), const_cast<void*>(vals_in), vals_out,
+      h->slab + SLAB_DESC + (size_t)p * desc_stride, h->slab + SLAB_COUNTERS + p * gs::COUNTERS_PER_PASS * gs::COUNTER_STRIDE,
+      h->slab + SLAB_INFO + p * gs::INFO_STRIDE, h->slab + gs::SLAB_HSUB, h->slab + SLAB_STATUS, n, shift, mode);
+}
 
 // Clears the scan state and runs GlobalHistogram + Scan for passes p0 .. p0+np-1
 // (pass p0 over position segments, later passes over digit groups of the previous digit).
@@ -383,11 +482,11 @@ gs_status prologue(gs_onesweep* h, const void* d_keys, uint32_t n, gs_key_type k
     const uint32_t seg_unit = (tile0 % gs::HIST_CHUNK == 0u) ? tile0 : gs::HIST_CHUNK;
     const uint32_t seg_len0 = div_up(div_up(n, gs::NCH), seg_unit) * seg_unit;
     // no separate clear: the histogram kernel zeroes the scan state while it reads the keys (profile slot 0 stays 0)
-    // hist_reduce_kernel OVERWRITES the np tables it sums; the tables it does not touch and the HX words (HX_SKEW and the keys'
-    // OR / AND, which the histogram kernel sets with atomics) rely on the HIST region being zero between calls — the first pass
-    // launched after the Scan, or the read-back entry points, hand it back zeroed.  A call that failed in between left it
-    // dirty: zero it here, once.
-    if (h->hist_dirty) GS_HIP(zero_hist(h, s));
+    // HIST must be zero here (hand_back_hist): a call that failed in between left it dirty, zero it now, once
+    if (h->hist_dirty) {
+        const gs_status st = hand_back_hist(h, s);
+        if (st != GS_OK) return st;
+    }
     // (64-bit keys: passes 4..7 — or the second round's kernels — are charged to slot 6; the events of round 0 stay where they are)
     const bool rec = h->profiling && word == 0;
     if (rec) GS_HIP(hipEventRecord(h->ev[0], s));
@@ -399,12 +498,12 @@ gs_status prologue(gs_onesweep* h, const void* d_keys, uint32_t n, gs_key_type k
         const uint32_t wg_per_seg = seg_tiles < h->hy_grid / gs::NCH ? (seg_tiles ? seg_tiles : 1u) : h->hy_grid / gs::NCH;
         const uint32_t G = wg_per_seg * gs::NCH;
         const uint32_t per_wg = div_up(div_up(seg_len0, wg_per_seg), gs::HIST_CHUNK) * gs::HIST_CHUNK;
-        g_hy_hist[kt](s, G, static_cast<const uint32_t*>(d_keys), h->slab, used_words, n, seg_len0, per_wg, wg_per_seg, h->partials, g_hy_class[hy_class(n)].cap);
+        hy_hist_launcher(kt)(s, G, static_cast<const uint32_t*>(d_keys), h->slab, used_words, n, seg_len0, per_wg, wg_per_seg, h->partials, g_hy_class[hy_class(n)].cap());
         hipLaunchKernelGGL(gs::hy_reduce_kernel, dim3(gs::RADIX + gs::NCH), dim3(256), 0, s, h->partials, G, wg_per_seg, h->hy_tab, h->slab + SLAB_HIST);
         if (rec) GS_HIP(hipEventRecord(h->ev[2], s));
-        hipLaunchKernelGGL(gs::hy_scan_kernel, dim3(1), dim3(1024), 0, s, h->slab, h->hy_tab, n, seg_len0, desc_stride, g_hy_class[hy_class(n)].cap, tile, pregrouped ? 1u : 0u);
+        hipLaunchKernelGGL(gs::hy_scan_kernel, dim3(1), dim3(1024), 0, s, h->slab, h->hy_tab, n, seg_len0, desc_stride, g_hy_class[hy_class(n)].cap(), tile, pregrouped ? 1u : 0u);
     } else {
-    g_hist[kt](s, hist_blocks(n, h->hist_blocks_opt), static_cast<const uint32_t*>(d_keys), h->slab, used_words, n, seg_len0, p0, np, word,
+    hist_launcher(kt)(s, hist_blocks(n, h->hist_blocks_opt), static_cast<const uint32_t*>(d_keys), h->slab, used_words, n, seg_len0, p0, np, word,
                (scan_plan & 4u) ? (h->pos_chains == 2 ? 3u : 1u) : 0u, h->partials);
     }
 #if (GS_EXP & 2)
@@ -433,86 +532,6 @@ gs_status check_common(gs_onesweep* h, const void* a, const void* b, uint32_t n,
     return GS_OK;
 }
 
-// single-tile fast path: one launch, no scan state.  Three tile sizes: 8192 slots (every mode), 16384
-// (keys-only and 4-byte values), 32768 (keys-only) — what fits 160 KiB of LDS.
-using SmallLauncher = void (*)(hipStream_t, uint32_t*, void*, uint32_t, uint32_t, uint32_t*);
-template <int T, int K, int VB, int KT, int RANK>
-void launch_small(hipStream_t s, uint32_t* keys, void* vals, uint32_t n, uint32_t descending, uint32_t* status) {
-    hipLaunchKernelGGL((gs::small_sort_kernel<T, K, VB, KT, RANK>), dim3(1), dim3(T), 0, s, keys, vals, n, descending, status);
-}
-#define GS_SMALL_ROW(T, K, VB, R) {launch_small<T, K, VB, 0, R>, launch_small<T, K, VB, 1, R>, launch_small<T, K, VB, 2, R>, nullptr, nullptr, nullptr}
-#define GS_SMALL_ROW64(T, K, VB, R)                                                                                   \
-    {launch_small<T, K, VB, 0, R>, launch_small<T, K, VB, 1, R>, launch_small<T, K, VB, 2, R>, launch_small<T, K, VB, 3, R>, \
-     launch_small<T, K, VB, 4, R>, launch_small<T, K, VB, 5, R>}
-#define GS_SMALL_NONE {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}
-// [size class][rank mode][vb index][key type]; 64-bit keys: the classes up to 8192 slots.  The two smallest classes (256 x 4 and
-// 256 x 8 slots) exist because a sort of 2^10 keys in the 8192-slot shape pays for 8192 slots in every pass: 10.5 us against
-// 8.1 (profiles/r04_small_shapes.txt; the reference's size sweep starts there, GPUSortingD3D12/Tests.h:392-393,415-416)
-#ifndef GS_MINIMAL
-const SmallLauncher g_small[5][2][3][6] = {
-    {{GS_SMALL_ROW64(256, 4, 0, 0), GS_SMALL_ROW64(256, 4, 4, 0), GS_SMALL_ROW64(256, 4, 8, 0)},
-     {GS_SMALL_ROW64(256, 4, 0, 1), GS_SMALL_ROW64(256, 4, 4, 1), GS_SMALL_ROW64(256, 4, 8, 1)}},
-    {{GS_SMALL_ROW64(256, 8, 0, 0), GS_SMALL_ROW64(256, 8, 4, 0), GS_SMALL_ROW64(256, 8, 8, 0)},
-     {GS_SMALL_ROW64(256, 8, 0, 1), GS_SMALL_ROW64(256, 8, 4, 1), GS_SMALL_ROW64(256, 8, 8, 1)}},
-    {{GS_SMALL_ROW64(512, 16, 0, 0), GS_SMALL_ROW64(512, 16, 4, 0), GS_SMALL_ROW64(512, 16, 8, 0)},
-     {GS_SMALL_ROW64(512, 16, 0, 1), GS_SMALL_ROW64(512, 16, 4, 1), GS_SMALL_ROW64(512, 16, 8, 1)}},
-    {{GS_SMALL_ROW(1024, 16, 0, 0), GS_SMALL_ROW(1024, 16, 4, 0), GS_SMALL_NONE},
-     {GS_SMALL_ROW(1024, 16, 0, 1), GS_SMALL_ROW(1024, 16, 4, 1), GS_SMALL_NONE}},
-    {{GS_SMALL_ROW(1024, 32, 0, 0), GS_SMALL_NONE, GS_SMALL_NONE},
-     {GS_SMALL_ROW(1024, 32, 0, 1), GS_SMALL_NONE, GS_SMALL_NONE}},
-};
-#endif
-inline SmallLauncher small_launcher(uint32_t n, int rank_mode, uint32_t vb, gs_key_type kt) {
-#ifdef GS_MINIMAL
-    return nullptr;
-#else
-    const int cls = n <= 1024 ? 0 : n <= 2048 ? 1 : n <= 8192 ? 2 : n <= 16384 ? 3 : n <= 32768 ? 4 : 5;
-    return cls < 5 ? g_small[cls][rank_mode][vb_index(vb)][kt] : nullptr;  // nullptr: no single-tile kernel for this case
-#endif
-}
-
-// mid sizes: two launches (mid_kernels.hpp).  [class][rank mode][vb index][key type]; classes by the bucket K2 can hold:
-// 8192 keys (n <= 2^20, every value width; K1: <= 128 tiles of 8192), 16 384 (n <= 2^21, keys-only and 4-byte values; K1: <= 128
-// tiles of 16 384), 32 768 (n <= 2^22, keys-only; K1: <= 256 tiles of 16 384 — the 32 768-key tile spilled there and kept
-// half the CUs idle, 44 us of a 67 us sort, profiles/r03_mid_size_timeline.txt)
-using MidLauncher = void (*)(hipStream_t, uint32_t n_tiles, uint32_t* keys, uint32_t* alt, void* vals, void* valt, uint32_t* scratch,
-                             uint32_t* status, uint32_t n, uint32_t descending);
-template <int VB, int KT, int RANK, int T, int K, int T2 = T, int K2 = K>
-void launch_mid(hipStream_t s, uint32_t tiles, uint32_t* keys, uint32_t* alt, void* vals, void* valt, uint32_t* scratch, uint32_t* status,
-                uint32_t n, uint32_t descending) {
-    hipLaunchKernelGGL((gs::mid_msd_kernel<VB, KT, RANK, T, K, T2 * K2>), dim3(tiles), dim3(T), 0, s, keys, alt, vals, valt, scratch, status,
-                       n, descending);
-    hipLaunchKernelGGL((gs::bucket_sort_kernel<VB, KT, RANK, T2, K2>), dim3(gs::RADIX), dim3(T2), 0, s, keys, alt, vals, valt, scratch,
-                       status, n, descending);
-}
-#ifndef GS_MINIMAL
-#define GS_MID_ROW(VB, R, ...) {launch_mid<VB, 0, R, __VA_ARGS__>, launch_mid<VB, 1, R, __VA_ARGS__>, launch_mid<VB, 2, R, __VA_ARGS__>}
-#define GS_MID_NONE {nullptr, nullptr, nullptr}
-const MidLauncher g_mid[5][2][3][3] = {
-    {{GS_MID_ROW(0, 0, 512, 16), GS_MID_ROW(4, 0, 512, 16), GS_MID_ROW(8, 0, 512, 16)},
-     {GS_MID_ROW(0, 1, 512, 16), GS_MID_ROW(4, 1, 512, 16), GS_MID_ROW(8, 1, 512, 16)}},
-    {{GS_MID_ROW(0, 0, 512, 32), GS_MID_ROW(4, 0, 512, 32), GS_MID_NONE}, {GS_MID_ROW(0, 1, 512, 32), GS_MID_ROW(4, 1, 512, 32), GS_MID_NONE}},
-    {{GS_MID_ROW(0, 0, 512, 32, 1024, 32), GS_MID_NONE, GS_MID_NONE}, {GS_MID_ROW(0, 1, 512, 32, 1024, 32), GS_MID_NONE, GS_MID_NONE}},
-    {{GS_MID_ROW(0, 0, 1024, 32, 1024, 34), GS_MID_NONE, GS_MID_NONE}, {GS_MID_ROW(0, 1, 1024, 32, 1024, 34), GS_MID_NONE, GS_MID_NONE}},
-    {{GS_MID_NONE, GS_MID_ROW(4, 0, 512, 32, 512, 34), GS_MID_NONE}, {GS_MID_NONE, GS_MID_ROW(4, 1, 512, 32, 512, 34), GS_MID_NONE}},
-};
-#endif
-// round 5: class 3 — keys-only up to 2^23 (K1: 256 tiles of 32 768, one per CU; K2 holds 34 816 keys: 6 % above the mean bucket) — and class 4 —
-// 4-byte values up to 2^22 pairs (K1: 256 tiles of 16 384; K2 holds 17 408 pairs): 74.6 -> 102 GKeys/s at 2^23 keys, profiles/r05_mid_classes.txt
-constexpr uint32_t g_mid_tile[5] = {512 * 16, 512 * 32, 512 * 32, 1024 * 32, 512 * 32};  // K1's tile
-constexpr uint32_t g_mid_tiles[5] = {128, 128, 256, 256, 256};                 // ... and how many of them at most (<= MID_MAX_TILES; never more than fit the chip at once:
-                                                                           // 512 tiles of 16 384 keys for 2^23 keys left half of them to be adopted one by one — 1.7 ms)
-static_assert(g_mid_tiles[3] <= gs::MID_MAX_TILES && g_mid_tiles[4] <= gs::MID_MAX_TILES, "mid-size classes");
-// class of a mid-size sort, -1: the general pipeline
-inline int mid_class(uint32_t n, uint32_t vb) {
-    if (n <= g_mid_tiles[0] * g_mid_tile[0]) return 0;
-    if (n <= g_mid_tiles[1] * g_mid_tile[1] && vb != 8) return 1;
-    if (n <= g_mid_tiles[2] * g_mid_tile[2] && vb == 0) return 2;
-    if (n <= g_mid_tiles[3] * g_mid_tile[3] && vb == 0) return 3;
-    if (n <= g_mid_tiles[4] * g_mid_tile[4] && vb == 4) return 4;
-    return -1;
-}
-
 // Which way a sort of n elements goes — decided on the host from sizes, modes and options alone (what the KEYS look like is the
 // device's business: identity passes, skew, the two-level plan's validity).  sort_impl enqueues accordingly; gs_onesweep_sort_sharded
 // asks whether a bucket it is about to receive will be offered the two-level plan (`hy`) before it chooses the exchange's layout.
@@ -530,22 +549,19 @@ SortRoute sort_route(const gs_onesweep* h, uint32_t n, gs_key_type kt, uint32_t 
     // values, 2^23 keys-only: mid_class); the general pipeline above.  (The 16 384- and 32 768-slot single-tile kernels serve when the mid-size route is switched off:
     // with it, 2^15 keys take 18 us instead of 34, profiles/r02_size_and_entropy_sweep.txt.)
     r.mid_cls = (h->mid_path && h->shape_auto && n > gs::SMALL_TILE && !is_key64(kt)) ? mid_class(n, vb) : -1;
-#ifdef GS_MINIMAL
-    r.mid_cls = -1;
-#endif
+    if (r.mid_cls >= 0 && !mid_launcher(r.mid_cls, h->rank_mode, vb, kt)) r.mid_cls = -1;  // (not in this build)
     r.small = (h->small_path && r.mid_cls < 0) ? small_launcher(n, h->rank_mode, vb, kt) : nullptr;
-    // 64-bit keys: 8-byte stage slots fit 8192-key tiles only (the mid-size shape), at every size
+    // 64-bit keys: the mid-size shape at every size (bin_shape)
     // (a sort that may be planned on position chains — see `pos` below — runs on the default tile: the dual kernel's shapes)
     const bool pos_size = h->skip_passes && h->rank_mode == 1 && !is_key64(kt) && h->pos_chains != 0 && n >= h->pos_min_keys;
-    r.shape = (h->shape_auto && n <= mid_keys(vb) && !pos_size) ? MID_SHAPE : h->shape;
-    if (is_key64(kt) && !g_shapes[r.shape].fn[h->rank_mode][vb_index(vb)][kt]) r.shape = MID_SHAPE;
+    r.shape = bin_shape(h, kt, vb, (h->shape_auto && n <= mid_keys(vb) && !pos_size) ? MID_SHAPE : h->shape);
     const Shape& sh = g_shapes[r.shape];
     // Mid sizes, keys-only (2^22 < n <= 2^25: the 8192-key tile): the FIRST pass runs on the 16 384-key tile.  Its position segments are
     // whole tiles (prologue), so 2^24 keys are exactly 1024 tiles — two launch rounds on the 512 slots of that shape instead of three
     // rounds of 8192-key tiles on 768 — and its input is cold, which the larger tile streams better; the later passes' chains are
     // digit groups with a partial tile at each end, which overflow the round.  gs_onesweep_options::first_pass_big = 0 switches it off (A/B).
     r.shape0 = (h->first_pass_big && h->shape_auto && r.shape == MID_SHAPE && vb == 0 && !is_key64(kt) && n > (1u << 22) &&
-                g_shapes[0].fn[h->rank_mode][0][kt] != nullptr) ? 0 : r.shape;
+                bin_launcher(0, h->rank_mode, 0, kt) != nullptr) ? 0 : r.shape;
     // The scan kernel decides on the device which passes run and which buffer each one reads (identity passes
     // are dropped in pairs, see scan_kernel); every pass is handed (keys, alt) and the sort's order.
     r.dyn = h->skip_passes ? 2u : 0u;
@@ -554,14 +570,14 @@ SortRoute sort_route(const gs_onesweep* h, uint32_t n, gs_key_type kt, uint32_t 
     // plan says which one works.  Sorts of 32-bit keys on the big tile shape, LDS-atomic ranking; gs_onesweep_options::position_chains = 0
     // switches it off.
     r.pos = r.dyn && h->rank_mode == 1 && !is_key64(kt) && h->pos_chains != 0 && n >= h->pos_min_keys &&
-            (vb == 0 ? g_dual[0][kt] : g_posv[vb == 8][0][kt]) != nullptr &&
+            pos_launcher(vb, false, kt) != nullptr &&
             (vb == 4 ? sh.threads * sh.kpt == 16384 : (sh.threads == 512 && sh.kpt == 32));  // (the plan's last pass runs on 16 384-key tiles)
     // Two-level plan (hybrid_kernels.hpp): sorts of 32-bit keys — keys-only and pairs with 4- / 8-byte values — that may also run on
     // position chains (its fall-back when the keys turn out skewed) — the histogram sweep counts the 16-bit prefixes, and the device decides which plan runs.
     // (position_chains = 2 asks for the position-chain plan whatever the keys look like: only plan 2 overrides that)
-    r.hy = r.pos && !r.small && r.mid_cls < 0 && h->hy_tab != nullptr && g_hy_hist[kt] != nullptr && h->plan != 1 &&
+    r.hy = r.pos && !r.small && r.mid_cls < 0 && h->hy_tab != nullptr && hy_hist_launcher(kt) != nullptr && h->plan != 1 &&
            (h->plan == 2 || (n >= (vb ? HY_MIN_PAIRS_DEFAULT : h->hy_min_keys) && h->pos_chains != 2)) &&
-           (vb == 0 || (g_persist[vb == 8][kt] != nullptr && g_hy_local_pairs[vb == 8][hy_class(n)][kt] != nullptr)) &&
+           (vb == 0 || (persist_launcher(vb, kt) != nullptr && hy_pairs_launcher(vb, n, kt) != nullptr)) &&
            (size_t)gs::SLAB_DESC + 4 * (size_t)(div_up(n, pos_tile_for(vb) & 0x7fffffffu) + 2 * gs::CHMAX + 8) * gs::RADIX <= h->slab_words;  // (prologue's row formula)
     return r;
 }
@@ -576,8 +592,6 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
     // finds the plan void, hy_void_copy_kernel moves the input to the caller's buffers and the four LSD passes run as ever.
     const SortRoute route = sort_route(h, n, kt, vb);
     if (pregrouped && !route.hy) return GS_ERR_ARG;  // (the caller asks sort_route first)
-    const int mid_cls = route.mid_cls;
-    const bool use_mid = mid_cls >= 0;
     if (SmallLauncher small = route.small) {
         if (values_ready) GS_HIP(hipStreamWaitEvent(s, values_ready, 0));
         if (h->profiling) GS_HIP(hipEventRecord(h->ev[0], s));
@@ -591,14 +605,13 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
         // the single-tile kernel has no spin and cannot time out: it sets the status word to OK
         return GS_OK;
     }
-#ifndef GS_MINIMAL
-    if (use_mid) {
+    if (route.mid_cls >= 0) {
         // one MSD pass + one LDS sort per top-byte bucket (a skewed top byte: the LSD passes inside the first kernel)
         if (values_ready) GS_HIP(hipStreamWaitEvent(s, values_ready, 0));
         if (h->profiling) GS_HIP(hipEventRecord(h->ev[0], s));
-        g_mid[mid_cls][h->rank_mode][vb_index(vb)][kt](s, div_up(n, g_mid_tile[mid_cls]), static_cast<uint32_t*>(d_keys), static_cast<uint32_t*>(d_alt_keys),
-                                              d_vals, d_alt_vals, h->slab + gs::SLAB_MID, h->slab + SLAB_STATUS, n,
-                                              order == GS_ORDER_DESCENDING ? 1u : 0u);
+        mid_launcher(route.mid_cls, h->rank_mode, vb, kt)(s, div_up(n, g_mid_class[route.mid_cls].tile()), static_cast<uint32_t*>(d_keys),
+                                                          static_cast<uint32_t*>(d_alt_keys), d_vals, d_alt_vals, h->slab + gs::SLAB_MID,
+                                                          h->slab + SLAB_STATUS, n, order == GS_ORDER_DESCENDING ? 1u : 0u);
         h->last_tile = 0;
         h->last_hy = 0;
         if (h->profiling)  // everything is charged to slot 0 (and the total)
@@ -607,12 +620,11 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
         h->profile_pending = h->profiling != 0;
         return GS_OK;
     }
-#endif
     const int shape = route.shape, shape0 = route.shape0;
     const Shape& sh = g_shapes[shape];
-    BinLauncher fn = sh.fn[h->rank_mode][vb_index(vb)][kt];
+    BinLauncher fn = bin_launcher(shape, h->rank_mode, vb, kt);
     if (!fn) return GS_ERR_ARG;
-    BinLauncher fn0 = g_shapes[shape0].fn[h->rank_mode][vb_index(vb)][kt];
+    BinLauncher fn0 = bin_launcher(shape0, h->rank_mode, vb, kt);
     const uint32_t dyn = route.dyn;
     const bool pos = route.pos, hy = route.hy;
     uint32_t* k[2] = {static_cast<uint32_t*>(d_keys), static_cast<uint32_t*>(d_alt_keys)};
@@ -650,9 +662,7 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
         }
         // one launch of pass p: form `f` on `grid` workgroups, reading k[a] / v[a] and writing the other pair, with pass p's scan state
         auto launch = [&](BinLauncher f, uint32_t grid, uint32_t p, uint32_t a, uint32_t shift, uint32_t mode) {
-            f(s, grid, k[a], k[a ^ 1u], v[a], v[a ^ 1u], h->slab + SLAB_DESC + (size_t)p * plan.desc_stride,
-              h->slab + SLAB_COUNTERS + p * gs::COUNTERS_PER_PASS * gs::COUNTER_STRIDE, h->slab + SLAB_INFO + p * gs::INFO_STRIDE,
-              h->slab + gs::SLAB_HSUB, h->slab + SLAB_STATUS, n, shift, mode);
+            launch_pass(h, f, s, grid, p, plan.desc_stride, k[a], k[a ^ 1u], v[a], v[a ^ 1u], n, shift, mode);
         };
         const bool skip_local = (h->debug_flags & 0x40000000u) != 0u;  // (tuning builds, tools/hy_bringup.py: pass B's output stays as it is)
         for (uint32_t p = 0; p < NP; ++p) {
@@ -662,22 +672,22 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
                 // (1) keys-only sorts that may run on position chains: ONE launch per pass serves every plan (persistent workgroups, two per
                 // CU).  Offered the two-level plan, the first two launches are pass A / pass B or LSD passes 0 / 1 — digit and chain count come
                 // from the info block — the bucket-local sort follows them, and LSD passes 2 and 3 exit on PF_SKIP if it ran.
-                launch(g_dual[p == 3][kt], pos_grid(), p, a, p * 8,
+                launch(pos_launcher(vb, p == 3, kt), pos_grid(), p, a, p * 8,
                        mode | ((hy && p < 2) ? gs::BM_INFO_SHIFT | gs::BM_INFO_CHAINS : 0u) | ((hy && p == 1) ? gs::BM_ZERO_DESC23 : 0u));
                 if (hy && p == 1) {
                     if (h->profiling) GS_HIP(hipEventRecord(h->ev[5], s));  // slot 4 = pass B; slot 5: the local sort (+ LSD pass 2's launch); slot 6: LSD pass 3's
-                    if (!skip_local) g_hy_local[hy_class(n)][kt](s, gs::HY_BINS, k[0], h->hy_tab, h->slab, n, desc_bit);
+                    if (!skip_local) hy_local_launcher(n, kt)(s, gs::HY_BINS, k[0], h->hy_tab, h->slab, n, desc_bit);
                 }
             } else if (hy) {
                 // (2) pairs that are offered the two-level plan: launches 0 and 1 = its two DigitBinningPasses (the plain form as persistent
                 // workgroups: digit and chain count from the info block) or, on position chains, LSD passes 0 and 1 (the position-chain
                 // form, which also serves LSD passes 2 and 3); the bucket-local sort sits between them.  The non-persistent plain forms
                 // are not launched at all: whichever plan the device picks, one of these two forms is the one that works.
-                if (p < 2) launch(g_persist[vb == 8][kt], pos_grid() / 2u, p, a, p * 8, mode | gs::BM_FORMS | gs::BM_INFO_SHIFT | gs::BM_INFO_CHAINS);
-                launch(g_posv[vb == 8][p == 3][kt], pos_grid(), p, a, p * 8, (mode & ~gs::BM_ZERO_HIST) | gs::BM_FORMS | (p == 1 ? gs::BM_ZERO_DESC23 : 0u));
+                if (p < 2) launch(persist_launcher(vb, kt), pos_grid() / 2u, p, a, p * 8, mode | gs::BM_FORMS | gs::BM_INFO_SHIFT | gs::BM_INFO_CHAINS);
+                launch(pos_launcher(vb, p == 3, kt), pos_grid(), p, a, p * 8, (mode & ~gs::BM_ZERO_HIST) | gs::BM_FORMS | (p == 1 ? gs::BM_ZERO_DESC23 : 0u));
                 if (p == 1) {
                     if (h->profiling) GS_HIP(hipEventRecord(h->ev[5], s));
-                    if (!skip_local) g_hy_local_pairs[vb == 8][hy_class(n)][kt](s, k[0], v[0], h->hy_tab, h->slab, n, desc_bit);
+                    if (!skip_local) hy_pairs_launcher(vb, n, kt)(s, k[0], v[0], h->hy_tab, h->slab, n, desc_bit);
                 }
             } else {
                 // (3) everything else: the plain form, one tile per workgroup.  8-byte values on the big tile come in two forms and the
@@ -685,8 +695,8 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
                 const bool two_forms = dyn && vb == 8 && !is_key64(kt) && sh.threads == 512 && sh.kpt == 32;
                 launch(p == 0 ? fn0 : fn, p == 0 ? plan.grid0 : plan.grid, p, a, word * 32 + p * 8,
                        mode | (two_forms ? gs::BM_IF_EVEN : 0u) | ((pos && vb != 0) ? gs::BM_FORMS : 0u) | exp_mode);
-                if (two_forms) launch(g_vr2[h->rank_mode][kt], plan.grid, p, a, word * 32 + p * 8, mode | gs::BM_IF_SKEW | ((pos && vb == 8) ? gs::BM_FORMS : 0u));
-                if (pos && vb != 0) launch(g_posv[vb == 8][p == 3][kt], pos_grid(), p, a, p * 8, (mode & ~gs::BM_ZERO_HIST) | gs::BM_FORMS);
+                if (two_forms) launch(bin_launcher(shape, h->rank_mode, vb, kt, 2), plan.grid, p, a, word * 32 + p * 8, mode | gs::BM_IF_SKEW | ((pos && vb == 8) ? gs::BM_FORMS : 0u));
+                if (pos && vb != 0) launch(pos_launcher(vb, p == 3, kt), pos_grid(), p, a, p * 8, (mode & ~gs::BM_ZERO_HIST) | gs::BM_FORMS);
             }
             if (h->profiling && word == 0 && p < 4 && !(hy && p == 1)) GS_HIP(hipEventRecord(h->ev[4 + p], s));
         }
@@ -807,7 +817,6 @@ gs_status gs_onesweep_create_ex(gs_onesweep** out, uint32_t max_keys, gs_mode mo
     h->mode = mode;
     h->value_bytes = value_bytes;
     h->shape = (mode == GS_MODE_PAIRS && value_bytes == 4) ? 1 : 0;
-    h->shape_auto = 1;
     if (shape_pick >= 0) { h->shape = shape_pick; h->shape_auto = 0; }
     h->small_path = o.small_path ? 1 : 0;
     h->pos_chains = o.position_chains;
@@ -817,34 +826,18 @@ gs_status gs_onesweep_create_ex(gs_onesweep** out, uint32_t max_keys, gs_mode mo
     h->mid_path = o.mid_path ? 1 : 0;
     h->hist_blocks_opt = o.hist_blocks;
     h->first_pass_big = o.first_pass_big ? 1 : 0;
+    // debug bits belong to tuning / experiment builds; the product build keeps 0 (bit 30 — skip the bucket-local sort,
+    // tools/hy_bringup.py — would hand back keys ordered on their top 16 bits only)
 #if defined(GS_TUNING) || GS_EXP
     h->debug_flags = o.debug_flags;
-#else
-    h->debug_flags = 0;  // debug bits belong to tuning / experiment builds (bit 30 — skip the bucket-local sort, tools/hy_bringup.py — would hand back keys ordered on their top 16 bits only)
 #endif
-    h->profiling = 0;
-    h->ev_valid = false;
-    h->profile_pending = false;
-    h->slab = nullptr;
-    h->pinned = nullptr;
-    h->trace_buf = nullptr;
-    h->msd_keys = nullptr;
-    h->last_n = h->last_tile = h->last_tile0 = h->last_p0 = h->last_np = h->last_dyn = h->last_desc_stride = h->last_pos_tile = 0;
-    h->hist_dirty = false;
     h->plan = o.plan;
-    h->hy_min_keys = HY_MIN_KEYS_DEFAULT;
-    h->hy_tab = nullptr;
     h->hy_grid = hy_grid_for_device();
-    h->last_hy = 0;
-    h->exp_keep_desc = false;
-    h->msd_n = h->msd_grid = 0;
-    h->msd_kt = GS_KEY_UINT32;
     h->slab_words = slab_words_for(max_keys);
     // Tile ranking: the returning-LDS-atomic path needs same-address lanes of one
     // wave-instruction served in ascending lane order.  Probe the device once per
     // process; fall back to the ballot multi-split if a single lane disagrees.
     h->rank_mode = o.rank_mode >= 0 ? o.rank_mode : (lds_atomic_order_ok() ? 1 : 0);
-    h->partials = nullptr;
     hipError_t e = hipMalloc(&h->slab, h->slab_words * sizeof(uint32_t));
     // the two-level plan's tables (0.8 MiB) and its histogram slices (hy_grid x 129 KiB: 33 MiB on 256 CUs): only for handles the default
     // routing can send there — keys-only and pairs handles that hold a sort of the plan's size — or that ask for plan 2 (tests, tools:
@@ -1046,8 +1039,7 @@ gs_status gs_onesweep_sort_pairs(gs_onesweep* h, void* d_keys, void* d_vals, voi
                                  uint32_t n, gs_key_type kt, gs_order order, void* stream) {
     gs_status st = check_common(h, d_keys, d_alt_keys, n, kt, order);
     if (st != GS_OK) return st;
-    if (h->mode != GS_MODE_PAIRS) return GS_ERR_MODE;
-    if (!d_vals || !d_alt_vals || misaligned(d_vals) || misaligned(d_alt_vals)) return GS_ERR_ARG;
+    if ((st = check_vals(h, d_vals, d_alt_vals)) != GS_OK) return st;
     return sort_impl(h, d_keys, d_vals, d_alt_keys, d_alt_vals, n, kt, order, static_cast<hipStream_t>(stream),
                      h->value_bytes);
 }
@@ -1110,8 +1102,7 @@ gs_status gs_onesweep_global_histogram(gs_onesweep* h, const void* d_keys, uint3
     if (st != GS_OK) return st;
     const size_t words = 4 * (size_t)gs::NCH * gs::RADIX;
     GS_HIP(hipMemcpyAsync(h->pinned, h->slab + SLAB_HIST, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(zero_hist(h, s));  // no pass follows: hand HIST back zeroed
-    h->hist_dirty = false;
+    if ((st = hand_back_hist(h, s)) != GS_OK) return st;  // no pass follows
     GS_HIP(hipStreamSynchronize(s));
     for (uint32_t q = 0; q < 4; ++q)  // digit totals = joint histogram summed over chains
         for (uint32_t d = 0; d < gs::RADIX; ++d) {
@@ -1133,8 +1124,7 @@ gs_status gs_onesweep_scan(gs_onesweep* h, const void* d_keys, uint32_t n, gs_ke
     for (uint32_t q = 0; q < 4; ++q)
         GS_HIP(hipMemcpyAsync(h->pinned + q * gs::RADIX, h->slab + SLAB_DESC + (size_t)q * plan.desc_stride, gs::RADIX * sizeof(uint32_t),
                               hipMemcpyDeviceToHost, s));
-    GS_HIP(zero_hist(h, s));  // no pass follows: hand HIST back zeroed
-    h->hist_dirty = false;
+    if ((st = hand_back_hist(h, s)) != GS_OK) return st;  // no pass follows
     GS_HIP(hipStreamSynchronize(s));
     memcpy(h_rows, h->pinned, 4 * gs::RADIX * sizeof(uint32_t));
     return GS_OK;
@@ -1146,25 +1136,18 @@ gs_status gs_onesweep_digit_pass(gs_onesweep* h, const void* d_keys_in, void* d_
     gs_status st = check_common(h, d_keys_in, d_keys_out, n, kt, GS_ORDER_ASCENDING);
     if (st != GS_OK) return st;
     if (pass > (is_key64(kt) ? 7u : 3u)) return GS_ERR_ARG;
-    uint32_t vb = 0;
-    if (d_vals_in || d_vals_out) {
-        if (h->mode != GS_MODE_PAIRS) return GS_ERR_MODE;
-        if (!d_vals_in || !d_vals_out || misaligned(d_vals_in) || misaligned(d_vals_out)) return GS_ERR_ARG;
-        vb = h->value_bytes;
-    }
-    int shape = h->shape;
-    if (is_key64(kt) && !g_shapes[shape].fn[h->rank_mode][vb_index(vb)][kt]) shape = MID_SHAPE;
-    const Shape& sh = g_shapes[shape];
-    BinLauncher fn = sh.fn[h->rank_mode][vb_index(vb)][kt];
+    const bool pairs = d_vals_in || d_vals_out;
+    if (pairs && (st = check_vals(h, d_vals_in, d_vals_out)) != GS_OK) return st;
+    const uint32_t vb = pairs ? h->value_bytes : 0u;
+    const int shape = bin_shape(h, kt, vb, h->shape);
+    BinLauncher fn = bin_launcher(shape, h->rank_mode, vb, kt);
     if (!fn) return GS_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     PassPlan plan;
     st = prologue(h, d_keys_in, n, kt, s, pass & 3u, 1, &plan, 0, shape, pass >> 2);  // a stand-alone pass: position segments on ANY input
     if (st != GS_OK) return st;
-    fn(s, plan.grid, const_cast<uint32_t*>(static_cast<const uint32_t*>(d_keys_in)), static_cast<uint32_t*>(d_keys_out),
-       const_cast<void*>(d_vals_in), d_vals_out,
-       h->slab + SLAB_DESC, h->slab + SLAB_COUNTERS, h->slab + SLAB_INFO, h->slab + gs::SLAB_HSUB, h->slab + SLAB_STATUS, n, pass * 8,
-       (reverse_index ? gs::BM_REVERSE : 0u) | gs::BM_ZERO_HIST);
+    launch_pass(h, fn, s, plan.grid, 0, plan.desc_stride, d_keys_in, d_keys_out, d_vals_in, d_vals_out, n, pass * 8,
+                (reverse_index ? gs::BM_REVERSE : 0u) | gs::BM_ZERO_HIST);
     GS_HIP(hipGetLastError());
     h->hist_dirty = false;
     if (h->profiling)  // slot 3 = this pass, slots 4..6 = 0
@@ -1184,8 +1167,7 @@ gs_status gs_onesweep_msd_prepare(gs_onesweep* h, const void* d_keys, uint32_t n
     if (st != GS_OK) return st;
     const size_t words = (size_t)gs::NCH * gs::RADIX;
     GS_HIP(hipMemcpyAsync(h->pinned, h->slab + SLAB_HIST, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(zero_hist(h, s));  // msd_partition may never be called
-    h->hist_dirty = false;
+    if ((st = hand_back_hist(h, s)) != GS_OK) return st;  // msd_partition may never be called
     GS_HIP(hipStreamSynchronize(s));
     for (uint32_t d = 0; d < gs::RADIX; ++d) {
         uint32_t g = 0;
@@ -1204,18 +1186,12 @@ gs_status gs_onesweep_msd_partition(gs_onesweep* h, const void* d_keys_in, void*
     if (!h || h->msd_keys == nullptr || h->msd_keys != d_keys_in || h->msd_n != n) return GS_ERR_ARG;  // needs its prepare
     gs_status st = check_common(h, d_keys_in, d_keys_out, n, h->msd_kt, GS_ORDER_ASCENDING);
     if (st != GS_OK) return st;
-    uint32_t vb = 0;
-    if (d_vals_in || d_vals_out) {
-        if (h->mode != GS_MODE_PAIRS) return GS_ERR_MODE;
-        if (!d_vals_in || !d_vals_out || misaligned(d_vals_in) || misaligned(d_vals_out)) return GS_ERR_ARG;
-        vb = h->value_bytes;
-    }
-    BinLauncher fn = g_shapes[h->shape].fn[h->rank_mode][vb_index(vb)][h->msd_kt];
+    const bool pairs = d_vals_in || d_vals_out;
+    if (pairs && (st = check_vals(h, d_vals_in, d_vals_out)) != GS_OK) return st;
+    BinLauncher fn = bin_launcher(h->shape, h->rank_mode, pairs ? h->value_bytes : 0u, h->msd_kt);
     if (!fn) return GS_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    fn(s, h->msd_grid, const_cast<uint32_t*>(static_cast<const uint32_t*>(d_keys_in)), static_cast<uint32_t*>(d_keys_out),
-       const_cast<void*>(d_vals_in), d_vals_out,
-       h->slab + SLAB_DESC, h->slab + SLAB_COUNTERS, h->slab + SLAB_INFO, h->slab + gs::SLAB_HSUB, h->slab + SLAB_STATUS, n, 24, gs::BM_ZERO_HIST);
+    launch_pass(h, fn, s, h->msd_grid, 0, 0, d_keys_in, d_keys_out, d_vals_in, d_vals_out, n, 24, gs::BM_ZERO_HIST);
     GS_HIP(hipGetLastError());
     h->msd_keys = nullptr;  // the scan state is consumed
     h->profile_pending = false;
@@ -1326,8 +1302,7 @@ gs_status gs_onesweep_msd_fine_histogram(gs_onesweep* h, const void* d_keys, uin
     if (st != GS_OK) return st;
     const size_t words = 2 * (size_t)gs::NCH * gs::RADIX;
     GS_HIP(hipMemcpyAsync(h->pinned, h->slab + SLAB_HIST, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(zero_hist(h, s));  // no pass follows: hand HIST back zeroed
-    h->hist_dirty = false;
+    if ((st = hand_back_hist(h, s)) != GS_OK) return st;  // no pass follows
     if (h->profiling)  // slots 0..2 (clear, histogram, scan) are this call's; the pass slots read 0
         for (int e = 4; e <= 7; ++e) GS_HIP(hipEventRecord(h->ev[e], s));
     h->profile_pending = h->profiling != 0;

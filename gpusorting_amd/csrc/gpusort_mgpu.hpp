@@ -257,10 +257,7 @@ gs_status mgpu_plan(gs_mgpu* c, const void* d_keys, uint32_t n, gs_key_type kt, 
     if (st == GS_OK && n) st = fine ? prologue(h, d_keys, n, kt, s, 2, 2, pp) : prologue(h, d_keys, n, kt, s, 3, 1, pp);
     if (st == GS_OK && n) {
         hipLaunchKernelGGL(gs::msd_fold_kernel, dim3(nbins / 256), dim3(256), 0, s, h->slab + SLAB_HIST, nbins, c->d_hist);
-        if (fine) {  // no pass follows this prologue: hand HIST back zeroed
-            if (zero_hist(h, s) != hipSuccess) st = GS_ERR_HIP;
-            h->hist_dirty = false;
-        }
+        if (fine) st = hand_back_hist(h, s);  // no pass follows this prologue
     } else if (st == GS_OK) {
         if (hipMemsetAsync(c->d_hist, 0, 4096 * sizeof(uint32_t), s) != hipSuccess) st = GS_ERR_HIP;
     }
@@ -454,10 +451,7 @@ gs_status gs_onesweep_sort_sharded(gs_mgpu* c, const void* d_keys, const void* d
         if (!c->h_plan[gs::PLAN_PEER_FAILED] && c->h_plan[gs::PLAN_OVERFLOW]) {
             // every rank sees the same gathered table and takes the same decision: split at the 12-bit prefix
             fine = true;
-            if (n && early == GS_OK) {  // the top-byte scan state is abandoned: its histogram region must be handed back zeroed
-                if (zero_hist(h, s) != hipSuccess) early = GS_ERR_HIP;
-                h->hist_dirty = false;
-            }
+            if (n && early == GS_OK) early = hand_back_hist(h, s);  // the top-byte scan state is abandoned
             st = mgpu_plan(c, d_keys, n, kt, s, true, &pp, &early);
             if (st != GS_OK) { c->failed = 1; return st; }
             if (!c->h_plan[gs::PLAN_PEER_FAILED] && c->h_plan[gs::PLAN_OVERFLOW]) return GS_ERR_SIZE;  // on every rank alike: raise the capacity
@@ -465,7 +459,7 @@ gs_status gs_onesweep_sort_sharded(gs_mgpu* c, const void* d_keys, const void* d
         if (c->h_plan[gs::PLAN_PEER_FAILED]) {  // on every rank alike: nobody enters the exchange
             c->debug_fail = 0;
             c->failed = 1;
-            if (n && h->hist_dirty) { (void)zero_hist(h, s); h->hist_dirty = false; }
+            if (n && h->hist_dirty) (void)hand_back_hist(h, s);
             return early != GS_OK ? early : GS_ERR_COMM;
         }
         c->last_fine = fine ? 1u : 0u;
@@ -496,13 +490,11 @@ gs_status gs_onesweep_sort_sharded(gs_mgpu* c, const void* d_keys, const void* d
         void* const land_vals = pre ? c->part_vals : d_out_vals;
         // group the shard by destination (stable)
         if (n && local == GS_OK) {
-            const BinLauncher fn = g_shapes[h->shape].fn[h->rank_mode][vb_index(vb)][kt];
+            const BinLauncher fn = bin_launcher(h->shape, h->rank_mode, vb, kt);
             if (!fn) {
                 local = GS_ERR_ARG;
             } else if (!fine) {
-                fn(s, pp.grid, const_cast<uint32_t*>(static_cast<const uint32_t*>(d_keys)), split_keys, const_cast<void*>(d_vals),
-                   split_vals, h->slab + SLAB_DESC, h->slab + SLAB_COUNTERS, h->slab + SLAB_INFO, h->slab + gs::SLAB_HSUB,
-                   h->slab + SLAB_STATUS, n, 24, gs::BM_ZERO_HIST);
+                launch_pass(h, fn, s, pp.grid, 0, pp.desc_stride, d_keys, split_keys, d_vals, split_vals, n, 24, gs::BM_ZERO_HIST);
                 if (hipGetLastError() != hipSuccess) local = GS_ERR_HIP;
                 h->hist_dirty = false;
             } else {  // order by the top two bytes: every 12-bit prefix range is contiguous (the output buffers are the scratch)
