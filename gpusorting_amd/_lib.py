@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("GPUSORT_LIB") or os.path.join(_HERE, "lib", "libgpusort.so")  # env: ablation builds
+LIB_PATH = os.environ.get("GPUSORT_LIB") or os.path.join(_HERE, "lib", "libgpusort.so")  # env: other builds (tuning, trace, fault)
 
 GS_OK, GS_ERR_ARG, GS_ERR_SIZE, GS_ERR_HIP, GS_ERR_TIMEOUT, GS_ERR_MODE, GS_ERR_NO_DEVICE, GS_ERR_COMM = range(8)
 GS_MGPU_UNIQUE_ID_BYTES = 128
@@ -57,11 +57,10 @@ def onesweep_options_from_env(**overrides) -> "OneSweepOptions":
                         ("GPUSORT_SKIP_PASSES", "skip_passes"), ("GPUSORT_POS", "position_chains"),
                         ("GPUSORT_POS_MIN_LOG2", "position_chains_min_log2"), ("GPUSORT_KEY64_SWEEPS", "key64_sweeps"),
                         ("GPUSORT_PLAN", "plan"), ("GPUSORT_FIRST_PASS_BIG", "first_pass_big"), ("GPUSORT_HIST_BLOCKS", "hist_blocks"),
-                        ("GPUSORT_LS_EXP", "debug_flags"), ("GPUSORT_EXPMODE", "debug_flags")):
+                        ("GPUSORT_LS_EXP", "debug_flags")):
         if name in env:
             try:
-                v = int(env[name], 0)
-                setattr(o, field, (getattr(o, field) | v) if field == "debug_flags" else v)  # (two variables feed debug_flags: their bits add up)
+                setattr(o, field, int(env[name], 0))
             except ValueError:
                 pass
     _apply_overrides(o, overrides)

@@ -59,9 +59,9 @@ void launch_bin(hipStream_t s, uint32_t grid, uint32_t* ka, uint32_t* kb, void* 
 // tile of the counting position-chain passes, as the Scan kernel takes it (bit 31: the plan's last pass runs on it as well).
 // Keys-only: the full tile, counters packed 2 x 16 bit; pairs: 512 x 24 with 32-bit counters — and for 8-byte values in the last
 // pass too (its two staging rounds run 9 % faster on the smaller tile, profiles/r04_pos_packed_counters.txt)
-constexpr uint32_t POS_TILE = 512 * GS_POS_KPT;
+constexpr uint32_t POS_TILE = 512 * gs::POS_KPT;
 inline uint32_t pos_tile_for(uint32_t vb) {
-    return vb == 0 ? POS_TILE : (512u * GS_POSV_KPT) | ((vb == 8 && GS_POSV8_LAST_SMALL) ? 0x80000000u : 0u);
+    return vb == 0 ? POS_TILE : (512u * gs::POSV_KPT) | ((vb == 8 && gs::POSV8_LAST_SMALL) ? 0x80000000u : 0u);
 }
 template <int KT, bool LAST>
 void launch_dual(hipStream_t s, uint32_t grid, uint32_t* ka, uint32_t* kb, void* va, void* vb, uint32_t* desc, uint32_t* counters,
@@ -364,7 +364,6 @@ struct gs_onesweep {
     uint32_t* hy_tab = nullptr;  // the two-level plan's tables (gs::HYT_WORDS), nullptr: the handle cannot run it (pairs, 64-bit keys only ...)
     uint32_t hy_grid;      // workgroups of its histogram kernel (a multiple of NCH)
     int last_hy = 0;       // the last sort was enqueued with the two-level plan's launches (whether it RAN on it is the device's decision: gs_onesweep_last_plan)
-    bool exp_keep_desc = false;  // experiment builds (GS_EXP & 1024): the histogram kernel leaves the descriptor rows alone
 };
 
 namespace {
@@ -474,7 +473,7 @@ gs_status prologue(gs_onesweep* h, const void* d_keys, uint32_t n, gs_key_type k
     const uint32_t rows = ((scan_plan & 4u) && (pos_tile & 0x7fffffffu) < tile ? div_up(n, pos_tile & 0x7fffffffu) : tiles) + (hy ? 2 * gs::CHMAX + 8 : 2 * gs::MAXCH + 2);
     const uint32_t desc_stride = rows * gs::RADIX;
     // (hy: the descriptor regions of LSD passes 2 and 3 are zeroed by the launch of LSD pass 1 (BM_ZERO_DESC23) if — and only if — those passes run)
-    const size_t used_words = h->exp_keep_desc ? (size_t)SLAB_DESC : SLAB_DESC + (size_t)(hy ? 2u : np) * desc_stride;
+    const size_t used_words = SLAB_DESC + (size_t)(hy ? 2u : np) * desc_stride;
     if (SLAB_DESC + (size_t)np * desc_stride > h->slab_words) return GS_ERR_SIZE;  // (cannot happen with the tiles the library picks)
     // position segments of the first pass: equal, multiples of the histogram chunk — and of the first pass's tile where that is a
     // multiple of the chunk (every shape the library picks): its chains then consist of whole tiles, 16 partial tiles fewer (at
@@ -638,12 +637,6 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
                            SLAB_DESC + (size_t)gs::MAX_PASSES * (div_up(n, (uint32_t)sh.threads * sh.kpt) + 2 * gs::MAXCH + 2) * gs::RADIX <= h->slab_words;
     const uint32_t rounds = (is_key64(kt) && !one_sweep) ? 2u : 1u;
     const uint32_t NP = one_sweep ? gs::MAX_PASSES : 4u;
-#if (GS_EXP & (1024 | 2048))
-    const uint32_t exp_mode = h->debug_flags & (256u | 512u | 1024u | 2048u);
-    h->exp_keep_desc = (exp_mode & 256u) != 0u;
-#else
-    const uint32_t exp_mode = 0u;
-#endif
     for (uint32_t word = 0; word < rounds; ++word) {
         const uint32_t desc_bit = (order == GS_ORDER_DESCENDING && word + 1 == rounds) ? 1u : 0u;
         PassPlan plan;
@@ -694,7 +687,7 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
                 // pass's skew flag picks one (BinCfg::VROUNDS); pairs that may run on position chains add that form as a launch of its own.
                 const bool two_forms = dyn && vb == 8 && !is_key64(kt) && sh.threads == 512 && sh.kpt == 32;
                 launch(p == 0 ? fn0 : fn, p == 0 ? plan.grid0 : plan.grid, p, a, word * 32 + p * 8,
-                       mode | (two_forms ? gs::BM_IF_EVEN : 0u) | ((pos && vb != 0) ? gs::BM_FORMS : 0u) | exp_mode);
+                       mode | (two_forms ? gs::BM_IF_EVEN : 0u) | ((pos && vb != 0) ? gs::BM_FORMS : 0u));
                 if (two_forms) launch(bin_launcher(shape, h->rank_mode, vb, kt, 2), plan.grid, p, a, word * 32 + p * 8, mode | gs::BM_IF_SKEW | ((pos && vb == 8) ? gs::BM_FORMS : 0u));
                 if (pos && vb != 0) launch(pos_launcher(vb, p == 3, kt), pos_grid(), p, a, p * 8, (mode & ~gs::BM_ZERO_HIST) | gs::BM_FORMS);
             }
@@ -826,9 +819,9 @@ gs_status gs_onesweep_create_ex(gs_onesweep** out, uint32_t max_keys, gs_mode mo
     h->mid_path = o.mid_path ? 1 : 0;
     h->hist_blocks_opt = o.hist_blocks;
     h->first_pass_big = o.first_pass_big ? 1 : 0;
-    // debug bits belong to tuning / experiment builds; the product build keeps 0 (bit 30 — skip the bucket-local sort,
+    // debug bits belong to tuning builds; every other build keeps 0 (bit 30 — skip the bucket-local sort,
     // tools/hy_bringup.py — would hand back keys ordered on their top 16 bits only)
-#if defined(GS_TUNING) || GS_EXP
+#ifdef GS_TUNING
     h->debug_flags = o.debug_flags;
 #endif
     h->plan = o.plan;
@@ -1051,17 +1044,6 @@ gs_status gs_onesweep_check(gs_onesweep* h, void* stream) {
     GS_HIP(hipStreamSynchronize(s));
     return h->pinned[0] == gs::STATUS_OK ? GS_OK : GS_ERR_TIMEOUT;
 }
-
-#if (GS_EXP & 1024)
-gs_status gs_debug_read_status_words(gs_onesweep* h, uint32_t out[32], void* stream) {  // experiment builds only
-    if (!h || !out) return GS_ERR_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    GS_HIP(hipMemcpyAsync(h->pinned, h->slab + SLAB_STATUS, 32 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));
-    memcpy(out, h->pinned, 32 * sizeof(uint32_t));
-    return GS_OK;
-}
-#endif
 
 gs_status gs_debug_poke_status(gs_onesweep* h, uint32_t word, void* stream) {  // tests: forge the device status word
     if (!h) return GS_ERR_ARG;

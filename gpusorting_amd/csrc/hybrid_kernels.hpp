@@ -139,19 +139,17 @@ __global__ __launch_bounds__(HY_HIST_THREADS, HY_HIST_THREADS / 256) void hy_his
             since_fold = 0;
         }
         ++since_fold;
-#ifndef GS_HY_ABL_NO_REPLICA  // (ablation: what the digit-0 counts cost)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint32_t d = b[j] & 255u;
             atomicAdd(&s_r[(d >> 1) * 32u + (lane & 31u)], 1u << ((d & 1u) * 16u));
         }
-#endif
         if (joint_off) return;  // uniform
         if (probe) {
             const uint32_t p0 = b[0] >> 16;
             const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)p0);
             const uint32_t pc = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(p0 == f));
-            if (pc >= GS_HIST_SKEW_LANES) {
+            if (pc >= HIST_SKEW_LANES) {
                 skew = true;
                 if (pc >= 24 || sticky == 0xffffffffu) sticky = f;
             }
@@ -187,11 +185,8 @@ __global__ __launch_bounds__(HY_HIST_THREADS, HY_HIST_THREADS / 256) void hy_his
             if (pc < 8) skew = false;
         }
     };
-    // One work item = 4 consecutive chunks; all their 16-byte loads are issued before the first is consumed.
-#ifndef GS_HY_HIST_UNROLL
-#define GS_HY_HIST_UNROLL 4
-#endif
-    constexpr uint32_t UNROLL = GS_HY_HIST_UNROLL;
+    // One work item = HY_HIST_UNROLL consecutive chunks; all their 16-byte loads are issued before the first is consumed.
+    constexpr uint32_t UNROLL = HY_HIST_UNROLL;
     for (uint32_t c0 = begin; c0 < end; c0 += UNROLL * HIST_CHUNK) {
         if ((unsigned long long)c0 + UNROLL * HIST_CHUNK <= end) {
             uint4 t[UNROLL];

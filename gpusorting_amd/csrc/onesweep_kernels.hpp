@@ -13,12 +13,12 @@
 //   * MULTI-CHAIN chained scan.  256 CUs start ~40 tiles per microsecond while one
 //     dependent descriptor read costs ~1.7 us under streaming load; a single
 //     chain then makes every tile walk ~30 rows (the walk obeys W = lambda*L^2/2b).
-//     Each pass is therefore split into GS_NCHAINS independent chains.  Pass p>=1
+//     Each pass is therefore split into NCH independent chains.  Pass p>=1
 //     reads an array that is already partitioned by digit p-1, so chain x = a group
 //     of digit-(p-1) values and its digit-p counts are a JOINT histogram the
 //     upfront GlobalHistogram kernel counts in the same single read; the first
 //     pass uses position segments.  Chain bases are therefore known before the
-//     pass starts and the per-chain arrival rate drops by GS_NCHAINS.
+//     pass starts and the per-chain arrival rate drops by NCH.
 //   * ranking inside a tile: one returning LDS atomic per key on a wave-private
 //     counter (the LDS serves same-address lanes of one instruction in lane
 //     order — probed on the device before use), with the 64-lane ballot
@@ -55,41 +55,23 @@ constexpr uint32_t STATUS_TIMEOUT = 4;  // == GS_ERR_TIMEOUT
 #endif
 constexpr uint32_t SPIN_LIMIT = GS_SPIN_LIMIT;
 
-#ifndef GS_NCHAINS
-#define GS_NCHAINS 16  // independent chained scans per pass (power of two, <= 32)
-#endif
-constexpr uint32_t NCH = GS_NCHAINS;
-static_assert(NCH >= 1 && NCH <= 32 && (NCH & (NCH - 1)) == 0, "GS_NCHAINS must be a power of two <= 32");
-
-// Ablation / instrumented / fault-injection builds (-DGS_EXP=<flags>, tools/ and tests/test_gpu_fault.py) hook into
-// the kernels through the GS_ABL_* / GS_TRACE* macros below; their code lives in onesweep_ablation.hpp and is not
-// part of the product translation unit (GS_EXP == 0: every hook is empty or a compile-time false).
+// Trace and fault-injection builds (-DGS_EXP=<flags>, tools/trace_tiles.py and tests/test_gpu_fault.py) hook into the
+// kernels through the GS_TRACE* / GS_FAULT_* macros below; their code lives in onesweep_ablation.hpp and is not part of
+// the product translation unit (GS_EXP == 0: every hook is empty or a compile-time false).
 #ifndef GS_EXP
 #define GS_EXP 0
 #endif
+static_assert(((GS_EXP) & ~(2 | 8)) == 0, "GS_EXP: only bit 2 (per-tile trace) and bit 8 (fault injection) exist");
 #if GS_EXP
 #include "onesweep_ablation.hpp"
 #else
 #define GS_FAULT_TILE(chain, tile) false       // fault injection: this tile never publishes its descriptor
+#define GS_FAULT_MID_SILENT(block) false       // fault injection: this workgroup of K1 (mid_kernels.hpp) claims its tile and then never publishes anything
+#define GS_FAULT_MID_ABSENT(block) false       // fault injection: this workgroup of K1 behaves as if it had never been dispatched
 #define GS_TRACE_SETUP() do { } while (0)      // per-tile phase timestamps
 #define GS_TRACE(slot) do { } while (0)
 #define GS_TRACE_TRIP() do { } while (0)
 #define GS_TRACE_END(chain) do { } while (0)
-#define GS_ABL_HIST_STREAM_ONLY(t) do { } while (0)   // histogram kernel: stream the keys, count nothing
-#define GS_ABL_LOOKBACK_SKIPPED false          // no look-back wait
-#define GS_ABL_ASSUME_PREV() do { } while (0)  // no wait, positions extrapolated from this tile's own counts
-#define GS_ABL_GENERIC_SCATTER false           // force the generic (masked) scatter loops
-#define GS_ABL_OUT_INDEX(o, i) do { } while (0)  // rewrite an output index (sequential / wrapped)
-#define GS_ABL_REPLAY false                    // descriptors of an identical earlier run are still there: no REDUCTION publish
-#define GS_ABL_EARLY_ROW(v) do { } while (0)   // request the predecessor's row before the key loads
-#define GS_ABL_EARLY_USE(v) do { } while (0)   // ... and take it in the look-back if it is INCLUSIVE
-#define GS_ABL_CLOCKS_BEGIN() do { } while (0)  // histogram kernel: shader clock against the 100 MHz wall clock
-#define GS_ABL_CLOCKS_END() do { } while (0)
-#define GS_HIST_STAMP(i) do { } while (0)       // histogram kernel: phase time stamps of its first and last workgroup
-#define GS_HIST_STAMPS_DECL() do { } while (0)
-#define GS_HIST_STAMPS_OUT() do { } while (0)
-#define GS_ABL_COUNT_LDS 0                     // extra LDS of the next-digit counting experiment
-#define GS_ABL_COUNT_NEXT(kb, o) do { } while (0)
 #endif
 // (measured and dropped: issuing the first look-back read before the staging phase, -4 %: the early read mostly
 //  returns a not-yet-final row and the wait moves in front of staging)
@@ -104,15 +86,24 @@ static_assert(NCH >= 1 && NCH <= 32 && (NCH & (NCH - 1)) == 0, "GS_NCHAINS must 
 #endif
 constexpr uint32_t FALLBACK_SPINS = GS_FALLBACK_SPINS;
 
-#ifndef GS_FUSED_PAIRS
-#define GS_FUSED_PAIRS 1  // (key, u32 value) pairs staged and scattered together (BinCfg::FUSED)
-#endif
-#ifndef GS_WALK_ROWS
-#define GS_WALK_ROWS 1  // descriptor rows per round trip of the look-back walk.  Measured in round 2 (profiles/
-                        // r02_ab_early_lookback_rows.txt): 4 rows per trip +3 %; 4 / 8 / 16 rows requested BEFORE the
-                        // staging phase and consumed after it +3 / +5 / +6 % — an INCLUSIVE row is further back than that
-                        // when the request is issued, so the walk repeats the reads and the chip only moved more bytes
-#endif
+// ---- tunables: the values measured best (where a profile is named, it holds the measurement) ----
+constexpr uint32_t NCH = 16;  // independent chained scans per pass (power of two, <= 32)
+static_assert(NCH >= 1 && NCH <= 32 && (NCH & (NCH - 1)) == 0, "NCH must be a power of two <= 32");
+constexpr int GHIST_THREADS = 1024;                        // threads of a global_histogram_kernel workgroup
+constexpr int GHIST_WAVES_PER_SIMD = GHIST_THREADS / 256;  // one workgroup per CU
+constexpr uint32_t HIST_UNROLL = 4;     // chunks per work item of global_histogram_kernel ...
+constexpr uint32_t HY_HIST_UNROLL = 4;  // ... and of the two-level plan's histogram kernel (hybrid_kernels.hpp)
+constexpr uint32_t HIST_SKEW_LANES = 8;  // lanes sharing the first lane's bin that switch a byte's counting to wave-aggregated adds
+constexpr uint32_t SKEW_SHIFT = 4;  // a pass is ranked with wave-aggregated adds (PF_SKEW, mode digit) when some digit holds more than n >> SKEW_SHIFT keys.
+                                    // Rounds 1-2: 3.  Entropy preset 2 (two ANDs: digit 0 holds 10 %) fell between — plain LDS adds with a 10 % digit:
+                                    // 4 takes 3 % off its keys-only sort and 6 % off its (u32, u64) pairs, nothing changes elsewhere
+                                    // (profiles/r03_ab_skew_threshold.txt)
+constexpr int POS_KPT = 32;   // keys per thread of the counting position-chain passes (512 threads): the full tile, with packed counters
+constexpr int POSV_KPT = 24;  // the same for pairs (32-bit counters: packing them costs these passes more than the larger tile returns)
+constexpr bool POSV8_LAST_SMALL = true;  // (u32, u64) pairs: the last position-chain pass runs on the smaller tile as well
+constexpr uint32_t POS_SHARE = 3;  // a digit group holding more than POS_SHARE / 16 of a workgroup's first 16 384 keys (even: 1 / 16) sends the
+                                   // sort to the position-chain kernels
+
 // Chains of a pass: chain c < NCH = position segment of the pass's input (first pass of every sort; every pass of a sort
 // planned on position chains, PF_POS) or group of the previous digit's values (NCH consecutive values per chain).  Every
 // chain is one contiguous range of the pass's input.
@@ -135,7 +126,7 @@ constexpr uint32_t I_DSTRIDE = PASS_FLAGS + 5;     // words of one pass's descri
 constexpr uint32_t I_SHIFT = PASS_FLAGS + 4;       // bit position of this pass's digit (launches with mode bit 7 take it from here: the plan is the device's)
 constexpr uint32_t I_MODE = PASS_FLAGS + 6;        // PF_SKEW passes: the most frequent value of this pass's digit
 constexpr uint32_t INFO_STRIDE = ((PASS_FLAGS + 7 + 31) / 32) * 32;
-constexpr uint32_t PF_SKEW = 1;    // some digit holds > n/16 keys (GS_SKEW_SHIFT): rank with wave-aggregated adds
+constexpr uint32_t PF_SKEW = 1;    // some digit holds > n/16 keys (SKEW_SHIFT): rank with wave-aggregated adds
 constexpr uint32_t PF_SKIP = 2;     // every key has the same digit AND the pass is one of an even number of such
                                     // passes: the pass is the identity permutation, its workgroups exit at once
 constexpr uint32_t PF_SRC_ALT = 4;  // an odd number of earlier passes ran: this pass reads alt and writes keys
@@ -182,51 +173,8 @@ constexpr uint32_t SLAB_HY = SLAB_MID + SLAB_MID_WORDS;
 constexpr uint32_t SLAB_HY_WORDS = 32;
 constexpr uint32_t SLAB_DESC = SLAB_HY + SLAB_HY_WORDS;
 static_assert(SLAB_HIST % 4 == 0 && SLAB_HSUB % 4 == 0 && SLAB_MID % 4 == 0 && SLAB_HY % 4 == 0 && SLAB_DESC % 4 == 0, "regions are cleared with 16-byte stores");
-#ifndef GS_GHIST_THREADS
-#define GS_GHIST_THREADS 1024
-#endif
-#ifndef GS_HIST_SKEW_LANES
-#define GS_HIST_SKEW_LANES 8  // lanes sharing the first lane's bin that switch a byte's counting to wave-aggregated adds
-#endif
-#ifndef GS_HIST_PROBE
-#define GS_HIST_PROBE 1  // 0 (ablation): no skew probe, plain adds only
-#endif
-#ifndef GS_GHIST_WAVES_PER_SIMD
-#define GS_GHIST_WAVES_PER_SIMD (GS_GHIST_THREADS / 256)  // one workgroup per CU
-#endif
-#ifndef GS_HIST_UNROLL
-#define GS_HIST_UNROLL 4
-#endif
-#ifndef GS_HIST_NT
-#define GS_HIST_NT 1  // non-temporal key loads in the histogram kernel: 0.296 -> 0.250 ms at 2^28 (the pass that follows pays 0.008 ms
-                     // of it back: fewer of its first reads hit the memory-side cache), profiles/r03_ab_hist_nt_loads.txt.  Measured
-                     // with it and not kept: the next work item's loads in flight while this one is counted (no change: the kernel
-                     // does not wait for its loads)
-#endif
-#ifndef GS_SKEW_SHIFT
-#define GS_SKEW_SHIFT 4  // a pass is ranked with wave-aggregated adds (PF_SKEW, mode digit) when some digit holds more than n >> GS_SKEW_SHIFT keys.
-                         // Rounds 1-2: 3.  Entropy preset 2 (two ANDs: digit 0 holds 10 %) fell between — plain LDS adds with a 10 % digit:
-                         // 4 takes 3 % off its keys-only sort and 6 % off its (u32, u64) pairs, nothing changes elsewhere
-                         // (profiles/r03_ab_skew_threshold.txt)
-#endif
-#ifndef GS_POS_KPT
-#define GS_POS_KPT 32  // keys per thread of the counting position-chain passes (512 threads): the full tile, with packed counters
-#endif
-#ifndef GS_POSV_KPT
-#define GS_POSV_KPT 24  // the same for pairs (32-bit counters: packing them costs these passes more than the larger tile returns)
-#endif
-#ifndef GS_POSV8_LAST_SMALL
-#define GS_POSV8_LAST_SMALL 1  // (u32, u64) pairs: the last position-chain pass runs on the smaller tile as well
-#endif
-#ifndef GS_POS_SHARE
-#define GS_POS_SHARE 3u  // a digit group holding more than GS_POS_SHARE / 16 of a workgroup's first 16 384 keys (even: 1 / 16) sends the
-                         // sort to the position-chain kernels
-#endif
-#ifndef GS_HIST_REPLICAS
-#define GS_HIST_REPLICAS 1  // pass-0 digit counts on 32 lane-private, bank-conflict-free replicas (see global_histogram_kernel)
-#endif
 constexpr uint32_t HIST_FOLD_CHUNKS = 256;  // replicas are folded at least this often (16-bit counters, 128 keys per replica per chunk)
-constexpr uint32_t HIST_CHUNK = 4 * GS_GHIST_THREADS;  // keys per histogram work item (4 per thread); position segments are multiples of it
+constexpr uint32_t HIST_CHUNK = 4 * GHIST_THREADS;  // keys per histogram work item (4 per thread); position segments are multiples of it
 
 enum : int { KEY_U32 = 0, KEY_I32 = 1, KEY_F32 = 2, KEY_U64 = 3, KEY_I64 = 4, KEY_F64 = 5 };
 // 64-bit keys (8 passes; the reference has 32-bit keys only) are sorted by eight passes of the SAME
@@ -256,23 +204,17 @@ __device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// streaming accesses of the key/value arrays (every element is touched once per pass)
-#ifndef GS_NT
-#define GS_NT 1  // bit 0: non-temporal key loads in keys-only sorts (pass 0: -7 %; pairs: +10 %, so not there),
-                 // bit 1: non-temporal stores (-40 %: the scatter needs L2 write-combining) — measured, r01_sweep_v21
-#endif
+// streaming accesses of the key/value arrays (every element is touched once per pass): non-temporal key loads in keys-only
+// sorts (NT; pass 0: -7 %; pairs: +10 %, so not there), plain stores (non-temporal ones: -40 %, the scatter needs L2
+// write-combining) — measured, r01_sweep_v21
 template <bool NT, class T>
 __device__ __forceinline__ T ld_stream(const T* p) {
-    if constexpr (NT && (GS_NT & 1)) return __builtin_nontemporal_load(p);
+    if constexpr (NT) return __builtin_nontemporal_load(p);
     else return *p;
 }
 template <class T>
 __device__ __forceinline__ void st_stream(T* p, T v) {
-#if (GS_NT & 2)
-    __builtin_nontemporal_store(v, p);
-#else
     *p = v;
-#endif
 }
 
 // 64-bit keys: native (lo, hi) words -> radix-sortable words and back (the 32-bit rules of SortCommon.hlsl:134-154
@@ -357,9 +299,8 @@ __device__ __forceinline__ uint32_t wave_reduce_sum(uint32_t v) {
 //   q >= 1 : x = group of the PREVIOUS digit = its top log2(NCH) bits; stored [d][x], which makes the
 //            bin ONE bit-field of the key: the 8 + log2(NCH) contiguous bits ending at the top of byte p0+q.
 // 16-byte loads; one LDS histogram per workgroup (ds_add_u32); one global atomic
-// per non-empty bin per workgroup.  grid-stride over HIST_CHUNK-key chunks.
+// per non-empty bin per workgroup.  One contiguous range of HIST_CHUNK-key chunks per workgroup.
 // ---------------------------------------------------------------------------
-constexpr int GHIST_THREADS = GS_GHIST_THREADS;
 constexpr uint32_t LOG_NCH = NCH == 1 ? 0 : NCH == 2 ? 1 : NCH == 4 ? 2 : NCH == 8 ? 3 : NCH == 16 ? 4 : 5;
 
 // index of joint-histogram bin (pass q, digit d, chain x)
@@ -373,7 +314,7 @@ __host__ __device__ constexpr uint32_t hist_index(uint32_t q, uint32_t d, uint32
 // the sort reads its keys once for the histogram instead of once per word (8 x 4096 bins: 128 KiB of LDS).  A work item is
 // still HIST_CHUNK keys — two 16-byte loads per thread instead of one.
 template <int KT>
-__global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global_histogram_kernel(const uint32_t* __restrict__ keys,
+__global__ __launch_bounds__(GHIST_THREADS, GHIST_WAVES_PER_SIMD) void global_histogram_kernel(const uint32_t* __restrict__ keys,
                                                                          uint32_t* slab, size_t slab_used_words,
                                                                          uint32_t n, uint32_t seg_len0, uint32_t p0,
                                                                          uint32_t np, uint32_t word,
@@ -385,8 +326,7 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
     constexpr int KW = KeyWords<KT>::value;
     constexpr uint32_t NQ = KW == 2 ? MAX_PASSES : 4;  // tables a workgroup can count
     __shared__ __attribute__((aligned(16))) uint32_t s_h[NQ * NCH * RADIX];  // (read as uint4 for the slice store)
-    __shared__ uint32_t s_uneven;  // a digit group of this workgroup's first work item holds more than GS_POS_SHARE of its keys
-#if GS_HIST_REPLICAS
+    __shared__ uint32_t s_uneven;  // a digit group of this workgroup's first work item holds more than POS_SHARE / 16 of its keys
     // Pass-0 digit counts on 32 lane-private replicas, 16-bit counters packed two per dword: dword (d >> 1) * 32 +
     // (lane & 31) lies in bank lane & 31, so a wave's add never meets a bank conflict — whatever the keys are: the
     // 256-bin table of one position segment was the most expensive of the four (9.7 clk per wave-add against 7.5
@@ -395,12 +335,8 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
     // counter, 128 clk — costs nothing here.  Folded into s_h when the workgroup's segment changes, every
     // HIST_FOLD_CHUNKS chunks (a replica sees 128 keys per chunk: 16-bit counters hold 511 chunks), and at the end.
     __shared__ __attribute__((aligned(16))) uint32_t s_r[RADIX / 2 * 32];
-#endif
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     uint32_t* hist = slab + SLAB_HIST;
-    GS_ABL_CLOCKS_BEGIN();
-    GS_HIST_STAMPS_DECL();
-    GS_HIST_STAMP(0);
     // This kernel is also the sort's CLEAR (reference: ClearMemory, OneSweepDispatcher.cuh:301-309): it zeroes the
     // scan state nobody reads before it ends — ticket counters, status, info, slice counts, descriptors — as
     // 16-byte grid-stride stores next to its read stream; a separate memset was one more launch (5 us of a 50 us
@@ -418,7 +354,6 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
     for (uint32_t i = tid; i < bins; i += GHIST_THREADS) s_h[i] = 0;
     if (tid == 0) s_uneven = 0;
     bool joint_off = (allow_pos & 2u) != 0u;  // uniform: the joint tables are given up (see the probe behind the first work item; bit 1: from the start)
-#if GS_HIST_REPLICAS
     for (uint32_t i = tid; i < RADIX / 2 * 32; i += GHIST_THREADS) s_r[i] = 0;
     uint32_t cur_x0 = 0xffffffffu, since_fold = 0;  // uniform: segment the replicas are counting for, chunks since the last fold
     // Eight threads share the 32 replicas of a counter pair (one 16-byte read each, conflict-free), sum them with three
@@ -446,9 +381,7 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
         }
         __syncthreads();
     };
-#endif
     __syncthreads();
-    GS_HIST_STAMP(1);
 
     const uint32_t shift0 = p0 * 8u;
     const bool both = KW == 2 && np > 4u;  // uniform: all eight tables of a 64-bit key in this sweep (p0 = 0)
@@ -467,17 +400,15 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
     for (uint32_t q = 0; q < NQ; ++q) sticky[q] = 0xffffffffu;
     // One work item = HIST_UNROLL consecutive chunks; all their 16-byte loads are issued before the
     // first is consumed (one load per thread in flight left the kernel latency-bound at 3.1 TB/s).
-    constexpr uint32_t HIST_UNROLL = GS_HIST_UNROLL;
     // JOINT = 0: the joint tables are given up (joint_off) — only the first digit is counted
     // t: four keys' digit words, sortable form; th: their high words (both)
     auto process = [&](auto joint_tag, const uint4 t, const uint4 th, const uint32_t x0, const bool probe) {
             constexpr bool JOINT = decltype(joint_tag)::value != 0;
-            GS_ABL_HIST_STREAM_ONLY(t);
             const uint32_t b[4] = {t.x, t.y, t.z, t.w};
             k_or |= t.x | t.y | t.z | t.w;
             k_nand |= ~(t.x & t.y & t.z & t.w);
             const uint32_t bh[4] = {th.x, th.y, th.z, th.w};
-#if GS_HIST_REPLICAS
+            // the first digit goes to the replicas; the joint tables (q >= 1) below
             if (x0 != cur_x0 || since_fold >= HIST_FOLD_CHUNKS) {  // uniform
                 fold(cur_x0);
                 cur_x0 = x0;
@@ -489,21 +420,21 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
                 const uint32_t d = (b[j] >> shift0) & 255u;
                 atomicAdd(&s_r[(d >> 1) * 32u + (lane & 31u)], 1u << ((d & 1u) * 16u));
             }
-#endif
+            if constexpr (!JOINT) return;
             // Skew (Thearling-Smith presets, constant bytes): same-address LDS atomics serialise per lane.  Cheap probe on
             // the first key of a work item's first chunk: do >= 8 lanes share the first lane's bin?  (On every chunk the
             // probe cost the uniform case 10 % of the kernel, profiles/r02_ab_hist_variants.txt; skew does not come and go
             // chunk by chunk.)  The probe runs BEFORE the adds so that a wave that has seen no dominant bin does every add of
             // the chunk in one basic block: the address arithmetic of one table overlaps the LDS adds of the previous one
             // (with uniform branches between the tables they could not: profiles/r04_hist_kernel_variants.txt).
-            if (GS_HIST_PROBE && probe) {
+            if (probe) {
 #pragma unroll
-                for (uint32_t q = GS_HIST_REPLICAS ? 1 : 0; q < NQ; ++q)
-                    if (q < np && (JOINT || q == 0)) {
+                for (uint32_t q = 1; q < NQ; ++q)
+                    if (q < np) {
                         const uint32_t bin0 = bin_of(b[0], bh[0], q, x0);
                         const uint32_t b0 = __builtin_amdgcn_readfirstlane(bin0);
                         const uint32_t pc = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(bin0 == b0));
-                        if (pc >= GS_HIST_SKEW_LANES) {
+                        if (pc >= HIST_SKEW_LANES) {
                             skew_mode |= 1u << q;
                             if (pc >= 24 || sticky[q] == 0xffffffffu) sticky[q] = b0;  // (re)learn the dominant bin
                         }
@@ -511,16 +442,16 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
             }
             if (skew_mode == 0u) {  // uniform
 #pragma unroll
-                for (uint32_t q = GS_HIST_REPLICAS ? 1 : 0; q < NQ; ++q)
-                    if (q < np && (JOINT || q == 0)) {
+                for (uint32_t q = 1; q < NQ; ++q)
+                    if (q < np) {
 #pragma unroll
                         for (int j = 0; j < 4; ++j) atomicAdd(&s_h[bin_of(b[j], bh[j], q, x0)], 1u);
                     }
                 return;
             }
 #pragma unroll
-            for (uint32_t q = GS_HIST_REPLICAS ? 1 : 0; q < NQ; ++q) {
-                if (q < np && (JOINT || q == 0)) {
+            for (uint32_t q = 1; q < NQ; ++q) {
+                if (q < np) {
                     uint32_t bin[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) bin[j] = bin_of(b[j], bh[j], q, x0);
@@ -561,13 +492,12 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
         return word ? b.y : b.x;
     };
     typedef uint32_t hv4 __attribute__((ext_vector_type(4)));
+    // non-temporal key loads: 0.296 -> 0.250 ms at 2^28 (the pass that follows pays 0.008 ms of it back: fewer of its first reads
+    // hit the memory-side cache), profiles/r03_ab_hist_nt_loads.txt.  Measured with it and not kept: the next work item's loads in
+    // flight while this one is counted (no change: the kernel does not wait for its loads)
     auto ld16 = [](const uint4* q) -> uint4 {
-#if GS_HIST_NT
         const hv4 v = __builtin_nontemporal_load(reinterpret_cast<const hv4*>(q));
         return uint4{v.x, v.y, v.z, v.w};
-#else
-        return *q;
-#endif
     };
     struct Chunk { uint4 w, hi; };  // the digit words of a thread's four keys (and, 64-bit keys counted in one sweep, their high words)
     auto load_chunk = [&](uint32_t c) -> Chunk {
@@ -586,17 +516,13 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
         }
     };
     const uint32_t nchunks_all = (n + HIST_CHUNK - 1) / HIST_CHUNK;
-#if GS_HIST_REPLICAS
     // every workgroup takes ONE contiguous range of chunks: it stays inside a position segment (the replicas
     // count for one segment at a time) and streams 1/gridDim of the array
     const uint32_t per_wg = (nchunks_all + gridDim.x - 1) / gridDim.x;
-    const uint32_t c_first = blockIdx.x * per_wg, c_step = HIST_UNROLL;
+    const uint32_t c_first = blockIdx.x * per_wg;
     const uint32_t nchunks = c_first + per_wg < nchunks_all ? c_first + per_wg : nchunks_all;
-#else
-    const uint32_t c_first = blockIdx.x * HIST_UNROLL, c_step = gridDim.x * HIST_UNROLL, nchunks = nchunks_all;
-#endif
     uint32_t c0 = c_first;
-    for (; c0 < nchunks; c0 += c_step) {
+    for (; c0 < nchunks; c0 += HIST_UNROLL) {
         if (c0 + HIST_UNROLL <= nchunks && (unsigned long long)(c0 + HIST_UNROLL) * HIST_CHUNK <= n) {
             // common case: HIST_UNROLL full chunks — UNCONDITIONAL loads (conditional ones get an
             // s_waitcnt vmcnt(0) each from the compiler and end up one at a time in flight)
@@ -610,12 +536,11 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
 #pragma unroll
                 for (uint32_t u = 0; u < HIST_UNROLL; ++u) process(IntTag<0>{}, t[u].w, t[u].hi, (c0 + u) * HIST_CHUNK / seg_len0, u == 0);
             }
-            if (c0 == c_first) GS_HIST_STAMP(2);
             if (allow_pos && c0 == c_first && !joint_off) {
                 // Are the digit groups even?  The chains of passes 1..3 are the NCH groups of the previous digit's values:
                 // with skewed keys (Thearling-Smith presets 2..5: group 0 holds 32 .. 88 % of them) one chain gets most
                 // tiles and commits in order, and the joint tables themselves cost 2-3x (same-address LDS adds).  The
-                // first work item (16 384 keys) is the sample: a group above GS_POS_SHARE / 16 of it ends the joint
+                // first work item (16 384 keys) is the sample: a group above POS_SHARE / 16 of it ends the joint
                 // counting HERE and tells the Scan kernel to plan the sort on position chains (HX_SKEW); the tables
                 // of other workgroups that go on counting are simply not used.
                 __syncthreads();
@@ -624,11 +549,10 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
                     uint32_t c = 0;
                     for (uint32_t d = 0; d < RADIX; ++d) c += s_h[hist_index(q, d, x)];
                     // (a group holding EVERY key of the sample: a constant byte — its pass is dropped, not a crowded chain)
-                    if (q < np && c > (HIST_UNROLL * HIST_CHUNK / 16u) * GS_POS_SHARE && c != HIST_UNROLL * HIST_CHUNK) s_uneven = 1u;
+                    if (q < np && c > (HIST_UNROLL * HIST_CHUNK / 16u) * POS_SHARE && c != HIST_UNROLL * HIST_CHUNK) s_uneven = 1u;
                 }
                 __syncthreads();
                 joint_off = joint_off || s_uneven != 0u;
-                GS_HIST_STAMP(3);
             }
             continue;
         }
@@ -665,13 +589,7 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
             }
         }
     }
-    GS_HIST_STAMP(4);
-#if GS_HIST_REPLICAS
     fold(cur_x0);
-#else
-    __syncthreads();
-#endif
-    GS_HIST_STAMP(5);
     // The workgroup's tables go out as they are — coalesced plain stores into its own slice — and hist_reduce_kernel sums the
     // slices.  (One global atomic per non-empty bin cost 256 workgroups x ~14 000 device-scope atomics on the same 16 384 words:
     // 20-40 us of every sort from 2^23 keys up, half of this kernel at 2^23, profiles/r03_mid_size_routes.txt.)
@@ -702,9 +620,6 @@ __global__ __launch_bounds__(GHIST_THREADS, GS_GHIST_WAVES_PER_SIMD) void global
             atomicOr(&hist[HIST_TABLE_WORDS + HX_NAND], s_h[1]);
         }
     }
-    GS_HIST_STAMP(6);
-    GS_ABL_CLOCKS_END();
-    GS_HIST_STAMPS_OUT();
 }
 
 // Sum of the histogram workgroups' tables: hist[i] = sum over workgroups of partials[w][i].  A workgroup of 256 threads owns
@@ -818,7 +733,7 @@ __global__ __launch_bounds__(256) void scan_kernel(const uint32_t* hist, uint32_
         if (t) atomicOr(&s_triv, t);
     }
     const bool counted = !pos || q == 0;  // this pass's digit totals g and chain rows hq are complete
-    if (counted && g >= (n >> GS_SKEW_SHIFT) + 1u) atomicMax(&s_mode, ((unsigned long long)g << 8) | (255u - tid));  // (ties: the smaller digit)
+    if (counted && g >= (n >> SKEW_SHIFT) + 1u) atomicMax(&s_mode, ((unsigned long long)g << 8) | (255u - tid));  // (ties: the smaller digit)
     // digit scans of this pass's totals and (for the segment starts) of the previous digit's totals
     const uint32_t incl = wave_inclusive_scan(g, lane);
     const uint32_t incl_prev = wave_inclusive_scan(gprev, lane);
@@ -903,7 +818,7 @@ __global__ __launch_bounds__(256) void scan_kernel(const uint32_t* hist, uint32_
 
     // skew flag for the pass: some digit holds more than 1/16 of the keys -> tiles rank with
     // wave-aggregated adds (a dominant digit would serialise 64 lanes on one LDS counter)
-    const unsigned long long skewed = __builtin_amdgcn_ballot_w64(g >= (n >> GS_SKEW_SHIFT) + 1u);
+    const unsigned long long skewed = __builtin_amdgcn_ballot_w64(g >= (n >> SKEW_SHIFT) + 1u);
     if (lane == 0 && skewed) atomicOr(&my_info[PASS_FLAGS], PF_SKEW);
     // digit starts and chain bases
     uint32_t run = base + incl - g;  // dstart[tid]
@@ -935,7 +850,7 @@ struct BinCfg {
     // the same loop — no second staging round, no saved positions/digits, two barriers fewer per tile
     // (8-byte values the same way need a 512 x 24 tile, 12 288 pairs x 12 B = 144 KiB in two LDS arrays: measured
     //  5.975 vs 6.014 ms, not worth a shape of its own; the code path stays generic in VB)
-    static constexpr bool FUSED = GS_FUSED_PAIRS && VB == 4 && KW == 1 && POS == 0;  // (the position-chain forms keep their LDS for the count table)
+    static constexpr bool FUSED = VB == 4 && KW == 1 && POS == 0;  // (the position-chain forms keep their LDS for the count table)
     // VR = 2: 8-byte values of 4-byte keys go through the stage in TWO rounds of TILE / 2 values: the stage stays at the
     // 4 bytes per key the keys need, and a 16 384-pair tile leaves room for a second workgroup on the CU.  Measured
     // (profiles/r02_ab_value_rounds.txt, 2^28 (u32, u64) pairs): uniform keys +5 % per pass (two predicated staging
@@ -954,7 +869,7 @@ struct BinCfg {
     static constexpr bool PACKED = POS == 1 && STAGE_BYTES + WAVES * RADIX * 4 + 2 * RADIX * 4 + 64 + NCH * RADIX * 4 + RADIX * 4 + 128 > 80 * 1024;
     static constexpr int WHIST_BYTES = WAVES * RADIX * (PACKED ? 2 : 4);
     static constexpr int POS_BYTES = POS == 1 ? (NCH * RADIX * (PACKED ? 2 : 4) + RADIX * 4 + 128) : POS == 2 ? (RADIX * 4 + 32) : 0;
-    static constexpr int LDS_BYTES = STAGE_BYTES + WHIST_BYTES + 2 * RADIX * 4 + 64 + POS_BYTES + GS_ABL_COUNT_LDS;
+    static constexpr int LDS_BYTES = STAGE_BYTES + WHIST_BYTES + 2 * RADIX * 4 + 64 + POS_BYTES;
     // residency we ask the register allocator for: as many workgroups per CU as
     // LDS (160 KiB) and the 2048-thread limit admit, so that one workgroup's
     // look-back wait is covered by its neighbours' work
@@ -985,7 +900,6 @@ constexpr uint32_t BM_FORMS = 64;         // the pass is also launched in its po
 constexpr uint32_t BM_INFO_SHIFT = 128;   // the digit's bit position comes from the info block (I_SHIFT), not from shift_full
 constexpr uint32_t BM_INFO_CHAINS = 256;  // the chain count comes from the info block BEFORE the first ticket (I_NCH may be CHMAX: the two-level plan's second pass)
 constexpr uint32_t BM_ZERO_DESC23 = 512;  // LSD pass 1 of a sort that was offered the two-level plan: zeroes the descriptor regions of passes 2 and 3 if the LSD plan runs
-// (experiment builds, GS_EXP & 1024 / 2048, reuse bits 256 .. 2048 as run-time ablation switches of plain LSD launches: onesweep_ablation.hpp)
 
 // ---------------------------------------------------------------------------
 // binning_body, phase "load": the tile's keys, wave-striped (lane l of wave w holds keys tile_base + 64 KPT w + 64 i + l: coalesced
@@ -1381,12 +1295,7 @@ __device__ __forceinline__ void binning_body(
     // time ~NCH chains are live with 32 workgroups each, exactly the LSD passes' picture: every (chain, digit) write cursor is fed by
     // a whole row of neighbouring tiles (with all 256 chains live at once, two workgroups each, the pass wrote through 65 536 cursors
     // with two tiles behind each and ran at 0.66 ms instead of 0.47: DRAM pages served 512 bytes per activation, profiles/r05_*).
-#ifndef GS_HY_GROUP_CHAINS
-#define GS_HY_GROUP_CHAINS NCH  // chains of a CHMAX-chain pass that are live at a time (a power of two >= NCH)
-#endif
-    const uint32_t nch_info = (mode & BM_INFO_CHAINS) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)info[I_NCH]) : NCH;
-    const uint32_t gchains = nch_info > NCH ? (uint32_t)GS_HY_GROUP_CHAINS : NCH;  // uniform
-    const uint32_t ngroups = (mode & BM_INFO_CHAINS) ? nch_info / gchains : 1u;
+    const uint32_t ngroups = (mode & BM_INFO_CHAINS) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)info[I_NCH]) / NCH : 1u;  // uniform
     uint32_t group = 0;  // uniform; persistent workgroups keep it across their tiles
     static_assert(!POS || (KW == 1 && RANK == 1 && (VB == 0 || VB == 4 || (VB == 8 && VR == 2))),
                   "the position-chain forms exist for 32-bit keys, keys-only, with 4-byte values (staged behind the keys) or with 8-byte values (two staging rounds), LDS-atomic ranking");
@@ -1447,7 +1356,7 @@ __device__ __forceinline__ void binning_body(
                 uint32_t wbase = 0;
                 for (uint32_t w = 0; w < wave; ++w) wbase += s_misc[4 + w];
                 s_dstart[tid] = wbase + incl - G;
-                if (G >= (n >> GS_SKEW_SHIFT) + 1u) {
+                if (G >= (n >> SKEW_SHIFT) + 1u) {
                     s_pos[0] = 1u;
                     atomicMax(reinterpret_cast<unsigned long long*>(s_pos + 2), ((unsigned long long)G << 8) | (255u - tid));
                 }
@@ -1496,7 +1405,7 @@ __device__ __forceinline__ void binning_body(
     // chain blockIdx % NCH (each counter has its own cache line).  Ticket order inside
     // a chain is the start order, so every predecessor of a claimed tile is running.
     // Only when that chain is already fully claimed does thread 0 try the others. ----
-    uint32_t chain = (blockIdx.x & (gchains - 1u)) + group * gchains;
+    uint32_t chain = (blockIdx.x & (NCH - 1u)) + group * NCH;
     // geometry of the fast-path chain: requested before the ticket is (scalar loads that depend on blockIdx only), so
     // their round trip runs beside the ticket atomic's instead of after the barrier
     const uint32_t seg_start_f = info[I_START + chain], seg_end_f = info[I_END + chain], row_f = info[I_ROW + chain];
@@ -1517,11 +1426,7 @@ __device__ __forceinline__ void binning_body(
     if (uni(s_misc[3]) != STATUS_OK) break;
     const uint32_t pflags = uni(s_misc[9]) | (pos_skew ? PF_SKEW : 0u);
     if ((mode & BM_PLANNED) && (pflags & PF_SKIP)) break;  // identity pass of a full sort
-#ifdef GS_STATIC_IO  // A/B aid: the pass always reads a and writes b (run with skip_passes = 0)
-    const bool swapped = false;
-#else
     const bool swapped = (mode & BM_PLANNED) && (pflags & PF_SRC_ALT);
-#endif
     const uint32_t* keys_in = swapped ? keys_b : keys_a;
     uint32_t* keys_out = swapped ? keys_a : keys_b;
     const void* vals_in_ = swapped ? vals_b : vals_a;
@@ -1567,8 +1472,6 @@ __device__ __forceinline__ void binning_body(
         }
     }
     GS_TRACE(1);
-    uint32_t early_row = 0;
-    GS_ABL_EARLY_ROW(early_row);
 
     // ---- load (wave-striped, coalesced 256 B per wave-instruction; 64-bit keys: 512 B) ----
     uint32_t key[KPT];
@@ -1622,7 +1525,7 @@ __device__ __forceinline__ void binning_body(
         // same numbers a fallback recount of this tile produces
         dummies = (tid == 0 ? head : 0u) + ((tid == RADIX - 1 && !full && !tail_unranked) ? TILE - head - count : 0u);
         tile_total = run - dummies;
-        if (!GS_FAULT_TILE(chain, tile) && !GS_ABL_REPLAY)
+        if (!GS_FAULT_TILE(chain, tile))
             st_agent(&cdesc[(size_t)(tile + 1u) * RADIX + tid], (tile_total << 2) | FLAG_REDUCTION);
         scan_incl = wave_inclusive_scan_dpp(run);
         if (lane == 63) s_misc[4 + wave] = scan_incl;
@@ -1697,9 +1600,9 @@ __device__ __forceinline__ void binning_body(
     // (profiles/r02_ab_early_lookback_rows.txt, r02_ab_scalar_lookback.txt).
     uint32_t prev = 0, spins = 0;
     int32_t k = (int32_t)tile;
-    bool done = GS_ABL_LOOKBACK_SKIPPED, poisoned = false, finished = tid >= RADIX;
-    auto walk = [&](auto nb_tag) {
-        constexpr int NB = decltype(nb_tag)::value;
+    bool done = false, poisoned = false, finished = tid >= RADIX;
+    auto walk = [&]() {
+        constexpr int NB = 1;  // rows per round trip (above); kept as a row loop: the straight-line form compiles differently
         while (!done) {
             GS_TRACE_TRIP();
             uint32_t v[NB];
@@ -1734,13 +1637,11 @@ __device__ __forceinline__ void binning_body(
         }
     };
     GS_TRACE(4);
-    GS_ABL_ASSUME_PREV();
-    GS_ABL_EARLY_USE(early_row);
     for (;;) {
         if (!finished) {
             // (measured in round 3 and not kept: four rows per trip in short sorts — 2^20 .. 2^25 keys, where the tiles of a chain
             //  run in step and the walks are ~5 trips: no change, the wait is for the predecessor, profiles/r03_mid_size_timeline.txt)
-            walk(IntTag<GS_WALK_ROWS>{});
+            walk();
             if (done) {
                 finished = true;
                 if (poisoned) {
@@ -1831,18 +1732,6 @@ __device__ __forceinline__ void binning_body(
         const uint32_t dn = (kb >> (next_shift & 31u)) & 255u;
         if constexpr (PK) { if (valid && dn != cnt_guess) atomicAdd(&s_cnt[((o >> seglog) << 7) + (dn >> 1)], 1u << ((dn & 1u) * 16u)); }
         else { if (valid && dn != cnt_guess) atomicAdd(&s_cnt[((o >> seglog) << 8) + dn], 1u); }
-#ifdef GS_ABL_CNT  // ablation (timing only, results stay exact): bit 0: the address arithmetic once more; bit 1: the LDS add once more (adds 0)
-        if (GS_ABL_CNT & 1) {
-            uint32_t kb2 = kb, o2 = o;
-            asm volatile("" : "+v"(kb2), "+v"(o2));
-            const uint32_t dn2 = (kb2 >> (next_shift & 31u)) & 255u;
-            uint32_t idx2 = ((o2 >> seglog) << 7) + (dn2 >> 1), inc2 = 1u << ((dn2 & 1u) * 16u);
-            if (valid && dn2 != cnt_guess) asm volatile("" :: "v"(idx2), "v"(inc2));
-        }
-        if (GS_ABL_CNT & 2) {
-            if constexpr (PK) { if (valid && dn != cnt_guess) atomicAdd(&s_cnt[((o >> seglog) << 7) + (dn >> 1)], 0u); }
-        }
-#endif
     };
     const bool counting = POS == 1 && next_shift != 0xffffffffu;  // uniform
     if constexpr (POS == 1) {
@@ -1876,7 +1765,7 @@ __device__ __forceinline__ void binning_body(
                 v = reinterpret_cast<const V*>(s_raw + TILE * 4)[slot];
             }
         };
-        if (GS_LIKELY(full) && !GS_ABL_GENERIC_SCATTER) {
+        if (GS_LIKELY(full)) {
             uint32_t kk[KPT];
             V vv[KPT];
 #pragma unroll
@@ -1896,14 +1785,13 @@ __device__ __forceinline__ void binning_body(
                 load_pair(i, k, v);
                 uint32_t o = s_gbase[(k >> shift) & 255u] + i;
                 if (reverse) o = n - 1u - o;
-                GS_ABL_OUT_INDEX(o, i);
                 if (full || (i >= head && i < head + count)) {
                     st_stream(keys_out + o, from_bits<KT>(k));
                     st_stream(vals_out + o, v);
                 }
             }
         }
-    } else if (GS_LIKELY(full) && !GS_ABL_GENERIC_SCATTER) {
+    } else if (GS_LIKELY(full)) {
         // the common case as straight-line code: all stage reads first, then the base look-ups, then the stores
         // (with the masks and the reversal in the loop every key got its own branches and LDS round trips).
         // Measured in round 3 and not kept: a RUN-aligned scatter — every wave walks the runs of its 32 digits, one store
@@ -1931,7 +1819,6 @@ __device__ __forceinline__ void binning_body(
                 const uint32_t d = (kb[j] >> shift) & 255u;
                 const uint32_t opos = s_gbase[d] + tid + j * THREADS;
                 st_stream(keys_out + ((opos ^ rev_xor) + rev_add), from_bits<KT>(kb[j]));
-                GS_ABL_COUNT_NEXT(kb[j], opos);
                 if constexpr (POS == 1) { if (counting) count_next(kb[j], opos, true); }
                 if constexpr (VB != 0) digs[j >> 2] |= d << (8 * (j & 3));
             }
@@ -1947,7 +1834,6 @@ __device__ __forceinline__ void binning_body(
             uint32_t o = s_gbase[d] + i;
             if constexpr (POS == 1) { if (counting) count_next(kb, o, full || (i >= head && i < head + count)); }
             if (reverse) o = n - 1u - o;
-            GS_ABL_OUT_INDEX(o, i);
             if (full || (i >= head && i < head + count)) {
                 if constexpr (KW == 2)
                     st_stream(reinterpret_cast<uint2*>(keys_out) + o, from_bits2<KT>(hi_word ? uint2{kb2.y, kb2.x} : kb2));
@@ -1982,7 +1868,7 @@ __device__ __forceinline__ void binning_body(
             }
             __syncthreads();
             constexpr int J0 = 0, JN = KPT / VRN;  // this round's stage slots: tid + (h * JN + j) * THREADS
-            if (GS_LIKELY(full) && !GS_ABL_GENERIC_SCATTER) {
+            if (GS_LIKELY(full)) {
                 // (batches of 8 stage reads: with two rounds the other round's values are still in registers)
                 constexpr int VBATCH = VRN == 2 ? (JN % 8 == 0 ? 8 : 4) : JN;
                 static_assert(JN % VBATCH == 0, "value batches must tile a staging round");
@@ -2004,7 +1890,6 @@ __device__ __forceinline__ void binning_body(
                     const uint32_t i = tid + jj * THREADS;
                     uint32_t o = s_gbase[(digs[jj >> 2] >> (8 * (jj & 3))) & 255u] + i;
                     if (reverse) o = n - 1u - o;
-                    GS_ABL_OUT_INDEX(o, i);
                     if (full || (i >= head && i < head + count)) st_stream(vals_out + o, s_vstage[tid + j * THREADS]);
                 }
             }
@@ -2097,7 +1982,7 @@ __global__ __launch_bounds__(512, 4) void digit_binning_dual_kernel(
     uint32_t* keys_a, uint32_t* keys_b, void* vals_a, void* vals_b, uint32_t* desc, uint32_t* counters, const uint32_t* info,
     uint32_t* hsub, uint32_t* status, uint32_t n, uint32_t shift_full, uint32_t mode) {
     constexpr int LDS_PLAIN = BinCfg<512, 32, 0, 1, 1, 0>::LDS_BYTES;
-    constexpr int LDS_POS = LAST ? BinCfg<512, 32, 0, 1, 1, 2>::LDS_BYTES : BinCfg<512, GS_POS_KPT, 0, 1, 1, 1>::LDS_BYTES;
+    constexpr int LDS_POS = LAST ? BinCfg<512, 32, 0, 1, 1, 2>::LDS_BYTES : BinCfg<512, POS_KPT, 0, 1, 1, 1>::LDS_BYTES;
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[LDS_PLAIN > LDS_POS ? LDS_PLAIN : LDS_POS];
     static_assert(sizeof(s_raw) * 2 <= 160 * 1024, "two workgroups per CU");
     if ((__builtin_amdgcn_readfirstlane((int)info[PASS_FLAGS]) & (int)PF_POS) == 0) {
@@ -2105,7 +1990,7 @@ __global__ __launch_bounds__(512, 4) void digit_binning_dual_kernel(
     } else if constexpr (LAST) {
         binning_body<512, 32, 0, KT, 1, 1, 2, true>(s_raw, keys_a, keys_b, vals_a, vals_b, desc, counters, info, hsub, status, n, shift_full, mode);
     } else {
-        binning_body<512, GS_POS_KPT, 0, KT, 1, 1, 1, true>(s_raw, keys_a, keys_b, vals_a, vals_b, desc, counters, info, hsub, status, n, shift_full, mode);
+        binning_body<512, POS_KPT, 0, KT, 1, 1, 1, true>(s_raw, keys_a, keys_b, vals_a, vals_b, desc, counters, info, hsub, status, n, shift_full, mode);
     }
 }
 
@@ -2118,7 +2003,7 @@ template <int VB, int KT, bool LAST>
 __global__ __launch_bounds__(512, 4) void digit_binning_posv_kernel(
     uint32_t* keys_a, uint32_t* keys_b, void* vals_a, void* vals_b, uint32_t* desc, uint32_t* counters, const uint32_t* info,
     uint32_t* hsub, uint32_t* status, uint32_t n, uint32_t shift_full, uint32_t mode) {
-    constexpr int KPT = (LAST && !(VB == 8 && GS_POSV8_LAST_SMALL)) ? 32 : GS_POSV_KPT, POS = LAST ? 2 : 1, VR = VB == 8 ? 2 : 1;
+    constexpr int KPT = (LAST && !(VB == 8 && POSV8_LAST_SMALL)) ? 32 : POSV_KPT, POS = LAST ? 2 : 1, VR = VB == 8 ? 2 : 1;
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[BinCfg<512, KPT, VB, 1, VR, POS>::LDS_BYTES];
     static_assert(sizeof(s_raw) * 2 <= 160 * 1024, "two workgroups per CU");
     binning_body<512, KPT, VB, KT, 1, VR, POS, true>(s_raw, keys_a, keys_b, vals_a, vals_b, desc, counters, info, hsub, status, n, shift_full, mode);

@@ -101,8 +101,8 @@ typedef struct gs_onesweep_options {
                                         keys turn out near-uniform, the four LSD passes otherwise; 1 LSD passes only; 2 two-level plan wherever it can run */
     int32_t first_pass_big;          /* 1 (default): keys-only mid sizes run their first pass on the 16 384-key tile */
     uint32_t hist_blocks;            /* workgroups of the GlobalHistogram kernel; 0 (default) = one per CU (tuning aid) */
-    uint32_t debug_flags;            /* 0.  The product build ignores every bit.  Tuning / experiment builds (-DGS_TUNING, -DGS_EXP): bit 30 = the two-level
-                                        plan stops behind its second pass (tools/hy_bringup.py; the result is NOT sorted), GS_EXP builds: bits 8-11 ablation modes */
+    uint32_t debug_flags;            /* 0.  Every build but the tuning build (-DGS_TUNING) ignores every bit.  There, bit 30 = the two-level
+                                        plan stops behind its second pass (tools/hy_bringup.py; the result is NOT sorted) */
 } gs_onesweep_options;
 void gs_onesweep_options_default(gs_onesweep_options* o);
 /* gs_onesweep_create with explicit options (NULL = defaults).  GS_ERR_ARG for a struct_size this library does not know, a tile

@@ -13,7 +13,7 @@ import gpusorting_amd as g  # noqa: E402
 
 def main():
     args = sys.argv[1:]
-    flags, preset, sizes, inp, check = [0], 0, [], "generator", True
+    flags, preset, sizes, inp = [0], 0, [], "generator"
     i = 0
     while i < len(args):
         if args[i] == "--flags":
@@ -22,9 +22,6 @@ def main():
         elif args[i] == "--input":   # generator | sorted | reverse | clustered (every 2^20 positions share their top byte)
             inp = args[i + 1]
             i += 2
-        elif args[i] == "--no-check":  # ablation builds (GS_EXP & 256: no look-back wait): the result is not sorted
-            check = False
-            i += 1
         elif args[i] == "--preset":
             preset = int(args[i + 1])
             i += 2
@@ -50,7 +47,7 @@ def main():
                 p = s.get_profile()
                 if it >= 1:
                     runs.append(p)
-                if it == 8 and check:
+                if it == 8:
                     assert g.validate(dk) == 0, "not sorted"
                     assert bool(((dk.to(torch.int64) & 0xFFFFFFFF) == want).all().item()), "differs from torch.sort"
                     del want
