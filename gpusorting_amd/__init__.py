@@ -5,7 +5,8 @@ Only the hot path of b0nes164/GPUSorting named by BASELINE.json is here:
   csrc/      hand-written gfx950 HIP kernels + the C-ABI (include/gpusort.h)
   onesweep   host-side mirror of the reference interface (ctypes over the C-ABI)
   sharded    one-process-per-GPU MSD split + RCCL all-to-all-v + local OneSweep
-  functional sort / sort_ / argsort on torch tensors (plumbing over OneSweep)
+  segsort    segmented sort (CSR offsets) over gs_segsort_*, and its numpy reference
+  functional sort / sort_ / argsort / segmented_sort on torch tensors (plumbing over OneSweep / SegmentedSort)
 """
 from .onesweep import (  # noqa: F401
     ENTROPY_PRESET_1, ENTROPY_PRESET_2, ENTROPY_PRESET_3, ENTROPY_PRESET_4, ENTROPY_PRESET_5,
@@ -13,4 +14,5 @@ from .onesweep import (  # noqa: F401
     GPUSortingConfig, OneSweep, OneSweepDispatcher, init_random, validate,
 )
 from ._lib import GpuSortError  # noqa: F401
-from .functional import argsort, sort, sort_  # noqa: F401
+from .functional import argsort, segmented_argsort, segmented_sort, segmented_sort_, sort, sort_  # noqa: F401
+from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401

@@ -17,6 +17,7 @@ GS_OK, GS_ERR_ARG, GS_ERR_SIZE, GS_ERR_HIP, GS_ERR_TIMEOUT, GS_ERR_MODE, GS_ERR_
 GS_MGPU_UNIQUE_ID_BYTES = 128
 GS_MAX_KEYS = (1 << 30) - 1
 GS_PROFILE_SLOTS = 8
+GS_SEGSORT_CLASSES = 9
 
 # every symbol include/gpusort.h declares: (name, restype, argtypes)
 _u32, _vp, _int = C.c_uint32, C.c_void_p, C.c_int
@@ -157,6 +158,15 @@ _PROTOS = [
     ("gs_mgpu_create_with_transport", _int, [C.POINTER(_vp), C.POINTER(MgpuTransport), _u32, _u32, _u32, _u32, _int, _u32]),
     ("gs_msd_plan", _int, [_u32p, _u32, _u32, _u32, _u32, _u32p]),
     ("gs_debug_msd_plan_device", _int, [_u32p, _u32, _u32, _u32, _u32, _u32p, _vp]),
+    ("gs_segsort_create", _int, [C.POINTER(_vp), _u32, _u32, _int, _u32]),
+    ("gs_segsort_destroy", _int, [_vp]),
+    ("gs_segsort_temp_bytes", C.c_size_t, [_u32, _u32]),
+    ("gs_segsort_class_of", _u32, [_u32, _int, _u32]),
+    ("gs_segsort_max_lds_segment", _u32, [_int, _u32]),
+    ("gs_segsort_sort_keys", _int, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _int, _int, _vp]),
+    ("gs_segsort_sort_pairs", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _int, _int, _vp]),
+    ("gs_segsort_check", _int, [_vp, _vp]),
+    ("gs_segsort_last_classes", _int, [_vp, _u32p, _u32, _vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

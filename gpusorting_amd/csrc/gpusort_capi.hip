@@ -15,6 +15,7 @@
 #include "onesweep_kernels.hpp"
 #include "mid_kernels.hpp"
 #include "hybrid_kernels.hpp"
+#include "segsort_kernels.hpp"
 
 #include <array>
 #include <cstdio>
@@ -140,6 +141,42 @@ void launch_small(hipStream_t s, uint32_t* keys, void* vals, uint32_t n, uint32_
 constexpr Shape g_small_class[5] = {{256, 4}, {256, 8}, {512, 16}, {1024, 16}, {1024, 32}};
 inline int small_class(uint32_t n) { return n <= 1024 ? 0 : n <= 2048 ? 1 : n <= 8192 ? 2 : n <= 16384 ? 3 : n <= 32768 ? 4 : 5; }
 
+// ---- segmented sort (segsort_kernels.hpp): the workgroup classes run the single-tile sort on the shapes of g_small_class ----
+using SegWgLauncher = void (*)(hipStream_t, uint32_t grid, uint32_t* keys, void* vals, const uint32_t* off, const uint32_t* list,
+                               const uint32_t* ctl, uint32_t num_segments, uint32_t cls, uint32_t descending);
+constexpr bool SEG_WG_LOOP(int threads, int kpt) { return threads * kpt < 32768; }  // the 1024 x 32 shape: one workgroup per possible segment
+template <int T, int K, int VB, int KT, int RANK>
+void launch_seg_wg(hipStream_t s, uint32_t grid, uint32_t* keys, void* vals, const uint32_t* off, const uint32_t* list, const uint32_t* ctl,
+                   uint32_t num_segments, uint32_t cls, uint32_t descending) {
+    hipLaunchKernelGGL((gs::seg_wg_kernel<T, K, VB, KT, RANK, SEG_WG_LOOP(T, K)>), dim3(grid), dim3(T), 0, s, keys, vals, off, list, ctl, num_segments, cls, descending);
+}
+// the kernels that do not depend on the key type (it is a run-time argument there): packed class, wave class, head merge
+struct SegVbLaunchers {
+    void (*packed)(hipStream_t, uint32_t grid, uint32_t* keys, void* vals, const uint32_t* off, uint32_t num_segments, uint32_t max_len,
+                   uint32_t kt, uint32_t descending, const uint32_t* ctl);
+    void (*wave)(hipStream_t, uint32_t grid, uint32_t* keys, void* vals, const uint32_t* off, const uint32_t* list, const uint32_t* ctl,
+                 uint32_t num_segments, uint32_t kt, uint32_t descending);
+    void (*merge_head)(hipStream_t, uint32_t grid, const uint32_t* keys, const void* vals, uint32_t* alt_keys, void* alt_vals, uint32_t start,
+                       uint32_t head, uint32_t len, uint32_t kt, uint32_t descending);
+};
+template <int VB>
+constexpr SegVbLaunchers seg_vb_launchers() {
+    return {
+        [](hipStream_t s, uint32_t grid, uint32_t* keys, void* vals, const uint32_t* off, uint32_t num_segments, uint32_t max_len, uint32_t kt,
+           uint32_t descending, const uint32_t* ctl) {
+            hipLaunchKernelGGL((gs::seg_packed_kernel<VB>), dim3(grid), dim3(64), 0, s, keys, vals, off, num_segments, max_len, kt, descending, ctl);
+        },
+        [](hipStream_t s, uint32_t grid, uint32_t* keys, void* vals, const uint32_t* off, const uint32_t* list, const uint32_t* ctl,
+           uint32_t num_segments, uint32_t kt, uint32_t descending) {
+            hipLaunchKernelGGL((gs::seg_wave_kernel<VB>), dim3(grid), dim3(64), 0, s, keys, vals, off, list, ctl, num_segments, kt, descending);
+        },
+        [](hipStream_t s, uint32_t grid, const uint32_t* keys, const void* vals, uint32_t* alt_keys, void* alt_vals, uint32_t start, uint32_t head,
+           uint32_t len, uint32_t kt, uint32_t descending) {
+            hipLaunchKernelGGL((gs::seg_merge_head_kernel<VB>), dim3(grid), dim3(256), 0, s, keys, vals, alt_keys, alt_vals, start, head, len, kt,
+                               descending);
+        }};
+}
+
 // ---- mid sizes: two launches (mid_kernels.hpp) ----
 using MidLauncher = void (*)(hipStream_t, uint32_t n_tiles, uint32_t* keys, uint32_t* alt, void* vals, void* valt, uint32_t* scratch,
                              uint32_t* status, uint32_t n, uint32_t descending);
@@ -226,6 +263,10 @@ constexpr bool small_built(int cls, int vb, int kt) { return FULL && (cls < 3 ||
 constexpr bool mid_built(int cls, int vb, int kt) {
     return FULL && kt < 3 && (cls == 0 || (cls == 1 ? vb != 8 : cls == 4 ? vb == 4 : vb == 0));
 }
+// the segmented sort's kernels: in the product build only (the fault-injection and tuning builds answer GS_ERR_MODE); workgroup class
+// c runs on g_small_class[c] and takes the value widths that shape holds: classes 0-2 all, class 3 no 8-byte values, class 4 keys only
+constexpr bool SEG_BUILT = FULL && GS_EXP == 0;
+constexpr bool seg_built(int cls, int vb, int kt) { return SEG_BUILT && kt < 3 && small_built(cls, vb, kt); }
 
 // A launcher table over D0 x D1 x ... (row-major): entry = f(c0, c1, ...), every coordinate a std::integral_constant, so that
 // f instantiates nothing but what it returns.
@@ -292,6 +333,15 @@ constexpr auto g_mid = MidTable::make([](auto c, auto r, auto v, auto kt) -> Mid
     if constexpr (mid_built(c, VB_OF[v], kt)) return launch_mid<VB_OF[v], kt, r, m.threads, m.kpt, m.threads2, m.kpt2>;
     else return nullptr;
 });
+using SegWgTable = Table<5, 2, 3, 3>;  // [workgroup class][rank mode][vb index][32-bit key type]
+constexpr auto g_seg_wg = SegWgTable::make([](auto c, auto r, auto v, auto kt) -> SegWgLauncher {
+    if constexpr (seg_built(c, VB_OF[v], kt)) return launch_seg_wg<g_small_class[c].threads, g_small_class[c].kpt, VB_OF[v], kt, r>;
+    else return nullptr;
+});
+constexpr auto g_seg_vb = Table<3>::make([](auto v) -> SegVbLaunchers {
+    if constexpr (SEG_BUILT) return seg_vb_launchers<VB_OF[v]>();
+    else return SegVbLaunchers{nullptr, nullptr, nullptr};
+});
 
 inline int vb_index(uint32_t vb) { return vb == 0 ? 0 : vb == 4 ? 1 : 2; }
 BinLauncher bin_launcher(int shape, int rank, uint32_t vb, int kt, int vr = 1) {
@@ -307,6 +357,8 @@ SmallLauncher small_launcher(uint32_t n, int rank, uint32_t vb, int kt) {
     const int c = small_class(n);
     return c < 5 ? g_small[SmallTable::index({c, rank, vb_index(vb), kt})] : nullptr;  // nullptr: no single-tile kernel for this case
 }
+SegWgLauncher seg_wg_launcher(int wg_cls, int rank, uint32_t vb, int kt) { return g_seg_wg[SegWgTable::index({wg_cls, rank, vb_index(vb), kt})]; }
+const SegVbLaunchers& seg_vb(uint32_t vb) { return g_seg_vb[vb_index(vb)]; }
 MidLauncher mid_launcher(int cls, int rank, uint32_t vb, int kt) { return g_mid[MidTable::index({cls, rank, vb_index(vb), kt})]; }
 // ---- end of the kernel registry -------------------------------------------------------------------------------------
 
@@ -1291,6 +1343,196 @@ gs_status gs_onesweep_msd_fine_histogram(gs_onesweep* h, const void* d_keys, uin
     GS_HIP(hipStreamSynchronize(s));
     for (uint32_t d = 0; d < gs::RADIX; ++d)
         for (uint32_t x = 0; x < gs::NCH; ++x) h_hist4096[d * gs::NCH + x] = h->pinned[gs::hist_index(1, d, x)];
+    return GS_OK;
+}
+
+}  // extern "C"
+
+// ---- segmented sort (segsort_kernels.hpp) -------------------------------------------------------------------------------
+// Replaces SplitSortAllocateTempMemory / SplitSortPairs / SplitSortFreeTempMemory (GPUSortingCUDA/SegSort/SplitSort/SplitSort.cuh:674-709).
+struct gs_segsort {
+    uint32_t max_keys, max_segments;
+    gs_mode mode;
+    uint32_t value_bytes;
+    gs_onesweep* engine = nullptr;  // long segments (and the rank mode of the workgroup classes)
+    uint32_t* ctl = nullptr;        // gs::SEGC_WORDS control words, then the class lists (max_segments words)
+    uint32_t* pinned = nullptr;     // read-backs: control block + SEG_LONG_CHUNK list entries
+    bool long_failed = false;       // a long segment's engine call failed on the host side
+};
+
+static_assert(GS_SEGSORT_CLASSES == gs::SEG_CLASSES, "header and kernels agree on the classes");
+namespace {
+constexpr uint32_t SEG_LONG_CHUNK = 1024;  // long-list entries per read-back
+inline uint32_t* seg_list(const gs_segsort* h) { return h->ctl + gs::SEGC_WORDS; }
+
+// workgroups of a fixed-grid class kernel: what the chip holds at once (waves and LDS), never more than the class can have segments
+uint32_t seg_grid(uint32_t bound, uint32_t waves, size_t lds_bytes) {
+    uint32_t per_cu = 32u / waves;
+    const uint32_t by_lds = (uint32_t)((160u * 1024u) / lds_bytes);
+    if (by_lds < per_cu) per_cu = by_lds;
+    if (per_cu == 0) per_cu = 1;
+    const uint32_t g = cu_count() * per_cu;
+    return bound < g ? (bound ? bound : 1u) : g;
+}
+
+gs_status segsort_impl(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t n, const uint32_t* d_offsets,
+                       uint32_t num_segments, uint32_t max_len, gs_key_type kt, gs_order order, hipStream_t s, bool pairs) {
+    if (!h || !d_keys || !d_offsets || misaligned(d_keys) || (reinterpret_cast<uintptr_t>(d_offsets) & 3u) || (int)kt < 0 || (int)kt > 2 ||
+        (order != GS_ORDER_ASCENDING && order != GS_ORDER_DESCENDING))
+        return GS_ERR_ARG;  // (64-bit key types: out of scope)
+    if (pairs != (h->mode == GS_MODE_PAIRS)) return GS_ERR_MODE;
+    if (pairs && (!d_vals || misaligned(d_vals))) return GS_ERR_ARG;
+    if (n == 0 || n > h->max_keys || num_segments == 0 || num_segments > h->max_segments) return GS_ERR_SIZE;
+    const uint32_t vb = h->value_bytes;
+    const bool allow_long = max_len == 0u || max_len > gs::seg_max_lds(vb);
+    if (allow_long && (!d_alt_keys || misaligned(d_alt_keys) || (pairs && (!d_alt_vals || misaligned(d_alt_vals))))) return GS_ERR_ARG;
+    if (!SEG_BUILT) return GS_ERR_MODE;  // this build flavour has no segmented-sort kernels
+    const uint32_t top = allow_long ? gs::SEG_CLASS_LONG : gs::seg_class_of(max_len, vb);  // the highest class a segment can fall in
+    const uint32_t desc = order == GS_ORDER_DESCENDING ? 1u : 0u;
+    uint32_t* keys = static_cast<uint32_t*>(d_keys);
+    h->long_failed = false;
+    hipLaunchKernelGGL(gs::seg_reset_kernel, dim3(1), dim3(64), 0, s, h->ctl);
+    const uint32_t seg_blocks = div_up(num_segments, 256);
+    hipLaunchKernelGGL(gs::seg_classify_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, n, vb, max_len, h->ctl);
+    if (top >= 2) hipLaunchKernelGGL(gs::seg_fill_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, vb, max_len, h->ctl, seg_list(h));
+    const SegVbLaunchers& f = seg_vb(vb);
+    if (top >= 1) f.packed(s, div_up(num_segments, 64), keys, d_vals, d_offsets, num_segments, max_len, (uint32_t)kt, desc, h->ctl);
+    // a class whose shortest segment has m elements holds at most n / m segments
+    auto bound = [&](uint32_t min_len) { const uint32_t b = n / min_len; return b < num_segments ? b : num_segments; };
+    if (top >= 2 && n > gs::SEG_PACK_MAX)
+        f.wave(s, seg_grid(bound(gs::SEG_PACK_MAX + 1), 1, gs::SEG_WAVE_MAX * (8 + vb)), keys, d_vals, d_offsets, seg_list(h), h->ctl, num_segments, (uint32_t)kt, desc);
+    for (uint32_t c = 3; c <= 7 && c <= top; ++c) {
+        const uint32_t min_len = gs::SEG_CLASS_MAX[c - 1] + 1;
+        if (n < min_len || gs::SEG_CLASS_MAX[c] > gs::seg_max_lds(vb)) continue;
+        const Shape sh = g_small_class[c - 3];
+        const SegWgLauncher wg = seg_wg_launcher((int)c - 3, h->engine->rank_mode, vb, (int)kt);
+        if (!wg) return GS_ERR_MODE;
+        const size_t lds = (size_t)sh.threads * sh.kpt * (4 + vb) + (size_t)sh.threads / 64 * gs::RADIX * 4 + 64;
+        wg(s, SEG_WG_LOOP(sh.threads, sh.kpt) ? seg_grid(bound(min_len), (uint32_t)sh.threads / 64, lds) : bound(min_len), keys, d_vals, d_offsets, seg_list(h), h->ctl, num_segments, c, desc);
+    }
+    GS_HIP(hipGetLastError());
+    if (!allow_long || n <= gs::seg_max_lds(vb)) return GS_OK;
+    // ---- long segments: the one host wait.  Control block + the head of the long list (it starts the list array) ----
+    const uint32_t most = bound(gs::seg_max_lds(vb) + 1);
+    uint32_t got = most < SEG_LONG_CHUNK ? most : SEG_LONG_CHUNK;
+    GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, (gs::SEGC_WORDS + got) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GS_HIP(hipStreamSynchronize(s));
+    if (h->pinned[gs::SEGC_STATUS] & gs::SEG_ST_ARG) return GS_OK;  // reported by gs_segsort_check; nothing was sorted
+    const uint32_t count = h->pinned[gs::SEGC_COUNT + gs::SEG_CLASS_LONG];
+    if (count > most) return GS_ERR_HIP;  // (cannot happen: the classify kernel counted more long segments than n holds)
+    char* vals = static_cast<char*>(d_vals);
+    char* alt_vals = static_cast<char*>(d_alt_vals);
+    uint32_t* alt_keys = static_cast<uint32_t*>(d_alt_keys);
+    for (uint32_t first = 0; first < count; first += SEG_LONG_CHUNK) {
+        const uint32_t chunk = count - first < SEG_LONG_CHUNK ? count - first : SEG_LONG_CHUNK;
+        if (first != 0) {
+            GS_HIP(hipMemcpyAsync(h->pinned + gs::SEGC_WORDS, seg_list(h) + first, chunk * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            GS_HIP(hipStreamSynchronize(s));
+        }
+        // the chunk's offsets: segment numbers come from the device's own (validated) classification
+        uint32_t* bounds = h->pinned + gs::SEGC_WORDS + SEG_LONG_CHUNK;
+        for (uint32_t i = 0; i < chunk; ++i) {
+            const uint32_t seg = h->pinned[gs::SEGC_WORDS + i];
+            if (seg >= num_segments) return GS_ERR_HIP;
+            GS_HIP(hipMemcpyAsync(bounds, d_offsets + seg, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            GS_HIP(hipStreamSynchronize(s));
+            const uint32_t start = bounds[0], end = bounds[1];
+            if (end > n || start >= end) return GS_ERR_HIP;
+            // the engine wants 16-byte aligned buffers: it sorts [start + head, end), seg_merge_head_kernel merges the head in
+            const uint32_t head = (4u - (start & 3u)) & 3u, a = start + head, len = end - start;
+            gs_status st = pairs ? gs_onesweep_sort_pairs(h->engine, keys + a, vals + (size_t)a * vb, alt_keys + a, alt_vals + (size_t)a * vb,
+                                                          len - head, kt, order, s)
+                                 : gs_onesweep_sort_keys(h->engine, keys + a, alt_keys + a, len - head, kt, order, s);
+            if (st != GS_OK) { h->long_failed = true; return st; }
+            if (head != 0) {
+                const uint32_t grid = div_up(len, 256 * 8);
+                f.merge_head(s, grid < 4096 ? grid : 4096, keys, d_vals, alt_keys, d_alt_vals, start, head, len, (uint32_t)kt, desc);
+                GS_HIP(hipMemcpyAsync(keys + start, alt_keys + start, (size_t)len * 4, hipMemcpyDeviceToDevice, s));
+                if (pairs) GS_HIP(hipMemcpyAsync(vals + (size_t)start * vb, alt_vals + (size_t)start * vb, (size_t)len * vb, hipMemcpyDeviceToDevice, s));
+            }
+        }
+    }
+    return GS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t gs_segsort_temp_bytes(uint32_t max_keys, uint32_t max_segments) {
+    return gs_onesweep_temp_bytes(max_keys) + ((size_t)gs::SEGC_WORDS + max_segments) * sizeof(uint32_t);
+}
+uint32_t gs_segsort_class_of(uint32_t length, gs_mode mode, uint32_t value_bytes) {
+    return gs::seg_class_of(length, mode == GS_MODE_PAIRS ? value_bytes : 0);
+}
+uint32_t gs_segsort_max_lds_segment(gs_mode mode, uint32_t value_bytes) { return gs::seg_max_lds(mode == GS_MODE_PAIRS ? value_bytes : 0); }
+
+gs_status gs_segsort_create(gs_segsort** out, uint32_t max_keys, uint32_t max_segments, gs_mode mode, uint32_t value_bytes) {
+    if (!out) return GS_ERR_ARG;
+    *out = nullptr;
+    if (max_segments == 0 || max_segments > GS_MAX_KEYS) return GS_ERR_SIZE;
+    gs_onesweep* engine = nullptr;
+    const gs_status st = gs_onesweep_create(&engine, max_keys, mode, value_bytes);  // checks max_keys, mode and value width
+    if (st != GS_OK) return st;
+    gs_segsort* h = new (std::nothrow) gs_segsort();
+    if (!h) { (void)gs_onesweep_destroy(engine); return GS_ERR_ARG; }
+    h->max_keys = max_keys;
+    h->max_segments = max_segments;
+    h->mode = mode;
+    h->value_bytes = value_bytes;
+    h->engine = engine;
+    hipError_t e = hipMalloc(&h->ctl, ((size_t)gs::SEGC_WORDS + max_segments) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(h->ctl, 0, gs::SEGC_WORDS * sizeof(uint32_t));  // gs_segsort_check may run before any sort
+    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, (gs::SEGC_WORDS + SEG_LONG_CHUNK + 2) * sizeof(uint32_t), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        g_last_hip_error = (int)e;
+        (void)gs_segsort_destroy(h);
+        return GS_ERR_HIP;
+    }
+    *out = h;
+    return GS_OK;
+}
+
+gs_status gs_segsort_destroy(gs_segsort* h) {
+    if (!h) return GS_ERR_ARG;
+    if (h->pinned) (void)hipHostFree(h->pinned);
+    if (h->ctl) (void)hipFree(h->ctl);
+    if (h->engine) (void)gs_onesweep_destroy(h->engine);
+    delete h;
+    return GS_OK;
+}
+
+gs_status gs_segsort_sort_keys(gs_segsort* h, void* d_keys, void* d_alt, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments,
+                               uint32_t max_segment_len, gs_key_type key_type, gs_order order, void* stream) {
+    return segsort_impl(h, d_keys, nullptr, d_alt, nullptr, n, d_offsets, num_segments, max_segment_len, key_type, order,
+                        static_cast<hipStream_t>(stream), false);
+}
+
+gs_status gs_segsort_sort_pairs(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t n,
+                                const uint32_t* d_offsets, uint32_t num_segments, uint32_t max_segment_len, gs_key_type key_type, gs_order order,
+                                void* stream) {
+    return segsort_impl(h, d_keys, d_vals, d_alt_keys, d_alt_vals, n, d_offsets, num_segments, max_segment_len, key_type, order,
+                        static_cast<hipStream_t>(stream), true);
+}
+
+gs_status gs_segsort_check(gs_segsort* h, void* stream) {
+    if (!h) return GS_ERR_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, gs::SEGC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GS_HIP(hipStreamSynchronize(s));
+    const uint32_t st = h->pinned[gs::SEGC_STATUS];
+    if (st & gs::SEG_ST_ARG) return GS_ERR_ARG;
+    if (h->long_failed) return GS_ERR_HIP;
+    if (st & gs::SEG_ST_SIZE) return GS_ERR_SIZE;
+    return gs_onesweep_check(h->engine, stream);  // the long segments' sorts
+}
+
+gs_status gs_segsort_last_classes(gs_segsort* h, uint32_t* counts, uint32_t words, void* stream) {
+    if (!h || !counts || words < GS_SEGSORT_CLASSES + 1) return GS_ERR_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, gs::SEGC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GS_HIP(hipStreamSynchronize(s));
+    for (uint32_t c = 0; c < GS_SEGSORT_CLASSES; ++c) counts[c] = h->pinned[gs::SEGC_COUNT + c];
+    counts[GS_SEGSORT_CLASSES] = h->pinned[gs::SEGC_MAXLEN];
     return GS_OK;
 }
 

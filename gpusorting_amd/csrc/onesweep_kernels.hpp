@@ -2066,9 +2066,12 @@ __global__ __launch_bounds__(256) void check_state_kernel(const uint32_t* slab, 
 constexpr uint32_t SMALL_TILE = 512 * 16;         // 8192: the size every mode can sort in one workgroup
 constexpr uint32_t SMALL_TILE_MAX = 1024 * 32;    // largest single-tile sort (keys-only)
 
-template <int SMALL_THREADS, int SMALL_KPT, int VB, int KT, int RANK>
-__global__ __launch_bounds__(SMALL_THREADS) void small_sort_kernel(uint32_t* keys, void* vals_, uint32_t n,
-                                                                   uint32_t descending, uint32_t* status) {
+// The sort of one tile by one workgroup: keys[0..n) (and vals_), 1 <= n <= SMALL_THREADS x SMALL_KPT, in place.  Body of small_sort_kernel
+// (STATUS: a sort of its own, `status` is its status word and is reset here) and of the segmented sort's workgroup classes
+// (segsort_kernels.hpp: one call per segment, a barrier between two calls).  The LDS is the body's own: a kernel that calls one
+// instantiation of it gets that instantiation's arrays.
+template <int SMALL_THREADS, int SMALL_KPT, int VB, int KT, int RANK, bool STATUS>
+__device__ __forceinline__ void tile_sort_body(uint32_t* keys, void* vals_, uint32_t n, uint32_t descending, uint32_t* status) {
     using V = typename ValT<VB>::type;
     constexpr int KW = KeyWords<KT>::value;  // 64-bit keys: eight passes, both words staged
     constexpr int KPT = SMALL_KPT, WAVES = SMALL_THREADS / 64;
@@ -2082,7 +2085,9 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_sort_kernel(uint32_t* key
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t my_base = wave * (64u * KPT) + lane;
     uint32_t* whist = s_whist + wave * RADIX;
-    if (tid == 0) st_agent(status, STATUS_OK);  // this sort cannot time out; an earlier call's verdict is not this call's
+    if constexpr (STATUS) {
+        if (tid == 0) st_agent(status, STATUS_OK);  // this sort cannot time out; an earlier call's verdict is not this call's
+    }
 
     uint32_t key[KPT];                      // low word (the only one for 32-bit keys)
     uint32_t keyh[KW == 2 ? KPT : 1];       // high word
@@ -2202,6 +2207,12 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_sort_kernel(uint32_t* key
             if constexpr (VB != 0) reinterpret_cast<V*>(vals_)[o] = val[i];
         }
     }
+}
+
+template <int SMALL_THREADS, int SMALL_KPT, int VB, int KT, int RANK>
+__global__ __launch_bounds__(SMALL_THREADS) void small_sort_kernel(uint32_t* keys, void* vals_, uint32_t n,
+                                                                   uint32_t descending, uint32_t* status) {
+    tile_sort_body<SMALL_THREADS, SMALL_KPT, VB, KT, RANK, true>(keys, vals_, n, descending, status);
 }
 
 // ---------------------------------------------------------------------------

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import torch
 
+from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
 
 _KEY_TYPE = {torch.int32: KEY_INT32, torch.float32: KEY_FLOAT32, torch.uint32: KEY_UINT32}
@@ -68,4 +69,69 @@ def argsort(keys: torch.Tensor, descending: bool = False, unsigned: bool = False
     idx = torch.arange(keys.numel(), dtype=torch.int32, device=keys.device)
     k = keys.clone()
     sort_(k, idx, descending, unsigned)
+    return idx
+
+
+# ---- segmented sort ---------------------------------------------------------------------------------------------------------
+_seg_cache: dict = {}
+
+
+def _seg_sorter(device: torch.device, n: int, num_segments: int, key_type: int, order: int, value_bytes: int) -> SegmentedSort:
+    """One cached handle per (device, stream, type, order, value width); re-created when keys or segments outgrow it."""
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+    s = _seg_cache.get(key)
+    if s is None or s.max_keys < n or s.max_segments < num_segments:
+        if s is not None:
+            s.close()
+        cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
+        s = SegmentedSort(cap(n), cap(num_segments), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes,
+                          device=device.index)
+        _seg_cache[key] = s
+    return s
+
+
+def segmented_sort_(keys: torch.Tensor, offsets: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False,
+                    unsigned: bool = False, max_segment_len: int = 0) -> None:
+    """Sort every segment ``keys[offsets[s]:offsets[s + 1]]`` (and carry ``values``) in place on the current stream.  ``offsets``:
+    int32 tensor of ``num_segments + 1`` on the device (CSR).  ``max_segment_len``: upper bound on the segment length if the caller
+    knows one (a bound that fits the LDS classes keeps the call free of host waits); 0 = unknown."""
+    if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+    if keys.dtype not in _KEY_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
+    if offsets.dim() != 1 or offsets.numel() < 2 or offsets.dtype not in (torch.int32, torch.uint32) or offsets.device != keys.device \
+            or not offsets.is_contiguous():
+        raise ValueError("offsets must be a contiguous 1-D int32 tensor of num_segments + 1 on the keys' device")
+    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    vb = 0
+    if values is not None:
+        if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:
+            raise ValueError("values must match keys in shape and device and be contiguous")
+        vb = values.element_size()
+        if vb not in (4, 8):
+            raise TypeError("values must be 4 or 8 bytes wide")
+    n = keys.numel()
+    if n == 0:
+        return
+    with torch.cuda.device(keys.device):
+        s = _seg_sorter(keys.device, n, offsets.numel() - 1, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb)
+        s.sort(keys.view(torch.int32) if keys.dtype != torch.int32 else keys, offsets, values, n=n, max_segment_len=max_segment_len)
+
+
+def segmented_sort(keys: torch.Tensor, offsets: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False,
+                   unsigned: bool = False, max_segment_len: int = 0):
+    """Out-of-place: returns ``sorted_keys`` or ``(sorted_keys, sorted_values)``."""
+    k = keys.clone()
+    v = None if values is None else values.clone()
+    segmented_sort_(k, offsets, v, descending, unsigned, max_segment_len)
+    return k if v is None else (k, v)
+
+
+def segmented_argsort(keys: torch.Tensor, offsets: torch.Tensor, descending: bool = False, unsigned: bool = False,
+                      max_segment_len: int = 0) -> torch.Tensor:
+    """Stable permutation of the WHOLE array that sorts every segment: position within the segment's slice plus its start (int32;
+    identity outside the segments)."""
+    idx = torch.arange(keys.numel(), dtype=torch.int32, device=keys.device)
+    k = keys.clone()
+    segmented_sort_(k, offsets, idx, descending, unsigned, max_segment_len)
     return idx

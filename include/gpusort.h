@@ -393,6 +393,61 @@ gs_status gs_msd_exchange_round(const uint32_t* table, uint32_t world, uint32_t 
 gs_status gs_debug_msd_plan_device(const uint32_t* h_table, uint32_t nbins, uint32_t world, uint32_t rank, uint32_t capacity,
                                    uint32_t* h_plan, void* stream);
 
+/* ---- segmented sort: many independent segments of one array in one call ------------------------------------
+ * Replaces: SplitSortAllocateTempMemory / SplitSortPairs / SplitSortFreeTempMemory
+ * (GPUSortingCUDA/SegSort/SplitSort/SplitSort.cuh:674-709).  The reference takes the segment STARTS plus the total
+ * length; this interface takes CSR offsets: d_offsets[0 .. num_segments] (num_segments + 1 uint32 words in device
+ * memory), segment s = [d_offsets[s], d_offsets[s + 1]).
+ *
+ * Every segment is sorted on its own, in place, and ends up exactly as gs_onesweep_sort_keys / _sort_pairs would leave
+ * that slice: stable by key, descending = exact reverse of the stable ascending result, floats by the order-preserving
+ * bit flip, values bit-copied.  Empty segments and segments of one element are legal anywhere; elements in front of
+ * d_offsets[0] and behind d_offsets[num_segments] are not touched.  32-bit key types only: GS_KEY_UINT64 / INT64 /
+ * FLOAT64 return GS_ERR_ARG (out of scope).  1 <= n <= max_keys, 1 <= num_segments <= max_segments (GS_ERR_SIZE).
+ *
+ * The offsets are validated ON THE DEVICE before anything is loaded through them (non-decreasing, last <= n): with bad
+ * offsets nothing is written to keys or values and gs_segsort_check reports GS_ERR_ARG.
+ *
+ * Length classes (gs_segsort_class_of; GS_SEGSORT_CLASSES of them), each with a kernel of its own, all enqueued by one call:
+ *   0  length 0 or 1: nothing to do (also counts the segments that broke the caller's promise, below)
+ *   1  2 .. 32: packed, 64 consecutive segments per wave, counting rank inside the segment
+ *   2  33 .. 256: one segment per wave, sorted in LDS
+ *   3 .. 7  up to 1024 / 2048 / 8192 / 16 384 / 32 768: one segment per workgroup, sorted in LDS by the single-tile sort
+ *      (class 6 not with 8-byte values, class 7 keys-only: what 160 KiB of LDS hold)
+ *   8  longer than gs_segsort_max_lds_segment(): sorted one by one by the handle's own gs_onesweep engine
+ *
+ * max_segment_len is a promise by the caller.  Non-zero and <= gs_segsort_max_lds_segment(): the call is asynchronous on
+ * `stream`, never touches the host after its launches (it can be captured into a graph) and d_alt* may be NULL; a segment
+ * that breaks the promise is left unsorted — noticed on the device — and gs_segsort_check reports GS_ERR_SIZE.  0 (unknown)
+ * or larger: long segments are allowed, d_alt* (n elements each, scratch) are required, and the call WAITS ON THE HOST ONCE
+ * for the list of long segments (then once per long segment for its two offsets) before it enqueues their sorts.
+ * One in-flight call per handle. */
+#define GS_SEGSORT_CLASSES 9
+typedef struct gs_segsort gs_segsort;
+/* value_bytes 0 (keys only), 4 or 8, as gs_onesweep_create.  Synchronous (allocates gs_segsort_temp_bytes of device memory). */
+gs_status gs_segsort_create(gs_segsort** out, uint32_t max_keys, uint32_t max_segments, gs_mode mode, uint32_t value_bytes);
+gs_status gs_segsort_destroy(gs_segsort* h);
+/* Host only.  gs_onesweep_temp_bytes(max_keys) (the embedded engine for long segments) + 4 x max_segments (the class lists: ONE
+ * array, filled class by class) + 256 (control block).  The reference needs 12 x max_segments plus small change for its bins
+ * (SplitSort.cuh:674-690). */
+size_t gs_segsort_temp_bytes(uint32_t max_keys, uint32_t max_segments);
+/* Host only: the class a segment of this length falls in (monotone in the length), and the longest segment sorted in LDS:
+ * 32 768 keys-only, 16 384 with 4-byte values, 8192 with 8-byte values. */
+uint32_t gs_segsort_class_of(uint32_t length, gs_mode mode, uint32_t value_bytes);
+uint32_t gs_segsort_max_lds_segment(gs_mode mode, uint32_t value_bytes);
+gs_status gs_segsort_sort_keys(gs_segsort* h, void* d_keys, void* d_alt, uint32_t n, const uint32_t* d_offsets,
+                               uint32_t num_segments, uint32_t max_segment_len, gs_key_type key_type, gs_order order, void* stream);
+gs_status gs_segsort_sort_pairs(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t n,
+                                const uint32_t* d_offsets, uint32_t num_segments, uint32_t max_segment_len, gs_key_type key_type,
+                                gs_order order, void* stream);
+/* Synchronises `stream` and reports the last call: GS_OK, GS_ERR_ARG (bad offsets: nothing was sorted), GS_ERR_SIZE (a segment
+ * longer than promised: that one is unsorted, every other one sorted), or what gs_onesweep_check says about the long segments'
+ * sorts.  Every call resets the status word itself. */
+gs_status gs_segsort_check(gs_segsort* h, void* stream);
+/* Synchronous: counts[c] = segments of class c in the last call, c < GS_SEGSORT_CLASSES; counts[GS_SEGSORT_CLASSES] = the longest
+ * segment seen.  words >= GS_SEGSORT_CLASSES + 1. */
+gs_status gs_segsort_last_classes(gs_segsort* h, uint32_t* counts, uint32_t words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
