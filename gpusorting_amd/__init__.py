@@ -6,7 +6,8 @@ Only the hot path of b0nes164/GPUSorting named by BASELINE.json is here:
   onesweep   host-side mirror of the reference interface (ctypes over the C-ABI)
   sharded    one-process-per-GPU MSD split + RCCL all-to-all-v + local OneSweep
   segsort    segmented sort (CSR offsets) over gs_segsort_*, and its numpy reference
-  functional sort / sort_ / argsort / segmented_sort on torch tensors (plumbing over OneSweep / SegmentedSort)
+  topk       top-k selection (the head of the sort without the sort) over gs_topk_*, and its numpy reference
+  functional sort / sort_ / argsort / segmented_sort / topk on torch tensors (plumbing over OneSweep / SegmentedSort / TopK)
 """
 from .onesweep import (  # noqa: F401
     ENTROPY_PRESET_1, ENTROPY_PRESET_2, ENTROPY_PRESET_3, ENTROPY_PRESET_4, ENTROPY_PRESET_5,
@@ -14,5 +15,6 @@ from .onesweep import (  # noqa: F401
     GPUSortingConfig, OneSweep, OneSweepDispatcher, init_random, validate,
 )
 from ._lib import GpuSortError  # noqa: F401
-from .functional import argsort, segmented_argsort, segmented_sort, segmented_sort_, sort, sort_  # noqa: F401
+from .functional import argsort, segmented_argsort, segmented_sort, segmented_sort_, sort, sort_, topk  # noqa: F401
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
+from .topk import TopK, topk_reference  # noqa: F401

@@ -18,6 +18,7 @@ GS_MGPU_UNIQUE_ID_BYTES = 128
 GS_MAX_KEYS = (1 << 30) - 1
 GS_PROFILE_SLOTS = 8
 GS_SEGSORT_CLASSES = 9
+GS_TOPK_REPORT_WORDS = 8
 
 # every symbol include/gpusort.h declares: (name, restype, argtypes)
 _u32, _vp, _int = C.c_uint32, C.c_void_p, C.c_int
@@ -167,6 +168,13 @@ _PROTOS = [
     ("gs_segsort_sort_pairs", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _int, _int, _vp]),
     ("gs_segsort_check", _int, [_vp, _vp]),
     ("gs_segsort_last_classes", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_topk_create", _int, [C.POINTER(_vp), _u32, _u32, _int, _u32]),
+    ("gs_topk_destroy", _int, [_vp]),
+    ("gs_topk_temp_bytes", C.c_size_t, [_u32, _u32, _u32]),
+    ("gs_topk_select_keys", _int, [_vp, _vp, _u32, _u32, _vp, _int, _int, _vp]),
+    ("gs_topk_select_pairs", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _int, _int, _vp]),
+    ("gs_topk_check", _int, [_vp, _vp]),
+    ("gs_topk_last", _int, [_vp, _u32p, _u32, _vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
+from .topk import TopK, topk_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
 
 _KEY_TYPE = {torch.int32: KEY_INT32, torch.float32: KEY_FLOAT32, torch.uint32: KEY_UINT32}
@@ -135,3 +136,48 @@ def segmented_argsort(keys: torch.Tensor, offsets: torch.Tensor, descending: boo
     k = keys.clone()
     segmented_sort_(k, offsets, idx, descending, unsigned, max_segment_len)
     return idx
+
+
+# ---- top-k selection --------------------------------------------------------------------------------------------------------
+_topk_cache: dict = {}
+
+
+def _topk_handle(device: torch.device, n: int, k: int, key_type: int, order: int, value_bytes: int) -> TopK:
+    """One cached handle per (device, stream, type, order, value width); re-created when n or k outgrow it."""
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+    s = _topk_cache.get(key)
+    if s is None or s.max_keys < n or s.max_k < k:
+        if s is not None:
+            s.close()
+        cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
+        s = TopK(cap(n), min(cap(k), cap(n)), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes, device=device.index)
+        _topk_cache[key] = s
+    return s
+
+
+def topk(keys: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor | None = None, unsigned: bool = False):
+    """The ``k`` largest (``largest=True``, as ``torch.topk``) or smallest elements of a 1-D tensor in sorted order, without sorting
+    the rest: returns ``(keys_k, indices_k)`` (int32 input positions) or, with ``values``, ``(keys_k, values_k)``.  The result is the
+    head of this library's sort: floats by the order-preserving bit flip (-0 < +0, NaNs by bit pattern — NOT ``torch.topk``'s "NaN is
+    largest"), ties by position (smallest: lowest positions first; largest: highest positions first).  The inputs are not written."""
+    if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+    if keys.dtype not in _KEY_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
+    n, k = keys.numel(), int(k)
+    if not 1 <= k <= n:
+        raise ValueError("1 <= k <= n")
+    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    vb = 4
+    if values is not None:
+        if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:
+            raise ValueError("values must match keys in shape and device and be contiguous")
+        vb = values.element_size()
+        if vb not in (4, 8):
+            raise TypeError("values must be 4 or 8 bytes wide")
+    out_k = torch.empty(k, dtype=keys.dtype, device=keys.device)
+    out_v = torch.empty(k, dtype=torch.int32 if values is None else values.dtype, device=keys.device)
+    with torch.cuda.device(keys.device):
+        s = _topk_handle(keys.device, n, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
+        s.select(keys, k, out_k, values, out_v, n=n)
+    return out_k, out_v

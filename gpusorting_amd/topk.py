@@ -1,0 +1,123 @@
+"""Top-k selection over the C-ABI (``gs_topk_*`` in include/gpusort.h): the first k elements of the sorted order — keys, and values or
+input positions — without sorting the rest.
+
+No counterpart in the reference project.  PyTorch is used only for device memory and the current HIP stream.  ``topk_reference`` is
+the pure-numpy statement of the semantics (tests and tools compare against it); it needs no torch and no GPU.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+from .segsort import sortable_bits
+
+MODE_KEYS_ONLY, MODE_PAIRS = 0, 1
+ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
+KEY_UINT32, KEY_INT32, KEY_FLOAT32 = 0, 1, 2
+ROUTE_NONE, ROUTE_SELECT, ROUTE_FULL_SORT, ROUTE_SINGLE_TILE = 0, 1, 2, 3
+_REPORT = ("route", "threshold", "in_front", "equal", "taken", "candidates", "level2", "ranges")
+
+
+def topk_reference(keys: np.ndarray, k: int, values: np.ndarray | None = None, key_type: int = KEY_UINT32, descending: bool = False):
+    """The first ``k`` elements of the library's sorted order: stable argsort on the sortable bit pattern, reversed as a whole for
+    descending (so ties go to the lowest positions ascending, to the highest descending), first ``k``.  Floats follow the
+    order-preserving bit flip: -0 < +0, NaNs by bit pattern (not ``torch.topk``'s NaN rule).  Returns ``(keys_k, values_k)``;
+    ``values=None`` returns the input positions (uint32) as values."""
+    keys = np.ascontiguousarray(keys)
+    if keys.ndim != 1 or not 1 <= k <= keys.size:
+        raise ValueError("keys must be 1-D and 1 <= k <= n")
+    perm = np.argsort(sortable_bits(keys, key_type), kind="stable")
+    if descending:
+        perm = perm[::-1]
+    perm = perm[:k]
+    vals = perm.astype(np.uint32) if values is None else np.ascontiguousarray(values)[perm]
+    return keys[perm], vals
+
+
+class TopK:
+    """One ``gs_topk`` handle: the selection's scratch and an embedded OneSweep engine for the final sort of k elements.
+
+    ``value_bytes`` 0 selects keys only; 4 or 8 carries values; on a 4-byte handle ``select(keys, k, out_keys, None, out_vals)``
+    delivers the input positions as values."""
+
+    def __init__(self, max_keys: int, max_k: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT32, mode: int = MODE_KEYS_ONLY,
+                 value_bytes: int = 0, device: int | None = None):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
+        if key_type not in (KEY_UINT32, KEY_INT32, KEY_FLOAT32):
+            raise ValueError("the selection takes 32-bit keys only")
+        self._lib = _lib.load()
+        if device is not None:
+            torch.cuda.set_device(device)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.max_keys, self.max_k = int(max_keys), int(max_k)
+        self.order, self.key_type, self.mode = order, key_type, mode
+        self.value_bytes = (value_bytes or 4) if mode == MODE_PAIRS else 0
+        h = C.c_void_p()
+        check(self._lib.gs_topk_create(C.byref(h), self.max_keys, self.max_k, mode, self.value_bytes), "gs_topk_create")
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.gs_topk_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def temp_bytes(self) -> int:
+        return int(self._lib.gs_topk_temp_bytes(self.max_keys, self.max_k, self.value_bytes))
+
+    def select(self, keys, k: int, out_keys, values=None, out_values=None, n: int | None = None, stream=None) -> None:
+        """The first ``k`` of ``keys[:n]`` in this handle's order into ``out_keys[:k]`` (and ``out_values[:k]``) on the current stream.
+        ``values=None`` with ``out_values`` given (4-byte handle): the values are the input positions.  Inputs are not written."""
+        from .onesweep import _require_cuda, _require_room, _stream_ptr
+        _require_cuda(keys, "keys")
+        _require_cuda(out_keys, "out_keys")
+        if keys.element_size() != 4 or out_keys.element_size() != 4:
+            raise ValueError("keys must be 32-bit")
+        if (out_values is not None) != (self.mode == MODE_PAIRS):
+            raise ValueError("out_values must be given exactly when the handle was built with MODE_PAIRS")
+        n = keys.numel() if n is None else int(n)
+        k = int(k)
+        _require_room(keys, n, "keys")
+        _require_room(values, n, "values")
+        _require_room(out_keys, k, "out_keys")
+        _require_room(out_values, k, "out_values")
+        for t, name in ((values, "values"), (out_values, "out_values")):
+            if t is not None:
+                _require_cuda(t, name)
+                if t.element_size() != self.value_bytes:
+                    raise ValueError(f"{name} must be {self.value_bytes} bytes wide for this handle")
+        s = _stream_ptr(stream)
+        if out_values is None:
+            st = self._lib.gs_topk_select_keys(self._h, keys.data_ptr(), n, k, out_keys.data_ptr(), self.key_type, self.order, s)
+        else:
+            st = self._lib.gs_topk_select_pairs(self._h, keys.data_ptr(), None if values is None else values.data_ptr(), n, k,
+                                                out_keys.data_ptr(), out_values.data_ptr(), self.key_type, self.order, s)
+        check(st, "gs_topk_select")
+
+    def status(self, stream=None) -> int:
+        """``gs_topk_check`` as a status code (synchronises)."""
+        from .onesweep import _stream_ptr
+        return int(self._lib.gs_topk_check(self._h, _stream_ptr(stream)))
+
+    def check(self, stream=None) -> None:
+        """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
+        check(self.status(stream), "gs_topk_check")
+
+    def last(self, stream=None) -> dict:
+        """Diagnostics of the last call (synchronises): route, threshold (the k-th key as sortable bits), in_front, equal, taken,
+        candidates (left after the first level), level2, ranges."""
+        from .onesweep import _stream_ptr
+        buf = (C.c_uint32 * _lib.GS_TOPK_REPORT_WORDS)()
+        check(self._lib.gs_topk_last(self._h, buf, _lib.GS_TOPK_REPORT_WORDS, _stream_ptr(stream)), "gs_topk_last")
+        return {name: int(buf[i]) for i, name in enumerate(_REPORT)}

@@ -448,6 +448,73 @@ gs_status gs_segsort_check(gs_segsort* h, void* stream);
  * segment seen.  words >= GS_SEGSORT_CLASSES + 1. */
 gs_status gs_segsort_last_classes(gs_segsort* h, uint32_t* counts, uint32_t words, void* stream);
 
+/* ---- top-k selection: the first k elements of the sorted order without sorting the rest --------------------
+ * No counterpart in the reference project.
+ *
+ * For 1 <= k <= n the output is exactly the first k elements of what gs_onesweep_sort_keys / _sort_pairs with the same key
+ * type and order would leave for that input, keys and values, bit for bit: ascending = the k smallest, descending = the k
+ * largest, delivered in sorted order; floats by the order-preserving bit flip (-0 < +0, NaNs by bit pattern: above +inf or
+ * below -inf by their sign — the library's order, not a "NaN is largest" rule); ties are deterministic: ascending, among the
+ * elements equal to the k-th key those at the LOWEST input positions are taken and equal keys come out in increasing position;
+ * descending is the exact reverse of the stable ascending result, so those at the HIGHEST positions are taken and equal keys
+ * come out in decreasing position.  Values are bit-copied.  The input arrays are not written; the output arrays hold k
+ * elements, must not overlap the input (GS_ERR_ARG) and nothing behind their k-th element is touched.
+ *
+ * 32-bit key types only: GS_KEY_UINT64 / INT64 / FLOAT64 return GS_ERR_ARG.  k == 0, k > n, k > max_k, n == 0, n > max_keys
+ * return GS_ERR_SIZE; NULL or not 16-byte aligned pointers GS_ERR_ARG; select_pairs on a keys-only handle (and the reverse)
+ * GS_ERR_MODE.  On a handle with 4-byte values d_vals == NULL means "the value is the element's input position" (uint32): the
+ * kernels produce the index themselves, no n-sized index array exists anywhere.
+ *
+ * Asynchronous on `stream`, no host round trip: every launch is enqueued up front (the output count is k whatever the data), so
+ * a call can be captured into a graph.  No kernel waits on another workgroup.  One in-flight call per handle.
+ *
+ * Routes (gs_topk_last): GS_TOPK_ROUTE_SINGLE_TILE for n up to the single-tile sort's capacity (32 768 keys only, 16 384 with
+ * 4-byte values, 8192 with 8-byte values): a copy is sorted in one launch and its head emitted.  GS_TOPK_ROUTE_SELECT otherwise, for
+ * every k: a two-level radix select (16 + 16 bits) finds the bit pattern T of the k-th element, gathers the elements in front of T
+ * and the wanted share of those equal to T into the output in input order — two reads of the keys, 8 bytes per key, for keys that
+ * spread over their top 16 bits, 20 at most — and the handle's embedded engine sorts those k.  GS_TOPK_ROUTE_FULL_SORT is reserved:
+ * no handle takes it today. */
+typedef struct gs_topk gs_topk;
+#define GS_TOPK_ROUTE_NONE 0u
+#define GS_TOPK_ROUTE_SELECT 1u
+#define GS_TOPK_ROUTE_FULL_SORT 2u
+#define GS_TOPK_ROUTE_SINGLE_TILE 3u
+/* gs_topk_last report words */
+#define GS_TOPK_R_ROUTE 0      /* GS_TOPK_ROUTE_* of the last call; the words below are zero unless it is GS_TOPK_ROUTE_SELECT */
+#define GS_TOPK_R_THRESHOLD 1  /* T: the k-th element's key as sortable bits (unsigned order = key order) */
+#define GS_TOPK_R_IN_FRONT 2   /* elements strictly in front of T in the requested order (< k) */
+#define GS_TOPK_R_EQUAL 3      /* elements equal to T (in_front + equal >= k) */
+#define GS_TOPK_R_TAKEN 4      /* how many of those were taken: k - in_front */
+#define GS_TOPK_R_CANDIDATES 5 /* elements left after the first level: those that share T's top 16 bits */
+#define GS_TOPK_R_LEVEL2 6     /* 1: the second level ran (always on the select route) */
+#define GS_TOPK_R_RANGES 7     /* workgroup ranges of level 1 | level 2 << 16 */
+#define GS_TOPK_REPORT_WORDS 8
+/* value_bytes 0 (keys only), 4 or 8, as gs_onesweep_create; 1 <= max_k <= max_keys <= GS_MAX_KEYS (GS_ERR_SIZE).  Synchronous
+ * (allocates gs_topk_temp_bytes of device memory). */
+gs_status gs_topk_create(gs_topk** out, uint32_t max_keys, uint32_t max_k, gs_mode mode, uint32_t value_bytes);
+gs_status gs_topk_destroy(gs_topk* h);
+/* Host only.  With e = 4 + value_bytes, c = max(max_k, min(max_keys, 32 768)) (what the embedded engine sorts at most) and
+ * every term rounded up to 256 bytes:
+ *     max_keys x e            candidate buffer: the elements that share T's top 16 bits, all of them in the worst case
+ *   + c x e                   the embedded engine's second buffer
+ *   + gs_onesweep_temp_bytes(c)
+ *   + 256 x 131 088           histogram slices: 256 workgroup ranges x (65 536 packed 16-bit counters + 16 bytes)
+ *   + 3 x 262 144             two recount histograms and the summed histogram
+ *   + 4096 + 256              per-range counts of both levels, control block
+ * Sort-and-slice needs gs_onesweep_temp_bytes(max_keys) + 2 x max_keys x e. */
+size_t gs_topk_temp_bytes(uint32_t max_keys, uint32_t max_k, uint32_t value_bytes);
+gs_status gs_topk_select_keys(gs_topk* h, const void* d_keys, uint32_t n, uint32_t k, void* d_out_keys, gs_key_type key_type,
+                              gs_order order, void* stream);
+/* d_vals == NULL on a handle with 4-byte values: the values are the input positions 0 .. n - 1. */
+gs_status gs_topk_select_pairs(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t n, uint32_t k, void* d_out_keys,
+                               void* d_out_vals, gs_key_type key_type, gs_order order, void* stream);
+/* Synchronises `stream` and reports the last call: GS_OK, GS_ERR_HIP (a count of the selection did not add up — cannot happen; no
+ * store leaves its buffer — or the engine refused the final sort), or what gs_onesweep_check says about the final sort
+ * (GS_ERR_TIMEOUT). */
+gs_status gs_topk_check(gs_topk* h, void* stream);
+/* Synchronous diagnostics of the last call: report[GS_TOPK_R_*], words >= GS_TOPK_REPORT_WORDS. */
+gs_status gs_topk_last(gs_topk* h, uint32_t* report, uint32_t words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
