@@ -1,5 +1,5 @@
 // gpusort_mgpu.hpp — multi-GPU sharded sort behind the C-ABI (include/gpusort.h, "multi-GPU" section); part of
-// the gpusort_capi.hip translation unit (it drives the handle's internals: prologue, pass launchers, sort_impl).
+// the gpusort_capi.hip translation unit (it drives the handle's internals in onesweep_host.hpp: prologue, pass launchers, sort_impl).
 //
 // One process per GPU.  BASELINE.json configs[3]: "MSD bucket split + RCCL Alltoallv across 8 MI355X then per-GPU
 // OneSweep"; the reference has no multi-GPU code.  Pipeline of gs_onesweep_sort_sharded, everything
@@ -254,7 +254,12 @@ gs_status mgpu_plan(gs_mgpu* c, const void* d_keys, uint32_t n, gs_key_type kt, 
     const uint32_t nbins = fine ? 4096u : gs::RADIX;
     gs_status st = GS_OK;
     if (c->debug_fail == 1) st = GS_ERR_HIP;  // test hook: as if the histogram launch had failed
-    if (st == GS_OK && n) st = fine ? prologue(h, d_keys, n, kt, s, 2, 2, pp) : prologue(h, d_keys, n, kt, s, 3, 1, pp);
+    if (st == GS_OK && n) {
+        PrologueIn in;  // fine: bytes 2 and 3 (row 1 = the 12-bit prefix); else the top byte
+        in.first_pass = fine ? 2 : 3;
+        in.num_passes = fine ? 2 : 1;
+        st = prologue(h, d_keys, n, kt, s, in, pp);
+    }
     if (st == GS_OK && n) {
         hipLaunchKernelGGL(gs::msd_fold_kernel, dim3(nbins / 256), dim3(256), 0, s, h->slab + SLAB_HIST, nbins, c->d_hist);
         if (fine) st = hand_back_hist(h, s);  // no pass follows this prologue
@@ -414,7 +419,7 @@ gs_status gs_onesweep_sort_sharded(gs_mgpu* c, const void* d_keys, const void* d
     //  returning early here would leave the peers waiting in the all-gather)
     if (!c || !d_out_keys || !out_n || misaligned(d_out_keys)) return GS_ERR_ARG;
     if (n != 0 && (!d_keys || misaligned(d_keys))) return GS_ERR_ARG;
-    if ((int)kt < 0 || (int)kt > 2) return GS_ERR_ARG;
+    if (!is_key32_type(kt)) return GS_ERR_ARG;
     if (n > c->shard_keys) return GS_ERR_SIZE;
     const uint32_t vb = c->value_bytes;
     if (vb) {

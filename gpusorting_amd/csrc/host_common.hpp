@@ -1,0 +1,67 @@
+// host_common.hpp — part of the gpusort_capi.hip translation unit: what every host file of the C-ABI shares — the HIP error
+// macro, the argument predicates, small arithmetic, and the device scratch word(s) of the diagnostic entries.
+#include <array>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <utility>
+
+namespace {
+
+thread_local int g_last_hip_error = 0;
+
+#define GS_HIP(call)                                   \
+    do {                                               \
+        hipError_t e_ = (call);                        \
+        if (e_ != hipSuccess) {                        \
+            g_last_hip_error = (int)e_;                \
+            return GS_ERR_HIP;                         \
+        }                                              \
+    } while (0)
+
+inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+
+bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+// ---- argument predicates: every test of a key type or an order in the host files goes through these ----
+inline bool valid_key_type(gs_key_type kt) { return (int)kt >= 0 && (int)kt <= 5; }
+inline bool is_key32_type(gs_key_type kt) { return (int)kt >= 0 && (int)kt <= 2; }  // what the 32-bit-only entries accept
+inline bool is_key64(gs_key_type kt) { return (int)kt >= 3; }
+inline bool valid_order(gs_order order) { return order == GS_ORDER_ASCENDING || order == GS_ORDER_DESCENDING; }
+
+// compute units of the device (read once per process; 256 if it cannot be read)
+uint32_t cu_count() {
+    static const uint32_t cus = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        return (uint32_t)v;
+    }();
+    return cus;
+}
+
+// Device scratch of a diagnostic entry (a counter or a small report): allocated and zeroed on the stream, read back with a wait,
+// freed when the entry returns — whichever way it returns.
+struct DeviceScratch {
+    void* d = nullptr;
+    const size_t bytes;
+    explicit DeviceScratch(size_t n) : bytes(n) {}
+    DeviceScratch(const DeviceScratch&) = delete;
+    ~DeviceScratch() {
+        if (d) (void)hipFree(d);
+    }
+    template <class T> T* as() const { return static_cast<T*>(d); }
+    gs_status alloc_zeroed(hipStream_t s) {
+        GS_HIP(hipMalloc(&d, bytes));
+        GS_HIP(hipMemsetAsync(d, 0, bytes, s));
+        return GS_OK;
+    }
+    gs_status read_back(void* host, hipStream_t s) {
+        GS_HIP(hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, s));
+        GS_HIP(hipStreamSynchronize(s));
+        return GS_OK;
+    }
+};
+
+}  // namespace

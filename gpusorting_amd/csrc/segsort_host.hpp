@@ -1,0 +1,190 @@
+// segsort_host.hpp — part of the gpusort_capi.hip translation unit: the gs_segsort handle (segsort_kernels.hpp) and its entries.
+// Replaces SplitSortAllocateTempMemory / SplitSortPairs / SplitSortFreeTempMemory (GPUSortingCUDA/SegSort/SplitSort/SplitSort.cuh:674-709).
+struct gs_segsort {
+    uint32_t max_keys, max_segments;
+    gs_mode mode;
+    uint32_t value_bytes;
+    gs_onesweep* engine = nullptr;  // long segments (and the rank mode of the workgroup classes)
+    uint32_t* ctl = nullptr;        // gs::SEGC_WORDS control words, then the class lists (max_segments words)
+    uint32_t* pinned = nullptr;     // read-backs: control block + SEG_LONG_CHUNK list entries
+    bool long_failed = false;       // a long segment's engine call failed on the host side
+};
+
+static_assert(GS_SEGSORT_CLASSES == gs::SEG_CLASSES, "header and kernels agree on the classes");
+namespace {
+constexpr uint32_t SEG_LONG_CHUNK = 1024;  // long-list entries per read-back
+inline uint32_t* seg_list(const gs_segsort* h) { return h->ctl + gs::SEGC_WORDS; }
+// the control block -> h->pinned (synchronises)
+gs_status read_ctl(gs_segsort* h, hipStream_t s) {
+    GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, gs::SEGC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GS_HIP(hipStreamSynchronize(s));
+    return GS_OK;
+}
+
+// workgroups of a fixed-grid class kernel: what the chip holds at once (waves and LDS), never more than the class can have segments
+uint32_t seg_grid(uint32_t bound, uint32_t waves, size_t lds_bytes) {
+    uint32_t per_cu = 32u / waves;
+    const uint32_t by_lds = (uint32_t)((160u * 1024u) / lds_bytes);
+    if (by_lds < per_cu) per_cu = by_lds;
+    if (per_cu == 0) per_cu = 1;
+    const uint32_t g = cu_count() * per_cu;
+    return bound < g ? (bound ? bound : 1u) : g;
+}
+
+gs_status segsort_impl(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t n, const uint32_t* d_offsets,
+                       uint32_t num_segments, uint32_t max_len, gs_key_type kt, gs_order order, hipStream_t s, bool pairs) {
+    if (!h || !d_keys || !d_offsets || misaligned(d_keys) || (reinterpret_cast<uintptr_t>(d_offsets) & 3u) || !is_key32_type(kt) || !valid_order(order))
+        return GS_ERR_ARG;  // (64-bit key types: out of scope)
+    if (pairs != (h->mode == GS_MODE_PAIRS)) return GS_ERR_MODE;
+    if (pairs && (!d_vals || misaligned(d_vals))) return GS_ERR_ARG;
+    if (n == 0 || n > h->max_keys || num_segments == 0 || num_segments > h->max_segments) return GS_ERR_SIZE;
+    const uint32_t vb = h->value_bytes;
+    const bool allow_long = max_len == 0u || max_len > gs::seg_max_lds(vb);
+    if (allow_long && (!d_alt_keys || misaligned(d_alt_keys) || (pairs && (!d_alt_vals || misaligned(d_alt_vals))))) return GS_ERR_ARG;
+    if (!SEG_BUILT) return GS_ERR_MODE;  // this build flavour has no segmented-sort kernels
+    const uint32_t top = allow_long ? gs::SEG_CLASS_LONG : gs::seg_class_of(max_len, vb);  // the highest class a segment can fall in
+    const uint32_t desc = order == GS_ORDER_DESCENDING ? 1u : 0u;
+    uint32_t* keys = static_cast<uint32_t*>(d_keys);
+    h->long_failed = false;
+    hipLaunchKernelGGL(gs::seg_reset_kernel, dim3(1), dim3(64), 0, s, h->ctl);
+    const uint32_t seg_blocks = div_up(num_segments, 256);
+    hipLaunchKernelGGL(gs::seg_classify_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, n, vb, max_len, h->ctl);
+    if (top >= 2) hipLaunchKernelGGL(gs::seg_fill_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, vb, max_len, h->ctl, seg_list(h));
+    const SegVbLaunchers& f = seg_vb(vb);
+    if (top >= 1) f.packed(s, div_up(num_segments, 64), keys, d_vals, d_offsets, num_segments, max_len, (uint32_t)kt, desc, h->ctl);
+    // a class whose shortest segment has m elements holds at most n / m segments
+    auto bound = [&](uint32_t min_len) { const uint32_t b = n / min_len; return b < num_segments ? b : num_segments; };
+    if (top >= 2 && n > gs::SEG_PACK_MAX)
+        f.wave(s, seg_grid(bound(gs::SEG_PACK_MAX + 1), 1, gs::SEG_WAVE_MAX * (8 + vb)), keys, d_vals, d_offsets, seg_list(h), h->ctl, num_segments, (uint32_t)kt, desc);
+    for (uint32_t c = 3; c <= 7 && c <= top; ++c) {
+        const uint32_t min_len = gs::SEG_CLASS_MAX[c - 1] + 1;
+        if (n < min_len || gs::SEG_CLASS_MAX[c] > gs::seg_max_lds(vb)) continue;
+        const Shape sh = g_small_class[c - 3];
+        const SegWgLauncher wg = seg_wg_launcher((int)c - 3, h->engine->rank_mode, vb, (int)kt);
+        if (!wg) return GS_ERR_MODE;
+        const size_t lds = (size_t)sh.threads * sh.kpt * (4 + vb) + (size_t)sh.threads / 64 * gs::RADIX * 4 + 64;
+        wg(s, SEG_WG_LOOP(sh.threads, sh.kpt) ? seg_grid(bound(min_len), (uint32_t)sh.threads / 64, lds) : bound(min_len), keys, d_vals, d_offsets, seg_list(h), h->ctl, num_segments, c, desc);
+    }
+    GS_HIP(hipGetLastError());
+    if (!allow_long || n <= gs::seg_max_lds(vb)) return GS_OK;
+    // ---- long segments: the one host wait.  Control block + the head of the long list (it starts the list array) ----
+    const uint32_t most = bound(gs::seg_max_lds(vb) + 1);
+    uint32_t got = most < SEG_LONG_CHUNK ? most : SEG_LONG_CHUNK;
+    GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, (gs::SEGC_WORDS + got) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GS_HIP(hipStreamSynchronize(s));
+    if (h->pinned[gs::SEGC_STATUS] & gs::SEG_ST_ARG) return GS_OK;  // reported by gs_segsort_check; nothing was sorted
+    const uint32_t count = h->pinned[gs::SEGC_COUNT + gs::SEG_CLASS_LONG];
+    if (count > most) return GS_ERR_HIP;  // (cannot happen: the classify kernel counted more long segments than n holds)
+    char* vals = static_cast<char*>(d_vals);
+    char* alt_vals = static_cast<char*>(d_alt_vals);
+    uint32_t* alt_keys = static_cast<uint32_t*>(d_alt_keys);
+    for (uint32_t first = 0; first < count; first += SEG_LONG_CHUNK) {
+        const uint32_t chunk = count - first < SEG_LONG_CHUNK ? count - first : SEG_LONG_CHUNK;
+        if (first != 0) {
+            GS_HIP(hipMemcpyAsync(h->pinned + gs::SEGC_WORDS, seg_list(h) + first, chunk * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            GS_HIP(hipStreamSynchronize(s));
+        }
+        // the chunk's offsets: segment numbers come from the device's own (validated) classification
+        uint32_t* bounds = h->pinned + gs::SEGC_WORDS + SEG_LONG_CHUNK;
+        for (uint32_t i = 0; i < chunk; ++i) {
+            const uint32_t seg = h->pinned[gs::SEGC_WORDS + i];
+            if (seg >= num_segments) return GS_ERR_HIP;
+            GS_HIP(hipMemcpyAsync(bounds, d_offsets + seg, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            GS_HIP(hipStreamSynchronize(s));
+            const uint32_t start = bounds[0], end = bounds[1];
+            if (end > n || start >= end) return GS_ERR_HIP;
+            // the engine wants 16-byte aligned buffers: it sorts [start + head, end), seg_merge_head_kernel merges the head in
+            const uint32_t head = (4u - (start & 3u)) & 3u, a = start + head, len = end - start;
+            const gs_status st = engine_sort(h->engine, pairs, keys + a, vals + (size_t)a * vb, alt_keys + a, alt_vals + (size_t)a * vb, len - head, kt, order, s);
+            if (st != GS_OK) { h->long_failed = true; return st; }
+            if (head != 0) {
+                const uint32_t grid = div_up(len, 256 * 8);
+                f.merge_head(s, grid < 4096 ? grid : 4096, keys, d_vals, alt_keys, d_alt_vals, start, head, len, (uint32_t)kt, desc);
+                GS_HIP(hipMemcpyAsync(keys + start, alt_keys + start, (size_t)len * 4, hipMemcpyDeviceToDevice, s));
+                if (pairs) GS_HIP(hipMemcpyAsync(vals + (size_t)start * vb, alt_vals + (size_t)start * vb, (size_t)len * vb, hipMemcpyDeviceToDevice, s));
+            }
+        }
+    }
+    return GS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t gs_segsort_temp_bytes(uint32_t max_keys, uint32_t max_segments) {
+    return gs_onesweep_temp_bytes(max_keys) + ((size_t)gs::SEGC_WORDS + max_segments) * sizeof(uint32_t);
+}
+uint32_t gs_segsort_class_of(uint32_t length, gs_mode mode, uint32_t value_bytes) {
+    return gs::seg_class_of(length, mode == GS_MODE_PAIRS ? value_bytes : 0);
+}
+uint32_t gs_segsort_max_lds_segment(gs_mode mode, uint32_t value_bytes) { return gs::seg_max_lds(mode == GS_MODE_PAIRS ? value_bytes : 0); }
+
+gs_status gs_segsort_create(gs_segsort** out, uint32_t max_keys, uint32_t max_segments, gs_mode mode, uint32_t value_bytes) {
+    if (!out) return GS_ERR_ARG;
+    *out = nullptr;
+    if (max_segments == 0 || max_segments > GS_MAX_KEYS) return GS_ERR_SIZE;
+    gs_onesweep* engine = nullptr;
+    const gs_status st = gs_onesweep_create(&engine, max_keys, mode, value_bytes);  // checks max_keys, mode and value width
+    if (st != GS_OK) return st;
+    gs_segsort* h = new (std::nothrow) gs_segsort();
+    if (!h) { (void)gs_onesweep_destroy(engine); return GS_ERR_ARG; }
+    h->max_keys = max_keys;
+    h->max_segments = max_segments;
+    h->mode = mode;
+    h->value_bytes = value_bytes;
+    h->engine = engine;
+    hipError_t e = hipMalloc(&h->ctl, ((size_t)gs::SEGC_WORDS + max_segments) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(h->ctl, 0, gs::SEGC_WORDS * sizeof(uint32_t));  // gs_segsort_check may run before any sort
+    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, (gs::SEGC_WORDS + SEG_LONG_CHUNK + 2) * sizeof(uint32_t), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        g_last_hip_error = (int)e;
+        (void)gs_segsort_destroy(h);
+        return GS_ERR_HIP;
+    }
+    *out = h;
+    return GS_OK;
+}
+
+gs_status gs_segsort_destroy(gs_segsort* h) {
+    if (!h) return GS_ERR_ARG;
+    if (h->pinned) (void)hipHostFree(h->pinned);
+    if (h->ctl) (void)hipFree(h->ctl);
+    if (h->engine) (void)gs_onesweep_destroy(h->engine);
+    delete h;
+    return GS_OK;
+}
+
+gs_status gs_segsort_sort_keys(gs_segsort* h, void* d_keys, void* d_alt, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments,
+                               uint32_t max_segment_len, gs_key_type key_type, gs_order order, void* stream) {
+    return segsort_impl(h, d_keys, nullptr, d_alt, nullptr, n, d_offsets, num_segments, max_segment_len, key_type, order,
+                        static_cast<hipStream_t>(stream), false);
+}
+
+gs_status gs_segsort_sort_pairs(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t n,
+                                const uint32_t* d_offsets, uint32_t num_segments, uint32_t max_segment_len, gs_key_type key_type, gs_order order,
+                                void* stream) {
+    return segsort_impl(h, d_keys, d_vals, d_alt_keys, d_alt_vals, n, d_offsets, num_segments, max_segment_len, key_type, order,
+                        static_cast<hipStream_t>(stream), true);
+}
+
+gs_status gs_segsort_check(gs_segsort* h, void* stream) {
+    if (!h) return GS_ERR_ARG;
+    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    if (rd != GS_OK) return rd;
+    const uint32_t st = h->pinned[gs::SEGC_STATUS];
+    if (st & gs::SEG_ST_ARG) return GS_ERR_ARG;
+    if (h->long_failed) return GS_ERR_HIP;
+    if (st & gs::SEG_ST_SIZE) return GS_ERR_SIZE;
+    return gs_onesweep_check(h->engine, stream);  // the long segments' sorts
+}
+
+gs_status gs_segsort_last_classes(gs_segsort* h, uint32_t* counts, uint32_t words, void* stream) {
+    if (!h || !counts || words < GS_SEGSORT_CLASSES + 1) return GS_ERR_ARG;
+    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    if (rd != GS_OK) return rd;
+    for (uint32_t c = 0; c < GS_SEGSORT_CLASSES; ++c) counts[c] = h->pinned[gs::SEGC_COUNT + c];
+    counts[GS_SEGSORT_CLASSES] = h->pinned[gs::SEGC_MAXLEN];
+    return GS_OK;
+}
+
+}  // extern "C"

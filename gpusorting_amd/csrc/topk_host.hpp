@@ -1,0 +1,217 @@
+// topk_host.hpp — part of the gpusort_capi.hip translation unit: the gs_topk handle (topk_kernels.hpp) and its entries.
+// No counterpart in the reference project.
+struct gs_topk {
+    uint32_t max_keys, max_k, sort_cap;
+    gs_mode mode;
+    uint32_t value_bytes;
+    gs_onesweep* engine = nullptr;  // the final sort of the k selected elements (and the single-tile route's sort)
+    char* dev = nullptr;            // one allocation: see topk_layout
+    uint32_t* pinned = nullptr;     // read-back of the control block
+    uint32_t last_route = GS_TOPK_ROUTE_NONE, last_flip = 0;
+    bool sort_failed = false;       // the engine refused a call on the host side
+};
+
+namespace {
+// Large k: there is no full-sort route — the select route serves every k <= n, at k = n it is a partition that keeps everything
+// followed by the sort; the measured rows for k = 2^20 are in DESIGN.md 3.9.  What the single-tile route takes is the one routing
+// constant: n up to the single-tile sort's capacity for the value width (one launch instead of eleven).
+inline uint32_t topk_single_max(uint32_t vb) { return gs::seg_max_lds(vb); }
+constexpr uint32_t TOPK_SINGLE_MAX_ANY = 32768;  // the largest of them (keys only): bounds the handle's sort capacity
+
+struct TopkLayout {
+    size_t ctl, extra, sums, rc, slices, cand_keys, cand_vals, alt_keys, alt_vals, total;
+};
+inline size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
+inline uint32_t topk_sort_cap(uint32_t max_keys, uint32_t max_k) {
+    const uint32_t small = max_keys < TOPK_SINGLE_MAX_ANY ? max_keys : TOPK_SINGLE_MAX_ANY;
+    return max_k > small ? max_k : small;
+}
+TopkLayout topk_layout(uint32_t max_keys, uint32_t max_k, uint32_t vb) {
+    TopkLayout l{};
+    const size_t cap = topk_sort_cap(max_keys, max_k);
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t a = at; at += up256(bytes); return a; };
+    l.ctl = take(gs::TKC_WORDS * 4u);
+    l.extra = take(2u * gs::TK_BINS * 4u);
+    l.sums = take(gs::TK_BINS * 4u);
+    l.rc = take(2u * 2u * gs::TK_MAX_RANGES * 4u);
+    l.slices = take((size_t)gs::TK_MAX_RANGES * gs::TK_SLICE_WORDS * 4u);
+    l.cand_keys = take((size_t)max_keys * 4u);
+    l.cand_vals = take((size_t)max_keys * vb);
+    l.alt_keys = take(cap * 4u);
+    l.alt_vals = take(cap * vb);
+    l.total = at;
+    return l;
+}
+
+using TkScatter = void (*)(hipStream_t, const uint32_t* src, const void* src_vals, uint32_t* ctl, uint32_t level, uint32_t kt, uint32_t flip,
+                           const uint32_t* rc, uint32_t* out, void* out_vals, uint32_t k, uint32_t* cand, void* cand_vals, uint32_t cand_cap);
+template <int VM>
+void launch_tk_scatter(hipStream_t s, const uint32_t* src, const void* src_vals, uint32_t* ctl, uint32_t level, uint32_t kt, uint32_t flip,
+                       const uint32_t* rc, uint32_t* out, void* out_vals, uint32_t k, uint32_t* cand, void* cand_vals, uint32_t cand_cap) {
+    hipLaunchKernelGGL((gs::tk_scatter_kernel<VM>), dim3(gs::TK_MAX_RANGES), dim3(gs::TK_THREADS), 0, s, src, src_vals, ctl, level, kt, flip, rc,
+                       out, out_vals, k, cand, cand_vals, cand_cap);
+}
+inline TkScatter tk_scatter(uint32_t vm) {
+    return vm == 0 ? launch_tk_scatter<0> : vm == 1 ? launch_tk_scatter<1> : vm == 4 ? launch_tk_scatter<4> : launch_tk_scatter<8>;
+}
+constexpr bool TK_BUILT = SEG_BUILT;  // the product build only, as the segmented sort
+
+// the control block -> h->pinned (synchronises)
+gs_status read_ctl(gs_topk* h, hipStream_t s) {
+    GS_HIP(hipMemcpyAsync(h->pinned, h->dev, gs::TKC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GS_HIP(hipStreamSynchronize(s));
+    return GS_OK;
+}
+
+bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+}
+
+gs_status topk_impl(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t n, uint32_t k, void* d_out_keys, void* d_out_vals,
+                    gs_key_type kt, gs_order order, hipStream_t s, bool pairs) {
+    if (!h || !d_keys || !d_out_keys || misaligned(d_keys) || misaligned(d_out_keys) || !is_key32_type(kt) || !valid_order(order))
+        return GS_ERR_ARG;  // (64-bit key types: out of scope)
+    if (pairs != (h->mode == GS_MODE_PAIRS)) return GS_ERR_MODE;
+    const uint32_t vb = h->value_bytes;
+    const bool pos = pairs && !d_vals;  // the value is the element's position
+    if (pairs && (!d_out_vals || misaligned(d_out_vals) || (pos ? vb != 4u : misaligned(d_vals)))) return GS_ERR_ARG;
+    if (n == 0 || n > h->max_keys || k == 0 || k > n || k > h->max_k) return GS_ERR_SIZE;
+    if (overlaps(d_keys, (size_t)n * 4u, d_out_keys, (size_t)k * 4u) ||
+        (pairs && !pos && overlaps(d_vals, (size_t)n * vb, d_out_vals, (size_t)k * vb)))
+        return GS_ERR_ARG;
+    if (!TK_BUILT) return GS_ERR_MODE;  // this build flavour has no selection
+    const TopkLayout l = topk_layout(h->max_keys, h->max_k, vb);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->dev + l.ctl);
+    uint32_t* cand_keys = reinterpret_cast<uint32_t*>(h->dev + l.cand_keys);
+    void* cand_vals = h->dev + l.cand_vals;
+    uint32_t* alt_keys = reinterpret_cast<uint32_t*>(h->dev + l.alt_keys);
+    void* alt_vals = h->dev + l.alt_vals;
+    const uint32_t* keys = static_cast<const uint32_t*>(d_keys);
+    uint32_t* out = static_cast<uint32_t*>(d_out_keys);
+    h->sort_failed = false;
+    h->last_route = GS_TOPK_ROUTE_NONE;
+    auto sort = [&](uint32_t* sk, void* sv, uint32_t m) {
+        const gs_status st = engine_sort(h->engine, pairs, sk, sv, alt_keys, alt_vals, m, kt, order, s);
+        if (st != GS_OK) h->sort_failed = true;
+        return st;
+    };
+    if (n <= topk_single_max(vb)) {  // one tile: sort a copy, emit the head
+        GS_HIP(hipMemcpyAsync(cand_keys, keys, (size_t)n * 4u, hipMemcpyDeviceToDevice, s));
+        if (pos) hipLaunchKernelGGL(gs::tk_iota_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, static_cast<uint32_t*>(cand_vals), n);
+        else if (pairs) GS_HIP(hipMemcpyAsync(cand_vals, d_vals, (size_t)n * vb, hipMemcpyDeviceToDevice, s));
+        GS_HIP(hipGetLastError());
+        const gs_status st = sort(cand_keys, cand_vals, n);
+        if (st != GS_OK) return st;
+        GS_HIP(hipMemcpyAsync(out, cand_keys, (size_t)k * 4u, hipMemcpyDeviceToDevice, s));
+        if (pairs) GS_HIP(hipMemcpyAsync(d_out_vals, cand_vals, (size_t)k * vb, hipMemcpyDeviceToDevice, s));
+        h->last_route = GS_TOPK_ROUTE_SINGLE_TILE;
+        return GS_OK;
+    }
+    uint32_t* extra = reinterpret_cast<uint32_t*>(h->dev + l.extra);
+    uint32_t* sums = reinterpret_cast<uint32_t*>(h->dev + l.sums);
+    uint32_t* rc = reinterpret_cast<uint32_t*>(h->dev + l.rc);
+    uint32_t* slices = reinterpret_cast<uint32_t*>(h->dev + l.slices);
+    const uint32_t flip = order == GS_ORDER_DESCENDING ? 0xffffffffu : 0u, ktu = (uint32_t)kt;
+    hipLaunchKernelGGL(gs::tk_init_kernel, dim3(2u * gs::TK_BINS / 4u / 256u), dim3(256), 0, s, ctl, extra, n, k);
+    for (uint32_t level = 0; level < 2; ++level) {
+        const uint32_t* src = level == 0 ? keys : cand_keys;
+        const void* src_vals = level == 0 ? d_vals : cand_vals;
+        // level 1 of the position mode makes the index the value; level 2 carries it as a 4-byte value
+        const uint32_t vm = !pairs ? 0u : (pos && level == 0) ? 1u : vb;
+        hipLaunchKernelGGL(gs::tk_hist_kernel, dim3(gs::TK_MAX_RANGES), dim3(gs::TK_THREADS), 0, s, src, ctl, level, ktu, flip, slices, extra);
+        hipLaunchKernelGGL(gs::tk_reduce_kernel, dim3(gs::TK_TABLE_WORDS / 256u), dim3(256), 0, s, slices, ctl, level, extra, sums);
+        hipLaunchKernelGGL(gs::tk_threshold_kernel, dim3(1), dim3(1024), 0, s, sums, ctl, level);
+        hipLaunchKernelGGL(gs::tk_rangecount_kernel, dim3(gs::TK_MAX_RANGES), dim3(256), 0, s, src, slices, ctl, level, ktu, flip, rc);
+        tk_scatter(vm)(s, src, src_vals, ctl, level, ktu, flip, rc, out, d_out_vals, k, cand_keys, cand_vals, h->max_keys);
+    }
+    GS_HIP(hipGetLastError());
+    h->last_route = GS_TOPK_ROUTE_SELECT;
+    h->last_flip = flip;
+    return sort(out, d_out_vals, k);
+}
+}  // namespace
+
+extern "C" {
+
+size_t gs_topk_temp_bytes(uint32_t max_keys, uint32_t max_k, uint32_t value_bytes) {
+    return topk_layout(max_keys, max_k, value_bytes).total + gs_onesweep_temp_bytes(topk_sort_cap(max_keys, max_k));
+}
+
+gs_status gs_topk_create(gs_topk** out, uint32_t max_keys, uint32_t max_k, gs_mode mode, uint32_t value_bytes) {
+    if (!out) return GS_ERR_ARG;
+    *out = nullptr;
+    if (max_keys == 0 || max_keys > GS_MAX_KEYS || max_k == 0 || max_k > max_keys) return GS_ERR_SIZE;
+    gs_onesweep* engine = nullptr;
+    const uint32_t cap = topk_sort_cap(max_keys, max_k);
+    const gs_status st = gs_onesweep_create(&engine, cap, mode, value_bytes);  // checks mode and value width
+    if (st != GS_OK) return st;
+    gs_topk* h = new (std::nothrow) gs_topk();
+    if (!h) { (void)gs_onesweep_destroy(engine); return GS_ERR_ARG; }
+    h->max_keys = max_keys;
+    h->max_k = max_k;
+    h->sort_cap = cap;
+    h->mode = mode;
+    h->value_bytes = mode == GS_MODE_PAIRS ? value_bytes : 0u;
+    h->engine = engine;
+    const TopkLayout l = topk_layout(max_keys, max_k, h->value_bytes);
+    hipError_t e = hipMalloc(&h->dev, l.total);
+    if (e == hipSuccess) e = hipMemset(h->dev + l.ctl, 0, gs::TKC_WORDS * sizeof(uint32_t));  // gs_topk_check may run before any call
+    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, gs::TKC_WORDS * sizeof(uint32_t), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        g_last_hip_error = (int)e;
+        (void)gs_topk_destroy(h);
+        return GS_ERR_HIP;
+    }
+    *out = h;
+    return GS_OK;
+}
+
+gs_status gs_topk_destroy(gs_topk* h) {
+    if (!h) return GS_ERR_ARG;
+    if (h->pinned) (void)hipHostFree(h->pinned);
+    if (h->dev) (void)hipFree(h->dev);
+    if (h->engine) (void)gs_onesweep_destroy(h->engine);
+    delete h;
+    return GS_OK;
+}
+
+gs_status gs_topk_select_keys(gs_topk* h, const void* d_keys, uint32_t n, uint32_t k, void* d_out_keys, gs_key_type key_type, gs_order order,
+                              void* stream) {
+    return topk_impl(h, d_keys, nullptr, n, k, d_out_keys, nullptr, key_type, order, static_cast<hipStream_t>(stream), false);
+}
+
+gs_status gs_topk_select_pairs(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t n, uint32_t k, void* d_out_keys, void* d_out_vals,
+                               gs_key_type key_type, gs_order order, void* stream) {
+    return topk_impl(h, d_keys, d_vals, n, k, d_out_keys, d_out_vals, key_type, order, static_cast<hipStream_t>(stream), true);
+}
+
+gs_status gs_topk_check(gs_topk* h, void* stream) {
+    if (!h) return GS_ERR_ARG;
+    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    if (rd != GS_OK) return rd;
+    if (h->sort_failed || (h->pinned[gs::TKC_STATUS] & gs::TK_ST_INTERNAL)) return GS_ERR_HIP;
+    return gs_onesweep_check(h->engine, stream);  // the final sort
+}
+
+gs_status gs_topk_last(gs_topk* h, uint32_t* report, uint32_t words, void* stream) {
+    if (!h || !report || words < GS_TOPK_REPORT_WORDS) return GS_ERR_ARG;
+    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    if (rd != GS_OK) return rd;
+    for (uint32_t i = 0; i < GS_TOPK_REPORT_WORDS; ++i) report[i] = 0;
+    report[GS_TOPK_R_ROUTE] = h->last_route;
+    if (h->last_route != GS_TOPK_ROUTE_SELECT) return GS_OK;
+    const uint32_t* l1 = h->pinned + gs::TKC_LEVEL;
+    const uint32_t* l2 = l1 + gs::TKL_WORDS;
+    report[GS_TOPK_R_THRESHOLD] = ((l1[gs::TKL_BIN] << 16) | l2[gs::TKL_BIN]) ^ h->last_flip;
+    report[GS_TOPK_R_IN_FRONT] = l1[gs::TKL_FRONT] + l2[gs::TKL_FRONT];
+    report[GS_TOPK_R_EQUAL] = l2[gs::TKL_EQUAL];
+    report[GS_TOPK_R_TAKEN] = l2[gs::TKL_TAKE];
+    report[GS_TOPK_R_CANDIDATES] = l1[gs::TKL_EQUAL];
+    report[GS_TOPK_R_LEVEL2] = 1u;  // the select route always runs both levels
+    report[GS_TOPK_R_RANGES] = l1[gs::TKL_RANGES] | (l2[gs::TKL_RANGES] << 16);
+    return GS_OK;
+}
+
+}  // extern "C"

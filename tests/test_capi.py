@@ -52,8 +52,11 @@ def test_library_reads_no_environment():
     if out.returncode != 0:
         pytest.skip("no nm on this box")
     assert "getenv" not in out.stdout
-    for f in ("gpusort_capi.hip", "gpusort_mgpu.hpp", "onesweep_kernels.hpp", "hybrid_kernels.hpp", "mid_kernels.hpp", "msd_kernels.hpp"):
-        assert "getenv" not in open(os.path.join(ROOT, "gpusorting_amd", "csrc", f)).read(), f
+    csrc = os.path.join(ROOT, "gpusorting_amd", "csrc")
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")))
+    assert "gpusort_capi.hip" in sources and len(sources) >= 6
+    for f in sources:
+        assert "getenv" not in open(os.path.join(csrc, f)).read(), f
 
 
 def test_options_structs_match_the_header_defaults(monkeypatch):
@@ -107,6 +110,32 @@ def test_argument_errors_without_touching_the_gpu():
     assert lib.gs_onesweep_destroy(None) == _lib.GS_ERR_ARG
     assert lib.gs_onesweep_temp_bytes(1 << 28) > 0
     assert lib.gs_onesweep_partition_size(0, 0) % 64 == 0
+
+
+def test_null_handle_is_an_argument_error_in_every_handle_entry():
+    """A null handle is refused with GS_ERR_ARG before anything else is looked at (every other argument is plausible)."""
+    from gpusorting_amd import _lib
+    lib = _lib.load()
+    buf = (C.c_uint32 * 4096)()
+    p, u32p = C.addressof(buf), C.cast(buf, C.POINTER(C.c_uint32))
+    calls = {
+        "gs_onesweep_global_histogram": (None, p, 1024, 0, u32p, None),
+        "gs_onesweep_scan": (None, p, 1024, 0, u32p, None),
+        "gs_onesweep_digit_pass": (None, p, p, None, None, 1024, 0, 0, 0, None),
+        "gs_onesweep_msd_prepare": (None, p, 1024, 0, u32p, None),
+        "gs_onesweep_msd_partition": (None, p, p, None, None, 1024, None),
+        "gs_onesweep_msd_fine_histogram": (None, p, 1024, 0, u32p, None),
+        "gs_onesweep_last_plan": (None, u32p, u32p, None),
+        "gs_onesweep_set_plan": (None, 1),
+        "gs_segsort_sort_keys": (None, p, p, 1024, p, 1, 0, 0, 0, None),
+        "gs_segsort_check": (None, None),
+        "gs_segsort_last_classes": (None, u32p, 4096, None),
+        "gs_topk_select_keys": (None, p, 1024, 8, p + 8192, 0, 0, None),
+        "gs_topk_check": (None, None),
+        "gs_topk_last": (None, u32p, 4096, None),
+    }
+    for name, args in calls.items():
+        assert getattr(lib, name)(*args) == _lib.GS_ERR_ARG, name
 
 
 def test_msd_splitters_match_oracle(oracle):
