@@ -17,4 +17,4 @@ from .onesweep import (  # noqa: F401
 from ._lib import GpuSortError  # noqa: F401
 from .functional import argsort, segmented_argsort, segmented_sort, segmented_sort_, sort, sort_, topk  # noqa: F401
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
-from .topk import TopK, topk_reference  # noqa: F401
+from .topk import TopK, topk_reference, topk_rows_reference  # noqa: F401

@@ -19,6 +19,7 @@ GS_MAX_KEYS = (1 << 30) - 1
 GS_PROFILE_SLOTS = 8
 GS_SEGSORT_CLASSES = 9
 GS_TOPK_REPORT_WORDS = 8
+GS_TOPK_ROWS_REPORT_WORDS = 8
 
 # every symbol include/gpusort.h declares: (name, restype, argtypes)
 _u32, _vp, _int = C.c_uint32, C.c_void_p, C.c_int
@@ -175,6 +176,10 @@ _PROTOS = [
     ("gs_topk_select_pairs", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _int, _int, _vp]),
     ("gs_topk_check", _int, [_vp, _vp]),
     ("gs_topk_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_topk_select_rows_keys", _int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _int, _int, _vp]),
+    ("gs_topk_select_rows_pairs", _int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _int, _int, _vp]),
+    ("gs_topk_rows_max_k", _u32, [_int, _u32]),
+    ("gs_topk_rows_last", _int, [_vp, _u32p, _u32, _vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

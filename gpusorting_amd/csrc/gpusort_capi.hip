@@ -17,11 +17,12 @@
 #include "hybrid_kernels.hpp"
 #include "segsort_kernels.hpp"
 #include "topk_kernels.hpp"
+#include "topk_rows_kernels.hpp"
 
 // One translation unit; one host file per concern, in this order (each may use what stands above it):
 #include "host_common.hpp"      // GS_HIP, argument predicates, div_up, cu_count, DeviceScratch
 #include "kernel_registry.hpp"  // launcher templates, which kernels a build flavour compiles
 #include "onesweep_host.hpp"    // gs_onesweep: slab sizing, prologue, routing, sort_impl; every gs_onesweep_* / gs_selftest_* / gs_debug_* entry
 #include "segsort_host.hpp"     // gs_segsort
-#include "topk_host.hpp"        // gs_topk
+#include "topk_host.hpp"        // gs_topk: the 1-D selection and the row-wise one
 #include "gpusort_mgpu.hpp"     // gs_mgpu, gs_onesweep_sort_sharded

@@ -2070,6 +2070,8 @@ constexpr uint32_t SMALL_TILE_MAX = 1024 * 32;    // largest single-tile sort (k
 // (STATUS: a sort of its own, `status` is its status word and is reset here) and of the segmented sort's workgroup classes
 // (segsort_kernels.hpp: one call per segment, a barrier between two calls).  The LDS is the body's own: a kernel that calls one
 // instantiation of it gets that instantiation's arrays.
+// A SECOND COPY of the pass loop below (one key word, keys already in registers) is tkr_tile_sort_passes in topk_rows_kernels.hpp: a
+// fix to the ranking, the prefix over waves and digits or the staging belongs in both.
 template <int SMALL_THREADS, int SMALL_KPT, int VB, int KT, int RANK, bool STATUS>
 __device__ __forceinline__ void tile_sort_body(uint32_t* keys, void* vals_, uint32_t n, uint32_t descending, uint32_t* status) {
     using V = typename ValT<VB>::type;

@@ -192,6 +192,70 @@ __global__ __launch_bounds__(64) void seg_packed_kernel(uint32_t* __restrict__ k
     }
 }
 
+// ---- the four ranking passes of the wave class (below) and of the row-wise top-k's wave route (topk_rows_kernels.hpp) -----------
+// On keys in registers: slot lane + r * 64 holds key[r] as sortable bits (and val[r]); rows: how many rows of 64 slots are in use; slots behind the end hold all-one dummies.  The tables are the calling wave's own.  Its
+// barriers are workgroup barriers: every wave of a workgroup that calls it must call it, and equally often.
+template <int VB>
+__device__ __forceinline__ void seg_wave_sort_passes(uint32_t (&key)[SEG_WAVE_MAX / 64], typename ValT<VB>::type (&val)[VB != 0 ? SEG_WAVE_MAX / 64 : 1],
+                                                     uint32_t rows, uint32_t lane, uint32_t* s_hist, uint32_t* s_stage,
+                                                     typename ValT<VB>::type* s_vstage) {
+    constexpr int KPT = SEG_WAVE_MAX / 64;
+#pragma unroll 1
+    for (uint32_t shift = 0; shift < 32u; shift += 8u) {
+        reinterpret_cast<uint4*>(s_hist)[lane] = uint4{0u, 0u, 0u, 0u};
+        __syncthreads();
+        uint32_t offp[KPT];
+#pragma unroll
+        for (int r = 0; r < KPT; ++r) {
+            offp[r] = 0;
+            if ((uint32_t)r < rows) {  // (uniform)
+                const uint32_t w = key[r];
+                const uint32_t d = (w >> shift) & 255u;
+                uint32_t acc_lo = 0, acc_hi = 0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const uint32_t B = (uint32_t)__builtin_amdgcn_sbfe((int32_t)w, shift + k, 1);
+                    const unsigned long long b = __builtin_amdgcn_ballot_w64(B != 0u);
+                    acc_lo = __builtin_amdgcn_bitop3_b32(acc_lo, (uint32_t)b, B, 0xF6);
+                    acc_hi = __builtin_amdgcn_bitop3_b32(acc_hi, (uint32_t)(b >> 32), B, 0xF6);
+                }
+                const uint32_t plo = ~acc_lo, phi = ~acc_hi;
+                const uint32_t below = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u));
+                const uint32_t total = __popc(plo) + __popc(phi);
+                const uint32_t pre = s_hist[d];
+                if (below == total - 1u) s_hist[d] = pre + total;
+                asm volatile("" ::: "memory");
+                offp[r] = pre + below;
+            }
+        }
+        __syncthreads();
+        {
+            const uint4 c = reinterpret_cast<const uint4*>(s_hist)[lane];
+            const uint32_t sum = c.x + c.y + c.z + c.w;
+            const uint32_t ex = wave_inclusive_scan(sum, lane) - sum;
+            reinterpret_cast<uint4*>(s_hist)[lane] = uint4{ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z};
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < KPT; ++r) {
+            if ((uint32_t)r < rows) {
+                const uint32_t pos = offp[r] + s_hist[(key[r] >> shift) & 255u];
+                s_stage[pos] = key[r];
+                if constexpr (VB != 0) s_vstage[pos] = val[r];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < KPT; ++r) {
+            if ((uint32_t)r < rows) {
+                key[r] = s_stage[lane + r * 64u];
+                if constexpr (VB != 0) val[r] = s_vstage[lane + r * 64u];
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // ---- wave class: SEG_PACK_MAX < length <= SEG_WAVE_MAX, one segment per wave ----------------------------------------------
 // One wave per workgroup (its barriers are wave barriers), up to four keys per lane in wave-striped order; four stable 8-bit passes,
 // each: 64-lane ballot multi-split on a 256-counter table, exclusive scan of the table (four counters per lane), staged by digit,
@@ -227,60 +291,7 @@ __global__ __launch_bounds__(64) void seg_wave_kernel(uint32_t* __restrict__ key
         }
 #pragma unroll
         for (int r = 0; r < KPT; ++r) key[r] = lane + r * 64u < len ? seg_to_bits(key[r], kt) : 0xffffffffu;
-#pragma unroll 1
-        for (uint32_t shift = 0; shift < 32u; shift += 8u) {
-            reinterpret_cast<uint4*>(s_hist)[lane] = uint4{0u, 0u, 0u, 0u};
-            __syncthreads();
-            uint32_t offp[KPT];
-#pragma unroll
-            for (int r = 0; r < KPT; ++r) {
-                offp[r] = 0;
-                if ((uint32_t)r < rows) {  // (uniform)
-                    const uint32_t w = key[r];
-                    const uint32_t d = (w >> shift) & 255u;
-                    uint32_t acc_lo = 0, acc_hi = 0;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const uint32_t B = (uint32_t)__builtin_amdgcn_sbfe((int32_t)w, shift + k, 1);
-                        const unsigned long long b = __builtin_amdgcn_ballot_w64(B != 0u);
-                        acc_lo = __builtin_amdgcn_bitop3_b32(acc_lo, (uint32_t)b, B, 0xF6);
-                        acc_hi = __builtin_amdgcn_bitop3_b32(acc_hi, (uint32_t)(b >> 32), B, 0xF6);
-                    }
-                    const uint32_t plo = ~acc_lo, phi = ~acc_hi;
-                    const uint32_t below = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u));
-                    const uint32_t total = __popc(plo) + __popc(phi);
-                    const uint32_t pre = s_hist[d];
-                    if (below == total - 1u) s_hist[d] = pre + total;
-                    asm volatile("" ::: "memory");
-                    offp[r] = pre + below;
-                }
-            }
-            __syncthreads();
-            {
-                const uint4 c = reinterpret_cast<const uint4*>(s_hist)[lane];
-                const uint32_t sum = c.x + c.y + c.z + c.w;
-                const uint32_t ex = wave_inclusive_scan(sum, lane) - sum;
-                reinterpret_cast<uint4*>(s_hist)[lane] = uint4{ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z};
-            }
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < KPT; ++r) {
-                if ((uint32_t)r < rows) {
-                    const uint32_t pos = offp[r] + s_hist[(key[r] >> shift) & 255u];
-                    s_stage[pos] = key[r];
-                    if constexpr (VB != 0) s_vstage[pos] = val[r];
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < KPT; ++r) {
-                if ((uint32_t)r < rows) {
-                    key[r] = s_stage[lane + r * 64u];
-                    if constexpr (VB != 0) val[r] = s_vstage[lane + r * 64u];
-                }
-            }
-            __syncthreads();
-        }
+        seg_wave_sort_passes<VB>(key, val, rows, lane, s_hist, s_stage, s_vstage);
 #pragma unroll
         for (int r = 0; r < KPT; ++r) {
             const uint32_t idx = lane + r * 64u;

@@ -13,7 +13,7 @@ from __future__ import annotations
 import torch
 
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
-from .topk import TopK, topk_reference  # noqa: F401
+from .topk import TopK, topk_reference, topk_rows_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
 
 _KEY_TYPE = {torch.int32: KEY_INT32, torch.float32: KEY_FLOAT32, torch.uint32: KEY_UINT32}
@@ -157,9 +157,13 @@ def _topk_handle(device: torch.device, n: int, k: int, key_type: int, order: int
 
 def topk(keys: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor | None = None, unsigned: bool = False):
     """The ``k`` largest (``largest=True``, as ``torch.topk``) or smallest elements of a 1-D tensor in sorted order, without sorting
-    the rest: returns ``(keys_k, indices_k)`` (int32 input positions) or, with ``values``, ``(keys_k, values_k)``.  The result is the
+    the rest: returns ``(keys_k, indices_k)`` (int32 input positions) or, with ``values``, ``(keys_k, values_k)``.  A 2-D tensor whose
+    last dimension is contiguous (``stride(1) == 1``, any ``stride(0) >= row_len``, so ``x[:, :row_len]`` works) is selected row by row
+    in one call, as ``torch.topk(x, k, dim=-1)``: ``[rows, k]`` keys and int32 positions within the row, or values.  The result is the
     head of this library's sort: floats by the order-preserving bit flip (-0 < +0, NaNs by bit pattern — NOT ``torch.topk``'s "NaN is
     largest"), ties by position (smallest: lowest positions first; largest: highest positions first).  The inputs are not written."""
+    if keys.dim() == 2:
+        return _topk_rows(keys, int(k), largest, values, unsigned)
     if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
         raise ValueError("keys must be a contiguous 1-D device tensor")
     if keys.dtype not in _KEY_TYPE:
@@ -180,4 +184,34 @@ def topk(keys: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor 
     with torch.cuda.device(keys.device):
         s = _topk_handle(keys.device, n, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
         s.select(keys, k, out_k, values, out_v, n=n)
+    return out_k, out_v
+
+
+def _topk_rows(keys: torch.Tensor, k: int, largest: bool, values: torch.Tensor | None, unsigned: bool):
+    """``topk`` on a 2-D tensor: one ``gs_topk_select_rows_*`` call; the handle is sized by the extent ``(rows - 1) * stride + row_len``."""
+    rows, row_len = keys.shape
+    if keys.device.type != "cuda" or rows == 0 or row_len == 0 or keys.stride(1) != 1 or (rows > 1 and keys.stride(0) < row_len):
+        raise ValueError("keys must be a non-empty 2-D device tensor with a contiguous last dimension and a row stride >= its row length")
+    if keys.dtype not in _KEY_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
+    if not 1 <= k <= row_len:
+        raise ValueError("1 <= k <= row length")
+    if keys.data_ptr() % 16:
+        raise ValueError("the first row must start on a 16-byte boundary")
+    stride = keys.stride(0) if rows > 1 else row_len
+    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    vb = 4
+    if values is not None:
+        # (the row stride of a single row is never used)
+        same_rows = values.stride(1) == 1 and (rows == 1 or values.stride(0) == keys.stride(0))
+        if values.shape != keys.shape or not same_rows or values.device != keys.device or values.data_ptr() % 16:
+            raise ValueError("values must match keys in shape, strides and device and start on a 16-byte boundary")
+        vb = values.element_size()
+        if vb not in (4, 8):
+            raise TypeError("values must be 4 or 8 bytes wide")
+    out_k = torch.empty((rows, k), dtype=keys.dtype, device=keys.device)
+    out_v = torch.empty((rows, k), dtype=torch.int32 if values is None else values.dtype, device=keys.device)
+    with torch.cuda.device(keys.device):
+        s = _topk_handle(keys.device, (rows - 1) * stride + row_len, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
+        s.select_rows(keys, rows, row_len, stride, k, out_k, values, out_v)
     return out_k, out_v

@@ -1,8 +1,8 @@
 """Top-k selection over the C-ABI (``gs_topk_*`` in include/gpusort.h): the first k elements of the sorted order — keys, and values or
 input positions — without sorting the rest.
 
-No counterpart in the reference project.  PyTorch is used only for device memory and the current HIP stream.  ``topk_reference`` is
-the pure-numpy statement of the semantics (tests and tools compare against it); it needs no torch and no GPU.
+No counterpart in the reference project.  PyTorch is used only for device memory and the current HIP stream.  ``topk_reference`` (and
+``topk_rows_reference`` for the row-wise calls, ``gs_topk_select_rows_*``) is the pure-numpy statement of the semantics (tests and tools compare against it); it needs no torch and no GPU.
 """
 from __future__ import annotations
 
@@ -19,6 +19,8 @@ ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 KEY_UINT32, KEY_INT32, KEY_FLOAT32 = 0, 1, 2
 ROUTE_NONE, ROUTE_SELECT, ROUTE_FULL_SORT, ROUTE_SINGLE_TILE = 0, 1, 2, 3
 _REPORT = ("route", "threshold", "in_front", "equal", "taken", "candidates", "level2", "ranges")
+ROWS_ROUTE_NONE, ROWS_ROUTE_WAVE, ROWS_ROUTE_TILE, ROWS_ROUTE_STREAM, ROWS_ROUTE_LOOP = 0, 1, 2, 3, 4
+_ROWS_REPORT = ("route", "rows", "row_len", "k", "status", "reads")
 
 
 def topk_reference(keys: np.ndarray, k: int, values: np.ndarray | None = None, key_type: int = KEY_UINT32, descending: bool = False):
@@ -35,6 +37,25 @@ def topk_reference(keys: np.ndarray, k: int, values: np.ndarray | None = None, k
     perm = perm[:k]
     vals = perm.astype(np.uint32) if values is None else np.ascontiguousarray(values)[perm]
     return keys[perm], vals
+
+
+def topk_rows_reference(keys2d: np.ndarray, k: int, values2d: np.ndarray | None = None, key_type: int = KEY_UINT32,
+                        descending: bool = False):
+    """``topk_reference`` applied to every row of a 2-D array: returns ``(keys[rows, k], values[rows, k])``; ``values2d=None``
+    returns the positions within the row (uint32)."""
+    keys2d = np.asarray(keys2d)
+    if keys2d.ndim != 2 or keys2d.shape[0] == 0:
+        raise ValueError("keys must be 2-D with at least one row")
+    if values2d is not None and np.asarray(values2d).shape != keys2d.shape:
+        raise ValueError("values must match keys in shape")
+    rows = [topk_reference(keys2d[r], k, None if values2d is None else np.asarray(values2d)[r], key_type, descending)
+            for r in range(keys2d.shape[0])]
+    return np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
+
+
+def rows_max_k(mode: int = MODE_KEYS_ONLY, value_bytes: int = 0) -> int:
+    """``gs_topk_rows_max_k``: the largest k the one-launch routes take for rows longer than LDS holds (host only)."""
+    return int(_lib.load().gs_topk_rows_max_k(mode, value_bytes))
 
 
 class TopK:
@@ -104,6 +125,55 @@ class TopK:
             st = self._lib.gs_topk_select_pairs(self._h, keys.data_ptr(), None if values is None else values.data_ptr(), n, k,
                                                 out_keys.data_ptr(), out_values.data_ptr(), self.key_type, self.order, s)
         check(st, "gs_topk_select")
+
+    def select_rows(self, keys, rows: int, row_len: int, row_stride: int, k: int, out_keys, values=None, out_values=None, stream=None) -> None:
+        """The first ``k`` of every row ``keys[r * row_stride : r * row_stride + row_len]`` (a 2-D or flat tensor; ``row_stride`` in
+        elements, any value >= ``row_len``) into ``out_keys[r * k : (r + 1) * k]`` (and ``out_values``) on the current stream.
+        ``values=None`` with ``out_values`` given (4-byte handle): the values are the positions within the row."""
+        import torch
+        from .onesweep import _require_cuda, _stream_ptr
+
+        def strided(t, name):  # an input: 1-D, or 2-D with any row stride; the last dimension contiguous
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() not in (1, 2) or t.stride(-1) != 1:
+                raise ValueError(f"{name} must be a 1-D or 2-D tensor on the GPU whose last dimension is contiguous")
+        strided(keys, "keys")
+        if values is not None:
+            strided(values, "values")
+        _require_cuda(out_keys, "out_keys")
+        if out_values is not None:
+            _require_cuda(out_values, "out_values")
+        if keys.element_size() != 4 or out_keys.element_size() != 4:
+            raise ValueError("keys must be 32-bit")
+        if (out_values is not None) != (self.mode == MODE_PAIRS):
+            raise ValueError("out_values must be given exactly when the handle was built with MODE_PAIRS")
+        rows, row_len, row_stride, k = int(rows), int(row_len), int(row_stride), int(k)
+        extent = (rows - 1) * row_stride + row_len if rows > 0 else 0
+
+        def room(t):  # elements reachable from the tensor's first one
+            return 0 if t.numel() == 0 else 1 + sum((n - 1) * st for n, st in zip(t.shape, t.stride()))
+        for t, need, name in ((keys, extent, "keys"), (values, extent, "values"), (out_keys, rows * k, "out_keys"),
+                              (out_values, rows * k, "out_values")):
+            if t is not None and room(t) < need:
+                raise ValueError(f"{name} holds {room(t)} elements, {need} are needed")
+        for t, name in ((values, "values"), (out_values, "out_values")):
+            if t is not None and t.element_size() != self.value_bytes:
+                raise ValueError(f"{name} must be {self.value_bytes} bytes wide for this handle")
+        s = _stream_ptr(stream)
+        if out_values is None:
+            st = self._lib.gs_topk_select_rows_keys(self._h, keys.data_ptr(), rows, row_len, row_stride, k, out_keys.data_ptr(),
+                                                    self.key_type, self.order, s)
+        else:
+            st = self._lib.gs_topk_select_rows_pairs(self._h, keys.data_ptr(), None if values is None else values.data_ptr(), rows, row_len,
+                                                     row_stride, k, out_keys.data_ptr(), out_values.data_ptr(), self.key_type, self.order, s)
+        check(st, "gs_topk_select_rows")
+
+    def rows_last(self, stream=None) -> dict:
+        """Diagnostics of the last row-wise call (synchronises): route, rows, row_len, k, status, reads (stream route: the most reads
+        of its row any row took)."""
+        from .onesweep import _stream_ptr
+        buf = (C.c_uint32 * _lib.GS_TOPK_ROWS_REPORT_WORDS)()
+        check(self._lib.gs_topk_rows_last(self._h, buf, _lib.GS_TOPK_ROWS_REPORT_WORDS, _stream_ptr(stream)), "gs_topk_rows_last")
+        return {name: int(buf[i]) for i, name in enumerate(_ROWS_REPORT)}
 
     def status(self, stream=None) -> int:
         """``gs_topk_check`` as a status code (synchronises)."""

@@ -515,6 +515,62 @@ gs_status gs_topk_check(gs_topk* h, void* stream);
 /* Synchronous diagnostics of the last call: report[GS_TOPK_R_*], words >= GS_TOPK_REPORT_WORDS. */
 gs_status gs_topk_last(gs_topk* h, uint32_t* report, uint32_t words, void* stream);
 
+/* ---- Row-wise top-k: the first k of every row of a [rows, row_len] matrix in one call, on the same handle ----
+ * Row r of the output is what gs_topk_select_keys / _pairs delivers for keys[r * row_stride .. r * row_stride + row_len) with the same
+ * k, key type and order, bit for bit: sorted, floats by the order-preserving bit flip, ties by position (ascending the lowest
+ * positions, in rising position; descending the exact reverse of the stable ascending result), values bit-copied.  d_vals == NULL on
+ * a handle with 4-byte values: the value is the element's position WITHIN ITS ROW (what torch.topk returns as indices).  The inputs
+ * are not written.  The output is dense, [rows, k] with row stride k; nothing behind element rows * k is touched.
+ *
+ * row_stride counts elements, for keys and values alike; any value >= row_len, it need not be a multiple of 4: only the base
+ * pointers must be 16-byte aligned, rows may start at any element.
+ *
+ * GS_ERR_ARG: null handle (before anything else is looked at), null or misaligned base pointer, 64-bit key type,
+ * row_stride < row_len, output overlapping input.  GS_ERR_MODE: pairs call on a keys-only handle or the reverse.  GS_ERR_SIZE:
+ * rows, row_len or k zero, k > row_len, k > max_k, (rows - 1) * row_stride + row_len > max_keys (in 64 bits).
+ *
+ * Asynchronous on `stream`, every launch enqueued up front, no host round trip, no kernel waits on another workgroup; a call can be
+ * captured into a graph.  gs_topk_check reports the call as it does a 1-D one.  No temp memory beyond gs_topk_temp_bytes on the
+ * one-launch routes (gs_topk_rows_last):
+ *   GS_TOPK_ROWS_ROUTE_WAVE    row_len <= 256: one wave per row, the row sorted in LDS, its head written; every k.
+ *   GS_TOPK_ROWS_ROUTE_TILE    row_len <= gs_segsort_max_lds_segment: one workgroup per row, the single-tile sort; every k.
+ *   GS_TOPK_ROWS_ROUTE_STREAM  longer rows, k <= gs_topk_rows_max_k: one workgroup per row, a radix select on LDS histograms:
+ *                              2 to 3 reads of the row (a 4th for a row in which more than gs_topk_rows_max_k elements share the
+ *                              top 24 bits of the k-th), the selected elements sorted in LDS, 1 write of k.
+ *   GS_TOPK_ROWS_ROUTE_LOOP    everything else, and few, very long rows whatever k is (row_len >= 2^19 and
+ *                              rows * (row_len + 7 * 2^19) <= 19 * row_len: 2 rows of 2^19, 4 of 2^20, 10 of 2^22; measured, DESIGN.md
+ *                              3.10): the 1-D select route enqueued row by row (rows x its eleven launches and final
+ *                              sort, one launch that gathers the rows' status: gs_topk_check and gs_topk_rows_last speak
+ *                              for every row).  With two rows or more and a row_stride or k that is no multiple of 4, rows and
+ *                              output rows pass through an aligned staging buffer of the handle: max_keys / 2 keys and
+ *                              min(max_k, max_keys / 2) outputs, its size fixed by the handle, allocated once by the first
+ *                              call that needs it and neither moved nor freed before gs_topk_destroy, so a captured graph stays
+ *                              valid whatever calls follow.  That first call allocates synchronously; made while `stream` is
+ *                              capturing it returns GS_ERR_MODE instead, launches nothing and leaves the capture intact: make
+ *                              one plain call of such a shape on the handle before capturing. */
+#define GS_TOPK_ROWS_ROUTE_NONE 0u
+#define GS_TOPK_ROWS_ROUTE_WAVE 1u
+#define GS_TOPK_ROWS_ROUTE_TILE 2u
+#define GS_TOPK_ROWS_ROUTE_STREAM 3u
+#define GS_TOPK_ROWS_ROUTE_LOOP 4u
+/* gs_topk_rows_last report words */
+#define GS_TOPK_ROWS_R_ROUTE 0   /* GS_TOPK_ROWS_ROUTE_* of the last row-wise call */
+#define GS_TOPK_ROWS_R_ROWS 1
+#define GS_TOPK_ROWS_R_ROW_LEN 2
+#define GS_TOPK_ROWS_R_K 3
+#define GS_TOPK_ROWS_R_STATUS 4  /* the device status word: 0, or 1 if a count did not add up (gs_topk_check: GS_ERR_HIP) */
+#define GS_TOPK_ROWS_R_READS 5   /* GS_TOPK_ROWS_ROUTE_STREAM: the most reads of its row any row took (2 .. 4); otherwise 0 */
+#define GS_TOPK_ROWS_REPORT_WORDS 8
+gs_status gs_topk_select_rows_keys(gs_topk* h, const void* d_keys, uint32_t rows, uint32_t row_len, uint32_t row_stride, uint32_t k,
+                                   void* d_out_keys, gs_key_type key_type, gs_order order, void* stream);
+gs_status gs_topk_select_rows_pairs(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t rows, uint32_t row_len,
+                                    uint32_t row_stride, uint32_t k, void* d_out_keys, void* d_out_vals, gs_key_type key_type,
+                                    gs_order order, void* stream);
+/* Host only: the largest k the one-launch routes take for rows longer than LDS holds (0 for an invalid mode or value width). */
+uint32_t gs_topk_rows_max_k(gs_mode mode, uint32_t value_bytes);
+/* Synchronous diagnostics of the last row-wise call: report[GS_TOPK_ROWS_R_*], words >= GS_TOPK_ROWS_REPORT_WORDS. */
+gs_status gs_topk_rows_last(gs_topk* h, uint32_t* report, uint32_t words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
