@@ -14,7 +14,7 @@ from .onesweep import (  # noqa: F401
     KEY_FLOAT32, KEY_FLOAT64, KEY_INT32, KEY_INT64, KEY_UINT32, KEY_UINT64, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING,
     GPUSortingConfig, OneSweep, OneSweepDispatcher, init_random, validate,
 )
-from ._lib import GpuSortError  # noqa: F401
+from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, GpuSortError  # noqa: F401
 from .functional import argsort, segmented_argsort, segmented_sort, segmented_sort_, sort, sort_, topk  # noqa: F401
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
 from .topk import TopK, topk_reference, topk_rows_reference  # noqa: F401

@@ -20,6 +20,8 @@ GS_PROFILE_SLOTS = 8
 GS_SEGSORT_CLASSES = 9
 GS_TOPK_REPORT_WORDS = 8
 GS_TOPK_ROWS_REPORT_WORDS = 8
+# gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs only
+KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16 = 6, 7, 8, 9
 
 # every symbol include/gpusort.h declares: (name, restype, argtypes)
 _u32, _vp, _int = C.c_uint32, C.c_void_p, C.c_int

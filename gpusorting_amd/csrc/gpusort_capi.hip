@@ -18,6 +18,7 @@
 #include "segsort_kernels.hpp"
 #include "topk_kernels.hpp"
 #include "topk_rows_kernels.hpp"
+#include "topk_rows16_kernels.hpp"
 
 // One translation unit; one host file per concern, in this order (each may use what stands above it):
 #include "host_common.hpp"      // GS_HIP, argument predicates, div_up, cu_count, DeviceScratch

@@ -29,6 +29,7 @@ bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) !
 inline bool valid_key_type(gs_key_type kt) { return (int)kt >= 0 && (int)kt <= 5; }
 inline bool is_key32_type(gs_key_type kt) { return (int)kt >= 0 && (int)kt <= 2; }  // what the 32-bit-only entries accept
 inline bool is_key64(gs_key_type kt) { return (int)kt >= 3; }
+inline bool is_key16(gs_key_type kt) { return (int)kt >= 6 && (int)kt <= 9; }  // 2-byte keys: the row-wise top-k entries only
 inline bool valid_order(gs_order order) { return order == GS_ORDER_ASCENDING || order == GS_ORDER_DESCENDING; }
 
 // compute units of the device (read once per process; 256 if it cannot be read)

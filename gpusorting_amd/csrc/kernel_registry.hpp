@@ -141,19 +141,23 @@ constexpr SegVbLaunchers seg_vb_launchers() {
         }};
 }
 
-// ---- row-wise top-k (topk_rows_kernels.hpp): VM 0 keys only, 1 positions, 4 / 8 value bytes ----
+// ---- row-wise top-k (topk_rows_kernels.hpp, topk_rows16_kernels.hpp): VM 0 keys only, 1 positions, 4 / 8 value bytes ----
 using TkrLauncher = void (*)(hipStream_t, uint32_t grid, const gs::TkrArgs& a);
-template <int VM>
+// K16 1: the kernel for 2-byte keys
+template <int VM, int K16>
 void launch_tkr_wave(hipStream_t s, uint32_t grid, const gs::TkrArgs& a) {
-    hipLaunchKernelGGL((gs::tkr_wave_kernel<VM>), dim3(grid), dim3(64 * gs::TKR_WAVE_ROWS), 0, s, a);
+    if constexpr (K16) hipLaunchKernelGGL((gs::tkr16_wave_kernel<VM>), dim3(grid), dim3(64 * gs::TKR_WAVE_ROWS), 0, s, a);
+    else hipLaunchKernelGGL((gs::tkr_wave_kernel<VM>), dim3(grid), dim3(64 * gs::TKR_WAVE_ROWS), 0, s, a);
 }
-template <int T, int K, int VM, int RANK>
+template <int T, int K, int VM, int RANK, int K16>
 void launch_tkr_tile(hipStream_t s, uint32_t grid, const gs::TkrArgs& a) {
-    hipLaunchKernelGGL((gs::tkr_tile_kernel<T, K, VM, RANK>), dim3(grid), dim3(T), 0, s, a);
+    if constexpr (K16) hipLaunchKernelGGL((gs::tkr16_tile_kernel<T, K, VM, RANK>), dim3(grid), dim3(T), 0, s, a);
+    else hipLaunchKernelGGL((gs::tkr_tile_kernel<T, K, VM, RANK>), dim3(grid), dim3(T), 0, s, a);
 }
-template <int VM>
+template <int VM, int K16>
 void launch_tkr_stream(hipStream_t s, uint32_t grid, const gs::TkrArgs& a) {
-    hipLaunchKernelGGL((gs::tkr_stream_kernel<VM, 0>), dim3(grid), dim3(gs::TKR_THREADS), 0, s, a);
+    if constexpr (K16) hipLaunchKernelGGL((gs::tkr16_stream_kernel<VM, 0>), dim3(grid), dim3(gs::TKR_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((gs::tkr_stream_kernel<VM, 0>), dim3(grid), dim3(gs::TKR_THREADS), 0, s, a);
 }
 constexpr int VM_OF[4] = {0, 1, 4, 8};  // value mode by vm index
 
@@ -247,8 +251,9 @@ constexpr bool mid_built(int cls, int vb, int kt) {
 // c runs on g_small_class[c] and takes the value widths that shape holds: classes 0-2 all, class 3 no 8-byte values, class 4 keys only
 constexpr bool SEG_BUILT = FULL && GS_EXP == 0;
 constexpr bool seg_built(int cls, int vb, int kt) { return SEG_BUILT && kt < 3 && small_built(cls, vb, kt); }
-// the selection's kernels (topk_kernels.hpp, topk_rows_kernels.hpp): the product build only, as the segmented sort.  The row-wise tile
-// kernel runs on g_small_class[c] with the value widths that shape holds (positions are 4-byte values)
+// the selection's kernels (topk_kernels.hpp, topk_rows_kernels.hpp, topk_rows16_kernels.hpp): the product build only, as the segmented
+// sort.  The row-wise tile kernel runs on g_small_class[c] with the value widths that shape holds (positions are 4-byte values), for
+// 4-byte and for 2-byte keys alike (the row-length borders of the routes are the same)
 constexpr bool TK_BUILT = SEG_BUILT;
 constexpr bool tkr_tile_built(int cls, int vm) { return TK_BUILT && small_built(cls, vm == 0 ? 0 : vm == 8 ? 8 : 4, 0); }
 
@@ -327,14 +332,15 @@ constexpr auto g_seg_vb = Table<3>::make([](auto v) -> SegVbLaunchers {
     else return SegVbLaunchers{nullptr, nullptr, nullptr};
 });
 
-using TkrTileTable = Table<5, 2, 4>;  // [workgroup class][rank mode][vm index]
-constexpr auto g_tkr_tile = TkrTileTable::make([](auto c, auto r, auto v) -> TkrLauncher {
-    if constexpr (tkr_tile_built(c, VM_OF[v])) return launch_tkr_tile<g_small_class[c].threads, g_small_class[c].kpt, VM_OF[v], r>;
+using TkrTileTable = Table<2, 5, 2, 4>;  // [2-byte keys][workgroup class][rank mode][vm index]
+constexpr auto g_tkr_tile = TkrTileTable::make([](auto k16, auto c, auto r, auto v) -> TkrLauncher {
+    if constexpr (tkr_tile_built(c, VM_OF[v])) return launch_tkr_tile<g_small_class[c].threads, g_small_class[c].kpt, VM_OF[v], r, k16>;
     else return nullptr;
 });
 struct TkrVmLaunchers { TkrLauncher wave, stream; };  // the kernels with one shape
-constexpr auto g_tkr_vm = Table<4>::make([](auto v) -> TkrVmLaunchers {
-    if constexpr (TK_BUILT) return TkrVmLaunchers{launch_tkr_wave<VM_OF[v]>, launch_tkr_stream<VM_OF[v]>};
+using TkrVmTable = Table<2, 4>;  // [2-byte keys][vm index]
+constexpr auto g_tkr_vm = TkrVmTable::make([](auto k16, auto v) -> TkrVmLaunchers {
+    if constexpr (TK_BUILT) return TkrVmLaunchers{launch_tkr_wave<VM_OF[v], k16>, launch_tkr_stream<VM_OF[v], k16>};
     else return TkrVmLaunchers{nullptr, nullptr};
 });
 
@@ -355,8 +361,10 @@ SmallLauncher small_launcher(uint32_t n, int rank, uint32_t vb, int kt) {
 SegWgLauncher seg_wg_launcher(int wg_cls, int rank, uint32_t vb, int kt) { return g_seg_wg[SegWgTable::index({wg_cls, rank, vb_index(vb), kt})]; }
 const SegVbLaunchers& seg_vb(uint32_t vb) { return g_seg_vb[vb_index(vb)]; }
 inline int vm_index(uint32_t vm) { return vm == 0 ? 0 : vm == 1 ? 1 : vm == 4 ? 2 : 3; }
-TkrLauncher tkr_tile_launcher(int wg_cls, int rank, uint32_t vm) { return g_tkr_tile[TkrTileTable::index({wg_cls, rank, vm_index(vm)})]; }
-const TkrVmLaunchers& tkr_vm(uint32_t vm) { return g_tkr_vm[vm_index(vm)]; }
+TkrLauncher tkr_tile_launcher(bool key16, int wg_cls, int rank, uint32_t vm) {
+    return g_tkr_tile[TkrTileTable::index({key16 ? 1 : 0, wg_cls, rank, vm_index(vm)})];
+}
+const TkrVmLaunchers& tkr_vm(bool key16, uint32_t vm) { return g_tkr_vm[TkrVmTable::index({key16 ? 1 : 0, vm_index(vm)})]; }
 MidLauncher mid_launcher(int cls, int rank, uint32_t vb, int kt) { return g_mid[MidTable::index({cls, rank, vb_index(vb), kt})]; }
 // ---- end of the kernel registry -------------------------------------------------------------------------------------
 

@@ -193,15 +193,16 @@ __global__ __launch_bounds__(64) void seg_packed_kernel(uint32_t* __restrict__ k
 }
 
 // ---- the four ranking passes of the wave class (below) and of the row-wise top-k's wave route (topk_rows_kernels.hpp) -----------
+// BITS: the key bits that are ranked, from bit 0 up (16: the two passes of the 16-bit row-wise top-k, topk_rows16_kernels.hpp).
 // On keys in registers: slot lane + r * 64 holds key[r] as sortable bits (and val[r]); rows: how many rows of 64 slots are in use; slots behind the end hold all-one dummies.  The tables are the calling wave's own.  Its
 // barriers are workgroup barriers: every wave of a workgroup that calls it must call it, and equally often.
-template <int VB>
+template <int VB, uint32_t BITS = 32u>
 __device__ __forceinline__ void seg_wave_sort_passes(uint32_t (&key)[SEG_WAVE_MAX / 64], typename ValT<VB>::type (&val)[VB != 0 ? SEG_WAVE_MAX / 64 : 1],
                                                      uint32_t rows, uint32_t lane, uint32_t* s_hist, uint32_t* s_stage,
                                                      typename ValT<VB>::type* s_vstage) {
     constexpr int KPT = SEG_WAVE_MAX / 64;
 #pragma unroll 1
-    for (uint32_t shift = 0; shift < 32u; shift += 8u) {
+    for (uint32_t shift = 0; shift < BITS; shift += 8u) {
         reinterpret_cast<uint4*>(s_hist)[lane] = uint4{0u, 0u, 0u, 0u};
         __syncthreads();
         uint32_t offp[KPT];

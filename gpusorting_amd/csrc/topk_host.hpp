@@ -150,7 +150,8 @@ gs_status topk_run(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t 
 // ---- row-wise selection (topk_rows_kernels.hpp) ---------------------------------------------------------------------------------
 // Routes by row length, then k: WAVE and TILE sort the row in LDS and take every k; STREAM takes k <= TKR_STAGE; LOOP, everything
 // else, is the 1-D select route enqueued row by row: rows x (its eleven launches, the final sort, one status launch), still without
-// a host round trip.
+// a host round trip.  The 2-byte key types (is_key16; these two entries only) take the same routes on the kernels of
+// topk_rows16_kernels.hpp, LOOP excepted.
 
 // The staging of the LOOP route, sized by the handle alone so that it is never regrown: a captured graph holds its address for as long
 // as the handle lives.  Only calls of two rows and more stage, and their rows are at most max_keys / 2 long
@@ -209,10 +210,11 @@ gs_status rows_loop(gs_topk* h, const uint32_t* keys, const char* vals, uint32_t
 
 gs_status rows_impl(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t rows, uint32_t row_len, uint32_t row_stride, uint32_t k,
                     void* d_out_keys, void* d_out_vals, gs_key_type kt, gs_order order, hipStream_t s, bool pairs) {
-    if (!h || !d_keys || !d_out_keys || misaligned(d_keys) || misaligned(d_out_keys) || !is_key32_type(kt) || !valid_order(order))
+    const bool key16 = is_key16(kt);  // 2-byte elements in d_keys and d_out_keys (topk_rows16_kernels.hpp)
+    if (!h || !d_keys || !d_out_keys || misaligned(d_keys) || misaligned(d_out_keys) || !(is_key32_type(kt) || key16) || !valid_order(order))
         return GS_ERR_ARG;  // (64-bit key types: out of scope)
     if (pairs != (h->mode == GS_MODE_PAIRS)) return GS_ERR_MODE;
-    const uint32_t vb = h->value_bytes;
+    const uint32_t vb = h->value_bytes, kb = key16 ? 2u : 4u;
     const bool pos = pairs && !d_vals;  // the value is the element's position in its row
     if (pairs && (!d_out_vals || misaligned(d_out_vals) || (pos ? vb != 4u : misaligned(d_vals)))) return GS_ERR_ARG;
     if (rows == 0 || row_len == 0 || k == 0 || k > row_len || k > h->max_k) return GS_ERR_SIZE;
@@ -220,7 +222,7 @@ gs_status rows_impl(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t
     const unsigned long long extent = (unsigned long long)(rows - 1u) * row_stride + row_len;
     if (extent > h->max_keys) return GS_ERR_SIZE;
     const size_t out_elems = (size_t)rows * k;
-    if (overlaps(d_keys, (size_t)extent * 4u, d_out_keys, out_elems * 4u) ||
+    if (overlaps(d_keys, (size_t)extent * kb, d_out_keys, out_elems * kb) ||
         (pairs && !pos && overlaps(d_vals, (size_t)extent * vb, d_out_vals, out_elems * vb)))
         return GS_ERR_ARG;
     if (!TK_BUILT) return GS_ERR_MODE;  // this build flavour has no selection
@@ -235,9 +237,12 @@ gs_status rows_impl(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t
     // 3.10): STREAM costs 0.415 ms per 2^20 elements of a row, LOOP 0.078 ms + 0.022 ms per 2^20 elements for every row; LOOP where
     // rows * (0.078 + 0.022 L) <= 0.415 L, in integers below, for the row lengths that were measured (2^19 and up)
     const bool few_long = row_len >= (1u << 19) && (unsigned long long)rows * ((unsigned long long)row_len + (7ull << 19)) <= 19ull * row_len;
+    // 2-byte keys have no LOOP route (the 1-D select is a 32-bit algorithm): every k <= TKR_STAGE of a long row takes STREAM, few, very
+    // long rows included (unmeasured there), and a larger k is refused before anything is launched
     const uint32_t route = row_len <= gs::SEG_WAVE_MAX ? GS_TOPK_ROWS_ROUTE_WAVE : row_len <= gs::seg_max_lds(vb) ? GS_TOPK_ROWS_ROUTE_TILE
-                           : k <= gs::TKR_STAGE && !few_long ? GS_TOPK_ROWS_ROUTE_STREAM : GS_TOPK_ROWS_ROUTE_LOOP;
+                           : k <= gs::TKR_STAGE && (key16 || !few_long) ? GS_TOPK_ROWS_ROUTE_STREAM : GS_TOPK_ROWS_ROUTE_LOOP;
     if (route == GS_TOPK_ROWS_ROUTE_LOOP) {
+        if (key16) return GS_ERR_SIZE;
         const gs_status st = rows_loop(h, static_cast<const uint32_t*>(d_keys), static_cast<const char*>(d_vals), rows, row_len, row_stride, k,
                                        static_cast<uint32_t*>(d_out_keys), static_cast<char*>(d_out_vals), kt, order, s, pairs);
         if (st == GS_OK) h->rows_route = route;
@@ -248,13 +253,13 @@ gs_status rows_impl(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t
     const uint32_t vm = !pairs ? 0u : pos ? 1u : vb;
     hipLaunchKernelGGL(gs::tkr_reset_kernel, dim3(1), dim3(64), 0, s, ctl);
     if (route == GS_TOPK_ROWS_ROUTE_WAVE) {
-        tkr_vm(vm).wave(s, div_up(rows, gs::TKR_WAVE_ROWS), a);
+        tkr_vm(key16, vm).wave(s, div_up(rows, gs::TKR_WAVE_ROWS), a);
     } else if (route == GS_TOPK_ROWS_ROUTE_TILE) {
-        const TkrLauncher f = tkr_tile_launcher((int)gs::seg_class_of(row_len, vb) - 3, h->engine->rank_mode, vm);
+        const TkrLauncher f = tkr_tile_launcher(key16, (int)gs::seg_class_of(row_len, vb) - 3, h->engine->rank_mode, vm);
         if (!f) return GS_ERR_MODE;
         f(s, rows, a);
     } else {
-        tkr_vm(vm).stream(s, rows, a);
+        tkr_vm(key16, vm).stream(s, rows, a);
     }
     GS_HIP(hipGetLastError());
     h->rows_route = route;

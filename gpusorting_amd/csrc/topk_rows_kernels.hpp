@@ -45,7 +45,7 @@ constexpr int TKR_SORT_KPT = 4;
 constexpr uint32_t TKR_STAGE = TKR_THREADS * TKR_SORT_KPT;  // staged (sel, position) pairs: the largest k of the stream kernel
 
 struct TkrArgs {
-    const uint32_t* keys;
+    const uint32_t* keys;  // (the 16-bit key types, topk_rows16_kernels.hpp: 2-byte elements behind keys and out_keys)
     const void* vals;
     uint32_t* out_keys;
     void* out_vals;
@@ -126,8 +126,8 @@ __global__ __launch_bounds__(64 * TKR_WAVE_ROWS) void tkr_wave_kernel(const TkrA
 // tile_sort_body loads from and stores to the array it sorts and a row must not be written: calling one shared function from both changed
 // the register allocation of the existing single-tile and segmented-sort kernels (4 to 17 more VGPRs, SGPR spills in the RANK 1 forms),
 // and those kernels stay as they are (tile_sort_body carries a note that points here: a fix to the passes belongs in both copies).
-// The LDS is this function's own.
-template <int SMALL_THREADS, int SMALL_KPT, int VB, int RANK>
+// The LDS is this function's own.  BITS: the key bits that are ranked, from bit 0 up (16: the two passes of topk_rows16_kernels.hpp).
+template <int SMALL_THREADS, int SMALL_KPT, int VB, int RANK, uint32_t BITS = 32u>
 __device__ __forceinline__ void tkr_tile_sort_passes(uint32_t (&key)[SMALL_KPT], typename ValT<VB>::type (&val)[VB != 0 ? SMALL_KPT : 1], uint32_t n) {
     using V = typename ValT<VB>::type;
     constexpr int KPT = SMALL_KPT, WAVES = SMALL_THREADS / 64;
@@ -140,7 +140,7 @@ __device__ __forceinline__ void tkr_tile_sort_passes(uint32_t (&key)[SMALL_KPT],
     const uint32_t my_base = wave * (64u * KPT) + lane;
     uint32_t* whist = s_whist + wave * RADIX;
 #pragma unroll 1
-    for (uint32_t shift_full = 0; shift_full < 32u; shift_full += 8) {
+    for (uint32_t shift_full = 0; shift_full < BITS; shift_full += 8) {
         const uint32_t shift = shift_full;
         auto dword = [&](int i) { return key[i]; };
         for (uint32_t i = tid; i < WAVES * RADIX; i += SMALL_THREADS) s_whist[i] = 0;

@@ -12,11 +12,16 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
-from .topk import TopK, topk_reference, topk_rows_reference  # noqa: F401
+from .topk import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, TopK, rows_max_k, topk_reference, topk_rows_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
 
 _KEY_TYPE = {torch.int32: KEY_INT32, torch.float32: KEY_FLOAT32, torch.uint32: KEY_UINT32}
+# 2-byte keys: the row-wise top-k only (torch.uint16 where this torch has it)
+_KEY16_TYPE = {torch.float16: KEY_FLOAT16, torch.bfloat16: KEY_BFLOAT16, torch.int16: KEY_INT16}
+if hasattr(torch, "uint16"):
+    _KEY16_TYPE[torch.uint16] = KEY_UINT16
 _cache: dict = {}
 
 
@@ -159,13 +164,17 @@ def topk(keys: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor 
     """The ``k`` largest (``largest=True``, as ``torch.topk``) or smallest elements of a 1-D tensor in sorted order, without sorting
     the rest: returns ``(keys_k, indices_k)`` (int32 input positions) or, with ``values``, ``(keys_k, values_k)``.  A 2-D tensor whose
     last dimension is contiguous (``stride(1) == 1``, any ``stride(0) >= row_len``, so ``x[:, :row_len]`` works) is selected row by row
-    in one call, as ``torch.topk(x, k, dim=-1)``: ``[rows, k]`` keys and int32 positions within the row, or values.  The result is the
-    head of this library's sort: floats by the order-preserving bit flip (-0 < +0, NaNs by bit pattern — NOT ``torch.topk``'s "NaN is
+    in one call, as ``torch.topk(x, k, dim=-1)``: ``[rows, k]`` keys and int32 positions within the row, or values.
+    2-D tensors may also hold 16-bit keys (float16, bfloat16, int16, uint16; ``unsigned=True`` on int16 storage selects uint16 keys): the
+    kernels read them at their own width.  There, a row longer than LDS holds takes ``k <= rows_max_k`` (``ValueError`` otherwise), and a
+    1-D tensor is a ``TypeError``: pass ``x[None, :]``.  The result is the head of this library's sort: floats by the order-preserving bit flip (-0 < +0, NaNs by bit pattern — NOT ``torch.topk``'s "NaN is
     largest"), ties by position (smallest: lowest positions first; largest: highest positions first).  The inputs are not written."""
     if keys.dim() == 2:
         return _topk_rows(keys, int(k), largest, values, unsigned)
     if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
         raise ValueError("keys must be a contiguous 1-D device tensor")
+    if keys.dtype in _KEY16_TYPE:
+        raise TypeError(f"a 1-D {keys.dtype} tensor is not taken: 16-bit keys are selected row-wise, pass the 2-D form x[None, :]")
     if keys.dtype not in _KEY_TYPE:
         raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
     n, k = keys.numel(), int(k)
@@ -192,14 +201,19 @@ def _topk_rows(keys: torch.Tensor, k: int, largest: bool, values: torch.Tensor |
     rows, row_len = keys.shape
     if keys.device.type != "cuda" or rows == 0 or row_len == 0 or keys.stride(1) != 1 or (rows > 1 and keys.stride(0) < row_len):
         raise ValueError("keys must be a non-empty 2-D device tensor with a contiguous last dimension and a row stride >= its row length")
-    if keys.dtype not in _KEY_TYPE:
-        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
+    key16 = keys.dtype in _KEY16_TYPE
+    if not key16 and keys.dtype not in _KEY_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys (int32, uint32, float32) and, row-wise, 16-bit keys "
+                        "(float16, bfloat16, int16, uint16)")
     if not 1 <= k <= row_len:
         raise ValueError("1 <= k <= row length")
     if keys.data_ptr() % 16:
         raise ValueError("the first row must start on a 16-byte boundary")
     stride = keys.stride(0) if rows > 1 else row_len
-    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    if key16:
+        kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    else:
+        kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
     vb = 4
     if values is not None:
         # (the row stride of a single row is never used)
@@ -209,6 +223,12 @@ def _topk_rows(keys: torch.Tensor, k: int, largest: bool, values: torch.Tensor |
         vb = values.element_size()
         if vb not in (4, 8):
             raise TypeError("values must be 4 or 8 bytes wide")
+    if key16:
+        # GS_ERR_SIZE of gs_topk_select_rows_* for 2-byte keys, stated here: they have no row-by-row route
+        lds_rows, max_k = _lib.load().gs_segsort_max_lds_segment(MODE_PAIRS, vb), rows_max_k(MODE_PAIRS, vb)
+        if row_len > lds_rows and k > max_k:
+            raise ValueError(f"16-bit keys: a row longer than {lds_rows} elements (with {vb}-byte values) takes k <= {max_k}, "
+                             f"got row length {row_len} and k = {k}")
     out_k = torch.empty((rows, k), dtype=keys.dtype, device=keys.device)
     out_v = torch.empty((rows, k), dtype=torch.int32 if values is None else values.dtype, device=keys.device)
     with torch.cuda.device(keys.device):

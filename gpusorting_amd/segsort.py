@@ -13,17 +13,30 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, check
 
 MODE_KEYS_ONLY, MODE_PAIRS = 0, 1
 ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 KEY_UINT32, KEY_INT32, KEY_FLOAT32 = 0, 1, 2
+KEY16_TYPES = (KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16)  # 2-byte keys: the row-wise top-k only (gs_topk_select_rows_*)
 SEGSORT_CLASSES = _lib.GS_SEGSORT_CLASSES
 
 
 def sortable_bits(keys: np.ndarray, key_type: int = KEY_UINT32) -> np.ndarray:
     """The uint32 pattern whose unsigned order is the key order (GPUSortingD3D12/Shaders/SortCommon.hlsl:134-154): signed keys flip
-    the sign bit, floats flip all bits of negatives too (-0 < +0, NaNs by bit pattern)."""
+    the sign bit, floats flip all bits of negatives too (-0 < +0, NaNs by bit pattern).  The 16-bit key types of the row-wise top-k
+    (6 .. 9: uint16, int16, float16, bfloat16) take 2-byte arrays, bfloat16 as its uint16 bit patterns, and return the same rule on
+    16 bits as uint16."""
+    if key_type in KEY16_TYPES:
+        k = np.ascontiguousarray(keys)
+        if k.dtype.itemsize != 2:
+            raise ValueError("the 16-bit key types take 2-byte elements (bfloat16 as its uint16 bit patterns)")
+        h = k.view(np.uint16)
+        if key_type == KEY_UINT16:
+            return h
+        if key_type == KEY_INT16:
+            return h ^ np.uint16(0x8000)
+        return h ^ np.where(h >> 15 != 0, np.uint16(0xFFFF), np.uint16(0x8000)).astype(np.uint16)
     u = np.ascontiguousarray(keys).view(np.uint32)
     if key_type == KEY_INT32:
         return u ^ np.uint32(0x80000000)

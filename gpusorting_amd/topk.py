@@ -12,7 +12,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .segsort import sortable_bits
+from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16  # noqa: F401
+from .segsort import KEY16_TYPES, sortable_bits
 
 MODE_KEYS_ONLY, MODE_PAIRS = 0, 1
 ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
@@ -27,7 +28,8 @@ def topk_reference(keys: np.ndarray, k: int, values: np.ndarray | None = None, k
     """The first ``k`` elements of the library's sorted order: stable argsort on the sortable bit pattern, reversed as a whole for
     descending (so ties go to the lowest positions ascending, to the highest descending), first ``k``.  Floats follow the
     order-preserving bit flip: -0 < +0, NaNs by bit pattern (not ``torch.topk``'s NaN rule).  Returns ``(keys_k, values_k)``;
-    ``values=None`` returns the input positions (uint32) as values."""
+    ``values=None`` returns the input positions (uint32) as values.  The 16-bit key types (``KEY_UINT16`` .. ``KEY_BFLOAT16``, row-wise
+    calls only on the device) take 2-byte arrays, bfloat16 as its uint16 bit patterns."""
     keys = np.ascontiguousarray(keys)
     if keys.ndim != 1 or not 1 <= k <= keys.size:
         raise ValueError("keys must be 1-D and 1 <= k <= n")
@@ -69,8 +71,8 @@ class TopK:
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type not in (KEY_UINT32, KEY_INT32, KEY_FLOAT32):
-            raise ValueError("the selection takes 32-bit keys only")
+        if key_type not in (KEY_UINT32, KEY_INT32, KEY_FLOAT32) + KEY16_TYPES:
+            raise ValueError("the selection takes 32-bit keys, and 16-bit keys (KEY_UINT16 .. KEY_BFLOAT16) in select_rows")
         self._lib = _lib.load()
         if device is not None:
             torch.cuda.set_device(device)
@@ -101,6 +103,8 @@ class TopK:
         """The first ``k`` of ``keys[:n]`` in this handle's order into ``out_keys[:k]`` (and ``out_values[:k]``) on the current stream.
         ``values=None`` with ``out_values`` given (4-byte handle): the values are the input positions.  Inputs are not written."""
         from .onesweep import _require_cuda, _require_room, _stream_ptr
+        if self.key_type in KEY16_TYPES:
+            raise ValueError("the 1-D selection takes 32-bit keys only: 16-bit keys go through select_rows (one row: rows=1)")
         _require_cuda(keys, "keys")
         _require_cuda(out_keys, "out_keys")
         if keys.element_size() != 4 or out_keys.element_size() != 4:
@@ -129,7 +133,9 @@ class TopK:
     def select_rows(self, keys, rows: int, row_len: int, row_stride: int, k: int, out_keys, values=None, out_values=None, stream=None) -> None:
         """The first ``k`` of every row ``keys[r * row_stride : r * row_stride + row_len]`` (a 2-D or flat tensor; ``row_stride`` in
         elements, any value >= ``row_len``) into ``out_keys[r * k : (r + 1) * k]`` (and ``out_values``) on the current stream.
-        ``values=None`` with ``out_values`` given (4-byte handle): the values are the positions within the row."""
+        ``values=None`` with ``out_values`` given (4-byte handle): the values are the positions within the row.  A handle of a 16-bit
+        key type takes 2-byte key tensors (float16, bfloat16, int16, uint16); a row longer than LDS holds with
+        ``k > rows_max_k`` is ``GS_ERR_SIZE`` there (no LOOP route)."""
         import torch
         from .onesweep import _require_cuda, _stream_ptr
 
@@ -142,8 +148,9 @@ class TopK:
         _require_cuda(out_keys, "out_keys")
         if out_values is not None:
             _require_cuda(out_values, "out_values")
-        if keys.element_size() != 4 or out_keys.element_size() != 4:
-            raise ValueError("keys must be 32-bit")
+        key_bytes = 2 if self.key_type in KEY16_TYPES else 4
+        if keys.element_size() != key_bytes or out_keys.element_size() != key_bytes:
+            raise ValueError(f"keys must be {8 * key_bytes}-bit for this handle's key type")
         if (out_values is not None) != (self.mode == MODE_PAIRS):
             raise ValueError("out_values must be given exactly when the handle was built with MODE_PAIRS")
         rows, row_len, row_stride, k = int(rows), int(row_len), int(row_stride), int(k)

@@ -55,7 +55,10 @@ typedef enum gs_key_type {
      * in pairs across the whole key); values as for 32-bit keys.  Accepted by
      * gs_onesweep_sort_keys / _sort_pairs / _digit_pass (pass 0..7) and gs_validate; not by the histogram read-back,
      * the MSD split and the generator, which are 32-bit. */
-    GS_KEY_UINT64 = 3, GS_KEY_INT64 = 4, GS_KEY_FLOAT64 = 5
+    GS_KEY_UINT64 = 3, GS_KEY_INT64 = 4, GS_KEY_FLOAT64 = 5,
+    /* 16-bit keys: 2-byte elements, FLOAT16 is IEEE binary16.  Accepted by gs_topk_select_rows_keys / _pairs ONLY (see there); every
+     * other entry that takes a gs_key_type treats them as it treats any value it does not know. */
+    GS_KEY_UINT16 = 6, GS_KEY_INT16 = 7, GS_KEY_FLOAT16 = 8, GS_KEY_BFLOAT16 = 9
 } gs_key_type;
 /* GPUSortingCUDA/UtilityKernels.cuh:16-24 (value = number of extra AND-ed draws) */
 typedef enum gs_entropy_preset {
@@ -525,7 +528,7 @@ gs_status gs_topk_last(gs_topk* h, uint32_t* report, uint32_t words, void* strea
  * row_stride counts elements, for keys and values alike; any value >= row_len, it need not be a multiple of 4: only the base
  * pointers must be 16-byte aligned, rows may start at any element.
  *
- * GS_ERR_ARG: null handle (before anything else is looked at), null or misaligned base pointer, 64-bit key type,
+ * GS_ERR_ARG: null handle (before anything else is looked at), null or misaligned base pointer, 64-bit or unknown key type,
  * row_stride < row_len, output overlapping input.  GS_ERR_MODE: pairs call on a keys-only handle or the reverse.  GS_ERR_SIZE:
  * rows, row_len or k zero, k > row_len, k > max_k, (rows - 1) * row_stride + row_len > max_keys (in 64 bits).
  *
@@ -548,6 +551,17 @@ gs_status gs_topk_last(gs_topk* h, uint32_t* report, uint32_t words, void* strea
  *                              valid whatever calls follow.  That first call allocates synchronously; made while `stream` is
  *                              capturing it returns GS_ERR_MODE instead, launches nothing and leaves the capture intact: make
  *                              one plain call of such a shape on the handle before capturing. */
+/* 16-bit keys (GS_KEY_UINT16 / INT16 / FLOAT16 / BFLOAT16), these two entries only: the elements of d_keys and d_out_keys are 2 bytes,
+ * read at that width (no widened copy, no staging, no temp memory beyond gs_topk_temp_bytes, which is unchanged).  row_stride, row_len,
+ * k, positions and max_keys keep counting ELEMENTS; values stay 4 or 8 bytes under the same element index.  The base pointers stay
+ * 16-byte aligned; rows and output rows may start at any element, so at 2-byte alignment.  The overlap test takes the keys' 2-byte
+ * extent, and nothing behind element rows * k of either output is written, at 2-byte granularity for the keys.  Everything said above
+ * holds on the 16 bits: uint16 sorts as it is, int16 with the sign bit flipped, float16 and bfloat16 by the order-preserving flip (sign
+ * bit set: all 16 bits inverted; otherwise the sign bit flipped: -0 < +0, NaNs by bit pattern).
+ * Routes: WAVE, TILE and STREAM at the same row lengths as for 32-bit keys.  There is NO LOOP route (the 1-D select is a 32-bit
+ * algorithm): a row longer than gs_segsort_max_lds_segment with k > gs_topk_rows_max_k returns GS_ERR_SIZE before anything is
+ * launched (gs_topk_rows_last then reports GS_TOPK_ROWS_ROUTE_NONE), and the "few, very long rows" rule is not applied: such shapes
+ * take STREAM.  GS_TOPK_ROWS_R_READS is 2 or 3, never 4: the select is exact after two levels (12 + 4 bits). */
 #define GS_TOPK_ROWS_ROUTE_NONE 0u
 #define GS_TOPK_ROWS_ROUTE_WAVE 1u
 #define GS_TOPK_ROWS_ROUTE_TILE 2u
@@ -559,7 +573,7 @@ gs_status gs_topk_last(gs_topk* h, uint32_t* report, uint32_t words, void* strea
 #define GS_TOPK_ROWS_R_ROW_LEN 2
 #define GS_TOPK_ROWS_R_K 3
 #define GS_TOPK_ROWS_R_STATUS 4  /* the device status word: 0, or 1 if a count did not add up (gs_topk_check: GS_ERR_HIP) */
-#define GS_TOPK_ROWS_R_READS 5   /* GS_TOPK_ROWS_ROUTE_STREAM: the most reads of its row any row took (2 .. 4); otherwise 0 */
+#define GS_TOPK_ROWS_R_READS 5   /* GS_TOPK_ROWS_ROUTE_STREAM: the most reads of its row any row took (2 .. 4; 16-bit keys: 2 .. 3); otherwise 0 */
 #define GS_TOPK_ROWS_REPORT_WORDS 8
 gs_status gs_topk_select_rows_keys(gs_topk* h, const void* d_keys, uint32_t rows, uint32_t row_len, uint32_t row_stride, uint32_t k,
                                    void* d_out_keys, gs_key_type key_type, gs_order order, void* stream);
