@@ -20,6 +20,11 @@ GS_PROFILE_SLOTS = 8
 GS_SEGSORT_CLASSES = 9
 GS_TOPK_REPORT_WORDS = 8
 GS_TOPK_ROWS_REPORT_WORDS = 8
+# gs_debug_sort_route / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
+GS_ROUTE_NONE = 0xFFFFFFFF
+GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
+(GS_KF_BIN, GS_KF_POS, GS_KF_PERSIST, GS_KF_SMALL, GS_KF_MID, GS_KF_SEG_WG, GS_KF_SEG_VB, GS_KF_TKR_TILE, GS_KF_TKR_VM, GS_KF_HIST,
+ GS_KF_HY_HIST, GS_KF_HY_LOCAL, GS_KF_HY_LOCAL_PAIRS, GS_KF_COUNT) = range(14)
 # gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs only
 KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16 = 6, 7, 8, 9
 
@@ -130,6 +135,10 @@ _PROTOS = [
     ("gs_debug_check_state", _int, [_vp, C.POINTER(C.c_uint64), _vp]),
     ("gs_debug_poke_status", _int, [_vp, _u32, _vp]),
     ("gs_debug_read_slab", _int, [_vp, _u32, _u32, _u32p, _vp]),
+    ("gs_debug_sort_route", _int, [_vp, _u32, _int, _u32p]),
+    ("gs_debug_pass_flags", _int, [_vp, _u32p, _vp]),
+    ("gs_debug_registry_dims", _int, [_u32, C.POINTER(C.c_int32)]),
+    ("gs_debug_registry_cell", _int, [_u32, C.POINTER(C.c_int32)]),
     ("gs_onesweep_global_histogram", _int, [_vp, _vp, _u32, _int, C.POINTER(_u32), _vp]),
     ("gs_onesweep_scan", _int, [_vp, _vp, _u32, _int, C.POINTER(_u32), _vp]),
     ("gs_onesweep_digit_pass", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _int, _vp]),
@@ -171,6 +180,7 @@ _PROTOS = [
     ("gs_segsort_sort_pairs", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _int, _int, _vp]),
     ("gs_segsort_check", _int, [_vp, _vp]),
     ("gs_segsort_last_classes", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_segsort_engine", _vp, [_vp]),
     ("gs_topk_create", _int, [C.POINTER(_vp), _u32, _u32, _int, _u32]),
     ("gs_topk_destroy", _int, [_vp]),
     ("gs_topk_temp_bytes", C.c_size_t, [_u32, _u32, _u32]),
@@ -178,6 +188,7 @@ _PROTOS = [
     ("gs_topk_select_pairs", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _int, _int, _vp]),
     ("gs_topk_check", _int, [_vp, _vp]),
     ("gs_topk_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_topk_engine", _vp, [_vp]),
     ("gs_topk_select_rows_keys", _int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _int, _int, _vp]),
     ("gs_topk_select_rows_pairs", _int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _int, _int, _vp]),
     ("gs_topk_rows_max_k", _u32, [_int, _u32]),

@@ -267,6 +267,20 @@ struct Table {
         for (int d : {D...}) i = i * d + c[k++];
         return i;
     }
+    // for gs_debug_registry_*: the extents -> out, returns how many; the index of a caller's coordinate, -1 if it lies outside
+    static int extents(int32_t* out) {
+        int k = 0;
+        for (int d : {D...}) out[k++] = d;
+        return k;
+    }
+    static int checked_index(const int32_t* c) {
+        int i = 0, k = 0;
+        for (int d : {D...}) {
+            if (c[k] < 0 || c[k] >= d) return -1;
+            i = i * d + c[k++];
+        }
+        return i;
+    }
   private:
     static constexpr int coord(int i, int k) {
         const int d[] = {D...};
@@ -366,6 +380,43 @@ TkrLauncher tkr_tile_launcher(bool key16, int wg_cls, int rank, uint32_t vm) {
 }
 const TkrVmLaunchers& tkr_vm(bool key16, uint32_t vm) { return g_tkr_vm[TkrVmTable::index({key16 ? 1 : 0, vm_index(vm)})]; }
 MidLauncher mid_launcher(int cls, int rank, uint32_t vb, int kt) { return g_mid[MidTable::index({cls, rank, vb_index(vb), kt})]; }
+
+// The registry as data (gs_debug_registry_dims / _cell; tests hold their case list against it): family = GS_KF_*.  dims != nullptr:
+// the table's extents, returns their number; otherwise 1 / 0 = the cell at coord holds a launcher or not.  -1: no such family or cell.
+template <class F> bool cell_built(F f) { return f != nullptr; }
+inline bool cell_built(const SegVbLaunchers& f) { return f.packed && f.wave && f.merge_head; }
+inline bool cell_built(const TkrVmLaunchers& f) { return f.wave && f.stream; }
+template <class Tab, class Cells>
+int registry_query(const Cells& cells, int32_t* dims, const int32_t* coord) {
+    if (dims) {
+        for (int k = 0; k < 5; ++k) dims[k] = 1;
+        return Tab::extents(dims);
+    }
+    int32_t ext[5] = {1, 1, 1, 1, 1};
+    for (int k = Tab::extents(ext); k < 5; ++k)
+        if (coord[k] != 0) return -1;
+    const int i = Tab::checked_index(coord);
+    return i < 0 ? -1 : cell_built(cells[i]) ? 1 : 0;
+}
+int registry_lookup(uint32_t family, int32_t* dims, const int32_t* coord) {
+    if (!dims && !coord) return -1;
+    switch (family) {
+        case GS_KF_BIN: return registry_query<BinTable>(g_bin, dims, coord);
+        case GS_KF_POS: return registry_query<PosTable>(g_pos, dims, coord);
+        case GS_KF_PERSIST: return registry_query<PersistTable>(g_persist, dims, coord);
+        case GS_KF_SMALL: return registry_query<SmallTable>(g_small, dims, coord);
+        case GS_KF_MID: return registry_query<MidTable>(g_mid, dims, coord);
+        case GS_KF_SEG_WG: return registry_query<SegWgTable>(g_seg_wg, dims, coord);
+        case GS_KF_SEG_VB: return registry_query<Table<3>>(g_seg_vb, dims, coord);
+        case GS_KF_TKR_TILE: return registry_query<TkrTileTable>(g_tkr_tile, dims, coord);
+        case GS_KF_TKR_VM: return registry_query<TkrVmTable>(g_tkr_vm, dims, coord);
+        case GS_KF_HIST: return registry_query<Table<NKT>>(g_hist, dims, coord);
+        case GS_KF_HY_HIST: return registry_query<Table<NKT>>(g_hy_hist, dims, coord);
+        case GS_KF_HY_LOCAL: return registry_query<HyTable>(g_hy_local, dims, coord);
+        case GS_KF_HY_LOCAL_PAIRS: return registry_query<HyPairsTable>(g_hy_local_pairs, dims, coord);
+    }
+    return -1;
+}
 // ---- end of the kernel registry -------------------------------------------------------------------------------------
 
 }  // namespace

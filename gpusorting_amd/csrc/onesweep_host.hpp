@@ -619,6 +619,39 @@ gs_status gs_debug_read_slab(gs_onesweep* h, uint32_t first_word, uint32_t count
     return GS_OK;
 }
 
+gs_status gs_debug_sort_route(gs_onesweep* h, uint32_t n, gs_key_type kt, uint32_t report[8]) {
+    if (!h || !report || !valid_key_type(kt)) return GS_ERR_ARG;
+    if (n == 0 || n > h->max_keys) return GS_ERR_SIZE;
+    const uint32_t vb = h->value_bytes;
+    const SortRoute r = sort_route(h, n, kt, vb);
+    report[GS_ROUTE_R_SMALL] = r.small ? (uint32_t)small_class(n) : GS_ROUTE_NONE;
+    report[GS_ROUTE_R_MID] = (uint32_t)r.mid_cls;
+    report[GS_ROUTE_R_SHAPE] = (uint32_t)r.shape;
+    report[GS_ROUTE_R_SHAPE0] = (uint32_t)r.shape0;
+    report[GS_ROUTE_R_DYN] = r.dyn;
+    report[GS_ROUTE_R_POS] = r.pos ? pos_tile_for(vb) : 0u;
+    report[GS_ROUTE_R_HY] = r.hy ? 1u : 0u;
+    report[GS_ROUTE_R_RANK] = (uint32_t)h->rank_mode;
+    return GS_OK;
+}
+
+static_assert(GS_PF_SKEW == gs::PF_SKEW && GS_PF_SKIP == gs::PF_SKIP && GS_PF_SRC_ALT == gs::PF_SRC_ALT && GS_PF_LAST == gs::PF_LAST &&
+              GS_PF_POS == gs::PF_POS, "header and kernels agree on the pass flags");
+gs_status gs_debug_pass_flags(gs_onesweep* h, uint32_t flags[8], void* stream) {
+    if (!h || !flags) return GS_ERR_ARG;
+    for (uint32_t q = 0; q < gs::MAX_PASSES; ++q) flags[q] = 0;
+    if (h->last_tile == 0) return GS_OK;  // single-tile or mid-size route, or nothing yet: no pass plan was made
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (uint32_t q = 0; q < gs::MAX_PASSES; ++q)
+        GS_HIP(hipMemcpyAsync(h->pinned + q, h->slab + SLAB_INFO + q * gs::INFO_STRIDE + gs::PASS_FLAGS, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GS_HIP(hipStreamSynchronize(s));
+    for (uint32_t q = 0; q < h->last_np && q < gs::MAX_PASSES; ++q) flags[q] = h->pinned[q];
+    return GS_OK;
+}
+
+int gs_debug_registry_dims(uint32_t family, int32_t dims[5]) { return dims ? registry_lookup(family, dims, nullptr) : -1; }
+int gs_debug_registry_cell(uint32_t family, const int32_t coord[5]) { return coord ? registry_lookup(family, nullptr, coord) : -1; }
+
 gs_status gs_onesweep_set_plan(gs_onesweep* h, int plan) {
     if (!h || plan < 0) return GS_ERR_ARG;
     if (plan > 2) return GS_ERR_ARG;

@@ -178,6 +178,8 @@ gs_status gs_segsort_check(gs_segsort* h, void* stream) {
     return gs_onesweep_check(h->engine, stream);  // the long segments' sorts
 }
 
+gs_onesweep* gs_segsort_engine(gs_segsort* h) { return h ? h->engine : nullptr; }
+
 gs_status gs_segsort_last_classes(gs_segsort* h, uint32_t* counts, uint32_t words, void* stream) {
     if (!h || !counts || words < GS_SEGSORT_CLASSES + 1) return GS_ERR_ARG;
     const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));

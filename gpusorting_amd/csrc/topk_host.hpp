@@ -351,6 +351,8 @@ gs_status gs_topk_rows_last(gs_topk* h, uint32_t* report, uint32_t words, void* 
     return GS_OK;
 }
 
+gs_onesweep* gs_topk_engine(gs_topk* h) { return h ? h->engine : nullptr; }
+
 gs_status gs_topk_check(gs_topk* h, void* stream) {
     if (!h) return GS_ERR_ARG;
     const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));

@@ -245,6 +245,24 @@ class OneSweep:
         return {"rows_not_inclusive": int(rep[0]), "rows_not_monotone": int(rep[1]), "chains_short_of_tickets": int(rep[2]),
                 "hist_words_nonzero": int(rep[3]), "keys_per_pass": [int(rep[4 + q]) for q in range(4)]}
 
+    def sort_route(self, n: int, key_type: int | None = None) -> dict:
+        """Which way a sort of ``n`` elements would go on this handle as it is set up now (gs_debug_sort_route; host only): ``small`` and
+        ``mid`` are the class of the one- / two-launch route or None; ``shape`` / ``shape0`` index the tile shapes 512x32, 1024x16,
+        512x16; ``pos`` is 0 or the tile word of the position-chain passes."""
+        rep = (C.c_uint32 * 8)()
+        kt = self.key_type if key_type is None else key_type
+        check(self._lib.gs_debug_sort_route(self._h, int(n), kt, rep), "gs_debug_sort_route")
+        none = _lib.GS_ROUTE_NONE
+        return {"small": None if rep[0] == none else int(rep[0]), "mid": None if rep[1] == none else int(rep[1]), "shape": int(rep[2]),
+                "shape0": int(rep[3]), "dyn": int(rep[4]), "pos": int(rep[5]), "hy": bool(rep[6]), "rank_mode": int(rep[7])}
+
+    def pass_flags(self, stream=None) -> list:
+        """The GS_PF_* flag word of every pass of the last sort (gs_debug_pass_flags; synchronises): all zero after a one- or two-launch
+        route."""
+        buf = (C.c_uint32 * 8)()
+        check(self._lib.gs_debug_pass_flags(self._h, buf, _stream_ptr(stream)), "gs_debug_pass_flags")
+        return [int(x) for x in buf]
+
     # -- structural entry points ------------------------------------------------
     def global_histogram(self, keys: torch.Tensor, n: int | None = None) -> np.ndarray:
         n = keys.numel() if n is None else int(n)

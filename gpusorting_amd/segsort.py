@@ -111,6 +111,14 @@ class SegmentedSort:
         """Longest segment sorted in LDS; a ``max_segment_len`` up to it keeps ``sort`` free of host waits."""
         return int(self._lib.gs_segsort_max_lds_segment(self.mode, self.value_bytes))
 
+    @property
+    def engine(self):
+        """The embedded OneSweep engine, borrowed (``gs_segsort_engine``): it sorts the long segments and its rank mode is the one the
+        workgroup classes run with.  For ``set_rank_mode`` / ``rank_mode`` / ``check``, with no call in flight; it lives as long as
+        this handle."""
+        from .onesweep import OneSweep
+        return OneSweep._borrow(self._lib.gs_segsort_engine(self._h), self.max_keys, self.mode, self.value_bytes, self.key_type)
+
     def class_of(self, length: int) -> int:
         return int(self._lib.gs_segsort_class_of(int(length), self.mode, self.value_bytes))
 

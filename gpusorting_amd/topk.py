@@ -99,6 +99,16 @@ class TopK:
     def temp_bytes(self) -> int:
         return int(self._lib.gs_topk_temp_bytes(self.max_keys, self.max_k, self.value_bytes))
 
+    @property
+    def engine(self):
+        """The embedded OneSweep engine, borrowed (``gs_topk_engine``): it runs the single-tile route and the final sort of k, and its
+        rank mode is the one the row-wise tile kernels run with.  For ``set_rank_mode`` / ``rank_mode`` / ``check``, with no call in
+        flight; it lives as long as this handle."""
+        from .onesweep import OneSweep
+        cap = max(self.max_k, min(self.max_keys, 32768))
+        kt = self.key_type if self.key_type in (KEY_UINT32, KEY_INT32, KEY_FLOAT32) else KEY_UINT32
+        return OneSweep._borrow(self._lib.gs_topk_engine(self._h), cap, self.mode, self.value_bytes, kt)
+
     def select(self, keys, k: int, out_keys, values=None, out_values=None, n: int | None = None, stream=None) -> None:
         """The first ``k`` of ``keys[:n]`` in this handle's order into ``out_keys[:k]`` (and ``out_values[:k]``) on the current stream.
         ``values=None`` with ``out_values`` given (4-byte handle): the values are the input positions.  Inputs are not written."""

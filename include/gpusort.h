@@ -222,6 +222,55 @@ gs_status gs_debug_check_state(gs_onesweep* h, uint64_t report[8], void* stream)
 gs_status gs_debug_poke_status(gs_onesweep* h, uint32_t word, void* stream);
 /* Test / tuning hook: copies `count` words of the handle's state slab, from word `first_word`, to the host.  Synchronous. */
 gs_status gs_debug_read_slab(gs_onesweep* h, uint32_t first_word, uint32_t count, uint32_t* h_out, void* stream);
+/* Test hook, host only (no device work, no allocation): which way gs_onesweep_sort_keys / _sort_pairs would send a sort of n
+ * elements of key_type on this handle as it is set up now (mode and value width are the handle's) — what the library decides from
+ * sizes, modes and options alone; what the keys look like is the device's business (gs_debug_pass_flags, gs_onesweep_last_plan).
+ * report[GS_ROUTE_R_*]; GS_ERR_ARG for a null handle or report or a key type the sorts do not take, GS_ERR_SIZE for n == 0 or
+ * n > max_keys. */
+#define GS_ROUTE_NONE 0xffffffffu
+#define GS_ROUTE_R_SMALL 0   /* single-tile route: its size class 0 .. 4 (up to 1024 / 2048 / 8192 / 16 384 / 32 768 elements), else GS_ROUTE_NONE */
+#define GS_ROUTE_R_MID 1     /* two-launch mid-size route: its class 0 .. 4, else GS_ROUTE_NONE (-1); the words below describe the general
+                                pipeline, which runs when both are GS_ROUTE_NONE */
+#define GS_ROUTE_R_SHAPE 2   /* tile shape of the binning passes: 0 = 512 x 32, 1 = 1024 x 16, 2 = 512 x 16 (the tuning build has three more) */
+#define GS_ROUTE_R_SHAPE0 3  /* ... of the first pass */
+#define GS_ROUTE_R_DYN 4     /* 2: the Scan kernel plans the passes on the device (identity passes dropped, source buffers); 0: fixed ping-pong */
+#define GS_ROUTE_R_POS 5     /* 0, or — the sort may be planned on position chains — the tile word of those passes: keys per tile, bit 31 set
+                                if the plan's last pass runs on that tile too */
+#define GS_ROUTE_R_HY 6      /* 1: the sort is offered the two-level plan */
+#define GS_ROUTE_R_RANK 7    /* the handle's rank mode, as gs_onesweep_get_rank_mode */
+gs_status gs_debug_sort_route(gs_onesweep* h, uint32_t n, gs_key_type key_type, uint32_t report[8]);
+/* Test hook: flags[q] = the flag word the Scan kernel and the passes left in the info block of the last sort's q-th pass (32-bit keys
+ * use the first four, 64-bit keys planned by one sweep all eight) — which passes ran, from which buffer, in which form.  All zero
+ * after a sort that left no scan state (the single-tile and mid-size routes).  Synchronous. */
+#define GS_PF_SKEW 1u     /* some digit holds more than 1/16 of the keys: the pass ranks with wave-aggregated adds (8-byte values on the
+                             512 x 32 tile: the two-round form of the pass works, the one-round form exits) */
+#define GS_PF_SKIP 2u     /* the pass was dropped: every key has the same digit, and so has another pass */
+#define GS_PF_SRC_ALT 4u  /* an odd number of earlier passes ran: this pass reads the alternate buffers */
+#define GS_PF_LAST 8u     /* the last pass that runs */
+#define GS_PF_POS 16u     /* the sort runs on position chains: the position-chain form of the pass works */
+gs_status gs_debug_pass_flags(gs_onesweep* h, uint32_t flags[8], void* stream);
+/* Test hooks, host only (they work without a GPU): the kernel registry of this build — one launcher table per kernel family
+ * (GS_KF_*), indexed by tile shape or size class, rank mode, value width and key type.  gs_debug_registry_dims: dims[0 .. r) = the
+ * table's extents, the rest 1; returns r, -1 for an unknown family or null dims.  gs_debug_registry_cell: 1 if this build compiled
+ * the kernel(s) of the cell at coord[0 .. r) (coord[r .. 5) must be 0), 0 if not, -1 for an unknown family or a coordinate outside
+ * the table.  Index orders (vb: 0 / 1 / 2 = no / 4-byte / 8-byte values; vm: 0 / 1 / 2 / 3 = keys only / positions / 4- / 8-byte
+ * values; kt: gs_key_type 0 .. 5; rank: the rank mode; class: the family's size class): */
+#define GS_KF_BIN 0u             /* [two-round form][shape][rank][vb][kt]   digit_binning_kernel */
+#define GS_KF_POS 1u             /* [vb][last pass][kt]                     the position-chain forms of the pass */
+#define GS_KF_PERSIST 2u         /* [8-byte values][kt]                     the two-level plan's passes for pairs */
+#define GS_KF_SMALL 3u           /* [class][rank][vb][kt]                   the single-tile sort */
+#define GS_KF_MID 4u             /* [class][rank][vb][kt]                   the mid-size route's two kernels */
+#define GS_KF_SEG_WG 5u          /* [class][rank][vb][32-bit kt]            segmented sort, one workgroup per segment */
+#define GS_KF_SEG_VB 6u          /* [vb]                                    segmented sort: packed, wave, head merge */
+#define GS_KF_TKR_TILE 7u        /* [2-byte keys][class][rank][vm]          row-wise top-k, one workgroup per row */
+#define GS_KF_TKR_VM 8u          /* [2-byte keys][vm]                       row-wise top-k: wave and stream kernels */
+#define GS_KF_HIST 9u            /* [kt]                                    GlobalHistogram */
+#define GS_KF_HY_HIST 10u        /* [kt]                                    the two-level plan's histogram */
+#define GS_KF_HY_LOCAL 11u       /* [class][kt]                             ... its bucket-local sort, keys only */
+#define GS_KF_HY_LOCAL_PAIRS 12u /* [8-byte values][class][kt]              ... and for pairs */
+#define GS_KF_COUNT 13u
+int gs_debug_registry_dims(uint32_t family, int32_t dims[5]);
+int gs_debug_registry_cell(uint32_t family, const int32_t coord[5]);
 
 /* ---- structural entry points (parity tests, MSD split) --------------------
  * GlobalHistogram + Scan only (GPUSortingCUDA/Sort/OneSweep.cu:44-162): writes
@@ -450,6 +499,10 @@ gs_status gs_segsort_check(gs_segsort* h, void* stream);
 /* Synchronous: counts[c] = segments of class c in the last call, c < GS_SEGSORT_CLASSES; counts[GS_SEGSORT_CLASSES] = the longest
  * segment seen.  words >= GS_SEGSORT_CLASSES + 1. */
 gs_status gs_segsort_last_classes(gs_segsort* h, uint32_t* counts, uint32_t words, void* stream);
+/* The handle's embedded engine, borrowed (as gs_mgpu_sorter; NULL for a null handle): it sorts the long segments and its rank mode is
+ * the one the workgroup classes run with.  For gs_onesweep_set_rank_mode / gs_onesweep_get_rank_mode / gs_onesweep_check, with no call of
+ * the handle in flight; the handle destroys it. */
+gs_onesweep* gs_segsort_engine(gs_segsort* h);
 
 /* ---- top-k selection: the first k elements of the sorted order without sorting the rest --------------------
  * No counterpart in the reference project.
@@ -517,6 +570,10 @@ gs_status gs_topk_select_pairs(gs_topk* h, const void* d_keys, const void* d_val
 gs_status gs_topk_check(gs_topk* h, void* stream);
 /* Synchronous diagnostics of the last call: report[GS_TOPK_R_*], words >= GS_TOPK_REPORT_WORDS. */
 gs_status gs_topk_last(gs_topk* h, uint32_t* report, uint32_t words, void* stream);
+/* The handle's embedded engine, borrowed (as gs_mgpu_sorter; NULL for a null handle): it runs the single-tile route and the final sort
+ * of k, and its rank mode is the one the row-wise tile kernels run with.  For gs_onesweep_set_rank_mode / gs_onesweep_get_rank_mode /
+ * gs_onesweep_check, with no call of the handle in flight; the handle destroys it. */
+gs_onesweep* gs_topk_engine(gs_topk* h);
 
 /* ---- Row-wise top-k: the first k of every row of a [rows, row_len] matrix in one call, on the same handle ----
  * Row r of the output is what gs_topk_select_keys / _pairs delivers for keys[r * row_stride .. r * row_stride + row_len) with the same

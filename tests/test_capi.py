@@ -133,9 +133,14 @@ def test_null_handle_is_an_argument_error_in_every_handle_entry():
         "gs_topk_select_keys": (None, p, 1024, 8, p + 8192, 0, 0, None),
         "gs_topk_check": (None, None),
         "gs_topk_last": (None, u32p, 4096, None),
+        "gs_debug_sort_route": (None, 1024, 0, u32p),
+        "gs_debug_pass_flags": (None, u32p, None),
     }
     for name, args in calls.items():
         assert getattr(lib, name)(*args) == _lib.GS_ERR_ARG, name
+    # the entries that hand out a borrowed engine answer NULL, as gs_mgpu_sorter does
+    for name in ("gs_segsort_engine", "gs_topk_engine", "gs_mgpu_sorter"):
+        assert getattr(lib, name)(None) is None, name
 
 
 def test_msd_splitters_match_oracle(oracle):
