@@ -20,7 +20,7 @@ GS_PROFILE_SLOTS = 8
 GS_SEGSORT_CLASSES = 9
 GS_TOPK_REPORT_WORDS = 8
 GS_TOPK_ROWS_REPORT_WORDS = 8
-# gs_debug_sort_route / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
+# gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
 GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
 (GS_KF_BIN, GS_KF_POS, GS_KF_PERSIST, GS_KF_SMALL, GS_KF_MID, GS_KF_SEG_WG, GS_KF_SEG_VB, GS_KF_TKR_TILE, GS_KF_TKR_VM, GS_KF_HIST,
@@ -136,6 +136,7 @@ _PROTOS = [
     ("gs_debug_poke_status", _int, [_vp, _u32, _vp]),
     ("gs_debug_read_slab", _int, [_vp, _u32, _u32, _u32p, _vp]),
     ("gs_debug_sort_route", _int, [_vp, _u32, _int, _u32p]),
+    ("gs_debug_set_hy_class", _int, [_vp, _int]),
     ("gs_debug_pass_flags", _int, [_vp, _u32p, _vp]),
     ("gs_debug_registry_dims", _int, [_u32, C.POINTER(C.c_int32)]),
     ("gs_debug_registry_cell", _int, [_u32, C.POINTER(C.c_int32)]),

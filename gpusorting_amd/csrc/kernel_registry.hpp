@@ -81,7 +81,8 @@ void launch_hy_local_pairs(hipStream_t s, uint32_t* keys, void* vals, const uint
     hipLaunchKernelGGL((gs::hy_local_sort_pairs_kernel<KT, VB, T, K>), dim3(gs::HY_BINS), dim3(T), 0, s, keys, vals, tab, slab, n, descending);
 }
 // the local sort's workgroup by the mean bucket n / 65 536: it holds 1.5 x the mean at the top of its class (uniform keys stay within
-// a few per cent of the mean; what does not fit sends the sort to the LSD passes)
+// a few per cent of the mean; what does not fit sends the sort to the LSD passes).  Tests force a class at any n (gs_debug_set_hy_class;
+// hy_class_of in onesweep_host.hpp): a bucket of exactly cap keys then takes a sort of 2^21 keys, not of 2^28
 struct HyLocalClass {
     uint32_t max_n;
     int threads, kpt;
@@ -366,8 +367,9 @@ BinLauncher pos_launcher(uint32_t vb, bool last, int kt) { return g_pos[PosTable
 BinLauncher persist_launcher(uint32_t vb, int kt) { return g_persist[PersistTable::index({vb == 8 ? 1 : 0, kt})]; }
 HistLauncher hist_launcher(int kt) { return g_hist[kt]; }
 HyHistLauncher hy_hist_launcher(int kt) { return g_hy_hist[kt]; }
-HyLocalLauncher hy_local_launcher(uint32_t n, int kt) { return g_hy_local[HyTable::index({hy_class(n), kt})]; }
-HyLocalPairsLauncher hy_pairs_launcher(uint32_t vb, uint32_t n, int kt) { return g_hy_local_pairs[HyPairsTable::index({vb == 8 ? 1 : 0, hy_class(n), kt})]; }
+// (cls: the size class of the sort — hy_class_of in onesweep_host.hpp, the one place that picks it)
+HyLocalLauncher hy_local_launcher(int cls, int kt) { return g_hy_local[HyTable::index({cls, kt})]; }
+HyLocalPairsLauncher hy_pairs_launcher(uint32_t vb, int cls, int kt) { return g_hy_local_pairs[HyPairsTable::index({vb == 8 ? 1 : 0, cls, kt})]; }
 SmallLauncher small_launcher(uint32_t n, int rank, uint32_t vb, int kt) {
     const int c = small_class(n);
     return c < 5 ? g_small[SmallTable::index({c, rank, vb_index(vb), kt})] : nullptr;  // nullptr: no single-tile kernel for this case

@@ -61,6 +61,7 @@ struct gs_onesweep {
     uint32_t* hy_tab = nullptr;  // the two-level plan's tables (gs::HYT_WORDS), nullptr: the handle cannot run it (pairs, 64-bit keys only ...)
     uint32_t hy_grid;      // workgroups of its histogram kernel (a multiple of NCH)
     int last_hy = 0;       // the last sort was enqueued with the two-level plan's launches (whether it RAN on it is the device's decision: gs_onesweep_last_plan)
+    int hy_class_forced = -1;  // gs_debug_set_hy_class: -1 the size class of the bucket-local sort follows n (hy_class), 0 .. 3 that class whatever n is
 };
 
 namespace {
@@ -74,6 +75,11 @@ inline uint32_t desc_rows(uint32_t n, uint32_t tile, bool hy_chains) {
 // slab words up to the end of the descriptor regions of `passes` passes
 inline size_t slab_words_with(uint32_t passes, uint32_t rows) { return SLAB_DESC + (size_t)passes * rows * gs::RADIX; }
 inline bool slab_fits(const gs_onesweep* h, uint32_t passes, uint32_t rows) { return slab_words_with(passes, rows) <= h->slab_words; }
+
+// The size class of the two-level plan's bucket-local sort for a sort of n keys on this handle: by n, unless a test forced one
+// (gs_debug_set_hy_class).  Everything that depends on the class asks here: the bucket limit the histogram and scan kernels judge
+// the plan by, the bucket-local sort's launcher, and sort_route's question whether that launcher exists.
+inline int hy_class_of(const gs_onesweep* h, uint32_t n) { return h->hy_class_forced >= 0 ? h->hy_class_forced : hy_class(n); }
 
 size_t slab_words_for(uint32_t max_keys) {
     // descriptor rows: four passes on the smallest tile, or the eight passes of a 64-bit sort on its 8192-key tile
@@ -200,10 +206,11 @@ gs_status prologue(gs_onesweep* h, const void* d_keys, uint32_t n, gs_key_type k
         const uint32_t wg_per_seg = seg_tiles < h->hy_grid / gs::NCH ? (seg_tiles ? seg_tiles : 1u) : h->hy_grid / gs::NCH;
         const uint32_t G = wg_per_seg * gs::NCH;
         const uint32_t per_wg = div_up(div_up(seg_len0, wg_per_seg), gs::HIST_CHUNK) * gs::HIST_CHUNK;
-        hy_hist_launcher(kt)(s, G, static_cast<const uint32_t*>(d_keys), h->slab, used_words, n, seg_len0, per_wg, wg_per_seg, h->partials, g_hy_class[hy_class(n)].cap());
+        const uint32_t cap = g_hy_class[hy_class_of(h, n)].cap();  // what the bucket-local sort's workgroup holds
+        hy_hist_launcher(kt)(s, G, static_cast<const uint32_t*>(d_keys), h->slab, used_words, n, seg_len0, per_wg, wg_per_seg, h->partials, cap);
         hipLaunchKernelGGL(gs::hy_reduce_kernel, dim3(gs::RADIX + gs::NCH), dim3(256), 0, s, h->partials, G, wg_per_seg, h->hy_tab, h->slab + SLAB_HIST);
         if (rec) GS_HIP(hipEventRecord(h->ev[2], s));
-        hipLaunchKernelGGL(gs::hy_scan_kernel, dim3(1), dim3(1024), 0, s, h->slab, h->hy_tab, n, seg_len0, desc_stride, g_hy_class[hy_class(n)].cap(), tile, pregrouped ? 1u : 0u);
+        hipLaunchKernelGGL(gs::hy_scan_kernel, dim3(1), dim3(1024), 0, s, h->slab, h->hy_tab, n, seg_len0, desc_stride, cap, tile, pregrouped ? 1u : 0u);
     } else {
     hist_launcher(kt)(s, hist_blocks(n, h->hist_blocks_opt), static_cast<const uint32_t*>(d_keys), h->slab, used_words, n, seg_len0, p0, np, word,
                (scan_plan & 4u) ? (h->pos_chains == 2 ? 3u : 1u) : 0u, h->partials);
@@ -315,7 +322,8 @@ SortRoute sort_route(const gs_onesweep* h, uint32_t n, gs_key_type kt, uint32_t 
     // (position_chains = 2 asks for the position-chain plan whatever the keys look like: only plan 2 overrides that)
     r.hy = r.pos && !r.small && r.mid_cls < 0 && h->hy_tab != nullptr && hy_hist_launcher(kt) != nullptr && h->plan != 1 &&
            (h->plan == 2 || (n >= (vb ? HY_MIN_PAIRS_DEFAULT : h->hy_min_keys) && h->pos_chains != 2)) &&
-           (vb == 0 || (persist_launcher(vb, kt) != nullptr && hy_pairs_launcher(vb, n, kt) != nullptr)) &&
+           (vb == 0 ? hy_local_launcher(hy_class_of(h, n), kt) != nullptr
+                    : (persist_launcher(vb, kt) != nullptr && hy_pairs_launcher(vb, hy_class_of(h, n), kt) != nullptr)) &&
            slab_fits(h, 4, desc_rows(n, pos_tile_for(vb) & 0x7fffffffu, true));  // (what sort_impl's prologue will ask for)
     return r;
 }
@@ -413,7 +421,7 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
                        mode | ((hy && p < 2) ? gs::BM_INFO_SHIFT | gs::BM_INFO_CHAINS : 0u) | ((hy && p == 1) ? gs::BM_ZERO_DESC23 : 0u));
                 if (hy && p == 1) {
                     if (h->profiling) GS_HIP(hipEventRecord(h->ev[5], s));  // slot 4 = pass B; slot 5: the local sort (+ LSD pass 2's launch); slot 6: LSD pass 3's
-                    if (!skip_local) hy_local_launcher(n, kt)(s, gs::HY_BINS, k[0], h->hy_tab, h->slab, n, desc_bit);
+                    if (!skip_local) hy_local_launcher(hy_class_of(h, n), kt)(s, gs::HY_BINS, k[0], h->hy_tab, h->slab, n, desc_bit);
                 }
             } else if (hy) {
                 // (2) pairs that are offered the two-level plan: launches 0 and 1 = its two DigitBinningPasses (the plain form as persistent
@@ -424,7 +432,7 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
                 launch(pos_launcher(vb, p == 3, kt), pos_grid(), p, a, p * 8, (mode & ~gs::BM_ZERO_HIST) | gs::BM_FORMS | (p == 1 ? gs::BM_ZERO_DESC23 : 0u));
                 if (p == 1) {
                     if (h->profiling) GS_HIP(hipEventRecord(h->ev[5], s));
-                    if (!skip_local) hy_pairs_launcher(vb, n, kt)(s, k[0], v[0], h->hy_tab, h->slab, n, desc_bit);
+                    if (!skip_local) hy_pairs_launcher(vb, hy_class_of(h, n), kt)(s, k[0], v[0], h->hy_tab, h->slab, n, desc_bit);
                 }
             } else {
                 // (3) everything else: the plain form, one tile per workgroup.  8-byte values on the big tile come in two forms and the
@@ -671,6 +679,12 @@ gs_status gs_onesweep_set_plan(gs_onesweep* h, int plan) {
         GS_HIP(hipMalloc(&h->hy_tab, gs::HYT_WORDS * sizeof(uint32_t)));
     }
     h->plan = plan;
+    return GS_OK;
+}
+
+gs_status gs_debug_set_hy_class(gs_onesweep* h, int cls) {
+    if (!h || cls < -1 || cls > 3) return GS_ERR_ARG;
+    h->hy_class_forced = cls;
     return GS_OK;
 }
 

@@ -256,6 +256,12 @@ class OneSweep:
         return {"small": None if rep[0] == none else int(rep[0]), "mid": None if rep[1] == none else int(rep[1]), "shape": int(rep[2]),
                 "shape0": int(rep[3]), "dyn": int(rep[4]), "pos": int(rep[5]), "hy": bool(rep[6]), "rank_mode": int(rep[7])}
 
+    def set_hy_class(self, cls: int) -> None:
+        """Test hook (gs_debug_set_hy_class; host only): force size class ``cls`` (0 .. 3: workgroups of 256 x 12, 512 x 12, 1024 x 12,
+        1024 x 24 keys) of the two-level plan's bucket-local sort for every later sort of this handle, whatever its size; -1 (the
+        default): the class follows ``n``.  Call it with no sort of the handle in flight."""
+        check(self._lib.gs_debug_set_hy_class(self._h, int(cls)), "gs_debug_set_hy_class")
+
     def pass_flags(self, stream=None) -> list:
         """The GS_PF_* flag word of every pass of the last sort (gs_debug_pass_flags; synchronises): all zero after a one- or two-launch
         route."""

@@ -239,6 +239,14 @@ gs_status gs_debug_read_slab(gs_onesweep* h, uint32_t first_word, uint32_t count
 #define GS_ROUTE_R_HY 6      /* 1: the sort is offered the two-level plan */
 #define GS_ROUTE_R_RANK 7    /* the handle's rank mode, as gs_onesweep_get_rank_mode */
 gs_status gs_debug_sort_route(gs_onesweep* h, uint32_t n, gs_key_type key_type, uint32_t report[8]);
+/* Test hook, host only (no device work): the size class of the two-level plan's bucket-local sort — 0 .. 3: a workgroup of
+ * 256 x 12, 512 x 12, 1024 x 12, 1024 x 24 keys — is picked from n alone (class 0 up to 2^27 keys, 1 up to 2^28, 2 up to 2^29, 3 above);
+ * cls = 0 .. 3 forces that class for every later sort of the handle, whatever its n: the bucket limit the device judges the plan by and
+ * the bucket-local kernel follow it, so a bucket of exactly the class's capacity is a few thousand keys of a small sort.  -1 (the
+ * default of every handle): by n.  A sort whose forced class has no kernel for its value width and key type (8-byte values, class 3)
+ * is not offered the plan (GS_ROUTE_R_HY 0) and runs on the LSD passes.  GS_ERR_ARG for a null handle or any other cls.  Call it with no
+ * sort of the handle in flight. */
+gs_status gs_debug_set_hy_class(gs_onesweep* h, int cls);
 /* Test hook: flags[q] = the flag word the Scan kernel and the passes left in the info block of the last sort's q-th pass (32-bit keys
  * use the first four, 64-bit keys planned by one sweep all eight) — which passes ran, from which buffer, in which form.  All zero
  * after a sort that left no scan state (the single-tile and mid-size routes).  Synchronous. */

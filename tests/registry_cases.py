@@ -13,7 +13,7 @@ A row:   (family, coord, case id | None, exemption | None)
            coord      the cell, in the table's index order (include/gpusort.h documents it next to GS_KF_*)
            case id    key of CASES: the GPU case that reaches the cell (several rows may share one: the two LAST forms of g_pos run in
                       one sort, a workgroup class per rank mode in one handle ...)
-           exemption  rows without a case: "tests.test_gpu_fullsize::<test>" — the full-size test that reaches the cell — or UNCOVERED
+           exemption  rows without a case: none today, and tests/test_registry_cpu.py accepts none (UNCOVERED is what such a row would say)
 A case:  dict(kind=..., **what the runner of that kind in test_gpu_registry.py needs): handle kind, options and setters, the sizes
          and input kinds; "evidence" names what is asserted after the call.
 """
@@ -91,21 +91,10 @@ for v, vb in enumerate(VB):
             _row("g_pos", (v, last, kt), cid)
 
 # ---- the two-level plan: g_hy_hist [kt], g_hy_local [class][kt], g_hy_local_pairs [8-byte values][class][kt], g_persist [8-byte
-# values][kt].  Class 0 (n <= 2^27) runs here; classes 1 .. 3 need n > 2^27: exempt, reached (or not) by tests/test_gpu_fullsize.py ----
-_TYPED = "tests.test_gpu_fullsize::test_two_level_plan_typed_and_descending_exact_default_routing"
-_HY_LOCAL_EXEMPT = {
-    (1, 0): "tests.test_gpu_fullsize::test_2pow28_keys_exact_vs_oracle", (1, 1): _TYPED, (1, 2): _TYPED,
-    (2, 0): _TYPED, (2, 1): UNCOVERED, (2, 2): UNCOVERED,
-    (3, 0): "tests.test_gpu_fullsize::test_maximum_size_2pow30_minus_1_exact_vs_oracle", (3, 1): _TYPED, (3, 2): UNCOVERED,
-}
-_3X27 = "tests.test_gpu_fullsize::test_3x2pow27_two_level_plan_against_the_lsd_passes"
-_HY_PAIRS_EXEMPT = {
-    (0, 1, 0): _TYPED, (0, 1, 1): UNCOVERED, (0, 1, 2): UNCOVERED,
-    (0, 2, 0): _3X27, (0, 2, 1): UNCOVERED, (0, 2, 2): _TYPED,
-    (0, 3, 0): UNCOVERED, (0, 3, 1): UNCOVERED, (0, 3, 2): UNCOVERED,
-    (1, 1, 0): "tests.test_gpu_fullsize::test_2pow28_pairs_u64_index_exact_vs_oracle", (1, 1, 1): UNCOVERED, (1, 1, 2): UNCOVERED,
-    (1, 2, 0): _3X27, (1, 2, 1): _TYPED, (1, 2, 2): UNCOVERED,
-}   # (8-byte values, class 3: not built — the 24 576-pair local sort does not fit LDS)
+# values][kt].  The class of the bucket-local sort follows n (class 0 up to 2^27 keys): class 0 runs as every sort of this size does;
+# classes 1 .. 3 are forced (gs_debug_set_hy_class) on the ladder input of tests/hy_bucket_inputs.py, whose largest buckets hold exactly
+# the class's cap.  (8-byte values, class 3: not built — the 24 576-pair local sort does not fit LDS) ----
+HY_CAP = (3072, 6144, 12288, 24576)   # keys the bucket-local sort's workgroup holds, by class
 for kt in range(3):
     for v, vb in enumerate(VB):
         cid = _case(f"hy-v{vb}-kt{kt}", kind="hy", handle="onesweep", vb=vb, kt=kt, max_keys=1 << 22,
@@ -117,10 +106,16 @@ for kt in range(3):
         else:
             _row("g_persist", (v - 1, kt), cid)
             _row("g_hy_local_pairs", (v - 1, 0, kt), cid)
-for coord, why in _HY_LOCAL_EXEMPT.items():
-    _row("g_hy_local", coord, exempt=why)
-for coord, why in _HY_PAIRS_EXEMPT.items():
-    _row("g_hy_local_pairs", coord, exempt=why)
+        for cls in (1, 2, 3):
+            if vb == 8 and cls == 3:
+                continue
+            cid = _case(f"hycls-c{cls}-v{vb}-kt{kt}", kind="hy_class", handle="onesweep", hy_class=cls, cap=HY_CAP[cls], vb=vb, kt=kt,
+                        max_keys=1 << 22, options=dict(plan=2, position_chains_min_log2=20, small_path=0, mid_path=0),
+                        inputs=("ladder",), evidence="last_plan two_level; largest_bucket == cap of the class")
+            if vb == 0:
+                _row("g_hy_local", (cls, kt), cid)
+            else:
+                _row("g_hy_local_pairs", (v - 1, cls, kt), cid)
 
 # ---- g_mid [class][rank][vb][kt]: the two-launch mid-size route, at the smallest n of each class ----------------------------------
 MID_VB = {0: (0, 4, 8), 1: (0, 4), 2: (0,), 3: (0,), 4: (4,)}

@@ -7,6 +7,8 @@ tests/registry_cases.py: one per cell (or small group of cells that share a call
      segmented_sort_reference, topk_reference / topk_rows_reference),
   4. asserts the evidence after the call: the passes' flag words (gs_debug_pass_flags: which form of a pass worked, which passes were
      dropped, from which buffer each read), gs_onesweep_last_plan, the chained-scan state, last_classes, gs_topk_rows_last.
+The bucket-local sorts of the two-level plan's classes 1 .. 3 (n > 2^27 in production) run with their class forced
+(gs_debug_set_hy_class) on buckets of exactly the class's capacity: largest_bucket == cap is the proof.
 Both orders everywhere.  Planted into the random keys: -0, +0, +-inf, NaN patterns of both signs, the integer minimum, -1, 0 and the
 maximum, at the key's width.  Values are distinct and derived from the position; 8-byte values differ in their high words
 ((i << 33) | 0x1F), so a pass that moves a value in two halves shows."""
@@ -248,6 +250,33 @@ def run_hy(c, gpu, oracle, handles):
         assert _clean(state) and state["keys_per_pass"] == [n, n, 0, 0], state   # pass A, pass B; the LSD passes behind them did not run
 
 
+def run_hy_class(c, gpu, oracle, handles):
+    """Classes 1 .. 3 of the bucket-local sorts: the class is forced, the input holds buckets of exactly the class's cap (the first and
+    the last prefix among them) and of every keys-per-thread value at its edges (tests/hy_bucket_inputs.py).  That the forced class
+    ran: the plan is valid with a largest bucket of cap, which the class n implies (class 0: 3072 keys) would have refused."""
+    import hy_bucket_inputs as hb
+    vb, kt, cls, n = c["vb"], c["kt"], c["hy_class"], hb.N
+    assert hb.cap(cls) == c["cap"] > hb.cap(0)
+    s = handles.onesweep(c["max_keys"], vb, kt, **c["options"])
+    assert s.rank_mode == 1
+    k = hb.ladder_input(cls, kt)
+    assert hb.prefix_histogram(k, kt).max() == c["cap"]
+    v = make_values(n, vb)
+    ref = reference(oracle, k, kt, v)
+    s.set_hy_class(cls)
+    try:
+        route = s.sort_route(n)
+        assert route["hy"] and route["pos"] and route["small"] is None and route["mid"] is None, route
+        for order in (0, 1):
+            _sort_and_compare(s, k, v, ref, order, order)
+            lp = s.last_plan()
+            assert lp["two_level"] and lp["largest_bucket"] == c["cap"], lp
+            state = s.check_state()
+            assert _clean(state) and state["keys_per_pass"] == [n, n, 0, 0], state
+    finally:
+        s.set_hy_class(-1)   # the handle is shared with the class-0 cases
+
+
 def run_mid(c, gpu, oracle, handles):
     vb, kt, cls = c["vb"], c["kt"], c["cls"]
     (n,) = c["sizes"]
@@ -450,7 +479,7 @@ def run_hist(c, gpu, oracle, handles):
     np.testing.assert_array_equal(s.global_histogram(_dev(k)), oracle.global_histogram(k, kt))
 
 
-RUNNERS = {"small": run_small, "bin": run_bin, "pos": run_pos, "hy": run_hy, "mid": run_mid, "seg_wg": run_seg_wg, "seg_vb": run_seg_vb,
+RUNNERS = {"small": run_small, "bin": run_bin, "pos": run_pos, "hy": run_hy, "hy_class": run_hy_class, "mid": run_mid, "seg_wg": run_seg_wg, "seg_vb": run_seg_vb,
            "tkr_tile": run_tkr_tile, "tkr_vm": run_tkr_vm, "topk1d": run_topk1d, "hist": run_hist}
 
 

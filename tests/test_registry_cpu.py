@@ -1,7 +1,6 @@
 """CPU tests of the kernel registry's ledger (tests/registry_cases.py): the set of kernel instantiations libgpusort.so reports as built
-(gs_debug_registry_dims / gs_debug_registry_cell, pure host functions) equals the ledger's rows — covered, exempt and uncovered
-together — so a new instantiation without a GPU case, or a case for a kernel that is gone, fails here, without a GPU."""
-import ast
+(gs_debug_registry_dims / gs_debug_registry_cell, pure host functions) equals the ledger's rows, and every row has a GPU case — so a
+new instantiation without a GPU case, or a case for a kernel that is gone, fails here, without a GPU."""
 import ctypes as C
 import itertools
 import os
@@ -66,35 +65,39 @@ def test_ledger_equals_the_registry():
         assert any(f == name and (c[1] if name == "g_seg_wg" else c[2]) == 0 and case for f, c, case, _ in rc.ROWS), name
 
 
-def test_every_row_has_a_case_or_a_reviewed_exemption():
-    fullsize = ast.parse(open(os.path.join(ROOT, "tests", "test_gpu_fullsize.py")).read())
-    tests = {n.name for n in fullsize.body if isinstance(n, ast.FunctionDef)}
+def test_every_row_has_a_case():
+    """No exemptions: the classes of the two-level plan's bucket-local sorts that n > 2^27 selects, once reached by full-size tests only
+    (or not at all), run with their class forced (gs_debug_set_hy_class)."""
     used = set()
     for family, coord, case, exempt in rc.ROWS:
         assert family in rc.FAMILIES
-        if case is not None:
-            assert case in rc.CASES, (family, coord, case)
-            used.add(case)
-            continue
-        # the closed list of exemptions: classes 1 .. 3 of the two-level plan's bucket-local sorts (n > 2^27)
-        assert family in ("g_hy_local", "g_hy_local_pairs") and coord[-2] >= 1, (family, coord)
-        if exempt != rc.UNCOVERED:
-            module, _, name = exempt.partition("::")
-            assert module == "tests.test_gpu_fullsize" and name in tests, (family, coord, exempt)
+        assert exempt is None and case in rc.CASES, (family, coord, case, exempt)
+        used.add(case)
     extra = {c for c, what in rc.CASES.items() if what["kind"] == "topk1d"}   # (cases without a registry table of their own)
     assert used | extra == set(rc.CASES), sorted(set(rc.CASES) - used - extra)
     for cid, what in rc.CASES.items():
         assert what["evidence"], cid
+    # the bucket-local sorts: 12 keys-only cells, 21 for pairs; classes 1 .. 3 by a case that forces the class and sorts a bucket of its cap
+    local = [(f, c, case) for f, c, case, _ in rc.ROWS if f in ("g_hy_local", "g_hy_local_pairs")]
+    assert sum(f == "g_hy_local" for f, _, _ in local) == 12 and sum(f == "g_hy_local_pairs" for f, _, _ in local) == 21
+    for family, coord, case in local:
+        cls, what = coord[-2], rc.CASES[case]
+        if cls == 0:
+            assert what["kind"] == "hy", (family, coord)
+        else:
+            assert what["kind"] == "hy_class" and what["hy_class"] == cls and what["cap"] == rc.HY_CAP[cls], (family, coord, what)
+            assert what["kt"] == coord[-1] and what["vb"] == (0 if family == "g_hy_local" else (4, 8)[coord[0]]), (family, coord, what)
+            assert what["evidence"] == "last_plan two_level; largest_bucket == cap of the class"
 
 
 def test_uncovered_cells_are_the_ones_the_design_document_lists():
-    """DESIGN.md carries the table of uncovered cells: it must name each of them (family and coordinate) and no other."""
+    """DESIGN.md carries the table of uncovered cells between its markers: the ledger has none, and the table is empty."""
     text = open(os.path.join(ROOT, "DESIGN.md")).read()
     start = text.index("<!-- uncovered-cells:begin -->")
     table = text[start:text.index("<!-- uncovered-cells:end -->")]
     listed = {ln.split("|")[1].strip() for ln in table.splitlines() if ln.startswith("| `g_")}
-    want = {f"`{family}{list(coord)}`" for family, coord, _, exempt in rc.ROWS if exempt == rc.UNCOVERED}
-    assert listed == want, (sorted(listed - want), sorted(want - listed))
+    want = {f"`{family}{list(coord)}`" for family, coord, _, exempt in rc.ROWS if exempt is not None}
+    assert want == set() and listed == want, (sorted(listed - want), sorted(want - listed))
 
 
 def test_registry_hooks_refuse_bad_families_and_coordinates():
@@ -123,6 +126,7 @@ def test_route_and_flag_hooks_refuse_null_arguments():
     buf = (C.c_uint32 * 8)()
     assert lib.gs_debug_sort_route(None, 1024, 0, buf) == L.GS_ERR_ARG
     assert lib.gs_debug_pass_flags(None, buf, None) == L.GS_ERR_ARG
+    assert lib.gs_debug_set_hy_class(None, -1) == L.GS_ERR_ARG
     assert lib.gs_segsort_engine(None) is None and lib.gs_topk_engine(None) is None
 
 
