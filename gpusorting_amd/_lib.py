@@ -20,12 +20,19 @@ GS_PROFILE_SLOTS = 8
 GS_SEGSORT_CLASSES = 9
 GS_TOPK_REPORT_WORDS = 8
 GS_TOPK_ROWS_REPORT_WORDS = 8
+# gs_sort16_last: report words, routes and the kernel-form bits
+GS_SORT16_REPORT_WORDS = 8
+GS_SORT16_ROUTE_NONE, GS_SORT16_ROUTE_KEYS, GS_SORT16_ROUTE_PAIRS = 0, 1, 2
+(GS_SORT16_R_ROUTE, GS_SORT16_R_RANGES, GS_SORT16_R_PER_RANGE, GS_SORT16_R_TILE, GS_SORT16_R_FORMS, GS_SORT16_R_STATUS, GS_SORT16_R_N,
+ GS_SORT16_R_RANK) = range(8)
+GS_SORT16_F_HIST, GS_SORT16_F_SCAN, GS_SORT16_F_FILL, GS_SORT16_F_COUNT, GS_SORT16_F_PSCAN, GS_SORT16_F_SCATTER = 1, 2, 4, 8, 16, 32
+GS_SORT16_F_ALL = 0x7FF
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
 GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
 (GS_KF_BIN, GS_KF_POS, GS_KF_PERSIST, GS_KF_SMALL, GS_KF_MID, GS_KF_SEG_WG, GS_KF_SEG_VB, GS_KF_TKR_TILE, GS_KF_TKR_VM, GS_KF_HIST,
  GS_KF_HY_HIST, GS_KF_HY_LOCAL, GS_KF_HY_LOCAL_PAIRS, GS_KF_COUNT) = range(14)
-# gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs only
+# gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs and by gs_sort16_*
 KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16 = 6, 7, 8, 9
 
 # every symbol include/gpusort.h declares: (name, restype, argtypes)
@@ -194,6 +201,17 @@ _PROTOS = [
     ("gs_topk_select_rows_pairs", _int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _int, _int, _vp]),
     ("gs_topk_rows_max_k", _u32, [_int, _u32]),
     ("gs_topk_rows_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_sort16_create", _int, [C.POINTER(_vp), _u32, _int, _u32]),
+    ("gs_sort16_destroy", _int, [_vp]),
+    ("gs_sort16_temp_bytes", C.c_size_t, [_u32, _int, _u32]),
+    ("gs_sort16_sort_keys", _int, [_vp, _vp, _u32, _int, _int, _vp]),
+    ("gs_sort16_sort_pairs", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _int, _int, _vp]),
+    ("gs_sort16_argsort", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _int, _int, _vp]),
+    ("gs_sort16_check", _int, [_vp, _vp]),
+    ("gs_sort16_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_sort16_plan", _int, [_u32, _int, _u32, _u32p]),
+    ("gs_sort16_set_rank_mode", _int, [_vp, _int]),
+    ("gs_sort16_get_rank_mode", _int, [_vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

@@ -19,6 +19,7 @@
 #include "topk_kernels.hpp"
 #include "topk_rows_kernels.hpp"
 #include "topk_rows16_kernels.hpp"
+#include "sort16_kernels.hpp"
 
 // One translation unit; one host file per concern, in this order (each may use what stands above it):
 #include "host_common.hpp"      // GS_HIP, argument predicates, div_up, cu_count, DeviceScratch
@@ -26,4 +27,5 @@
 #include "onesweep_host.hpp"    // gs_onesweep: slab sizing, prologue, routing, sort_impl; every gs_onesweep_* / gs_selftest_* / gs_debug_* entry
 #include "segsort_host.hpp"     // gs_segsort
 #include "topk_host.hpp"        // gs_topk: the 1-D selection and the row-wise one
+#include "sort16_host.hpp"      // gs_sort16: the sort of 16-bit keys
 #include "gpusort_mgpu.hpp"     // gs_mgpu, gs_onesweep_sort_sharded

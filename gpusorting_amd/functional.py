@@ -1,7 +1,8 @@
 """Tensor-in / tensor-out convenience on top of ``OneSweep`` (PyTorch-ROCm plumbing only: dtype -> key type,
 handle cache, buffers).  The reference has no such layer; it is what a torch user types:
 
-    sorted_keys = gpusorting_amd.sort(keys)                                  # int32 / uint32-as-int32 / float32
+    sorted_keys = gpusorting_amd.sort(keys)                                  # int32 / uint32-as-int32 / float32,
+                                                                             # float16 / bfloat16 / int16 / uint16 (Sort16)
     sorted_keys, sorted_vals = gpusorting_amd.sort(keys, values, descending=True)
     gpusorting_amd.sort_(keys, values)                                       # in place
 
@@ -14,11 +15,12 @@ import torch
 
 from . import _lib
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
+from .sort16 import Sort16, sort16_reference  # noqa: F401
 from .topk import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, TopK, rows_max_k, topk_reference, topk_rows_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
 
 _KEY_TYPE = {torch.int32: KEY_INT32, torch.float32: KEY_FLOAT32, torch.uint32: KEY_UINT32}
-# 2-byte keys: the row-wise top-k only (torch.uint16 where this torch has it)
+# 2-byte keys: sort / sort_ / argsort (Sort16) and the row-wise top-k (torch.uint16 where this torch has it)
 _KEY16_TYPE = {torch.float16: KEY_FLOAT16, torch.bfloat16: KEY_BFLOAT16, torch.int16: KEY_INT16}
 if hasattr(torch, "uint16"):
     _KEY16_TYPE[torch.uint16] = KEY_UINT16
@@ -39,13 +41,59 @@ def _sorter(device: torch.device, n: int, key_type: int, order: int, value_bytes
     return s
 
 
-def sort_(keys: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False, unsigned: bool = False) -> None:
-    """Sort ``keys`` (and carry ``values``) in place on the current stream.  ``unsigned=True`` treats int32 storage
-    as uint32 keys (torch has little uint32 support)."""
+def _sorter16(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> Sort16:
+    """The same cache rule for 16-bit keys: one ``Sort16`` handle per (device, stream, type, order, value width)."""
+    key = (16, device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+    s = _cache.get(key)
+    if s is None or s.max_keys < n:
+        if s is not None:
+            s.close()
+        cap = 1 << max(int(n - 1).bit_length(), 16)
+        s = Sort16(min(cap, (1 << 30) - 1), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes, device=device.index)
+        _cache[key] = s
+    return s
+
+
+def _values_width(keys: torch.Tensor, values: torch.Tensor | None) -> int:
+    if values is None:
+        return 0
+    if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:
+        raise ValueError("values must match keys in shape and device and be contiguous")
+    if values.element_size() not in (4, 8):
+        raise TypeError("values must be 4 or 8 bytes wide")
+    return values.element_size()
+
+
+def _sort16_(keys: torch.Tensor, values: torch.Tensor | None, descending: bool, unsigned: bool, positions: torch.Tensor | None = None) -> None:
+    """``sort_`` / ``argsort`` on 2-byte keys: one ``gs_sort16_*`` call (``positions``: argsort's output, made by the kernels)."""
+    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    vb = 4 if positions is not None else _values_width(keys, values)
+    n = keys.numel()
+    if n == 0:
+        return
+    with torch.cuda.device(keys.device):
+        s = _sorter16(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb)
+        if positions is not None:
+            s.argsort(keys, positions, n=n)
+        else:
+            s.sort(keys, values, n=n)
+
+
+def _require_1d_keys(keys: torch.Tensor) -> None:
     if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
         raise ValueError("keys must be a contiguous 1-D device tensor")
+
+
+def sort_(keys: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False, unsigned: bool = False) -> None:
+    """Sort ``keys`` (and carry ``values``) in place on the current stream.  ``unsigned=True`` treats int32 storage
+    as uint32 keys (torch has little uint32 support), and int16 storage as uint16 keys.  16-bit keys (float16, bfloat16, int16, uint16)
+    are sorted at their own width (``Sort16``)."""
+    _require_1d_keys(keys)
+    if keys.dtype in _KEY16_TYPE:
+        return _sort16_(keys, values, descending, unsigned)
     if keys.dtype not in _KEY_TYPE:
-        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
+        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys (int32, uint32, float32) and 16-bit keys "
+                        "(float16, bfloat16, int16, uint16)")
     kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
     vb = 0
     if values is not None:
@@ -71,7 +119,12 @@ def sort(keys: torch.Tensor, values: torch.Tensor | None = None, descending: boo
 
 
 def argsort(keys: torch.Tensor, descending: bool = False, unsigned: bool = False) -> torch.Tensor:
-    """Stable permutation that sorts ``keys`` (int32 indices; n < 2^30)."""
+    """Stable permutation that sorts ``keys`` (int32 indices; n < 2^30).  16-bit keys: the kernels make the positions themselves."""
+    if keys.dtype in _KEY16_TYPE:
+        _require_1d_keys(keys)
+        idx = torch.empty(keys.numel(), dtype=torch.int32, device=keys.device)
+        _sort16_(keys.clone(), None, descending, unsigned, positions=idx)
+        return idx
     idx = torch.arange(keys.numel(), dtype=torch.int32, device=keys.device)
     k = keys.clone()
     sort_(k, idx, descending, unsigned)

@@ -56,7 +56,8 @@ typedef enum gs_key_type {
      * gs_onesweep_sort_keys / _sort_pairs / _digit_pass (pass 0..7) and gs_validate; not by the histogram read-back,
      * the MSD split and the generator, which are 32-bit. */
     GS_KEY_UINT64 = 3, GS_KEY_INT64 = 4, GS_KEY_FLOAT64 = 5,
-    /* 16-bit keys: 2-byte elements, FLOAT16 is IEEE binary16.  Accepted by gs_topk_select_rows_keys / _pairs ONLY (see there); every
+    /* 16-bit keys: 2-byte elements, FLOAT16 is IEEE binary16.  Accepted by gs_topk_select_rows_keys / _pairs (see there) and by the
+     * gs_sort16_* family (gs_sort16_sort_keys / _sort_pairs / _argsort, at the end of this header), which takes nothing else; every
      * other entry that takes a gs_key_type treats them as it treats any value it does not know. */
     GS_KEY_UINT16 = 6, GS_KEY_INT16 = 7, GS_KEY_FLOAT16 = 8, GS_KEY_BFLOAT16 = 9
 } gs_key_type;
@@ -649,6 +650,79 @@ gs_status gs_topk_select_rows_pairs(gs_topk* h, const void* d_keys, const void* 
 uint32_t gs_topk_rows_max_k(gs_mode mode, uint32_t value_bytes);
 /* Synchronous diagnostics of the last row-wise call: report[GS_TOPK_ROWS_R_*], words >= GS_TOPK_ROWS_REPORT_WORDS. */
 gs_status gs_topk_rows_last(gs_topk* h, uint32_t* report, uint32_t words, void* stream);
+
+/* ---- sort of 16-bit keys: GS_KEY_UINT16 / INT16 / FLOAT16 / BFLOAT16 at their own width, keys, pairs and argsort -----------------
+ * No counterpart in the reference project.  The library's own semantics on 16 bits: uint16 sorts as it is, int16 with the sign bit
+ * flipped, float16 and bfloat16 by the order-preserving flip (sign bit set: all 16 bits inverted; otherwise the sign bit flipped:
+ * -0 < +0, NaNs by bit pattern); stable by key; descending = the exact reverse of the stable ascending result (equal keys come out in
+ * falling position); values are bit-copied; every key bit pattern is preserved exactly (NaN payloads, subnormals, -0).
+ *
+ * Keys only is a counting sort: one histogram over all 65 536 patterns (the array is cut into ranges, gs_sort16_plan, and every
+ * range is read by two workgroups, one per half of the bin space: 4 bytes read per key), a scan, and a fill that writes the sorted
+ * array from the histogram (2 bytes written per key) — in place, no n-sized scratch, three launches and a clear.  Pairs and argsort are
+ * two stable 8-bit passes (low byte into d_alt_*, high byte back), each a count, a scan and a scatter launch: one workgroup per range
+ * walks its tiles in order with running per-digit bases.  No kernel waits on another workgroup.
+ *
+ * 1 <= n <= max_keys <= GS_MAX_KEYS; base pointers 16-byte aligned; key elements are 2 bytes; nothing at or behind element n of any
+ * buffer is written, at 2-byte granularity for the keys.
+ * GS_ERR_ARG: null handle (before anything else is looked at), null or misaligned pointer, a key type outside 6 .. 9, any two of the
+ * call's buffers overlapping.  GS_ERR_MODE: keys call on a pairs handle or the reverse, gs_sort16_argsort on anything but a handle with
+ * 4-byte values (and every sort call on a build flavour without these kernels: the tuning and fault-injection libraries).
+ * GS_ERR_SIZE: n == 0 or n > max_keys.
+ * Precedence, as in gs_topk_select_*: GS_ERR_ARG for the handle, d_keys, the key type and the order; then GS_ERR_MODE; then GS_ERR_ARG
+ * for the value and alternate pointers of a pairs call; then GS_ERR_SIZE; then GS_ERR_ARG for overlapping buffers (the overlap test
+ * needs a valid n).
+ * Asynchronous on `stream`, every launch enqueued up front, no host round trip: a call can be captured into a graph.  One in-flight
+ * call per handle. */
+typedef struct gs_sort16 gs_sort16;
+#define GS_SORT16_ROUTE_NONE 0u
+#define GS_SORT16_ROUTE_KEYS 1u    /* histogram, scan, fill */
+#define GS_SORT16_ROUTE_PAIRS 2u   /* two passes of count, scan, scatter (gs_sort16_sort_pairs and gs_sort16_argsort) */
+/* gs_sort16_last report words */
+#define GS_SORT16_R_ROUTE 0      /* GS_SORT16_ROUTE_* of the last call */
+#define GS_SORT16_R_RANGES 1     /* as gs_sort16_plan: ranges, */
+#define GS_SORT16_R_PER_RANGE 2  /* elements per range, */
+#define GS_SORT16_R_TILE 3       /* tile */
+#define GS_SORT16_R_FORMS 4      /* GS_SORT16_F_*: the kernel forms the call launched */
+#define GS_SORT16_R_STATUS 5     /* the device status word: 0, or 1 if a count did not add up (gs_sort16_check: GS_ERR_HIP) */
+#define GS_SORT16_R_N 6
+#define GS_SORT16_R_RANK 7       /* the handle's rank mode */
+#define GS_SORT16_REPORT_WORDS 8
+#define GS_SORT16_F_HIST 1u
+#define GS_SORT16_F_SCAN 2u
+#define GS_SORT16_F_FILL 4u
+#define GS_SORT16_F_COUNT 8u
+#define GS_SORT16_F_PSCAN 16u
+#define GS_SORT16_F_SCATTER 32u  /* << (2 x v + rank mode), v = 0 positions made in registers (argsort, first pass), 1 4-byte, 2 8-byte values: bits 5 .. 10 */
+#define GS_SORT16_F_ALL 0x7ffu
+/* value_bytes 0 (keys only), 4 or 8, as gs_onesweep_create.  Synchronous (allocates gs_sort16_temp_bytes of device memory). */
+gs_status gs_sort16_create(gs_sort16** out, uint32_t max_keys, gs_mode mode, uint32_t value_bytes);
+gs_status gs_sort16_destroy(gs_sort16* h);
+/* Host only.  Keys only: a 256-byte control block + the 65 536-word histogram + its 65 537-word prefix; pairs: the control block + two
+ * tables of (range cap) x 256 words.  Independent of max_keys; 0 for an invalid size, mode or value width. */
+size_t gs_sort16_temp_bytes(uint32_t max_keys, gs_mode mode, uint32_t value_bytes);
+/* In place; no scratch array. */
+gs_status gs_sort16_sort_keys(gs_sort16* h, void* d_keys, uint32_t n, gs_key_type key_type, gs_order order, void* stream);
+/* Result in d_keys / d_vals; d_alt_* are scratch of n elements each. */
+gs_status gs_sort16_sort_pairs(gs_sort16* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t n,
+                               gs_key_type key_type, gs_order order, void* stream);
+/* Handle with 4-byte values: d_pos is OUTPUT only (the uint32 input positions of the sorted order) and never read on entry: the first
+ * pass makes the positions in registers. */
+gs_status gs_sort16_argsort(gs_sort16* h, void* d_keys, void* d_pos, void* d_alt_keys, void* d_alt_pos, uint32_t n,
+                            gs_key_type key_type, gs_order order, void* stream);
+/* Synchronises `stream` and reads the device status word, which every call resets: GS_OK, or GS_ERR_HIP if a count did not add up
+ * (cannot happen; no store leaves its buffer either way). */
+gs_status gs_sort16_check(gs_sort16* h, void* stream);
+/* Synchronous diagnostics of the last call: report[GS_SORT16_R_*], words >= GS_SORT16_REPORT_WORDS. */
+gs_status gs_sort16_last(gs_sort16* h, uint32_t* report, uint32_t words, void* stream);
+/* Host only: how a sort of n elements is cut — plan[0] ranges, [1] elements per range (a multiple of the tile; the smallest range is
+ * one tile), [2] tile (8192 keys only, 4096 pairs), [3] range cap (128 keys only, 512 pairs).  ranges x per-range >= n.  GS_ERR_ARG
+ * for a null plan, GS_ERR_MODE for an invalid mode or value width, GS_ERR_SIZE for n == 0 or n > GS_MAX_KEYS. */
+gs_status gs_sort16_plan(uint32_t n, gs_mode mode, uint32_t value_bytes, uint32_t plan[4]);
+/* The scatter's ranking inside a tile, as gs_onesweep_set_rank_mode: 0 = 64-lane ballot multi-split, 1 = one returning LDS atomic per
+ * key; gs_sort16_create probes the device as gs_onesweep_create does.  get: -1 for a null handle. */
+gs_status gs_sort16_set_rank_mode(gs_sort16* h, int mode);
+int gs_sort16_get_rank_mode(gs_sort16* h);
 
 #ifdef __cplusplus
 }
