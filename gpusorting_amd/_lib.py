@@ -27,6 +27,16 @@ GS_SORT16_ROUTE_NONE, GS_SORT16_ROUTE_KEYS, GS_SORT16_ROUTE_PAIRS = 0, 1, 2
  GS_SORT16_R_RANK) = range(8)
 GS_SORT16_F_HIST, GS_SORT16_F_SCAN, GS_SORT16_F_FILL, GS_SORT16_F_COUNT, GS_SORT16_F_PSCAN, GS_SORT16_F_SCATTER = 1, 2, 4, 8, 16, 32
 GS_SORT16_F_ALL = 0x7FF
+# gs_sort_rows_plan / gs_sort_rows_last: plan and report words, routes and the kernel-form bits
+GS_SORT_ROWS_PLAN_WORDS = GS_SORT_ROWS_REPORT_WORDS = 8
+GS_SORT_ROWS_ROUTE_NONE, GS_SORT_ROWS_ROUTE_LDS, GS_SORT_ROWS_ROUTE_PASSES = 0, 1, 2
+GS_SORT_ROWS_TILE, GS_SORT_ROWS_PCAP, GS_SORT_ROWS_MIN_TILES, GS_SORT_ROWS_PASSES = 4096, 1024, 2, 4
+(GS_SORT_ROWS_P_ROUTE, GS_SORT_ROWS_P_PARTS, GS_SORT_ROWS_P_PER_PART, GS_SORT_ROWS_P_TILE, GS_SORT_ROWS_P_PASSES, GS_SORT_ROWS_P_CAP) = range(6)
+(GS_SORT_ROWS_R_ROUTE, GS_SORT_ROWS_R_ROWS, GS_SORT_ROWS_R_ROW_LEN, GS_SORT_ROWS_R_PARTS, GS_SORT_ROWS_R_FORMS, GS_SORT_ROWS_R_STATUS,
+ GS_SORT_ROWS_R_RANK, GS_SORT_ROWS_R_PER_PART) = range(8)
+(GS_SORT_ROWS_F_CLEAR, GS_SORT_ROWS_F_OFFSETS, GS_SORT_ROWS_F_LDS, GS_SORT_ROWS_F_COUNT, GS_SORT_ROWS_F_SCAN,
+ GS_SORT_ROWS_F_SCATTER) = 1, 2, 4, 8, 16, 32
+GS_SORT_ROWS_F_ALL = 0x7FF
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
 GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
@@ -212,6 +222,16 @@ _PROTOS = [
     ("gs_sort16_plan", _int, [_u32, _int, _u32, _u32p]),
     ("gs_sort16_set_rank_mode", _int, [_vp, _int]),
     ("gs_sort16_get_rank_mode", _int, [_vp]),
+    ("gs_sort_rows_create", _int, [C.POINTER(_vp), _u32, _int, _u32]),
+    ("gs_sort_rows_destroy", _int, [_vp]),
+    ("gs_sort_rows_temp_bytes", C.c_size_t, [_u32, _int, _u32]),
+    ("gs_sort_rows_plan", _int, [_u32, _u32, _int, _u32, _u32p]),
+    ("gs_sort_rows_keys", _int, [_vp, _vp, _vp, _u32, _u32, _int, _int, _vp]),
+    ("gs_sort_rows_pairs", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _int, _vp]),
+    ("gs_sort_rows_check", _int, [_vp, _vp]),
+    ("gs_sort_rows_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_sort_rows_set_rank_mode", _int, [_vp, _int]),
+    ("gs_sort_rows_get_rank_mode", _int, [_vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

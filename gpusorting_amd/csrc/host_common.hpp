@@ -32,6 +32,16 @@ inline bool is_key64(gs_key_type kt) { return (int)kt >= 3; }
 inline bool is_key16(gs_key_type kt) { return (int)kt >= 6 && (int)kt <= 9; }  // 2-byte keys: the row-wise top-k entries only
 inline bool valid_order(gs_order order) { return order == GS_ORDER_ASCENDING || order == GS_ORDER_DESCENDING; }
 
+// a handle's mode and value width: keys only without values, pairs with 4- or 8-byte values
+inline bool mode_value_ok(gs_mode mode, uint32_t vb) {
+    return mode == GS_MODE_KEYS_ONLY ? vb == 0u : mode == GS_MODE_PAIRS && (vb == 4u || vb == 8u);
+}
+// do [a, a + na) and [b, b + nb) share a byte
+inline bool buffers_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+}
+
 // compute units of the device (read once per process; 256 if it cannot be read)
 uint32_t cu_count() {
     static const uint32_t cus = [] {

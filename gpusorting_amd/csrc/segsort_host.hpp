@@ -31,6 +31,35 @@ uint32_t seg_grid(uint32_t bound, uint32_t waves, size_t lds_bytes) {
     return bound < g ? (bound ? bound : 1u) : g;
 }
 
+// The launches of every class that fits LDS (0 .. 7, up to `top`): reset, classify, fill, packed, wave, workgroup classes.  ctl: a
+// control block of gs::SEGC_WORDS words with the class lists behind it; rank_mode: the ranking of the workgroup classes.  No host
+// wait.  Shared with the row-wise sort (sortrows_host.hpp), whose short rows are segments at uniform offsets.
+gs_status seg_enqueue_lds(uint32_t* ctl, int rank_mode, uint32_t vb, uint32_t* keys, void* d_vals, uint32_t n, const uint32_t* d_offsets,
+                          uint32_t num_segments, uint32_t max_len, uint32_t top, gs_key_type kt, uint32_t desc, hipStream_t s) {
+    uint32_t* list = ctl + gs::SEGC_WORDS;
+    hipLaunchKernelGGL(gs::seg_reset_kernel, dim3(1), dim3(64), 0, s, ctl);
+    const uint32_t seg_blocks = div_up(num_segments, 256);
+    hipLaunchKernelGGL(gs::seg_classify_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, n, vb, max_len, ctl);
+    if (top >= 2) hipLaunchKernelGGL(gs::seg_fill_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, vb, max_len, ctl, list);
+    const SegVbLaunchers& f = seg_vb(vb);
+    if (top >= 1) f.packed(s, div_up(num_segments, 64), keys, d_vals, d_offsets, num_segments, max_len, (uint32_t)kt, desc, ctl);
+    // a class whose shortest segment has m elements holds at most n / m segments
+    auto bound = [&](uint32_t min_len) { const uint32_t b = n / min_len; return b < num_segments ? b : num_segments; };
+    if (top >= 2 && n > gs::SEG_PACK_MAX)
+        f.wave(s, seg_grid(bound(gs::SEG_PACK_MAX + 1), 1, gs::SEG_WAVE_MAX * (8 + vb)), keys, d_vals, d_offsets, list, ctl, num_segments, (uint32_t)kt, desc);
+    for (uint32_t c = 3; c <= 7 && c <= top; ++c) {
+        const uint32_t min_len = gs::SEG_CLASS_MAX[c - 1] + 1;
+        if (n < min_len || gs::SEG_CLASS_MAX[c] > gs::seg_max_lds(vb)) continue;
+        const Shape sh = g_small_class[c - 3];
+        const SegWgLauncher wg = seg_wg_launcher((int)c - 3, rank_mode, vb, (int)kt);
+        if (!wg) return GS_ERR_MODE;
+        const size_t lds = (size_t)sh.threads * sh.kpt * (4 + vb) + (size_t)sh.threads / 64 * gs::RADIX * 4 + 64;
+        wg(s, SEG_WG_LOOP(sh.threads, sh.kpt) ? seg_grid(bound(min_len), (uint32_t)sh.threads / 64, lds) : bound(min_len), keys, d_vals, d_offsets, list, ctl, num_segments, c, desc);
+    }
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
 gs_status segsort_impl(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t n, const uint32_t* d_offsets,
                        uint32_t num_segments, uint32_t max_len, gs_key_type kt, gs_order order, hipStream_t s, bool pairs) {
     if (!h || !d_keys || !d_offsets || misaligned(d_keys) || (reinterpret_cast<uintptr_t>(d_offsets) & 3u) || !is_key32_type(kt) || !valid_order(order))
@@ -46,29 +75,12 @@ gs_status segsort_impl(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_ke
     const uint32_t desc = order == GS_ORDER_DESCENDING ? 1u : 0u;
     uint32_t* keys = static_cast<uint32_t*>(d_keys);
     h->long_failed = false;
-    hipLaunchKernelGGL(gs::seg_reset_kernel, dim3(1), dim3(64), 0, s, h->ctl);
-    const uint32_t seg_blocks = div_up(num_segments, 256);
-    hipLaunchKernelGGL(gs::seg_classify_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, n, vb, max_len, h->ctl);
-    if (top >= 2) hipLaunchKernelGGL(gs::seg_fill_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, vb, max_len, h->ctl, seg_list(h));
-    const SegVbLaunchers& f = seg_vb(vb);
-    if (top >= 1) f.packed(s, div_up(num_segments, 64), keys, d_vals, d_offsets, num_segments, max_len, (uint32_t)kt, desc, h->ctl);
-    // a class whose shortest segment has m elements holds at most n / m segments
-    auto bound = [&](uint32_t min_len) { const uint32_t b = n / min_len; return b < num_segments ? b : num_segments; };
-    if (top >= 2 && n > gs::SEG_PACK_MAX)
-        f.wave(s, seg_grid(bound(gs::SEG_PACK_MAX + 1), 1, gs::SEG_WAVE_MAX * (8 + vb)), keys, d_vals, d_offsets, seg_list(h), h->ctl, num_segments, (uint32_t)kt, desc);
-    for (uint32_t c = 3; c <= 7 && c <= top; ++c) {
-        const uint32_t min_len = gs::SEG_CLASS_MAX[c - 1] + 1;
-        if (n < min_len || gs::SEG_CLASS_MAX[c] > gs::seg_max_lds(vb)) continue;
-        const Shape sh = g_small_class[c - 3];
-        const SegWgLauncher wg = seg_wg_launcher((int)c - 3, h->engine->rank_mode, vb, (int)kt);
-        if (!wg) return GS_ERR_MODE;
-        const size_t lds = (size_t)sh.threads * sh.kpt * (4 + vb) + (size_t)sh.threads / 64 * gs::RADIX * 4 + 64;
-        wg(s, SEG_WG_LOOP(sh.threads, sh.kpt) ? seg_grid(bound(min_len), (uint32_t)sh.threads / 64, lds) : bound(min_len), keys, d_vals, d_offsets, seg_list(h), h->ctl, num_segments, c, desc);
-    }
-    GS_HIP(hipGetLastError());
+    const gs_status lds = seg_enqueue_lds(h->ctl, h->engine->rank_mode, vb, keys, d_vals, n, d_offsets, num_segments, max_len, top, kt, desc, s);
+    if (lds != GS_OK) return lds;
     if (!allow_long || n <= gs::seg_max_lds(vb)) return GS_OK;
     // ---- long segments: the one host wait.  Control block + the head of the long list (it starts the list array) ----
-    const uint32_t most = bound(gs::seg_max_lds(vb) + 1);
+    const SegVbLaunchers& f = seg_vb(vb);
+    const uint32_t by_len = n / (gs::seg_max_lds(vb) + 1), most = by_len < num_segments ? by_len : num_segments;  // long segments at most
     uint32_t got = most < SEG_LONG_CHUNK ? most : SEG_LONG_CHUNK;
     GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, (gs::SEGC_WORDS + got) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     GS_HIP(hipStreamSynchronize(s));

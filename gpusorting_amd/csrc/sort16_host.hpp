@@ -31,10 +31,6 @@ Sort16Layout sort16_layout(bool pairs) {
     return l;
 }
 
-inline bool sort16_mode_ok(gs_mode mode, uint32_t vb) {
-    return mode == GS_MODE_KEYS_ONLY ? vb == 0u : mode == GS_MODE_PAIRS && (vb == 4u || vb == 8u);
-}
-
 // plan[0] ranges, [1] elements per range (a multiple of the tile), [2] tile, [3] range cap.  The smallest range is one tile.
 void sort16_plan(uint32_t n, bool pairs, uint32_t plan[4]) {
     const uint32_t tile = pairs ? gs::S16_PTILE : gs::S16_KTILE, cap = pairs ? gs::S16_PCAP : gs::S16_KCAP;
@@ -43,11 +39,6 @@ void sort16_plan(uint32_t n, bool pairs, uint32_t plan[4]) {
     plan[1] = per;
     plan[2] = tile;
     plan[3] = cap;
-}
-
-bool sort16_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
 }
 
 #if GS_SORT16_BUILT
@@ -126,7 +117,7 @@ gs_status sort16_impl(gs_sort16* h, void* d_keys, void* d_vals, void* d_alt_keys
         const size_t b[4] = {kb, kb, vb, vb};
         for (int i = 0; i < 4; ++i)
             for (int j = i + 1; j < 4; ++j)
-                if (sort16_overlap(p[i], b[i], p[j], b[j])) return GS_ERR_ARG;
+                if (buffers_overlap(p[i], b[i], p[j], b[j])) return GS_ERR_ARG;
     }
     if (!S16_BUILT) return GS_ERR_MODE;  // this build flavour has no 16-bit sort
 #if GS_SORT16_BUILT
@@ -150,13 +141,13 @@ gs_status sort16_impl(gs_sort16* h, void* d_keys, void* d_vals, void* d_alt_keys
 extern "C" {
 
 size_t gs_sort16_temp_bytes(uint32_t max_keys, gs_mode mode, uint32_t value_bytes) {
-    if (max_keys == 0 || max_keys > GS_MAX_KEYS || !sort16_mode_ok(mode, value_bytes)) return 0;
+    if (max_keys == 0 || max_keys > GS_MAX_KEYS || !mode_value_ok(mode, value_bytes)) return 0;
     return sort16_layout(mode == GS_MODE_PAIRS).total;
 }
 
 gs_status gs_sort16_plan(uint32_t n, gs_mode mode, uint32_t value_bytes, uint32_t plan[4]) {
     if (!plan) return GS_ERR_ARG;
-    if (!sort16_mode_ok(mode, value_bytes)) return GS_ERR_MODE;
+    if (!mode_value_ok(mode, value_bytes)) return GS_ERR_MODE;
     if (n == 0 || n > GS_MAX_KEYS) return GS_ERR_SIZE;
     sort16_plan(n, mode == GS_MODE_PAIRS, plan);
     return GS_OK;
@@ -166,7 +157,7 @@ gs_status gs_sort16_create(gs_sort16** out, uint32_t max_keys, gs_mode mode, uin
     if (!out) return GS_ERR_ARG;
     *out = nullptr;
     if (max_keys == 0 || max_keys > GS_MAX_KEYS) return GS_ERR_SIZE;
-    if (!sort16_mode_ok(mode, value_bytes)) return GS_ERR_MODE;
+    if (!mode_value_ok(mode, value_bytes)) return GS_ERR_MODE;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return GS_ERR_NO_DEVICE;
     gs_sort16* h = new (std::nothrow) gs_sort16();

@@ -5,6 +5,7 @@ handle cache, buffers).  The reference has no such layer; it is what a torch use
                                                                              # float16 / bfloat16 / int16 / uint16 (Sort16)
     sorted_keys, sorted_vals = gpusorting_amd.sort(keys, values, descending=True)
     gpusorting_amd.sort_(keys, values)                                       # in place
+    sorted_rows = gpusorting_amd.sort(matrix)                                # 2-D: every row on its own, torch.sort(x, dim=-1) (RowSort)
 
 Semantics are the library's: stable LSD radix sort; descending = exact reverse of the stable ascending result;
 float keys ordered by the order-preserving bit flip (-0 < +0, NaNs by bit pattern); values bit-copied.
@@ -15,6 +16,7 @@ import torch
 
 from . import _lib
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
+from .rowsort import RowSort, sort_rows_reference  # noqa: F401
 from .sort16 import Sort16, sort16_reference  # noqa: F401
 from .topk import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, TopK, rows_max_k, topk_reference, topk_rows_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
@@ -54,6 +56,19 @@ def _sorter16(device: torch.device, n: int, key_type: int, order: int, value_byt
     return s
 
 
+def _row_sorter(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> RowSort:
+    """The same cache rule for the row-wise sort: one ``RowSort`` handle per (device, stream, type, order, value width)."""
+    key = ("rows", device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+    s = _cache.get(key)
+    if s is None or s.max_keys < n:
+        if s is not None:
+            s.close()
+        cap = 1 << max(int(n - 1).bit_length(), 16)
+        s = RowSort(min(cap, (1 << 30) - 1), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes, device=device.index)
+        _cache[key] = s
+    return s
+
+
 def _values_width(keys: torch.Tensor, values: torch.Tensor | None) -> int:
     if values is None:
         return 0
@@ -79,6 +94,26 @@ def _sort16_(keys: torch.Tensor, values: torch.Tensor | None, descending: bool, 
             s.sort(keys, values, n=n)
 
 
+class RowKeyTypeError(TypeError, ValueError):
+    """A 2-D tensor whose dtype the row-wise sort does not take.  A TypeError like every unsupported dtype; also a ValueError,
+    which is what a 2-D tensor of 16-bit keys raised while ``sort_`` took 1-D tensors only."""
+
+
+def _sort_rows_(keys: torch.Tensor, values: torch.Tensor | None, descending: bool, unsigned: bool) -> None:
+    """``sort_`` on a 2-D tensor: every row sorted along the last dimension by one ``gs_sort_rows_*`` call."""
+    if not keys.is_contiguous() or keys.device.type != "cuda":
+        raise ValueError("keys must be a contiguous 2-D device tensor")
+    if keys.dtype not in _KEY_TYPE:
+        raise RowKeyTypeError(f"unsupported key dtype {keys.dtype} for a 2-D tensor: rows are sorted on 32-bit keys only (int32, uint32, float32)")
+    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    vb = _values_width(keys, values)
+    if keys.numel() == 0:
+        return
+    with torch.cuda.device(keys.device):
+        s = _row_sorter(keys.device, keys.numel(), kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb)
+        s.sort(keys.view(torch.int32) if keys.dtype != torch.int32 else keys, values)
+
+
 def _require_1d_keys(keys: torch.Tensor) -> None:
     if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
         raise ValueError("keys must be a contiguous 1-D device tensor")
@@ -87,7 +122,10 @@ def _require_1d_keys(keys: torch.Tensor) -> None:
 def sort_(keys: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False, unsigned: bool = False) -> None:
     """Sort ``keys`` (and carry ``values``) in place on the current stream.  ``unsigned=True`` treats int32 storage
     as uint32 keys (torch has little uint32 support), and int16 storage as uint16 keys.  16-bit keys (float16, bfloat16, int16, uint16)
-    are sorted at their own width (``Sort16``)."""
+    are sorted at their own width (``Sort16``).  A contiguous 2-D tensor of 32-bit keys is sorted along its last dimension, every row
+    on its own (``RowSort``; ``values`` of the same shape move with their keys)."""
+    if keys.dim() == 2:
+        return _sort_rows_(keys, values, descending, unsigned)
     _require_1d_keys(keys)
     if keys.dtype in _KEY16_TYPE:
         return _sort16_(keys, values, descending, unsigned)
@@ -119,7 +157,13 @@ def sort(keys: torch.Tensor, values: torch.Tensor | None = None, descending: boo
 
 
 def argsort(keys: torch.Tensor, descending: bool = False, unsigned: bool = False) -> torch.Tensor:
-    """Stable permutation that sorts ``keys`` (int32 indices; n < 2^30).  16-bit keys: the kernels make the positions themselves."""
+    """Stable permutation that sorts ``keys`` (int32 indices; n < 2^30).  16-bit keys: the kernels make the positions themselves.
+    2-D tensors of 32-bit keys: int32 positions within the row, ``[rows, row_len]``."""
+    if keys.dim() == 2:
+        rows, row_len = keys.shape
+        idx = torch.arange(row_len, dtype=torch.int32, device=keys.device).repeat(rows, 1)
+        _sort_rows_(keys.clone(), idx, descending, unsigned)
+        return idx
     if keys.dtype in _KEY16_TYPE:
         _require_1d_keys(keys)
         idx = torch.empty(keys.numel(), dtype=torch.int32, device=keys.device)

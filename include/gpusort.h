@@ -724,6 +724,93 @@ gs_status gs_sort16_plan(uint32_t n, gs_mode mode, uint32_t value_bytes, uint32_
 gs_status gs_sort16_set_rank_mode(gs_sort16* h, int mode);
 int gs_sort16_get_rank_mode(gs_sort16* h);
 
+/* ---- row-wise sort: every row of a contiguous [rows, row_len] matrix of 32-bit keys sorted on its own, in one call ------------------
+ * No counterpart in the reference project.  Row r is elements [r * row_len, (r + 1) * row_len) of the array; after the call every row
+ * holds exactly what gs_onesweep_sort_keys / _sort_pairs leaves for that slice, bit for bit: stable by key, descending = the exact
+ * reverse of the row's stable ascending result, floats by the order-preserving bit flip, values bit-copied.  Strided rows are not
+ * taken.  Key types GS_KEY_UINT32 / INT32 / FLOAT32.
+ *
+ * Routes (gs_sort_rows_plan says which; gs_sort_rows_last reports the one taken):
+ *   GS_SORT_ROWS_ROUTE_LDS     row_len <= gs_segsort_max_lds_segment(mode, value_bytes): the packed / wave / workgroup kernels of the
+ *                              segmented sort on uniform offsets that a small kernel writes into the handle's temp memory.  In place;
+ *                              d_alt* are not touched and may be NULL.
+ *   GS_SORT_ROWS_ROUTE_PASSES  longer rows: GS_SORT_ROWS_PASSES stable 8-bit LSD passes over all rows at once, ping-pong between the
+ *                              caller's buffers and d_alt* (the result is back in the caller's buffers), each a count, a scan and a
+ *                              scatter launch behind one clear: 13 launches whatever `rows` is.  Every row is cut into `parts` ranges of
+ *                              whole tiles (a tile never straddles two rows); one workgroup per (row, part) counts, one per row scans,
+ *                              one per (row, part) walks its tiles in order with running per-digit bases.  No kernel waits on another
+ *                              workgroup.  d_alt* are required: rows * row_len elements of scratch each.
+ *
+ * rows >= 1, row_len >= 1, rows * row_len <= max_keys <= GS_MAX_KEYS; only the base pointers need 16-byte alignment (rows start
+ * wherever they start; there is no head-merge step); nothing at or behind element rows * row_len of any buffer is written.
+ * GS_ERR_ARG: null handle (before anything else is looked at), null or misaligned d_keys, a key type outside 0 .. 2 (the 64-bit and the
+ * 16-bit ones), a bad order; then GS_ERR_MODE: keys call on a pairs handle or the reverse (and every call on a build flavour without
+ * these kernels: the tuning and fault-injection libraries); then GS_ERR_ARG for a null or misaligned d_vals; then GS_ERR_SIZE: rows == 0,
+ * row_len == 0 or rows * row_len > max_keys; then, on the pass route, GS_ERR_ARG for a null or misaligned d_alt* and for any two of the
+ * call's buffers overlapping.
+ * Asynchronous on `stream`, every launch enqueued up front, the host is never waited on: a call can be captured into a graph, and
+ * every node of a captured call is a kernel launch.  One in-flight call per handle. */
+typedef struct gs_sort_rows gs_sort_rows;
+#define GS_SORT_ROWS_ROUTE_NONE 0u
+#define GS_SORT_ROWS_ROUTE_LDS 1u
+#define GS_SORT_ROWS_ROUTE_PASSES 2u
+#define GS_SORT_ROWS_TILE 4096u   /* elements a workgroup of the pass route ranks and stages at a time */
+#define GS_SORT_ROWS_PCAP 1024u   /* workgroups rows x parts aims at; with parts > 1 it is never above it */
+#define GS_SORT_ROWS_MIN_TILES 2u /* tiles of a range at least (a row of fewer tiles is one range) */
+#define GS_SORT_ROWS_PASSES 4u
+/* gs_sort_rows_plan words */
+#define GS_SORT_ROWS_P_ROUTE 0     /* GS_SORT_ROWS_ROUTE_LDS / _PASSES */
+#define GS_SORT_ROWS_P_PARTS 1     /* ranges per row (LDS route: 1) */
+#define GS_SORT_ROWS_P_PER_PART 2  /* elements per range: a multiple of the tile, parts x per-part >= row_len > (parts - 1) x per-part (LDS route: row_len) */
+#define GS_SORT_ROWS_P_TILE 3      /* GS_SORT_ROWS_TILE (LDS route: 0) */
+#define GS_SORT_ROWS_P_PASSES 4    /* GS_SORT_ROWS_PASSES (LDS route: 0) */
+#define GS_SORT_ROWS_P_CAP 5       /* max(rows, GS_SORT_ROWS_PCAP): rows x parts never exceeds it */
+#define GS_SORT_ROWS_PLAN_WORDS 8
+/* gs_sort_rows_last report words */
+#define GS_SORT_ROWS_R_ROUTE 0     /* GS_SORT_ROWS_ROUTE_* of the last call */
+#define GS_SORT_ROWS_R_ROWS 1
+#define GS_SORT_ROWS_R_ROW_LEN 2
+#define GS_SORT_ROWS_R_PARTS 3     /* as gs_sort_rows_plan */
+#define GS_SORT_ROWS_R_FORMS 4     /* GS_SORT_ROWS_F_*: the kernel forms the call launched */
+#define GS_SORT_ROWS_R_STATUS 5    /* the device status: 0; bit 0: a row's counts did not add up or a position left its row (pass route); bits 8 .. : the segmented sort's status word (LDS route) */
+#define GS_SORT_ROWS_R_RANK 6      /* the handle's rank mode */
+#define GS_SORT_ROWS_R_PER_PART 7  /* as gs_sort_rows_plan */
+#define GS_SORT_ROWS_REPORT_WORDS 8
+#define GS_SORT_ROWS_F_CLEAR 1u
+#define GS_SORT_ROWS_F_OFFSETS 2u
+#define GS_SORT_ROWS_F_LDS 4u      /* the segmented sort's kernels for the row's length class */
+#define GS_SORT_ROWS_F_COUNT 8u
+#define GS_SORT_ROWS_F_SCAN 16u
+#define GS_SORT_ROWS_F_SCATTER 32u /* << (2 x v + rank mode), v = 0 keys only, 1 4-byte, 2 8-byte values: bits 5 .. 10 */
+#define GS_SORT_ROWS_F_ALL 0x7ffu
+/* value_bytes 0 (keys only), 4 or 8, as gs_onesweep_create.  Synchronous (allocates gs_sort_rows_temp_bytes of device memory). */
+gs_status gs_sort_rows_create(gs_sort_rows** out, uint32_t max_keys, gs_mode mode, uint32_t value_bytes);
+gs_status gs_sort_rows_destroy(gs_sort_rows* h);
+/* Host only.  With L = gs_segsort_max_lds_segment(mode, value_bytes), R = max_keys / (L + 1) (the most rows of a pass-route call) and
+ * U = R == 0 ? 0 : min(max(R, GS_SORT_ROWS_PCAP), max_keys / GS_SORT_ROWS_TILE + R) (the most rows x parts), each term rounded up to
+ * 256 bytes: a 256-byte control block + the segmented sort's (64 + max_keys / 33 + 1 words) + the offsets (max_keys + 1 words) + the
+ * table and the bases (U x 256 words each).  0 for an invalid size, mode or value width. */
+size_t gs_sort_rows_temp_bytes(uint32_t max_keys, gs_mode mode, uint32_t value_bytes);
+/* Host only: how a call is routed and cut — plan[GS_SORT_ROWS_P_*], GS_SORT_ROWS_PLAN_WORDS words.  Pass route: parts =
+ * max(1, min(tiles of a row / GS_SORT_ROWS_MIN_TILES, GS_SORT_ROWS_PCAP / rows)), evened out over whole tiles.  GS_ERR_ARG for a null plan, GS_ERR_MODE for an
+ * invalid mode or value width, GS_ERR_SIZE for rows == 0, row_len == 0 or rows * row_len > GS_MAX_KEYS. */
+gs_status gs_sort_rows_plan(uint32_t rows, uint32_t row_len, gs_mode mode, uint32_t value_bytes, uint32_t* plan);
+/* Result in d_keys; d_alt: scratch of rows * row_len keys (pass route; may be NULL on the LDS route). */
+gs_status gs_sort_rows_keys(gs_sort_rows* h, void* d_keys, void* d_alt, uint32_t rows, uint32_t row_len, gs_key_type key_type,
+                            gs_order order, void* stream);
+/* Result in d_keys / d_vals; d_alt_*: scratch of rows * row_len elements each (pass route; may be NULL on the LDS route). */
+gs_status gs_sort_rows_pairs(gs_sort_rows* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t rows,
+                             uint32_t row_len, gs_key_type key_type, gs_order order, void* stream);
+/* Synchronises `stream` and reads the device status, which every call resets: GS_OK, or GS_ERR_HIP if a row's counts did not add up
+ * (cannot happen; the scatter then writes nothing, and no store leaves its row either way). */
+gs_status gs_sort_rows_check(gs_sort_rows* h, void* stream);
+/* Synchronous diagnostics of the last call: report[GS_SORT_ROWS_R_*], words >= GS_SORT_ROWS_REPORT_WORDS. */
+gs_status gs_sort_rows_last(gs_sort_rows* h, uint32_t* report, uint32_t words, void* stream);
+/* The ranking inside a tile (the pass route's scatter and the LDS route's workgroup classes), as gs_sort16_set_rank_mode: 0 = 64-lane
+ * ballot multi-split, 1 = one returning LDS atomic per key; gs_sort_rows_create probes the device.  get: -1 for a null handle. */
+gs_status gs_sort_rows_set_rank_mode(gs_sort_rows* h, int mode);
+int gs_sort_rows_get_rank_mode(gs_sort_rows* h);
+
 #ifdef __cplusplus
 }
 #endif
