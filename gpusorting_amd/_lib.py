@@ -37,12 +37,17 @@ GS_SORT_ROWS_TILE, GS_SORT_ROWS_PCAP, GS_SORT_ROWS_MIN_TILES, GS_SORT_ROWS_PASSE
 (GS_SORT_ROWS_F_CLEAR, GS_SORT_ROWS_F_OFFSETS, GS_SORT_ROWS_F_LDS, GS_SORT_ROWS_F_COUNT, GS_SORT_ROWS_F_SCAN,
  GS_SORT_ROWS_F_SCATTER) = 1, 2, 4, 8, 16, 32
 GS_SORT_ROWS_F_ALL = 0x7FF
+# gs_sort_rows16_*: the plan and report words and the routes are gs_sort_rows_*'s; two passes, and its own kernel-form bits
+GS_SORT_ROWS16_PASSES = 2
+(GS_SORT_ROWS16_F_CLEAR, GS_SORT_ROWS16_F_LDS_WAVE, GS_SORT_ROWS16_F_LDS_TILE, GS_SORT_ROWS16_F_COUNT, GS_SORT_ROWS16_F_SCAN,
+ GS_SORT_ROWS16_F_SCATTER) = 1, 2, 4, 8, 16, 32
+GS_SORT_ROWS16_F_ALL = 0x1FFF
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
 GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
 (GS_KF_BIN, GS_KF_POS, GS_KF_PERSIST, GS_KF_SMALL, GS_KF_MID, GS_KF_SEG_WG, GS_KF_SEG_VB, GS_KF_TKR_TILE, GS_KF_TKR_VM, GS_KF_HIST,
  GS_KF_HY_HIST, GS_KF_HY_LOCAL, GS_KF_HY_LOCAL_PAIRS, GS_KF_COUNT) = range(14)
-# gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs and by gs_sort16_*
+# gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs, gs_sort16_* and gs_sort_rows16_*
 KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16 = 6, 7, 8, 9
 
 # every symbol include/gpusort.h declares: (name, restype, argtypes)
@@ -232,6 +237,17 @@ _PROTOS = [
     ("gs_sort_rows_last", _int, [_vp, _u32p, _u32, _vp]),
     ("gs_sort_rows_set_rank_mode", _int, [_vp, _int]),
     ("gs_sort_rows_get_rank_mode", _int, [_vp]),
+    ("gs_sort_rows16_create", _int, [C.POINTER(_vp), _u32, _int, _u32]),
+    ("gs_sort_rows16_destroy", _int, [_vp]),
+    ("gs_sort_rows16_temp_bytes", C.c_size_t, [_u32, _int, _u32]),
+    ("gs_sort_rows16_plan", _int, [_u32, _u32, _int, _u32, _u32p]),
+    ("gs_sort_rows16_keys", _int, [_vp, _vp, _vp, _u32, _u32, _int, _int, _vp]),
+    ("gs_sort_rows16_pairs", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _int, _vp]),
+    ("gs_sort_rows16_argsort", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _int, _vp]),
+    ("gs_sort_rows16_check", _int, [_vp, _vp]),
+    ("gs_sort_rows16_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_sort_rows16_set_rank_mode", _int, [_vp, _int]),
+    ("gs_sort_rows16_get_rank_mode", _int, [_vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

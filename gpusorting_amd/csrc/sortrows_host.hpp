@@ -122,7 +122,7 @@ gs_status sort_rows_run_passes(gs_sort_rows* h, const SortRowsLayout& l, uint32_
 
 gs_status sort_rows_impl(gs_sort_rows* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t rows, uint32_t row_len, gs_key_type kt,
                          gs_order order, hipStream_t s, bool pairs) {
-    if (!h || !d_keys || misaligned(d_keys) || !is_key32_type(kt) || !valid_order(order)) return GS_ERR_ARG;  // (64- and 16-bit key types: out of scope)
+    if (!h || !d_keys || misaligned(d_keys) || !is_key32_type(kt) || !valid_order(order)) return GS_ERR_ARG;  // (16-bit key types: gs_sort_rows16_*; 64-bit ones: out of scope)
     if (pairs != (h->mode == GS_MODE_PAIRS)) return GS_ERR_MODE;
     if (pairs && (!d_vals || misaligned(d_vals))) return GS_ERR_ARG;
     if (rows == 0 || row_len == 0 || (uint64_t)rows * row_len > h->max_keys) return GS_ERR_SIZE;

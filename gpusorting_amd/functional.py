@@ -6,6 +6,8 @@ handle cache, buffers).  The reference has no such layer; it is what a torch use
     sorted_keys, sorted_vals = gpusorting_amd.sort(keys, values, descending=True)
     gpusorting_amd.sort_(keys, values)                                       # in place
     sorted_rows = gpusorting_amd.sort(matrix)                                # 2-D: every row on its own, torch.sort(x, dim=-1) (RowSort)
+    sorted_rows = gpusorting_amd.sort_rows(half_matrix, descending=True)     # 2-D, 16- and 32-bit keys (RowSort16 / RowSort)
+    positions = gpusorting_amd.argsort_rows(half_matrix)                     # int32 positions within the row
 
 Semantics are the library's: stable LSD radix sort; descending = exact reverse of the stable ascending result;
 float keys ordered by the order-preserving bit flip (-0 < +0, NaNs by bit pattern); values bit-copied.
@@ -17,6 +19,7 @@ import torch
 from . import _lib
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
 from .rowsort import RowSort, sort_rows_reference  # noqa: F401
+from .rowsort16 import RowSort16, sort_rows16_reference  # noqa: F401
 from .sort16 import Sort16, sort16_reference  # noqa: F401
 from .topk import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, TopK, rows_max_k, topk_reference, topk_rows_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
@@ -69,6 +72,19 @@ def _row_sorter(device: torch.device, n: int, key_type: int, order: int, value_b
     return s
 
 
+def _row_sorter16(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> RowSort16:
+    """The same cache rule for the row-wise sort of 16-bit keys: one ``RowSort16`` handle per (device, stream, type, order, value width)."""
+    key = ("rows16", device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+    s = _cache.get(key)
+    if s is None or s.max_keys < n:
+        if s is not None:
+            s.close()
+        cap = 1 << max(int(n - 1).bit_length(), 16)
+        s = RowSort16(min(cap, (1 << 30) - 1), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes, device=device.index)
+        _cache[key] = s
+    return s
+
+
 def _values_width(keys: torch.Tensor, values: torch.Tensor | None) -> int:
     if values is None:
         return 0
@@ -104,7 +120,8 @@ def _sort_rows_(keys: torch.Tensor, values: torch.Tensor | None, descending: boo
     if not keys.is_contiguous() or keys.device.type != "cuda":
         raise ValueError("keys must be a contiguous 2-D device tensor")
     if keys.dtype not in _KEY_TYPE:
-        raise RowKeyTypeError(f"unsupported key dtype {keys.dtype} for a 2-D tensor: rows are sorted on 32-bit keys only (int32, uint32, float32)")
+        raise RowKeyTypeError(f"unsupported key dtype {keys.dtype} for a 2-D tensor: rows are sorted on 32-bit keys only (int32, uint32, float32); "
+                              "sort_rows / argsort_rows take 16-bit keys")
     kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
     vb = _values_width(keys, values)
     if keys.numel() == 0:
@@ -172,6 +189,53 @@ def argsort(keys: torch.Tensor, descending: bool = False, unsigned: bool = False
     idx = torch.arange(keys.numel(), dtype=torch.int32, device=keys.device)
     k = keys.clone()
     sort_(k, idx, descending, unsigned)
+    return idx
+
+
+# ---- row-wise sort of 16- and 32-bit keys -----------------------------------------------------------------------------------
+def _require_rows(keys: torch.Tensor) -> None:
+    if keys.dim() != 2 or not keys.is_contiguous() or keys.device.type != "cuda":
+        raise ValueError("keys must be a contiguous 2-D device tensor")
+    if keys.dtype not in _KEY16_TYPE and keys.dtype not in _KEY_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: rows are sorted on 16-bit keys (float16, bfloat16, int16, uint16) and "
+                        "32-bit keys (int32, uint32, float32)")
+
+
+def sort_rows_(keys: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False, unsigned: bool = False) -> None:
+    """Sort every row of the contiguous 2-D device tensor ``keys`` along its last dimension (and carry ``values``, same shape, 4 or 8
+    bytes wide) in place on the current stream.  16-bit keys (float16, bfloat16, int16, uint16) are sorted at their own width
+    (``RowSort16``), 32-bit keys go to ``RowSort``.  ``unsigned=True`` treats int16 storage as uint16 keys and int32 storage as uint32."""
+    _require_rows(keys)
+    if keys.dtype in _KEY_TYPE:
+        return _sort_rows_(keys, values, descending, unsigned)
+    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    vb = _values_width(keys, values)
+    if keys.numel() == 0:
+        return
+    with torch.cuda.device(keys.device):
+        _row_sorter16(keys.device, keys.numel(), kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb).sort(keys, values)
+
+
+def sort_rows(keys: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False, unsigned: bool = False):
+    """Out-of-place ``sort_rows_``: returns ``sorted_keys`` or ``(sorted_keys, sorted_values)``; the inputs are not written."""
+    k = keys.clone()
+    v = None if values is None else values.clone()
+    sort_rows_(k, v, descending, unsigned)
+    return k if v is None else (k, v)
+
+
+def argsort_rows(keys: torch.Tensor, descending: bool = False, unsigned: bool = False) -> torch.Tensor:
+    """The stable permutation that sorts every row of ``keys``: int32 positions within the row, ``[rows, row_len]``.  For 16-bit keys the
+    kernels make the positions themselves; 32-bit keys forward to ``argsort``.  ``keys`` is not written."""
+    _require_rows(keys)
+    if keys.dtype in _KEY_TYPE:
+        return argsort(keys, descending, unsigned)
+    idx = torch.empty(keys.shape, dtype=torch.int32, device=keys.device)
+    if keys.numel() == 0:
+        return idx
+    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    with torch.cuda.device(keys.device):
+        _row_sorter16(keys.device, keys.numel(), kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, 4).argsort(keys.clone(), idx)
     return idx
 
 

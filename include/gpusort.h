@@ -811,6 +811,72 @@ gs_status gs_sort_rows_last(gs_sort_rows* h, uint32_t* report, uint32_t words, v
 gs_status gs_sort_rows_set_rank_mode(gs_sort_rows* h, int mode);
 int gs_sort_rows_get_rank_mode(gs_sort_rows* h);
 
+/* ---- row-wise sort on 16-bit keys: every row of a contiguous [rows, row_len] matrix of GS_KEY_UINT16 / INT16 / FLOAT16 / BFLOAT16 ----
+ * No counterpart in the reference project.  Row r is the 2-byte elements [r * row_len, (r + 1) * row_len) of the array; after the call
+ * every row holds exactly what gs_sort16_sort_pairs / gs_sort16_argsort leaves for that slice alone, bit for bit, with positions
+ * relative to the row: stable by the sortable 16 bits, descending = the exact reverse of the row's stable ascending result, floats by
+ * the order-preserving bit flip (-0 < +0, NaNs by bit pattern), every key bit pattern preserved, values bit-copied.  Strided rows are
+ * not taken.  The 32-bit key types stay with gs_sort_rows_* (which keeps answering GS_ERR_ARG for the 16-bit ones).
+ *
+ * Routes (the words of gs_sort_rows_plan and gs_sort_rows_last, GS_SORT_ROWS_P_* / _R_* / _ROUTE_*, are reused):
+ *   GS_SORT_ROWS_ROUTE_LDS     row_len <= gs_segsort_max_lds_segment(mode, value_bytes) (positions count as 4-byte values): ONE launch
+ *                              behind the clear, the 2-byte LDS sorts of the row-wise top-k with k = row_len, in place: one wave per row
+ *                              up to 256 elements, one workgroup per row above.  d_alt* are not touched and may be NULL.
+ *   GS_SORT_ROWS_ROUTE_PASSES  longer rows: GS_SORT_ROWS16_PASSES stable 8-bit LSD passes over all rows at once, the low byte from the
+ *                              caller's buffers into d_alt*, the high byte back, each a count, a scan and a scatter launch behind one
+ *                              clear: 7 launches whatever `rows` is.  Rows are cut into parts of whole tiles exactly as gs_sort_rows_plan
+ *                              cuts them (GS_SORT_ROWS_TILE, _PCAP, _MIN_TILES).  No kernel waits on another workgroup.  d_alt* are
+ *                              required: rows * row_len elements of scratch each.
+ *
+ * rows >= 1, row_len >= 1, rows * row_len <= max_keys <= GS_MAX_KEYS; only the base pointers need 16-byte alignment (row r starts
+ * wherever r * row_len * 2 bytes falls); nothing at or behind element rows * row_len of any buffer is written, at 2-byte granularity
+ * for the keys.
+ * GS_ERR_ARG: null handle (before anything else is looked at), null or misaligned d_keys, a key type outside 6 .. 9 (the 32- and the
+ * 64-bit ones), a bad order; then GS_ERR_MODE: keys call on a pairs handle or the reverse, gs_sort_rows16_argsort on anything but a
+ * handle with 4-byte values (and every call on a build flavour without these kernels: the tuning and fault-injection libraries); then
+ * GS_ERR_ARG for a null or misaligned d_vals / d_pos; then GS_ERR_SIZE: rows == 0, row_len == 0 or rows * row_len > max_keys; then, on
+ * the pass route, GS_ERR_ARG for a null or misaligned d_alt* and for any two of the call's buffers overlapping.  A refused call writes
+ * nothing.
+ * Asynchronous on `stream`, every launch enqueued up front, the host is never waited on: a call can be captured into a graph on one
+ * linear stream, and every node of a captured call is a kernel launch.  One in-flight call per handle. */
+typedef struct gs_sort_rows16 gs_sort_rows16;
+#define GS_SORT_ROWS16_PASSES 2u
+/* gs_sort_rows16_last: report[GS_SORT_ROWS_R_FORMS], the kernel forms the call launched */
+#define GS_SORT_ROWS16_F_CLEAR 1u
+#define GS_SORT_ROWS16_F_LDS_WAVE 2u  /* tkr16_wave_kernel: rows of up to 256 elements */
+#define GS_SORT_ROWS16_F_LDS_TILE 4u  /* tkr16_tile_kernel of the row length's class */
+#define GS_SORT_ROWS16_F_COUNT 8u
+#define GS_SORT_ROWS16_F_SCAN 16u
+#define GS_SORT_ROWS16_F_SCATTER 32u  /* << (2 x v + rank mode), v = 0 keys only, 1 positions made in registers (argsort, first pass), 2 4-byte, 3 8-byte values: bits 5 .. 12 */
+#define GS_SORT_ROWS16_F_ALL 0x1fffu
+/* value_bytes 0 (keys only), 4 or 8, as gs_onesweep_create.  Synchronous (allocates gs_sort_rows16_temp_bytes of device memory). */
+gs_status gs_sort_rows16_create(gs_sort_rows16** out, uint32_t max_keys, gs_mode mode, uint32_t value_bytes);
+gs_status gs_sort_rows16_destroy(gs_sort_rows16* h);
+/* Host only.  With U as in gs_sort_rows_temp_bytes (the most rows x parts of a pass-route call): a 256-byte control block + the table
+ * and the bases (U x 256 words each, rounded up to 256 bytes).  0 for an invalid size, mode or value width. */
+size_t gs_sort_rows16_temp_bytes(uint32_t max_keys, gs_mode mode, uint32_t value_bytes);
+/* Host only: plan[GS_SORT_ROWS_P_*], GS_SORT_ROWS_PLAN_WORDS words, as gs_sort_rows_plan — the same route border and the same cut — with
+ * plan[GS_SORT_ROWS_P_PASSES] = GS_SORT_ROWS16_PASSES on the pass route.  Same errors. */
+gs_status gs_sort_rows16_plan(uint32_t rows, uint32_t row_len, gs_mode mode, uint32_t value_bytes, uint32_t* plan);
+/* Result in d_keys; d_alt: scratch of rows * row_len keys (pass route; may be NULL on the LDS route). */
+gs_status gs_sort_rows16_keys(gs_sort_rows16* h, void* d_keys, void* d_alt, uint32_t rows, uint32_t row_len, gs_key_type key_type,
+                              gs_order order, void* stream);
+/* Result in d_keys / d_vals; d_alt_*: scratch of rows * row_len elements each (pass route; may be NULL on the LDS route). */
+gs_status gs_sort_rows16_pairs(gs_sort_rows16* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t rows,
+                               uint32_t row_len, gs_key_type key_type, gs_order order, void* stream);
+/* Handle with 4-byte values: d_pos is OUTPUT only (the uint32 positions within the row of the sorted order) and never read on entry:
+ * the kernels make the positions in registers. */
+gs_status gs_sort_rows16_argsort(gs_sort_rows16* h, void* d_keys, void* d_pos, void* d_alt_keys, void* d_alt_pos, uint32_t rows,
+                                 uint32_t row_len, gs_key_type key_type, gs_order order, void* stream);
+/* Synchronises `stream` and reads the device status, which every call resets: GS_OK, or GS_ERR_HIP if a row's counts did not add up
+ * (cannot happen; the scatter then writes nothing, and no store leaves its row either way). */
+gs_status gs_sort_rows16_check(gs_sort_rows16* h, void* stream);
+/* Synchronous diagnostics of the last call: report[GS_SORT_ROWS_R_*], words >= GS_SORT_ROWS_REPORT_WORDS; the forms are GS_SORT_ROWS16_F_*. */
+gs_status gs_sort_rows16_last(gs_sort_rows16* h, uint32_t* report, uint32_t words, void* stream);
+/* The ranking inside a tile (the pass route's scatter and the LDS route's workgroup kernel), as gs_sort_rows_set_rank_mode. */
+gs_status gs_sort_rows16_set_rank_mode(gs_sort_rows16* h, int mode);
+int gs_sort_rows16_get_rank_mode(gs_sort_rows16* h);
+
 #ifdef __cplusplus
 }
 #endif
