@@ -6,12 +6,13 @@ Only the hot path of b0nes164/GPUSorting named by BASELINE.json is here:
   onesweep   host-side mirror of the reference interface (ctypes over the C-ABI)
   sharded    one-process-per-GPU MSD split + RCCL all-to-all-v + local OneSweep
   segsort    segmented sort (CSR offsets) over gs_segsort_*, and its numpy reference
+  segsort16  segmented sort of 16-bit keys at their own width over gs_segsort16_*, and its numpy reference
   rowsort    row-wise sort of a [rows, row_len] matrix of 32-bit keys over gs_sort_rows_*, and its numpy reference
   rowsort16  row-wise sort of a [rows, row_len] matrix of 16-bit keys at their own width over gs_sort_rows16_*, and its numpy reference
   sort16     sort of 16-bit keys (float16, bfloat16, int16, uint16) at their own width over gs_sort16_*, and its numpy reference
   topk       top-k selection (the head of the sort without the sort) over gs_topk_*, and its numpy reference
   functional sort / sort_ / argsort / sort_rows / argsort_rows / segmented_sort / topk on torch tensors (plumbing over OneSweep / RowSort /
-             RowSort16 / SegmentedSort / TopK)
+             RowSort16 / SegmentedSort / SegmentedSort16 / TopK)
 """
 from .onesweep import (  # noqa: F401
     ENTROPY_PRESET_1, ENTROPY_PRESET_2, ENTROPY_PRESET_3, ENTROPY_PRESET_4, ENTROPY_PRESET_5,
@@ -23,5 +24,6 @@ from .functional import argsort, argsort_rows, segmented_argsort, segmented_sort
 from .rowsort import RowSort, sort_rows_plan, sort_rows_reference  # noqa: F401
 from .rowsort16 import SORT_ROWS16_FORMS, RowSort16, sort_rows16_plan, sort_rows16_reference  # noqa: F401
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
+from .segsort16 import SEGSORT16_FORMS, SegmentedSort16, segmented_sort16_reference, segsort16_units  # noqa: F401
 from .sort16 import Sort16, sort16_plan, sort16_reference  # noqa: F401
 from .topk import TopK, topk_reference, topk_rows_reference  # noqa: F401

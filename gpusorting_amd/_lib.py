@@ -42,12 +42,29 @@ GS_SORT_ROWS16_PASSES = 2
 (GS_SORT_ROWS16_F_CLEAR, GS_SORT_ROWS16_F_LDS_WAVE, GS_SORT_ROWS16_F_LDS_TILE, GS_SORT_ROWS16_F_COUNT, GS_SORT_ROWS16_F_SCAN,
  GS_SORT_ROWS16_F_SCATTER) = 1, 2, 4, 8, 16, 32
 GS_SORT_ROWS16_F_ALL = 0x1FFF
+# gs_segsort16_*: two passes over parts of GS_SEGSORT16_PART elements, the report words and the kernel-form bits
+GS_SEGSORT16_PASSES = 2
+GS_SEGSORT16_PART = 8 * GS_SORT_ROWS_TILE
+(GS_SEGSORT16_R_UNITS, GS_SEGSORT16_R_FORMS, GS_SEGSORT16_R_WG_FORMS, GS_SEGSORT16_R_STATUS, GS_SEGSORT16_R_RANK, GS_SEGSORT16_R_LONG,
+ GS_SEGSORT16_R_UNIT_CAP, GS_SEGSORT16_R_N) = range(8)
+GS_SEGSORT16_REPORT_WORDS = 8
+(GS_SEGSORT16_F_CLASSIFY, GS_SEGSORT16_F_FILL, GS_SEGSORT16_F_PACKED, GS_SEGSORT16_F_WAVE, GS_SEGSORT16_F_UNITS, GS_SEGSORT16_F_COUNT,
+ GS_SEGSORT16_F_SCAN, GS_SEGSORT16_F_SCATTER) = 1, 2, 4, 64, 1024, 2048, 4096, 8192
+GS_SEGSORT16_F_ALL = 0x1FFFFF
+GS_SEGSORT16_WG_ALL = 0xFFFFFFFF
+
+
+def GS_SEGSORT16_WG_FORM(cls: int, v: int, rank: int) -> int:
+    """The bit of a workgroup-class kernel in report[GS_SEGSORT16_R_WG_FORMS] (the macro of include/gpusort.h)."""
+    return 1 << (16 * rank + (4 * (cls - 3) + v if cls <= 5 else 12 + v if cls == 6 else 15))
+
+
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
 GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
 (GS_KF_BIN, GS_KF_POS, GS_KF_PERSIST, GS_KF_SMALL, GS_KF_MID, GS_KF_SEG_WG, GS_KF_SEG_VB, GS_KF_TKR_TILE, GS_KF_TKR_VM, GS_KF_HIST,
  GS_KF_HY_HIST, GS_KF_HY_LOCAL, GS_KF_HY_LOCAL_PAIRS, GS_KF_COUNT) = range(14)
-# gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs, gs_sort16_* and gs_sort_rows16_*
+# gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs, gs_sort16_*, gs_sort_rows16_* and gs_segsort16_*
 KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16 = 6, 7, 8, 9
 
 # every symbol include/gpusort.h declares: (name, restype, argtypes)
@@ -248,6 +265,18 @@ _PROTOS = [
     ("gs_sort_rows16_last", _int, [_vp, _u32p, _u32, _vp]),
     ("gs_sort_rows16_set_rank_mode", _int, [_vp, _int]),
     ("gs_sort_rows16_get_rank_mode", _int, [_vp]),
+    ("gs_segsort16_create", _int, [C.POINTER(_vp), _u32, _u32, _int, _u32]),
+    ("gs_segsort16_destroy", _int, [_vp]),
+    ("gs_segsort16_units", _u32, [_u32, _u32, _int, _u32]),
+    ("gs_segsort16_temp_bytes", C.c_size_t, [_u32, _u32, _int, _u32]),
+    ("gs_segsort16_sort_keys", _int, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _int, _int, _vp]),
+    ("gs_segsort16_sort_pairs", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _int, _int, _vp]),
+    ("gs_segsort16_argsort", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _int, _int, _vp]),
+    ("gs_segsort16_check", _int, [_vp, _vp]),
+    ("gs_segsort16_last_classes", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_segsort16_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_segsort16_set_rank_mode", _int, [_vp, _int]),
+    ("gs_segsort16_get_rank_mode", _int, [_vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

@@ -22,6 +22,7 @@
 #include "sort16_kernels.hpp"
 #include "sortrows_kernels.hpp"
 #include "sortrows16_kernels.hpp"
+#include "segsort16_kernels.hpp"
 
 // One translation unit; one host file per concern, in this order (each may use what stands above it):
 #include "host_common.hpp"      // GS_HIP, argument predicates, div_up, cu_count, DeviceScratch
@@ -32,4 +33,5 @@
 #include "sort16_host.hpp"      // gs_sort16: the sort of 16-bit keys
 #include "sortrows_host.hpp"    // gs_sort_rows: every row of a matrix sorted in one call
 #include "sortrows16_host.hpp"  // gs_sort_rows16: the same on 16-bit keys
+#include "segsort16_host.hpp"   // gs_segsort16: the segmented sort on 16-bit keys
 #include "gpusort_mgpu.hpp"     // gs_mgpu, gs_onesweep_sort_sharded

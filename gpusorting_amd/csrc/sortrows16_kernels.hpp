@@ -49,11 +49,11 @@ __device__ __forceinline__ uint4 sr16_load8(const uint16_t* q, uint32_t i, uint3
     return uint4{e[0], e[1], e[2], e[3]};
 }
 
-// table[row][part][d] = keys of the part whose byte at `shift` of the sortable bits is d.  Workgroup = row * parts + part.  The part
-// is the index range [lo, hi) of the 16-byte aligned pointer q (lo <= 7: the peel; the base pointer is 16-byte aligned, so q never
-// lies in front of it).
-__global__ __launch_bounds__(SR_THREADS) void sr16_count_kernel(const uint16_t* __restrict__ keys, uint32_t row_len, uint32_t parts, uint32_t per_part,
-                                                                uint32_t kt, uint32_t shift, uint32_t* __restrict__ table) {
+// The count of one part, shared with the segmented sort's long route (seg16_count_kernel, segsort16_kernels.hpp): out[d] = keys among
+// the `len` elements at p whose byte at `shift` of the sortable bits is d.  The part is the index range [lo, hi) of the 16-byte aligned
+// pointer q (lo <= 7: the peel; the base pointer is 16-byte aligned, so q never lies in front of it).  Every thread of the workgroup
+// calls it (its barriers are the workgroup's); the LDS is its own.
+__device__ __forceinline__ void sr16_count_body(const uint16_t* __restrict__ p, uint32_t len, uint32_t kt, uint32_t shift, uint32_t* __restrict__ out) {
     constexpr uint32_t W = SR_THREADS / 64;
     __shared__ __attribute__((aligned(16))) uint32_t s_h[W * RADIX];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -61,11 +61,7 @@ __global__ __launch_bounds__(SR_THREADS) void sr16_count_kernel(const uint16_t* 
     static_assert(W * RADIX == 4u * SR_THREADS, "one 16-byte store per thread clears the counters");
     __syncthreads();
     uint32_t* mine = s_h + wave * RADIX;
-    const uint32_t row = blockIdx.x / parts, part = blockIdx.x - row * parts;
-    const uint32_t plo = part * per_part;
-    const uint32_t len = plo < row_len ? (row_len - plo < per_part ? row_len - plo : per_part) : 0u;
     if (len != 0u) {  // (uniform)
-        const uint16_t* p = keys + (size_t)row * row_len + plo;
         const uint32_t lo = (uint32_t)((reinterpret_cast<uintptr_t>(p) >> 1) & 7u), hi = lo + len;
         const uint16_t* q = p - lo;
         for (uint32_t c = 0; c < hi; c += SR_TILE) {
@@ -96,8 +92,17 @@ __global__ __launch_bounds__(SR_THREADS) void sr16_count_kernel(const uint16_t* 
         uint32_t sum = 0;
 #pragma unroll
         for (uint32_t w = 0; w < W; ++w) sum += s_h[w * RADIX + tid];
-        table[(size_t)blockIdx.x * RADIX + tid] = sum;
+        out[tid] = sum;
     }
+}
+
+// table[row][part][d] = keys of the part whose byte at `shift` of the sortable bits is d.  Workgroup = row * parts + part.
+__global__ __launch_bounds__(SR_THREADS) void sr16_count_kernel(const uint16_t* __restrict__ keys, uint32_t row_len, uint32_t parts, uint32_t per_part,
+                                                                uint32_t kt, uint32_t shift, uint32_t* __restrict__ table) {
+    const uint32_t row = blockIdx.x / parts, part = blockIdx.x - row * parts;
+    const uint32_t plo = part * per_part;
+    const uint32_t len = plo < row_len ? (row_len - plo < per_part ? row_len - plo : per_part) : 0u;
+    sr16_count_body(keys + (size_t)row * row_len + plo, len, kt, shift, table + (size_t)blockIdx.x * RADIX);
 }
 
 // One workgroup per (row, part), its tiles in order: sr_scatter_kernel on 2-byte keys.  VM: 0 keys only, 1 = the value is the element's
@@ -106,10 +111,16 @@ __global__ __launch_bounds__(SR_THREADS) void sr16_count_kernel(const uint16_t* 
 // wave (element wave * 512 + i * 64 + lane: rounds and lanes in element order, so ranks are stable), the wave counters are turned into
 // tile positions, keys (at their own width) and values are staged in digit order and written out run by run; the running base of a
 // digit moves on by the tile's count.  reverse != 0 (descending, last pass): position p goes to row_len - 1 - p.
+//
+// sr16_scatter_body: the scatter of one part [lo, hi) of a row of row_len elements, shared with the segmented sort's long route (seg16_scatter_kernel,
+// segsort16_kernels.hpp).  rkin / rvin / rkout / rvout: the row's first element in each buffer; bases: the part's 256 bases (positions
+// relative to the row); pos_base: what the VM 1 form adds to the position within the row; status: the word a broken count sets — a
+// call that finds it set writes nothing.  Every thread of the workgroup calls it; the LDS is its own.
 template <int VM, int RANK>
-__global__ __launch_bounds__(SR_THREADS) void sr16_scatter_kernel(const uint16_t* __restrict__ kin, const void* __restrict__ vin_, uint16_t* __restrict__ kout,
-                                                                  void* __restrict__ vout_, uint32_t row_len, uint32_t parts, uint32_t per_part, uint32_t kt,
-                                                                  uint32_t shift, uint32_t reverse, const uint32_t* __restrict__ bases, uint32_t* __restrict__ ctl) {
+__device__ __forceinline__ void sr16_scatter_body(const uint16_t* __restrict__ rkin, const typename S16Val<VM>::type* __restrict__ rvin,
+                                                  uint16_t* __restrict__ rkout, typename S16Val<VM>::type* __restrict__ rvout, uint32_t row_len,
+                                                  uint32_t lo, uint32_t hi, uint32_t pos_base, uint32_t kt, uint32_t shift, uint32_t reverse,
+                                                  const uint32_t* __restrict__ bases, uint32_t* __restrict__ status) {
     using V = typename S16Val<VM>::type;
     constexpr uint32_t THREADS = SR_THREADS, KPT = SR_KPT, WAVES = THREADS / 64, TILE = SR_TILE;
     static_assert(WAVES * RADIX == 4u * THREADS, "one 16-byte store per thread clears the wave counters");
@@ -118,18 +129,10 @@ __global__ __launch_bounds__(SR_THREADS) void sr16_scatter_kernel(const uint16_t
     __shared__ V s_val[VM != 0 ? TILE : 1];
     __shared__ uint32_t s_base[RADIX], s_gofs[RADIX], s_wtot[RADIX / 64], s_stop;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t row = blockIdx.x / parts, part = blockIdx.x - row * parts;
-    const size_t row_at = (size_t)row * row_len;
-    const uint16_t* rkin = kin + row_at;
-    uint16_t* rkout = kout + row_at;
-    const V* rvin = static_cast<const V*>(vin_) + ((VM == 4 || VM == 8) ? row_at : 0);
-    V* rvout = static_cast<V*>(vout_) + (VM != 0 ? row_at : 0);
-    const uint32_t lo = part * per_part;
-    if (tid == 0) s_stop = ctl[SRC_STATUS];
+    if (tid == 0) s_stop = *status;
     __syncthreads();
-    if (s_stop != 0u || lo >= row_len) return;  // (uniform; a count that did not add up was reported by the scan: nothing is written)
-    const uint32_t hi = row_len - lo < per_part ? row_len : lo + per_part;
-    if (tid < RADIX) s_base[tid] = bases[(size_t)blockIdx.x * RADIX + tid];  // (read and written by thread `tid` only)
+    if (s_stop != 0u || lo >= hi) return;  // (uniform; a count that did not add up was reported by the scan: nothing is written)
+    if (tid < RADIX) s_base[tid] = bases[tid];  // (read and written by thread `tid` only)
     uint32_t* whist = s_whist + wave * RADIX;
     const uint32_t my_base = wave * (64u * KPT) + lane;
     for (uint32_t t0 = lo; t0 < hi; t0 += TILE) {
@@ -141,7 +144,7 @@ __global__ __launch_bounds__(SR_THREADS) void sr16_scatter_kernel(const uint16_t
         for (uint32_t i = 0; i < KPT; ++i) {
             const uint32_t idx = my_base + i * 64u, ci = idx < m ? idx : m - 1u;
             key[i] = rkin[t0 + ci];
-            if constexpr (VM == 1) val[i] = t0 + ci;  // the position within the row
+            if constexpr (VM == 1) val[i] = pos_base + t0 + ci;  // the position within the row (+ the row's place in the array)
             else if constexpr (VM != 0) val[i] = rvin[t0 + ci];
         }
 #pragma unroll
@@ -209,7 +212,7 @@ __global__ __launch_bounds__(SR_THREADS) void sr16_scatter_kernel(const uint16_t
                     s_key[lpos] = (uint16_t)key[i];
                     if constexpr (VM != 0) s_val[lpos] = val[i];
                 } else {
-                    atomicOr(&ctl[SRC_STATUS], SR_ST_INTERNAL);
+                    atomicOr(status, SR_ST_INTERNAL);
                 }
             }
         }
@@ -225,12 +228,27 @@ __global__ __launch_bounds__(SR_THREADS) void sr16_scatter_kernel(const uint16_t
                     rkout[o] = (uint16_t)k;
                     if constexpr (VM != 0) rvout[o] = s_val[j];
                 } else {
-                    atomicOr(&ctl[SRC_STATUS], SR_ST_INTERNAL);
+                    atomicOr(status, SR_ST_INTERNAL);
                 }
             }
         }
         // the next tile's first barrier stands between these reads and the next writes of s_gofs and the staging
     }
+}
+
+
+template <int VM, int RANK>
+__global__ __launch_bounds__(SR_THREADS) void sr16_scatter_kernel(const uint16_t* __restrict__ kin, const void* __restrict__ vin_, uint16_t* __restrict__ kout,
+                                                                  void* __restrict__ vout_, uint32_t row_len, uint32_t parts, uint32_t per_part, uint32_t kt,
+                                                                  uint32_t shift, uint32_t reverse, const uint32_t* __restrict__ bases, uint32_t* __restrict__ ctl) {
+    using V = typename S16Val<VM>::type;
+    const uint32_t row = blockIdx.x / parts, part = blockIdx.x - row * parts;
+    const size_t row_at = (size_t)row * row_len;
+    const uint32_t lo = part * per_part;
+    const uint32_t hi = lo < row_len ? (row_len - lo < per_part ? row_len : lo + per_part) : lo;
+    sr16_scatter_body<VM, RANK>(kin + row_at, static_cast<const V*>(vin_) + ((VM == 4 || VM == 8) ? row_at : 0), kout + row_at,
+                                static_cast<V*>(vout_) + (VM != 0 ? row_at : 0), row_len, lo, hi, 0u, kt, shift, reverse,
+                                bases + (size_t)blockIdx.x * RADIX, ctl + SRC_STATUS);
 }
 
 #endif  // GS_SORT_ROWS_BUILT

@@ -83,15 +83,14 @@ __global__ __launch_bounds__(SR_THREADS) void sr_count_kernel(const uint32_t* __
     }
 }
 
-// One workgroup per row, thread = digit: bases[row][part][d] = keys of the row with a digit below d + keys of digit d in the parts in
-// front; the row's total must be row_len.
-__global__ __launch_bounds__(RADIX) void sr_scan_kernel(const uint32_t* __restrict__ table, uint32_t* __restrict__ bases, uint32_t parts, uint32_t row_len,
-                                                        uint32_t* __restrict__ ctl) {
+// Thread = digit, over the `parts` tables at t: b[part][d] = keys of the row with a digit below d + keys of digit d in the parts in
+// front; the row's total must be row_len, or `status` gets SR_ST_INTERNAL.  Shared with the segmented sort of 16-bit keys
+// (seg16_scan_kernel, segsort16_kernels.hpp).
+__device__ __forceinline__ void sr_scan_body(const uint32_t* __restrict__ t, uint32_t* __restrict__ b, uint32_t parts, uint32_t row_len,
+                                             uint32_t* __restrict__ status) {
     constexpr uint32_t W = RADIX / 64;
     __shared__ uint32_t s_w[W];
     const uint32_t d = threadIdx.x, lane = d & 63u, wave = d >> 6;
-    const uint32_t* t = table + (size_t)blockIdx.x * parts * RADIX;
-    uint32_t* b = bases + (size_t)blockIdx.x * parts * RADIX;
     uint32_t total = 0;
 #pragma unroll 8
     for (uint32_t p = 0; p < parts; ++p) total += t[p * RADIX + d];
@@ -103,13 +102,20 @@ __global__ __launch_bounds__(RADIX) void sr_scan_kernel(const uint32_t* __restri
         if (x < wave) run += s_w[x];
         all += s_w[x];
     }
-    if (d == 0 && all != row_len) atomicOr(&ctl[SRC_STATUS], SR_ST_INTERNAL);
+    if (d == 0 && all != row_len) atomicOr(status, SR_ST_INTERNAL);
 #pragma unroll 8
     for (uint32_t p = 0; p < parts; ++p) {
         const uint32_t c = t[p * RADIX + d];
         b[p * RADIX + d] = run;
         run += c;
     }
+}
+
+// One workgroup per row, thread = digit: bases[row][part][d] = keys of the row with a digit below d + keys of digit d in the parts in
+// front; the row's total must be row_len.
+__global__ __launch_bounds__(RADIX) void sr_scan_kernel(const uint32_t* __restrict__ table, uint32_t* __restrict__ bases, uint32_t parts, uint32_t row_len,
+                                                        uint32_t* __restrict__ ctl) {
+    sr_scan_body(table + (size_t)blockIdx.x * parts * RADIX, bases + (size_t)blockIdx.x * parts * RADIX, parts, row_len, ctl + SRC_STATUS);
 }
 
 // One workgroup per (row, part), its tiles in order: s16_scatter_kernel on 4-byte keys and positions relative to the row.  VB: 0 keys

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
+from .segsort16 import SegmentedSort16, segmented_sort16_reference  # noqa: F401
 from .rowsort import RowSort, sort_rows_reference  # noqa: F401
 from .rowsort16 import RowSort16, sort_rows16_reference  # noqa: F401
 from .sort16 import Sort16, sort16_reference  # noqa: F401
@@ -257,18 +258,59 @@ def _seg_sorter(device: torch.device, n: int, num_segments: int, key_type: int, 
     return s
 
 
+def _seg_sorter16(device: torch.device, n: int, num_segments: int, key_type: int, order: int, value_bytes: int) -> SegmentedSort16:
+    """The same cache rule for 16-bit keys: one ``SegmentedSort16`` handle per (device, stream, type, order, value width)."""
+    key = (16, device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+    s = _seg_cache.get(key)
+    if s is None or s.max_keys < n or s.max_segments < num_segments:
+        if s is not None:
+            s.close()
+        cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
+        s = SegmentedSort16(cap(n), cap(num_segments), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes,
+                            device=device.index)
+        _seg_cache[key] = s
+    return s
+
+
+def _require_offsets(keys: torch.Tensor, offsets: torch.Tensor) -> None:
+    if offsets.dim() != 1 or offsets.numel() < 2 or offsets.dtype not in (torch.int32, torch.uint32) or offsets.device != keys.device \
+            or not offsets.is_contiguous():
+        raise ValueError("offsets must be a contiguous 1-D int32 tensor of num_segments + 1 on the keys' device")
+
+
+def _segmented_sort16_(keys: torch.Tensor, offsets: torch.Tensor, values: torch.Tensor | None, descending: bool, unsigned: bool,
+                       max_segment_len: int, positions: torch.Tensor | None = None) -> None:
+    """``segmented_sort_`` / ``segmented_argsort`` on 2-byte keys: one ``gs_segsort16_*`` call (``positions``: the argsort's output, made
+    by the kernels inside the segments)."""
+    _require_offsets(keys, offsets)
+    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    vb = 4 if positions is not None else _values_width(keys, values)
+    n = keys.numel()
+    if n == 0:
+        return
+    with torch.cuda.device(keys.device):
+        s = _seg_sorter16(keys.device, n, offsets.numel() - 1, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb)
+        if positions is not None:
+            s.argsort(keys, offsets, positions, n=n, max_segment_len=max_segment_len)
+        else:
+            s.sort(keys, offsets, values, n=n, max_segment_len=max_segment_len)
+
+
 def segmented_sort_(keys: torch.Tensor, offsets: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False,
                     unsigned: bool = False, max_segment_len: int = 0) -> None:
     """Sort every segment ``keys[offsets[s]:offsets[s + 1]]`` (and carry ``values``) in place on the current stream.  ``offsets``:
     int32 tensor of ``num_segments + 1`` on the device (CSR).  ``max_segment_len``: upper bound on the segment length if the caller
-    knows one (a bound that fits the LDS classes keeps the call free of host waits); 0 = unknown."""
+    knows one (a bound that fits the LDS classes keeps the call free of host waits); 0 = unknown.  16-bit keys (float16, bfloat16,
+    int16, uint16; ``unsigned=True`` on int16 storage selects uint16 keys) are sorted at their own width (``SegmentedSort16``), and
+    that call never waits on the host."""
     if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
         raise ValueError("keys must be a contiguous 1-D device tensor")
+    if keys.dtype in _KEY16_TYPE:
+        return _segmented_sort16_(keys, offsets, values, descending, unsigned, max_segment_len)
     if keys.dtype not in _KEY_TYPE:
-        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
-    if offsets.dim() != 1 or offsets.numel() < 2 or offsets.dtype not in (torch.int32, torch.uint32) or offsets.device != keys.device \
-            or not offsets.is_contiguous():
-        raise ValueError("offsets must be a contiguous 1-D int32 tensor of num_segments + 1 on the keys' device")
+        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys (int32, uint32, float32) and 16-bit keys "
+                        "(float16, bfloat16, int16, uint16)")
+    _require_offsets(keys, offsets)
     kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
     vb = 0
     if values is not None:
@@ -297,9 +339,14 @@ def segmented_sort(keys: torch.Tensor, offsets: torch.Tensor, values: torch.Tens
 def segmented_argsort(keys: torch.Tensor, offsets: torch.Tensor, descending: bool = False, unsigned: bool = False,
                       max_segment_len: int = 0) -> torch.Tensor:
     """Stable permutation of the WHOLE array that sorts every segment: position within the segment's slice plus its start (int32;
-    identity outside the segments)."""
+    identity outside the segments).  16-bit keys: the kernels make the indices inside the segments themselves."""
     idx = torch.arange(keys.numel(), dtype=torch.int32, device=keys.device)
     k = keys.clone()
+    if keys.dtype in _KEY16_TYPE:
+        if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
+            raise ValueError("keys must be a contiguous 1-D device tensor")
+        _segmented_sort16_(k, offsets, None, descending, unsigned, max_segment_len, positions=idx)
+        return idx
     segmented_sort_(k, offsets, idx, descending, unsigned, max_segment_len)
     return idx
 

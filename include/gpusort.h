@@ -877,6 +877,103 @@ gs_status gs_sort_rows16_last(gs_sort_rows16* h, uint32_t* report, uint32_t word
 gs_status gs_sort_rows16_set_rank_mode(gs_sort_rows16* h, int mode);
 int gs_sort_rows16_get_rank_mode(gs_sort_rows16* h);
 
+/* ---- segmented sort on 16-bit keys: many independent segments of one array of GS_KEY_UINT16 / INT16 / FLOAT16 / BFLOAT16 in one call ----
+ * No counterpart in the reference project.  gs_segsort_* on 2-byte elements: CSR offsets d_offsets[0 .. num_segments] (num_segments + 1
+ * uint32 words in device memory, counting elements), segment s = [d_offsets[s], d_offsets[s + 1]).  Every segment is sorted on its own,
+ * in place, and ends exactly as gs_sort16_sort_keys / _sort_pairs would leave that slice alone: stable by the sortable 16 bits,
+ * descending = the exact reverse of the stable ascending result, floats by the order-preserving bit flip (-0 < +0, NaNs by bit pattern),
+ * every key bit pattern preserved, values bit-copied.  Empty segments and segments of one element are legal anywhere.  Elements in front
+ * of d_offsets[0] and behind d_offsets[num_segments] are never written — at 2-byte granularity: not even the other half of a dword they
+ * share with a segment.  The 32-bit key types stay with gs_segsort_* (which keeps answering GS_ERR_ARG for the 16-bit ones).
+ *
+ * The offsets are validated ON THE DEVICE before anything is loaded through them (non-decreasing, last <= n): with bad offsets nothing
+ * is written and gs_segsort16_check reports GS_ERR_ARG.
+ *
+ * Length classes: those of gs_segsort_class_of, with the same LDS limits (gs_segsort_max_lds_segment: 32 768 keys-only, 16 384 with
+ * 4-byte values or positions, 8192 with 8-byte values; a key occupies a 32-bit register and LDS word while it is ranked).  Classes
+ * 1 .. 7 are sorted in LDS by two 8-bit ranking passes, in place.  Class 8 (longer) takes GS_SEGSORT16_PASSES stable 8-bit LSD passes
+ * over ALL long segments at once, the low byte from the caller's buffers into d_alt*, the high byte back: the (segment, part) work list
+ * — parts of GS_SEGSORT16_PART elements — is built on the device, and each pass is a count, a scan and a scatter launch on fixed
+ * grids sized by gs_segsort16_units.  No kernel waits on another workgroup.
+ *
+ * max_segment_len is a promise by the caller, as in gs_segsort_*: a segment that breaks it is left unsorted — noticed on the device —
+ * and gs_segsort16_check reports GS_ERR_SIZE.  Non-zero and <= gs_segsort_max_lds_segment(): d_alt* are not touched and may be NULL.  0
+ * (unknown) or larger: long segments are allowed and d_alt* (n elements each, scratch) are required.  UNLIKE gs_segsort_*, the call
+ * never waits on the host, whatever the segment lengths: every launch is enqueued up front and a call can be captured into a graph on
+ * one linear stream with max_segment_len = 0; every node of a captured call is a kernel launch.
+ *
+ * 1 <= n <= max_keys, 1 <= num_segments <= max_segments; only the base pointers need 16-byte alignment.
+ * GS_ERR_ARG: null handle (before anything else is looked at), null or misaligned d_keys, null d_offsets or one off a 4-byte boundary,
+ * a key type outside 6 .. 9 (the 32- and the 64-bit ones), a bad order; then GS_ERR_MODE: keys call on a pairs handle or the reverse,
+ * gs_segsort16_argsort on anything but a handle with 4-byte values (and every call on a build flavour without these kernels: the
+ * tuning and fault-injection libraries); then GS_ERR_ARG for a null or misaligned d_vals / d_pos; then GS_ERR_SIZE: n == 0,
+ * n > max_keys, num_segments == 0 or num_segments > max_segments; then, where long segments are allowed, GS_ERR_ARG for a null or
+ * misaligned d_alt* and for any two of the call's buffers overlapping.  A refused call writes nothing.  One in-flight call per handle. */
+typedef struct gs_segsort16 gs_segsort16;
+#define GS_SEGSORT16_PASSES 2u
+#define GS_SEGSORT16_PART (8u * GS_SORT_ROWS_TILE)  /* elements of a part of a long segment: 8 tiles (measured against 4 and 16) */
+/* gs_segsort16_last: report[GS_SEGSORT16_R_*] */
+#define GS_SEGSORT16_R_UNITS 0     /* (segment, part) units counted on the device (0: no long segment, or the long launches were skipped) */
+#define GS_SEGSORT16_R_FORMS 1     /* GS_SEGSORT16_F_*: the kernel forms the call launched */
+#define GS_SEGSORT16_R_WG_FORMS 2  /* the workgroup-class kernels among them: bit GS_SEGSORT16_WG_FORM(class, v, rank mode) */
+#define GS_SEGSORT16_R_STATUS 3    /* the device status: bit 0 bad offsets, bit 1 a promise broken (the segmented sort's status word); bit 8: a long segment's counts did not add up */
+#define GS_SEGSORT16_R_RANK 4      /* the handle's rank mode */
+#define GS_SEGSORT16_R_LONG 5      /* long segments counted on the device */
+#define GS_SEGSORT16_R_UNIT_CAP 6  /* gs_segsort16_units of the call: the fixed grids (0: the long launches were skipped) */
+#define GS_SEGSORT16_R_N 7
+#define GS_SEGSORT16_REPORT_WORDS 8
+/* v below: 0 keys only, 1 positions made in registers (argsort; in the long route its first pass only), 2 4-byte, 3 8-byte values */
+#define GS_SEGSORT16_F_CLASSIFY 1u     /* seg_reset_kernel + seg_classify_kernel */
+#define GS_SEGSORT16_F_FILL 2u         /* seg_fill_kernel */
+#define GS_SEGSORT16_F_PACKED 4u       /* << v: bits 2 .. 5 */
+#define GS_SEGSORT16_F_WAVE 64u        /* << v: bits 6 .. 9 */
+#define GS_SEGSORT16_F_UNITS 1024u
+#define GS_SEGSORT16_F_COUNT 2048u
+#define GS_SEGSORT16_F_SCAN 4096u
+#define GS_SEGSORT16_F_SCATTER 8192u   /* << (2 x v + rank mode): bits 13 .. 20 */
+#define GS_SEGSORT16_F_ALL 0x1fffffu
+/* The workgroup-class kernels that exist: classes 3 .. 5 with every v, class 6 without 8-byte values, class 7 keys only: 16 per rank
+ * mode.  Bit = 16 x rank mode + 4 x (class - 3) + v for classes 3 .. 5, 12 + v for class 6, 15 for class 7. */
+#define GS_SEGSORT16_WG_FORM(cls, v, rank) (1u << (16u * (rank) + ((cls) <= 5u ? 4u * ((cls) - 3u) + (v) : (cls) == 6u ? 12u + (v) : 15u)))
+#define GS_SEGSORT16_WG_ALL 0xffffffffu
+/* value_bytes 0 (keys only), 4 or 8, as gs_onesweep_create.  Synchronous (allocates gs_segsort16_temp_bytes of device memory). */
+gs_status gs_segsort16_create(gs_segsort16** out, uint32_t max_keys, uint32_t max_segments, gs_mode mode, uint32_t value_bytes);
+gs_status gs_segsort16_destroy(gs_segsort16* h);
+/* Host only.  The bound on (segment, part) units of a call, which sizes the tables and the fixed grids of the long route: with
+ * L = gs_segsort_max_lds_segment(mode, value_bytes), n / GS_SEGSORT16_PART + min(num_segments, n / (L + 1)) — a segment of length len
+ * has at most len / GS_SEGSORT16_PART + 1 parts, and at most n / (L + 1) segments are long.  0 for n == 0, n > GS_MAX_KEYS,
+ * num_segments == 0, num_segments > GS_MAX_KEYS or an invalid mode or value width. */
+uint32_t gs_segsort16_units(uint32_t n, uint32_t num_segments, gs_mode mode, uint32_t value_bytes);
+/* Host only.  With U = gs_segsort16_units(max_keys, max_segments, ..) and G = min(max_segments, max_keys / (L + 1)): a 256-byte
+ * control block + the class lists (4 x max_segments) + 16 x U (unit descriptors) + 16 x G (long-segment records) + the table and the
+ * bases (U x 256 words each), each rounded up to 256 bytes.  0 for arguments gs_segsort16_units refuses. */
+size_t gs_segsort16_temp_bytes(uint32_t max_keys, uint32_t max_segments, gs_mode mode, uint32_t value_bytes);
+/* Result in d_keys; d_alt: scratch of n keys (required where long segments are allowed). */
+gs_status gs_segsort16_sort_keys(gs_segsort16* h, void* d_keys, void* d_alt, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments,
+                                 uint32_t max_segment_len, gs_key_type key_type, gs_order order, void* stream);
+/* Result in d_keys / d_vals; d_alt_*: scratch of n elements each (required where long segments are allowed). */
+gs_status gs_segsort16_sort_pairs(gs_segsort16* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t n,
+                                  const uint32_t* d_offsets, uint32_t num_segments, uint32_t max_segment_len, gs_key_type key_type,
+                                  gs_order order, void* stream);
+/* Handle with 4-byte values: d_pos is OUTPUT only and never read on entry.  For every i inside the segments, d_pos[i] = the ARRAY index
+ * (segment start + position in the segment) of the element the order puts at i; a segment of one element gets its own index; d_pos
+ * outside the segments, and inside a segment that broke the promise, is not written. */
+gs_status gs_segsort16_argsort(gs_segsort16* h, void* d_keys, void* d_pos, void* d_alt_keys, void* d_alt_pos, uint32_t n,
+                               const uint32_t* d_offsets, uint32_t num_segments, uint32_t max_segment_len, gs_key_type key_type,
+                               gs_order order, void* stream);
+/* Synchronises `stream` and reports the last call: GS_OK, GS_ERR_ARG (bad offsets: nothing was sorted), GS_ERR_HIP (a long segment's
+ * counts did not add up — cannot happen; the scatters then write nothing), GS_ERR_SIZE (a segment longer than promised: that one is
+ * unsorted, every other one sorted).  Every call resets the status itself. */
+gs_status gs_segsort16_check(gs_segsort16* h, void* stream);
+/* Synchronous, as gs_segsort_last_classes: counts[c] = segments of class c in the last call, counts[GS_SEGSORT_CLASSES] = the longest
+ * segment seen.  words >= GS_SEGSORT_CLASSES + 1. */
+gs_status gs_segsort16_last_classes(gs_segsort16* h, uint32_t* counts, uint32_t words, void* stream);
+/* Synchronous diagnostics of the last call: report[GS_SEGSORT16_R_*], words >= GS_SEGSORT16_REPORT_WORDS. */
+gs_status gs_segsort16_last(gs_segsort16* h, uint32_t* report, uint32_t words, void* stream);
+/* The ranking inside a tile (the workgroup classes and the long route's scatter), as gs_sort_rows16_set_rank_mode. */
+gs_status gs_segsort16_set_rank_mode(gs_segsort16* h, int mode);
+int gs_segsort16_get_rank_mode(gs_segsort16* h);
+
 #ifdef __cplusplus
 }
 #endif
