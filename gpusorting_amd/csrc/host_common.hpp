@@ -41,6 +41,13 @@ inline bool buffers_overlap(const void* a, size_t na, const void* b, size_t nb) 
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return x < y + nb && y < x + na;
 }
+// do any two of the first `count` buffers p[i] of bytes[i] bytes share a byte
+inline bool any_overlap(const void* const* p, const size_t* bytes, int count) {
+    for (int i = 0; i < count; ++i)
+        for (int j = i + 1; j < count; ++j)
+            if (buffers_overlap(p[i], bytes[i], p[j], bytes[j])) return true;
+    return false;
+}
 
 // compute units of the device (read once per process; 256 if it cannot be read)
 uint32_t cu_count() {

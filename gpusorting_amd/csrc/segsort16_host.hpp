@@ -173,9 +173,7 @@ gs_status segsort16_impl(gs_segsort16* h, void* d_keys, void* d_vals, void* d_al
         const size_t kb = (size_t)n * 2u, vbytes = (size_t)n * vb;
         const void* p[4] = {d_keys, d_alt_keys, d_vals, d_alt_vals};
         const size_t b[4] = {kb, kb, vbytes, vbytes};
-        for (int i = 0; i < (pairs ? 4 : 2); ++i)
-            for (int j = i + 1; j < (pairs ? 4 : 2); ++j)
-                if (buffers_overlap(p[i], b[i], p[j], b[j])) return GS_ERR_ARG;
+        if (any_overlap(p, b, pairs ? 4 : 2)) return GS_ERR_ARG;
     }
     if (!SR_BUILT) return GS_ERR_MODE;  // this build flavour has no segmented sort
 #if GS_SORT_ROWS_BUILT

@@ -18,21 +18,20 @@
 //                         prefix over (digit major, part minor) within the segment; the counts must add up to its length),
 //                         seg16_scatter_kernel (one workgroup per unit, its tiles in order with running bases)
 //     count, scan and scatter run on fixed grids sized by the host's bound on units and long segments (gs_segsort16_units):
-//     workgroups beyond the device's own counts leave at once.  The count and scatter bodies are those of the row-wise sort
-//     (sr16_count_body / sr16_scatter_body, sortrows16_kernels.hpp) with (row, part) replaced by a unit descriptor.
+//     workgroups beyond the device's own counts leave at once.  Count, scan and scatter are the bodies of radix_pass.hpp, which tells
+//     the pass's structure and invariants, with a long segment as the row and a unit descriptor as its part.
 //
 // In place at 2-byte boundaries: a packed, wave or workgroup segment is whole in registers (packed: in LDS) before
 // its first store, and belongs to one wave or one workgroup.  Neighbouring segments, sorted by other workgroups, share dwords and
 // 16-byte lines at every odd boundary, so EVERY key store here is a 2-byte store and nothing is read-modify-written.
-// The all-one dummies of the slots behind a segment's end tie with a real key whose sortable bits are 0xFFFF: they stay behind it
-// only because the ranking is stable and the dummies sit in the highest slots (in the RANK 1 forms they take no part at all).
-// Whoever changes the dummies' place or the ranking's stability breaks that.
+// The all-one dummies of the slots behind a segment's end tie with a real key whose sortable bits are 0xFFFF; what keeps them behind
+// it (highest slots, stable ranking) is the rule radix_pass.hpp states, and it holds for every class here.
 // No kernel waits on another workgroup.  Every LDS and global store index is checked against its segment's bounds; a count that does
 // not add up sets SEG16C_INTERNAL, and a scatter that finds it set writes nothing.  Registers, LDS and scratch per kernel: DESIGN.md 3.15.
 #pragma once
 #include "segsort_kernels.hpp"
 #include "topk_rows16_kernels.hpp"  // tkr16_to_bits / tkr16_from_bits, TkrVal, tkr_tile_sort_passes
-#include "sortrows16_kernels.hpp"   // sr16_count_body, sr16_scatter_body, sr_scan_body
+#include "sortrows16_kernels.hpp"   // SR_* constants; through it radix_pass.hpp: the three bodies of the pass
 
 namespace gs {
 
@@ -257,7 +256,7 @@ __global__ __launch_bounds__(SR_THREADS) void seg16_count_kernel(const uint16_t*
     if (u >= unit_cap || u >= ctl[SEG16C_UNITS] || ctl[SEG16C_INTERNAL] != 0u) return;
     const uint4 d = desc[u];
     const uint32_t len = (d.z < d.w && d.w <= d.y) ? d.w - d.z : 0u;
-    sr16_count_body(keys + d.x + d.z, len, kt, shift, table + (size_t)u * RADIX);
+    pass_count16_body(keys + d.x + d.z, len, kt, shift, table + (size_t)u * RADIX);
 }
 
 // One workgroup per long segment (fixed grid), thread = digit: sr_scan_kernel over the segment's units.
@@ -267,7 +266,7 @@ __global__ __launch_bounds__(RADIX) void seg16_scan_kernel(const uint32_t* __res
     if ((ctl[SEGC_STATUS] & SEG_ST_ARG) || i >= long_cap || i >= ctl[SEGC_COUNT + SEG_CLASS_LONG]) return;  // (uniform)
     const uint4 r = rec[i];  // (first unit, parts, start, length)
     if (r.y == 0u || r.x > unit_cap || r.y > unit_cap - r.x) return;
-    sr_scan_body(table + (size_t)r.x * RADIX, bases + (size_t)r.x * RADIX, r.y, r.w, ctl + SEG16C_INTERNAL);
+    pass_scan_body(table + (size_t)r.x * RADIX, bases + (size_t)r.x * RADIX, r.y, r.w, ctl + SEG16C_INTERNAL);
 }
 
 // One workgroup per unit (fixed grid), its tiles in order: sr16_scatter_kernel with (row, part) replaced by the unit's descriptor.
@@ -282,9 +281,9 @@ __global__ __launch_bounds__(SR_THREADS) void seg16_scatter_kernel(const uint16_
     if (u >= unit_cap || u >= ctl[SEG16C_UNITS]) return;  // (uniform)
     const uint4 d = desc[u];  // (start, length, part's first element, part's end)
     if (d.w > d.y) return;
-    sr16_scatter_body<VM, RANK>(kin + d.x, static_cast<const V*>(vin_) + ((VM == 4 || VM == 8) ? d.x : 0u), kout + d.x,
-                                static_cast<V*>(vout_) + (VM != 0 ? d.x : 0u), d.y, d.z, d.w, d.x, kt, shift, reverse, bases + (size_t)u * RADIX,
-                                ctl + SEG16C_INTERNAL);
+    pass_scatter_body<uint16_t, VM, RANK>(kin + d.x, static_cast<const V*>(vin_) + ((VM == 4 || VM == 8) ? d.x : 0u), kout + d.x,
+                                          static_cast<V*>(vout_) + (VM != 0 ? d.x : 0u), d.y, d.z, d.w, d.x, kt, shift, reverse,
+                                          bases + (size_t)u * RADIX, ctl + SEG16C_INTERNAL);
 }
 
 #endif  // GS_SORT_ROWS_BUILT

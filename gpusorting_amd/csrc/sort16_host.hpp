@@ -115,9 +115,7 @@ gs_status sort16_impl(gs_sort16* h, void* d_keys, void* d_vals, void* d_alt_keys
         const size_t kb = (size_t)n * 2u, vb = (size_t)n * h->value_bytes;
         const void* p[4] = {d_keys, d_alt_keys, d_vals, d_alt_vals};
         const size_t b[4] = {kb, kb, vb, vb};
-        for (int i = 0; i < 4; ++i)
-            for (int j = i + 1; j < 4; ++j)
-                if (buffers_overlap(p[i], b[i], p[j], b[j])) return GS_ERR_ARG;
+        if (any_overlap(p, b, 4)) return GS_ERR_ARG;
     }
     if (!S16_BUILT) return GS_ERR_MODE;  // this build flavour has no 16-bit sort
 #if GS_SORT16_BUILT

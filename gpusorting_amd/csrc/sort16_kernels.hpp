@@ -4,17 +4,16 @@
 // Keys only is a counting sort: s16_hist_kernel reads the keys once per half of the bin space into the handle's exact 65 536-bin
 // histogram, s16_scan_kernel turns it into prefix[65 537], and s16_fill_kernel writes the sorted array FROM THE PREFIX — the keys
 // are never read again, so the sort works in place and needs no n-sized scratch.
-// Pairs and argsort are two stable 8-bit passes (low byte into the alternate buffers, high byte back), each count -> scan ->
-// scatter: s16_count_kernel writes one 256-bin digit histogram per range, s16_pscan_kernel the exclusive prefix over (digit major,
-// range minor), and s16_scatter_kernel — one workgroup per range — walks its tiles in order with running per-digit bases in LDS.
-// Descending ranks in ascending space and lets the last pass write to n - 1 - position (the reverse-index rule of
-// gs_onesweep_digit_pass): the exact reverse of the stable ascending result.
+// Pairs and argsort are two stable 8-bit passes (low byte into the alternate buffers, high byte back) of radix_pass.hpp, which
+// tells the pass's structure and invariants: the whole array is the one row, cut into ranges of whole tiles; s16_count_kernel writes
+// one 256-bin digit histogram per range, s16_pscan_kernel the exclusive prefix over (digit major, range minor), and
+// s16_scatter_kernel — one workgroup per range — walks its tiles in order.
 //
 // No kernel waits on another workgroup: no look-back, no chain, no ticket.  Every LDS and global store index is checked against
 // its buffer's length; a count that does not add up sets S16_ST_INTERNAL in the handle's status word.  Registers, LDS and scratch
 // per kernel: DESIGN.md 3.12.
 #pragma once
-#include "topk_rows16_kernels.hpp"  // tkr16_to_bits / tkr16_from_bits, KEY_U16 .. KEY_BF16
+#include "radix_pass.hpp"  // the pass; through it tkr16_to_bits / tkr16_from_bits, KEY_U16 .. KEY_BF16 (topk_rows16_kernels.hpp)
 
 namespace gs {
 
@@ -23,21 +22,14 @@ constexpr uint32_t S16_KTHREADS = 1024;
 constexpr uint32_t S16_KTILE = 8 * S16_KTHREADS;  // keys only: one 16-byte load per thread; ranges and fill slices are multiples of it
 constexpr uint32_t S16_KUNROLL = 4;               // loads in flight per thread of the histogram
 constexpr uint32_t S16_KCAP = 128;                // most ranges of the histogram (two workgroups each: one per CU of a 256-CU device)
-constexpr uint32_t S16_PTHREADS = 512, S16_PKPT = 8;
-constexpr uint32_t S16_PTILE = S16_PTHREADS * S16_PKPT;  // pairs: elements ranked and staged at a time
+constexpr uint32_t S16_PTHREADS = PASS_THREADS, S16_PKPT = PASS_KPT, S16_PTILE = PASS_TILE;  // pairs: the pass's tile
 constexpr uint32_t S16_PCAP = 512;                       // most ranges of a pass: table and bases are S16_PCAP x 256 words each
 constexpr uint32_t S16C_STATUS = 0, S16C_WORDS = 64;     // the handle's control block
-constexpr uint32_t S16_ST_INTERNAL = 1;
+constexpr uint32_t S16_ST_INTERNAL = PASS_ST_INTERNAL;
+static_assert(S16_PTHREADS == 512 && S16_PKPT == 8 && S16_PTILE == 4096 && S16_ST_INTERNAL == 1, "the pass's shape and status bit");
 static_assert(S16_HALF * 4u <= 160u * 1024u && S16_KTILE % 8u == 0 && S16_PTILE % 8u == 0, "LDS, 16-byte loads");
 
-// the kernels are in the product build only (as the segmented sort and the selection): the tuning and fault-injection flavours
-// keep the constants and answer GS_ERR_MODE
-#if !defined(GS_MINIMAL) && GS_EXP == 0
-#define GS_SORT16_BUILT 1
-#else
-#define GS_SORT16_BUILT 0
-#endif
-#if GS_SORT16_BUILT
+#if GS_SORT16_BUILT  // (radix_pass.hpp: the product build only)
 
 // eight elements from index i of the 16-byte aligned array q (i a multiple of 8), two to a word; mask: which lie below hi
 __device__ __forceinline__ uint4 s16_load8(const uint16_t* __restrict__ q, uint32_t i, uint32_t hi, uint32_t& mask) {
@@ -230,204 +222,36 @@ __global__ __launch_bounds__(S16_KTHREADS) void s16_fill_kernel(uint16_t* __rest
 }
 
 // ---- pairs and argsort ----------------------------------------------------------------------------------------------------------------
-template <int VM>
-struct S16Val { using type = uint32_t; };
-template <>
-struct S16Val<8> { using type = uint64_t; };
+// The three kernels of a pass are pass_count16_body, pass_scan_body and pass_scatter_body (radix_pass.hpp) with the whole array as
+// the one row and range r = [r * per_range, ...) as its part r.
 
-// table[r][d] = keys of range r whose byte at `shift` of the sortable bits is d
+// table[r][d] = keys of range r whose byte at `shift` of the sortable bits is d.  keys is 16-byte aligned and per_range a multiple of
+// the tile, so the body's peel is 0.
 __global__ __launch_bounds__(S16_PTHREADS) void s16_count_kernel(const uint16_t* __restrict__ keys, uint32_t n, uint32_t per_range, uint32_t kt,
                                                                  uint32_t shift, uint32_t* __restrict__ table) {
-    constexpr uint32_t W = S16_PTHREADS / 64;
-    __shared__ __attribute__((aligned(16))) uint32_t s_h[W * RADIX];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    reinterpret_cast<uint4*>(s_h)[tid] = uint4{0u, 0u, 0u, 0u};
-    static_assert(W * RADIX == 4u * S16_PTHREADS, "one 16-byte store per thread clears the counters");
-    __syncthreads();
-    uint32_t* mine = s_h + wave * RADIX;
     const uint32_t lo = blockIdx.x * per_range;
     const uint32_t hi = lo < n ? (n - lo < per_range ? n : lo + per_range) : lo;
-    for (uint32_t c = lo; c < hi; c += S16_PTILE) {
-        const uint32_t i = c + tid * 8u;
-        uint32_t mask = 0u;
-        uint4 t = uint4{0u, 0u, 0u, 0u};
-        if (i < hi) t = s16_load8(keys, i, hi, mask);
-        const uint32_t w4[4] = {t.x, t.y, t.z, t.w};
-        uint32_t d[8];
-        bool one = true;
-#pragma unroll
-        for (uint32_t j = 0; j < 8; ++j) {
-            d[j] = (tkr16_to_bits(tkr16_elem(w4, j), kt) >> shift) & 255u;
-            one = one && d[j] == d[0];
-        }
-        const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)d[0]);
-        if (__builtin_amdgcn_ballot_w64(mask == 255u && one && d[0] == f) == ~0ull) {  // the wave's 512 keys share the digit: one add
-            if (lane == 0) atomicAdd(&mine[f], 512u);
-            continue;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < 8; ++j)
-            if ((mask >> j) & 1u) atomicAdd(&mine[d[j]], 1u);
-    }
-    __syncthreads();
-    if (tid < RADIX) {
-        uint32_t sum = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < W; ++w) sum += s_h[w * RADIX + tid];
-        table[blockIdx.x * RADIX + tid] = sum;
-    }
+    pass_count16_body(keys + lo, hi - lo, kt, shift, table + blockIdx.x * RADIX);
 }
 
 // One workgroup: bases[r][d] = keys with a digit below d + keys of digit d in the ranges in front of r; the total must be n.
 __global__ __launch_bounds__(RADIX) void s16_pscan_kernel(const uint32_t* __restrict__ table, uint32_t* __restrict__ bases, uint32_t ranges, uint32_t n,
                                                           uint32_t* __restrict__ ctl) {
-    constexpr uint32_t W = RADIX / 64;
-    __shared__ uint32_t s_w[W];
-    const uint32_t d = threadIdx.x, lane = d & 63u, wave = d >> 6;
-    uint32_t total = 0;
-#pragma unroll 8
-    for (uint32_t r = 0; r < ranges; ++r) total += table[r * RADIX + d];
-    const uint32_t incl = wave_inclusive_scan(total, lane);
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t run = incl - total, all = 0;
-    for (uint32_t x = 0; x < W; ++x) {
-        if (x < wave) run += s_w[x];
-        all += s_w[x];
-    }
-    if (d == 0 && all != n) atomicOr(&ctl[S16C_STATUS], S16_ST_INTERNAL);
-#pragma unroll 8
-    for (uint32_t r = 0; r < ranges; ++r) {
-        const uint32_t c = table[r * RADIX + d];
-        bases[r * RADIX + d] = run;
-        run += c;
-    }
+    pass_scan_body(table, bases, ranges, n, ctl + S16C_STATUS);
 }
 
 // One workgroup per range, its tiles in order.  VM: 1 = the value is the element's input position (argsort, first pass: made in
-// registers, 4 bytes), 4 / 8 = values of that width.  RANK 0: 64-lane ballot multi-split; 1: one returning LDS atomic per key (needs the
-// lane-order probe, as everywhere).  A tile is ranked per wave (element wave * 512 + i * 64 + lane: rounds and lanes in element order, so
-// ranks are stable), the wave counters are turned into tile positions, keys and values are staged in digit order and written out run
-// by run; the running base of a digit moves on by the tile's count.  reverse != 0 (descending, last pass): position p goes to n - 1 - p.
+// registers, 4 bytes), 4 / 8 = values of that width.  reverse != 0 (descending, last pass): position p goes to n - 1 - p.  As on
+// the other routes of the pass, a scatter that finds the status word set (s16_pscan_kernel: the counts did not add up) writes nothing.
 template <int VM, int RANK>
 __global__ __launch_bounds__(S16_PTHREADS) void s16_scatter_kernel(const uint16_t* __restrict__ kin, const void* __restrict__ vin_, uint16_t* __restrict__ kout,
                                                                    void* __restrict__ vout_, uint32_t n, uint32_t per_range, uint32_t kt, uint32_t shift,
                                                                    uint32_t reverse, const uint32_t* __restrict__ bases, uint32_t* __restrict__ ctl) {
     using V = typename S16Val<VM>::type;
-    constexpr uint32_t THREADS = S16_PTHREADS, KPT = S16_PKPT, WAVES = THREADS / 64, TILE = S16_PTILE;
-    static_assert(WAVES * RADIX == 4u * THREADS, "one 16-byte store per thread clears the wave counters");
-    __shared__ __attribute__((aligned(16))) uint32_t s_whist[WAVES * RADIX];
-    __shared__ uint16_t s_key[TILE];  // raw keys, at their own width
-    __shared__ V s_val[TILE];
-    __shared__ uint32_t s_base[RADIX], s_gofs[RADIX], s_wtot[RADIX / 64];
-    const V* vin = static_cast<const V*>(vin_);
-    V* vout = static_cast<V*>(vout_);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t lo = blockIdx.x * per_range;
-    if (lo >= n) return;  // (uniform)
-    const uint32_t hi = n - lo < per_range ? n : lo + per_range;
-    if (tid < RADIX) s_base[tid] = bases[blockIdx.x * RADIX + tid];  // (read and written by thread `tid` only)
-    uint32_t* whist = s_whist + wave * RADIX;
-    const uint32_t my_base = wave * (64u * KPT) + lane;
-    for (uint32_t t0 = lo; t0 < hi; t0 += TILE) {
-        const uint32_t m = hi - t0 < TILE ? hi - t0 : TILE;
-        uint32_t key[KPT], bits[KPT], off[KPT];
-        V val[KPT];
-        // unconditional loads on a clamped index, masked afterwards
-#pragma unroll
-        for (uint32_t i = 0; i < KPT; ++i) {
-            const uint32_t idx = my_base + i * 64u, ci = idx < m ? idx : m - 1u;
-            key[i] = kin[t0 + ci];
-            if constexpr (VM == 1) val[i] = t0 + ci;
-            else val[i] = vin[t0 + ci];
-        }
-#pragma unroll
-        for (uint32_t i = 0; i < KPT; ++i) bits[i] = my_base + i * 64u < m ? tkr16_to_bits(key[i], kt) : 0xffffu;  // dummies: digit 255, highest slots
-        reinterpret_cast<uint4*>(s_whist)[tid] = uint4{0u, 0u, 0u, 0u};
-        __syncthreads();  // (also: the previous tile's staging has been read)
-        if constexpr (RANK == 0) {
-#pragma unroll
-            for (uint32_t i = 0; i < KPT; ++i) {
-                const uint32_t d = (bits[i] >> shift) & 255u;
-                uint32_t acc_lo = 0, acc_hi = 0;
-#pragma unroll
-                for (uint32_t k = 0; k < 8; ++k) {
-                    const uint32_t B = (uint32_t)__builtin_amdgcn_sbfe((int32_t)bits[i], shift + k, 1);
-                    const unsigned long long b = __builtin_amdgcn_ballot_w64(B != 0u);
-                    acc_lo = __builtin_amdgcn_bitop3_b32(acc_lo, (uint32_t)b, B, 0xF6);
-                    acc_hi = __builtin_amdgcn_bitop3_b32(acc_hi, (uint32_t)(b >> 32), B, 0xF6);
-                }
-                const uint32_t plo = ~acc_lo, phi = ~acc_hi;
-                const uint32_t below = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u));
-                const uint32_t total = __popc(plo) + __popc(phi);
-                const uint32_t pre = whist[d];
-                if (below == total - 1u) whist[d] = pre + total;
-                asm volatile("" ::: "memory");
-                off[i] = pre + below;
-            }
-        } else {
-            // slots >= m take no part: validity is a property of the slot
-#pragma unroll
-            for (uint32_t i = 0; i < KPT; ++i) {
-                const uint32_t d = (bits[i] >> shift) & 255u;
-                off[i] = 0;
-                if (my_base + i * 64u < m) off[i] = __hip_atomic_fetch_add(&whist[d], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        }
-        __syncthreads();
-        uint32_t run = 0, scan_incl = 0;
-        if (tid < RADIX) {
-#pragma unroll
-            for (uint32_t w = 0; w < WAVES; ++w) {
-                const uint32_t c = s_whist[w * RADIX + tid];
-                s_whist[w * RADIX + tid] = run;
-                run += c;
-            }
-            scan_incl = wave_inclusive_scan(run, lane);
-            if (lane == 63) s_wtot[wave] = scan_incl;
-        }
-        __syncthreads();
-        if (tid < RADIX) {
-            uint32_t wbase = 0;
-            for (uint32_t w = 0; w < wave; ++w) wbase += s_wtot[w];
-            const uint32_t dpre = wbase + scan_incl - run;  // the digit's first slot in the staged tile
-#pragma unroll
-            for (uint32_t w = 0; w < WAVES; ++w) s_whist[w * RADIX + tid] += dpre;
-            s_gofs[tid] = s_base[tid] - dpre;  // staged slot j of this digit goes to s_gofs + j (may wrap: the sum does not)
-            // the digit's count among the tile's m real keys (RANK 0 ranked the TILE - m dummies under digit 255 as well)
-            s_base[tid] += (RANK == 0 && tid == RADIX - 1u) ? run - (TILE - m) : run;
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t i = 0; i < KPT; ++i) {
-            const uint32_t lpos = off[i] + s_whist[wave * RADIX + ((bits[i] >> shift) & 255u)];
-            if (my_base + i * 64u < m) {
-                if (lpos < m) {
-                    s_key[lpos] = (uint16_t)key[i];
-                    s_val[lpos] = val[i];
-                } else {
-                    atomicOr(&ctl[S16C_STATUS], S16_ST_INTERNAL);
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t i = 0; i < KPT; ++i) {
-            const uint32_t j = tid + i * THREADS;
-            if (j < m) {
-                const uint32_t k = s_key[j];
-                const uint32_t pos = s_gofs[(tkr16_to_bits(k, kt) >> shift) & 255u] + j;
-                if (pos < n) {
-                    const uint32_t o = reverse ? n - 1u - pos : pos;
-                    kout[o] = (uint16_t)k;
-                    vout[o] = s_val[j];
-                } else {
-                    atomicOr(&ctl[S16C_STATUS], S16_ST_INTERNAL);
-                }
-            }
-        }
-        // the next tile's first barrier stands between these reads and the next writes of s_gofs and the staging
-    }
+    const uint32_t hi = lo < n ? (n - lo < per_range ? n : lo + per_range) : lo;
+    pass_scatter_body<uint16_t, VM, RANK>(kin, static_cast<const V*>(vin_), kout, static_cast<V*>(vout_), n, lo, hi, 0u, kt, shift, reverse,
+                                          bases + blockIdx.x * RADIX, ctl + S16C_STATUS);
 }
 
 #endif  // GS_SORT16_BUILT

@@ -172,6 +172,25 @@ def test_ranges_of_several_tiles(gpu, entry, rank, desc):
     h.close()
 
 
+@pytest.mark.parametrize("rank", (0, 1))
+@pytest.mark.parametrize("entry", ("pairs4", "pairs8", "argsort"))
+def test_all_ones_keys_tie_with_the_dummies_of_a_partial_tile(gpu, entry, rank):
+    """Real keys whose sortable bits are 0xFFFF, in the partial last tile of a range, under both ranking forms: on both bytes they share
+    digit 255 with the tile's dummies and must come out in front of them, in input order.  With them 0xFF00 and 0x00FF (the tie on one
+    byte only) and a key of digits below.  Three one-tile ranges with 37 elements in the last, both orders; and the size at which a
+    range holds two tiles and the last one three elements, descending (the running bases and the reverse index)."""
+    tile = _plan(entry)["tile"]
+    pool = np.array([0xFFFF, 0xFF00, 0x00FF, 0x1234], dtype=np.uint16)
+    for n, orders in ((2 * tile + 37, (False, True)), (_multi_tile_sizes(entry)[0], (True,))):
+        bits = pool[np.random.default_rng(n + rank).integers(0, 4, n)]
+        bits[-3:] = (0xFFFF, 0x1234, 0xFFFF)
+        assert np.count_nonzero(bits[-(n % tile):] == 0xFFFF) >= 2 and 0 < n % tile < tile
+        for desc in orders:
+            h = _handle(gpu, entry, n, U16, desc, rank)
+            assert _run(gpu, h, entry, bits, U16, desc, seed=3)["rank_mode"] == rank
+            h.close()
+
+
 @pytest.mark.parametrize("desc", (False, True))
 def test_keys_ranges_of_several_tiles(gpu, desc):
     """Keys only above the cap: two and five tiles per range (the histogram's unrolled loop makes a second trip), partial last tile;
