@@ -23,7 +23,7 @@ from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, GpuSortError
 from .functional import argsort, argsort_rows, segmented_argsort, segmented_sort, segmented_sort_, sort, sort_, sort_rows, sort_rows_, topk  # noqa: F401
 from .rowsort import RowSort, sort_rows_plan, sort_rows_reference  # noqa: F401
 from .rowsort16 import SORT_ROWS16_FORMS, RowSort16, sort_rows16_plan, sort_rows16_reference  # noqa: F401
-from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
+from .segsort import SegmentedSort, segmented_sort_reference, segsort_long_units  # noqa: F401
 from .segsort16 import SEGSORT16_FORMS, SegmentedSort16, segmented_sort16_reference, segsort16_units  # noqa: F401
 from .sort16 import Sort16, sort16_plan, sort16_reference  # noqa: F401
 from .topk import TopK, topk_reference, topk_rows_reference  # noqa: F401

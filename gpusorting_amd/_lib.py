@@ -59,6 +59,16 @@ def GS_SEGSORT16_WG_FORM(cls: int, v: int, rank: int) -> int:
     return 1 << (16 * rank + (4 * (cls - 3) + v if cls <= 5 else 12 + v if cls == 6 else 15))
 
 
+# gs_segsort_set_long_route / gs_segsort_last: the long routes, the device route's plan, the report words and the kernel-form bits
+GS_SEGSORT_LONG_HOST, GS_SEGSORT_LONG_DEVICE = 0, 1
+GS_SEGSORT_LONG_PASSES = 4
+GS_SEGSORT_LONG_PART = 4 * GS_SORT_ROWS_TILE
+(GS_SEGSORT_R_ROUTE, GS_SEGSORT_R_UNITS, GS_SEGSORT_R_LONG, GS_SEGSORT_R_UNIT_CAP, GS_SEGSORT_R_FORMS, GS_SEGSORT_R_STATUS, GS_SEGSORT_R_RANK,
+ GS_SEGSORT_R_N) = range(8)
+GS_SEGSORT_REPORT_WORDS = 8
+GS_SEGSORT_LF_UNITS, GS_SEGSORT_LF_COUNT, GS_SEGSORT_LF_SCAN, GS_SEGSORT_LF_SCATTER = 1, 2, 4, 8
+GS_SEGSORT_LF_ALL = 0x1FF
+
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
 GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
@@ -221,6 +231,11 @@ _PROTOS = [
     ("gs_segsort_check", _int, [_vp, _vp]),
     ("gs_segsort_last_classes", _int, [_vp, _u32p, _u32, _vp]),
     ("gs_segsort_engine", _vp, [_vp]),
+    ("gs_segsort_set_long_route", _int, [_vp, _u32]),
+    ("gs_segsort_get_long_route", _u32, [_vp]),
+    ("gs_segsort_long_units", _u32, [_u32, _u32, _int, _u32]),
+    ("gs_segsort_long_temp_bytes", C.c_size_t, [_u32, _u32, _int, _u32]),
+    ("gs_segsort_last", _int, [_vp, _u32p, _u32, _vp]),
     ("gs_topk_create", _int, [C.POINTER(_vp), _u32, _u32, _int, _u32]),
     ("gs_topk_destroy", _int, [_vp]),
     ("gs_topk_temp_bytes", C.c_size_t, [_u32, _u32, _u32]),

@@ -23,6 +23,7 @@
 #include "sortrows_kernels.hpp"
 #include "sortrows16_kernels.hpp"
 #include "segsort16_kernels.hpp"
+#include "segsort_long_kernels.hpp"
 
 // One translation unit; one host file per concern, in this order (each may use what stands above it):
 #include "host_common.hpp"      // GS_HIP, argument predicates, div_up, cu_count, DeviceScratch

@@ -1,14 +1,17 @@
 // radix_pass.hpp — the one stable 8-bit LSD pass above the LDS limit, count -> scan -> scatter, that the sort of 16-bit keys
-// (sort16_kernels.hpp), the row-wise sorts (sortrows_kernels.hpp, sortrows16_kernels.hpp) and the segmented sort of 16-bit keys
-// (segsort16_kernels.hpp) run.  Those files hold the __global__ kernels: thin wrappers that turn their own work unit (a range of the
-// array, a (row, part), a unit descriptor) into the arguments of the three bodies here.  No counterpart in the reference project.
+// (sort16_kernels.hpp), the row-wise sorts (sortrows_kernels.hpp, sortrows16_kernels.hpp), the segmented sort of 16-bit keys
+// (segsort16_kernels.hpp) and the device route of the 32-bit segmented sort's long segments (segsort_long_kernels.hpp) run.  Those
+// files hold the __global__ kernels: thin wrappers that turn their own work unit (a range of the array, a (row, part), a unit
+// descriptor) into the arguments of the bodies here.  No counterpart in the reference project.
 //
 // Structure.  A "row" is what is sorted on its own: the whole array, a matrix row, a long segment.  It is cut into parts of whole
-// tiles.  pass_count16_body writes one 256-bin digit histogram per part (2-byte keys; the 4-byte count, another load pattern, is
-// sr_count_kernel), pass_scan_body — one workgroup per row, thread = digit — the exclusive prefix over (digit major, part minor)
-// WITHIN the row, and pass_scatter_body — one workgroup per part — walks the part's tiles in order with running per-digit bases in
-// LDS.  All positions are relative to the row.  Descending ranks in ascending space and lets the last pass write to
-// row_len - 1 - position (the reverse-index rule of gs_onesweep_digit_pass): the exact reverse of the stable ascending result.
+// tiles.  pass_count16_body writes one 256-bin digit histogram per part of 2-byte keys, pass_count32_body of 4-byte keys (another
+// load pattern; sr_count_kernel keeps its own copy of that loop: as a wrapper of the body it compiled to 420 instructions and 38
+// VGPRs instead of 410 and 36, with 52 SGPRs, 8192 bytes of LDS and no scratch either way), pass_scan_body — one
+// workgroup per row, thread = digit — the exclusive prefix over (digit major, part minor) WITHIN the row, and pass_scatter_body —
+// one workgroup per part — walks the part's tiles in order with running per-digit bases in LDS.  All positions are relative to the row.  Descending ranks in ascending space and lets the last
+// pass write to row_len - 1 - position (the reverse-index rule of gs_onesweep_digit_pass): the exact reverse of the stable
+// ascending result.
 // No body waits on another workgroup: no look-back, no chain, no ticket.
 //
 // Stability.  A tile is ranked per wave, element wave * 512 + i * 64 + lane: rounds and lanes in element order, so within a wave the
@@ -122,6 +125,51 @@ __device__ __forceinline__ void pass_count16_body(const uint16_t* __restrict__ p
             for (uint32_t j = 0; j < 8; ++j)
                 if ((mask >> j) & 1u) atomicAdd(&mine[d[j]], 1u);
         }
+    }
+    __syncthreads();
+    if (tid < RADIX) {
+        uint32_t sum = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < W; ++w) sum += s_h[w * RADIX + tid];
+        out[tid] = sum;
+    }
+}
+
+// The count of one part of 4-byte keys (sr_count_kernel's loop): out[d] = keys among the `len` elements at p whose byte at `shift` of
+// the sortable bits is d.  p is aligned to its element only (a row or a segment starts wherever it starts): one dword per lane,
+// coalesced, unconditional loads on an index clamped to the tile.  The wave-uniform-digit shortcut is taken on full tiles only.
+// Every thread of the workgroup calls it (its barriers are the workgroup's); the LDS is its own.
+__device__ __forceinline__ void pass_count32_body(const uint32_t* __restrict__ p, uint32_t len, uint32_t kt, uint32_t shift, uint32_t* __restrict__ out) {
+    constexpr uint32_t W = PASS_THREADS / 64;
+    __shared__ __attribute__((aligned(16))) uint32_t s_h[W * RADIX];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    reinterpret_cast<uint4*>(s_h)[tid] = uint4{0u, 0u, 0u, 0u};
+    static_assert(W * RADIX == 4u * PASS_THREADS, "one 16-byte store per thread clears the counters");
+    __syncthreads();
+    uint32_t* mine = s_h + wave * RADIX;
+    for (uint32_t c = 0; c < len; c += PASS_TILE) {
+        const uint32_t m = len - c < PASS_TILE ? len - c : PASS_TILE;
+        uint32_t d[PASS_KPT];
+        // unconditional loads on a clamped index, masked afterwards
+#pragma unroll
+        for (uint32_t i = 0; i < PASS_KPT; ++i) {
+            const uint32_t idx = tid + i * PASS_THREADS;
+            d[i] = p[c + (idx < m ? idx : m - 1u)];
+        }
+        bool one = true;
+#pragma unroll
+        for (uint32_t i = 0; i < PASS_KPT; ++i) {
+            d[i] = (seg_to_bits(d[i], kt) >> shift) & 255u;
+            one = one && d[i] == d[0];
+        }
+        const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)d[0]);
+        if (__builtin_amdgcn_ballot_w64(m == PASS_TILE && one && d[0] == f) == ~0ull) {  // the wave's 512 keys share the digit: one add
+            if (lane == 0) atomicAdd(&mine[f], 64u * PASS_KPT);
+            continue;
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < PASS_KPT; ++i)
+            if (tid + i * PASS_THREADS < m) atomicAdd(&mine[d[i]], 1u);
     }
     __syncthreads();
     if (tid < RADIX) {

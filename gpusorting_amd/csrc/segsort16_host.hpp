@@ -15,15 +15,11 @@ namespace {
 static_assert(GS_SEGSORT16_PASSES == gs::SR16_PASSES && GS_SEGSORT16_PART % GS_SORT_ROWS_TILE == 0 && GS_SORT_ROWS_TILE == gs::SR_TILE,
               "header and kernels agree on the plan: a part is whole tiles");
 
-// most long segments of a call, and the bound on its (segment, part) units: a segment of length len has at most len / PART + 1 parts
-uint32_t segsort16_long_cap(uint32_t n, uint32_t num_segments, uint32_t vb) {
-    const uint32_t by_len = n / (gs::seg_max_lds(vb) + 1u);
-    return by_len < num_segments ? by_len : num_segments;
-}
-uint32_t segsort16_units(uint32_t n, uint32_t num_segments, uint32_t vb) { return n / GS_SEGSORT16_PART + segsort16_long_cap(n, num_segments, vb); }
-bool segsort16_sizes_ok(uint32_t n, uint32_t num_segments, gs_mode mode, uint32_t vb) {
-    return n != 0 && n <= GS_MAX_KEYS && num_segments != 0 && num_segments <= GS_MAX_KEYS && mode_value_ok(mode, vb);
-}
+// most long segments of a call and the bound on its (segment, part) units: seg_long_cap / seg_long_units / seg_long_sizes_ok of
+// segsort_host.hpp, shared with the 32-bit sort's device route, with this sort's part
+uint32_t segsort16_long_cap(uint32_t n, uint32_t num_segments, uint32_t vb) { return seg_long_cap(n, num_segments, vb); }
+uint32_t segsort16_units(uint32_t n, uint32_t num_segments, uint32_t vb) { return seg_long_units(n, num_segments, vb, GS_SEGSORT16_PART); }
+bool segsort16_sizes_ok(uint32_t n, uint32_t num_segments, gs_mode mode, uint32_t vb) { return seg_long_sizes_ok(n, num_segments, mode, vb); }
 
 struct SegSort16Layout {
     size_t ctl, desc, rec, table, bases, total;

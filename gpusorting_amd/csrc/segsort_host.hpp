@@ -8,9 +8,16 @@ struct gs_segsort {
     uint32_t* ctl = nullptr;        // gs::SEGC_WORDS control words, then the class lists (max_segments words)
     uint32_t* pinned = nullptr;     // read-backs: control block + SEG_LONG_CHUNK list entries
     bool long_failed = false;       // a long segment's engine call failed on the host side
+    uint32_t long_route = GS_SEGSORT_LONG_HOST;
+    char* long_dev = nullptr;       // the device route's buffers (seg_long_layout), from the first switch to it until destroy
+    // the last call (gs_segsort_last)
+    uint32_t last_route = 0, last_forms = 0, last_unit_cap = 0, last_n = 0;
 };
 
 static_assert(GS_SEGSORT_CLASSES == gs::SEG_CLASSES, "header and kernels agree on the classes");
+static_assert(GS_SEGSORT_LONG_PASSES == gs::SR_PASSES && GS_SEGSORT_LONG_PASSES % 2u == 0 && GS_SEGSORT_LONG_PART % GS_SORT_ROWS_TILE == 0 &&
+                  GS_SORT_ROWS_TILE == gs::SR_TILE,
+              "header and kernels agree on the plan: a part is whole tiles, and an even number of passes ends in the caller's buffers");
 namespace {
 constexpr uint32_t SEG_LONG_CHUNK = 1024;  // long-list entries per read-back
 inline uint32_t* seg_list(const gs_segsort* h) { return h->ctl + gs::SEGC_WORDS; }
@@ -60,6 +67,79 @@ gs_status seg_enqueue_lds(uint32_t* ctl, int rank_mode, uint32_t vb, uint32_t* k
     return GS_OK;
 }
 
+// ---- long segments on the device: sizes shared with the 16-bit sort (segsort16_host.hpp), the part size as a parameter ----
+// most long segments of a call, and the bound on its (segment, part) units: a segment of length len has at most len / part + 1 parts
+uint32_t seg_long_cap(uint32_t n, uint32_t num_segments, uint32_t vb) {
+    const uint32_t by_len = n / (gs::seg_max_lds(vb) + 1u);
+    return by_len < num_segments ? by_len : num_segments;
+}
+uint32_t seg_long_units(uint32_t n, uint32_t num_segments, uint32_t vb, uint32_t part) { return n / part + seg_long_cap(n, num_segments, vb); }
+bool seg_long_sizes_ok(uint32_t n, uint32_t num_segments, gs_mode mode, uint32_t vb) {
+    return n != 0 && n <= GS_MAX_KEYS && num_segments != 0 && num_segments <= GS_MAX_KEYS && mode_value_ok(mode, vb);
+}
+
+struct SegLongLayout {
+    size_t desc, rec, table, bases, total;
+};
+// desc: one uint4 per unit; rec: one uint4 per long segment; table, bases: units x 256 words each
+SegLongLayout seg_long_layout(uint32_t max_keys, uint32_t max_segments, uint32_t vb) {
+    SegLongLayout l{};
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t a = at; at += (bytes + 255u) & ~(size_t)255u; return a; };
+    const size_t units = seg_long_units(max_keys, max_segments, vb, GS_SEGSORT_LONG_PART), longs = seg_long_cap(max_keys, max_segments, vb);
+    l.desc = take(units * 16u);
+    l.rec = take(longs * 16u);
+    l.table = take(units * gs::RADIX * 4u);
+    l.bases = take(units * gs::RADIX * 4u);
+    l.total = at;
+    return l;
+}
+
+#if GS_SORT_ROWS_BUILT
+// the kernels are launched directly (no registry family; gs_segsort_last's forms word accounts for them)
+using SegLongScatter = void (*)(hipStream_t, uint32_t grid, const uint32_t*, const void*, uint32_t*, void*, const uint4* desc, uint32_t unit_cap, uint32_t kt,
+                                uint32_t shift, uint32_t reverse, const uint32_t* bases, uint32_t* ctl);
+template <int VB, int RANK>
+void launch_segl_scatter(hipStream_t s, uint32_t grid, const uint32_t* kin, const void* vin, uint32_t* kout, void* vout, const uint4* desc, uint32_t unit_cap,
+                         uint32_t kt, uint32_t shift, uint32_t reverse, const uint32_t* bases, uint32_t* ctl) {
+    hipLaunchKernelGGL((gs::segl_scatter_kernel<VB, RANK>), dim3(grid), dim3(gs::SR_THREADS), 0, s, kin, vin, kout, vout, desc, unit_cap, kt, shift, reverse,
+                       bases, ctl);
+}
+constexpr auto g_segl_scatter = Table<2, 3>::make([](auto r, auto v) -> SegLongScatter { return launch_segl_scatter<VB_OF[v], r>; });  // [rank mode][vb index]
+
+// The long segments of a call on the device route, behind seg_enqueue_lds: the work list, then four passes, ping-pong between the
+// caller's buffers and the alternates.  No host wait.
+gs_status seg_enqueue_long(gs_segsort* h, uint32_t* keys, void* vals, uint32_t* alt_keys, void* alt_vals, uint32_t n, const uint32_t* d_offsets,
+                           uint32_t num_segments, uint32_t kt, bool descending, hipStream_t s) {
+    const uint32_t vb = h->value_bytes, v = vb / 4u, rank = h->engine->rank_mode ? 1u : 0u;
+    const SegLongLayout l = seg_long_layout(h->max_keys, h->max_segments, vb);
+    const uint32_t unit_cap = seg_long_units(n, num_segments, vb, GS_SEGSORT_LONG_PART), long_cap = seg_long_cap(n, num_segments, vb);
+    uint32_t* ctl = h->ctl;
+    uint4* desc4 = reinterpret_cast<uint4*>(h->long_dev + l.desc);
+    uint4* rec = reinterpret_cast<uint4*>(h->long_dev + l.rec);
+    uint32_t* table = reinterpret_cast<uint32_t*>(h->long_dev + l.table);
+    uint32_t* bases = reinterpret_cast<uint32_t*>(h->long_dev + l.bases);
+    h->last_unit_cap = unit_cap;
+    hipLaunchKernelGGL(gs::seg16_units_kernel, dim3(div_up(long_cap, 256)), dim3(256), 0, s, d_offsets, seg_list(h), ctl, num_segments, GS_SEGSORT_LONG_PART,
+                       unit_cap, long_cap, desc4, rec);
+    h->last_forms |= GS_SEGSORT_LF_UNITS | GS_SEGSORT_LF_COUNT | GS_SEGSORT_LF_SCAN;
+    for (uint32_t pass = 0; pass < GS_SEGSORT_LONG_PASSES; ++pass) {
+        const bool fwd = (pass & 1u) == 0u, last = pass + 1u == GS_SEGSORT_LONG_PASSES;
+        const uint32_t* kin = fwd ? keys : alt_keys;
+        uint32_t* kout = fwd ? alt_keys : keys;
+        const void* vin = fwd ? vals : alt_vals;
+        void* vout = fwd ? alt_vals : vals;
+        hipLaunchKernelGGL(gs::segl_count_kernel, dim3(unit_cap), dim3(gs::SR_THREADS), 0, s, kin, desc4, ctl, unit_cap, kt, pass * 8u, table);
+        hipLaunchKernelGGL(gs::seg16_scan_kernel, dim3(long_cap), dim3(gs::RADIX), 0, s, table, bases, rec, ctl, unit_cap, long_cap);
+        g_segl_scatter[Table<2, 3>::index({(int)rank, (int)v})](s, unit_cap, kin, vin, kout, vout, desc4, unit_cap, kt, pass * 8u,
+                                                               (descending && last) ? 1u : 0u, bases, ctl);
+    }
+    h->last_forms |= GS_SEGSORT_LF_SCATTER << (2u * v + rank);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+#endif
+
 gs_status segsort_impl(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_keys, void* d_alt_vals, uint32_t n, const uint32_t* d_offsets,
                        uint32_t num_segments, uint32_t max_len, gs_key_type kt, gs_order order, hipStream_t s, bool pairs) {
     if (!h || !d_keys || !d_offsets || misaligned(d_keys) || (reinterpret_cast<uintptr_t>(d_offsets) & 3u) || !is_key32_type(kt) || !valid_order(order))
@@ -70,14 +150,27 @@ gs_status segsort_impl(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_ke
     const uint32_t vb = h->value_bytes;
     const bool allow_long = max_len == 0u || max_len > gs::seg_max_lds(vb);
     if (allow_long && (!d_alt_keys || misaligned(d_alt_keys) || (pairs && (!d_alt_vals || misaligned(d_alt_vals))))) return GS_ERR_ARG;
+    if (allow_long && h->long_route == GS_SEGSORT_LONG_DEVICE) {  // the passes read one buffer while they write the other
+        const size_t kb = (size_t)n * 4u, vbytes = (size_t)n * vb;
+        const void* p[4] = {d_keys, d_alt_keys, d_vals, d_alt_vals};
+        const size_t b[4] = {kb, kb, vbytes, vbytes};
+        if (any_overlap(p, b, pairs ? 4 : 2)) return GS_ERR_ARG;
+    }
     if (!SEG_BUILT) return GS_ERR_MODE;  // this build flavour has no segmented-sort kernels
     const uint32_t top = allow_long ? gs::SEG_CLASS_LONG : gs::seg_class_of(max_len, vb);  // the highest class a segment can fall in
     const uint32_t desc = order == GS_ORDER_DESCENDING ? 1u : 0u;
     uint32_t* keys = static_cast<uint32_t*>(d_keys);
     h->long_failed = false;
+    h->last_route = h->long_route;
+    h->last_forms = h->last_unit_cap = 0;
+    h->last_n = n;
     const gs_status lds = seg_enqueue_lds(h->ctl, h->engine->rank_mode, vb, keys, d_vals, n, d_offsets, num_segments, max_len, top, kt, desc, s);
     if (lds != GS_OK) return lds;
     if (!allow_long || n <= gs::seg_max_lds(vb)) return GS_OK;
+#if GS_SORT_ROWS_BUILT
+    if (h->long_route == GS_SEGSORT_LONG_DEVICE)
+        return seg_enqueue_long(h, keys, d_vals, static_cast<uint32_t*>(d_alt_keys), d_alt_vals, n, d_offsets, num_segments, (uint32_t)kt, desc != 0u, s);
+#endif
     // ---- long segments: the one host wait.  Control block + the head of the long list (it starts the list array) ----
     const SegVbLaunchers& f = seg_vb(vb);
     const uint32_t by_len = n / (gs::seg_max_lds(vb) + 1), most = by_len < num_segments ? by_len : num_segments;  // long segments at most
@@ -131,6 +224,13 @@ uint32_t gs_segsort_class_of(uint32_t length, gs_mode mode, uint32_t value_bytes
 }
 uint32_t gs_segsort_max_lds_segment(gs_mode mode, uint32_t value_bytes) { return gs::seg_max_lds(mode == GS_MODE_PAIRS ? value_bytes : 0); }
 
+uint32_t gs_segsort_long_units(uint32_t n, uint32_t num_segments, gs_mode mode, uint32_t value_bytes) {
+    return seg_long_sizes_ok(n, num_segments, mode, value_bytes) ? seg_long_units(n, num_segments, value_bytes, GS_SEGSORT_LONG_PART) : 0u;
+}
+size_t gs_segsort_long_temp_bytes(uint32_t max_keys, uint32_t max_segments, gs_mode mode, uint32_t value_bytes) {
+    return seg_long_sizes_ok(max_keys, max_segments, mode, value_bytes) ? seg_long_layout(max_keys, max_segments, value_bytes).total : 0;
+}
+
 gs_status gs_segsort_create(gs_segsort** out, uint32_t max_keys, uint32_t max_segments, gs_mode mode, uint32_t value_bytes) {
     if (!out) return GS_ERR_ARG;
     *out = nullptr;
@@ -161,6 +261,7 @@ gs_status gs_segsort_destroy(gs_segsort* h) {
     if (!h) return GS_ERR_ARG;
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->ctl) (void)hipFree(h->ctl);
+    if (h->long_dev) (void)hipFree(h->long_dev);
     if (h->engine) (void)gs_onesweep_destroy(h->engine);
     delete h;
     return GS_OK;
@@ -185,12 +286,49 @@ gs_status gs_segsort_check(gs_segsort* h, void* stream) {
     if (rd != GS_OK) return rd;
     const uint32_t st = h->pinned[gs::SEGC_STATUS];
     if (st & gs::SEG_ST_ARG) return GS_ERR_ARG;
-    if (h->long_failed) return GS_ERR_HIP;
+    if (h->long_failed || h->pinned[gs::SEG16C_INTERNAL] != 0u) return GS_ERR_HIP;  // (the word is the device route's: a long segment's counts did not add up)
     if (st & gs::SEG_ST_SIZE) return GS_ERR_SIZE;
     return gs_onesweep_check(h->engine, stream);  // the long segments' sorts
 }
 
 gs_onesweep* gs_segsort_engine(gs_segsort* h) { return h ? h->engine : nullptr; }
+
+gs_status gs_segsort_set_long_route(gs_segsort* h, uint32_t route) {
+    if (!h || (route != GS_SEGSORT_LONG_HOST && route != GS_SEGSORT_LONG_DEVICE)) return GS_ERR_ARG;
+    if (route == GS_SEGSORT_LONG_DEVICE) {
+        if (!GS_SORT_ROWS_BUILT) return GS_ERR_MODE;  // this build flavour has no pass kernels
+        if (!h->long_dev) {
+            const hipError_t e = hipMalloc(&h->long_dev, seg_long_layout(h->max_keys, h->max_segments, h->value_bytes).total);
+            if (e != hipSuccess) {
+                g_last_hip_error = (int)e;
+                h->long_dev = nullptr;
+                return GS_ERR_HIP;
+            }
+        }
+    }
+    h->long_route = route;
+    return GS_OK;
+}
+
+uint32_t gs_segsort_get_long_route(gs_segsort* h) { return h ? h->long_route : 0xffffffffu; }
+
+gs_status gs_segsort_last(gs_segsort* h, uint32_t* report, uint32_t words, void* stream) {
+    if (!h || !report || words < GS_SEGSORT_REPORT_WORDS) return GS_ERR_ARG;
+    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    if (rd != GS_OK) return rd;
+    for (uint32_t i = 0; i < GS_SEGSORT_REPORT_WORDS; ++i) report[i] = 0;
+    report[GS_SEGSORT_R_ROUTE] = h->last_route;
+    if (h->last_route == GS_SEGSORT_LONG_DEVICE) {
+        report[GS_SEGSORT_R_UNITS] = h->pinned[gs::SEG16C_UNITS];
+        report[GS_SEGSORT_R_UNIT_CAP] = h->last_unit_cap;
+        report[GS_SEGSORT_R_FORMS] = h->last_forms;
+    }
+    report[GS_SEGSORT_R_LONG] = h->pinned[gs::SEGC_COUNT + gs::SEG_CLASS_LONG];
+    report[GS_SEGSORT_R_STATUS] = h->pinned[gs::SEGC_STATUS] | (h->pinned[gs::SEG16C_INTERNAL] != 0u ? 256u : 0u);
+    report[GS_SEGSORT_R_RANK] = (uint32_t)h->engine->rank_mode;
+    report[GS_SEGSORT_R_N] = h->last_n;
+    return GS_OK;
+}
 
 gs_status gs_segsort_last_classes(gs_segsort* h, uint32_t* counts, uint32_t words, void* stream) {
     if (!h || !counts || words < GS_SEGSORT_CLASSES + 1) return GS_ERR_ARG;

@@ -244,16 +244,17 @@ def argsort_rows(keys: torch.Tensor, descending: bool = False, unsigned: bool = 
 _seg_cache: dict = {}
 
 
-def _seg_sorter(device: torch.device, n: int, num_segments: int, key_type: int, order: int, value_bytes: int) -> SegmentedSort:
-    """One cached handle per (device, stream, type, order, value width); re-created when keys or segments outgrow it."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+def _seg_sorter(device: torch.device, n: int, num_segments: int, key_type: int, order: int, value_bytes: int,
+                long_route: str = "host") -> SegmentedSort:
+    """One cached handle per (device, stream, type, order, value width, long route); re-created when keys or segments outgrow it."""
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes, long_route)
     s = _seg_cache.get(key)
     if s is None or s.max_keys < n or s.max_segments < num_segments:
         if s is not None:
             s.close()
         cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
         s = SegmentedSort(cap(n), cap(num_segments), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes,
-                          device=device.index)
+                          device=device.index, long_route=long_route)
         _seg_cache[key] = s
     return s
 
@@ -297,12 +298,16 @@ def _segmented_sort16_(keys: torch.Tensor, offsets: torch.Tensor, values: torch.
 
 
 def segmented_sort_(keys: torch.Tensor, offsets: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False,
-                    unsigned: bool = False, max_segment_len: int = 0) -> None:
+                    unsigned: bool = False, max_segment_len: int = 0, long_route: str = "host") -> None:
     """Sort every segment ``keys[offsets[s]:offsets[s + 1]]`` (and carry ``values``) in place on the current stream.  ``offsets``:
     int32 tensor of ``num_segments + 1`` on the device (CSR).  ``max_segment_len``: upper bound on the segment length if the caller
-    knows one (a bound that fits the LDS classes keeps the call free of host waits); 0 = unknown.  16-bit keys (float16, bfloat16,
-    int16, uint16; ``unsigned=True`` on int16 storage selects uint16 keys) are sorted at their own width (``SegmentedSort16``), and
-    that call never waits on the host."""
+    knows one (a bound that fits the LDS classes keeps the call free of host waits); 0 = unknown.  ``long_route``: how 32-bit
+    segments longer than LDS holds are sorted: ``"host"`` (the default) waits on the host once for their list and sorts them one by
+    one, ``"device"`` sorts all of them at once in four passes and never waits on the host, with the same result.  16-bit keys
+    (float16, bfloat16, int16, uint16; ``unsigned=True`` on int16 storage selects uint16 keys) are sorted at their own width
+    (``SegmentedSort16``); that call never waits on the host anyway and ignores ``long_route``."""
+    if long_route not in ("host", "device"):
+        raise ValueError('long_route must be "host" or "device"')
     if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
         raise ValueError("keys must be a contiguous 1-D device tensor")
     if keys.dtype in _KEY16_TYPE:
@@ -323,23 +328,24 @@ def segmented_sort_(keys: torch.Tensor, offsets: torch.Tensor, values: torch.Ten
     if n == 0:
         return
     with torch.cuda.device(keys.device):
-        s = _seg_sorter(keys.device, n, offsets.numel() - 1, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb)
+        s = _seg_sorter(keys.device, n, offsets.numel() - 1, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb, long_route)
         s.sort(keys.view(torch.int32) if keys.dtype != torch.int32 else keys, offsets, values, n=n, max_segment_len=max_segment_len)
 
 
 def segmented_sort(keys: torch.Tensor, offsets: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False,
-                   unsigned: bool = False, max_segment_len: int = 0):
+                   unsigned: bool = False, max_segment_len: int = 0, long_route: str = "host"):
     """Out-of-place: returns ``sorted_keys`` or ``(sorted_keys, sorted_values)``."""
     k = keys.clone()
     v = None if values is None else values.clone()
-    segmented_sort_(k, offsets, v, descending, unsigned, max_segment_len)
+    segmented_sort_(k, offsets, v, descending, unsigned, max_segment_len, long_route)
     return k if v is None else (k, v)
 
 
 def segmented_argsort(keys: torch.Tensor, offsets: torch.Tensor, descending: bool = False, unsigned: bool = False,
-                      max_segment_len: int = 0) -> torch.Tensor:
+                      max_segment_len: int = 0, long_route: str = "host") -> torch.Tensor:
     """Stable permutation of the WHOLE array that sorts every segment: position within the segment's slice plus its start (int32;
-    identity outside the segments).  16-bit keys: the kernels make the indices inside the segments themselves."""
+    identity outside the segments).  16-bit keys: the kernels make the indices inside the segments themselves.  ``long_route``: as
+    ``segmented_sort_``."""
     idx = torch.arange(keys.numel(), dtype=torch.int32, device=keys.device)
     k = keys.clone()
     if keys.dtype in _KEY16_TYPE:
@@ -347,7 +353,7 @@ def segmented_argsort(keys: torch.Tensor, offsets: torch.Tensor, descending: boo
             raise ValueError("keys must be a contiguous 1-D device tensor")
         _segmented_sort16_(k, offsets, None, descending, unsigned, max_segment_len, positions=idx)
         return idx
-    segmented_sort_(k, offsets, idx, descending, unsigned, max_segment_len)
+    segmented_sort_(k, offsets, idx, descending, unsigned, max_segment_len, long_route)
     return idx
 
 

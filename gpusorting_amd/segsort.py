@@ -20,6 +20,14 @@ ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 KEY_UINT32, KEY_INT32, KEY_FLOAT32 = 0, 1, 2
 KEY16_TYPES = (KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16)  # 2-byte keys: the row-wise top-k only (gs_topk_select_rows_*)
 SEGSORT_CLASSES = _lib.GS_SEGSORT_CLASSES
+LONG_ROUTES = {"host": _lib.GS_SEGSORT_LONG_HOST, "device": _lib.GS_SEGSORT_LONG_DEVICE}
+_REPORT = ("route", "units", "long", "unit_cap", "forms", "status", "rank", "n")  # GS_SEGSORT_R_*
+
+
+def segsort_long_units(n: int, num_segments: int, mode: int = MODE_KEYS_ONLY, value_bytes: int = 0) -> int:
+    """``gs_segsort_long_units``: the bound on the (segment, part) units of a device-route call, the fixed grid of its passes (host
+    only; 0 for sizes or a mode / value width the sort refuses)."""
+    return int(_lib.load().gs_segsort_long_units(int(n), int(num_segments), mode, value_bytes))
 
 
 def sortable_bits(keys: np.ndarray, key_type: int = KEY_UINT32) -> np.ndarray:
@@ -74,15 +82,19 @@ def segmented_sort_reference(keys: np.ndarray, offsets: np.ndarray, values: np.n
 
 
 class SegmentedSort:
-    """One ``gs_segsort`` handle (class lists + an embedded OneSweep engine for long segments) + lazily sized alt buffers."""
+    """One ``gs_segsort`` handle (class lists + an embedded OneSweep engine for long segments) + lazily sized alt buffers.
+    ``long_route``: ``"host"`` (the default: one host wait for the list of long segments, the engine sorts them one by one) or
+    ``"device"`` (four passes over all long segments at once, no host wait: ``gs_segsort_set_long_route``)."""
 
     def __init__(self, max_keys: int, max_segments: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT32,
-                 mode: int = MODE_KEYS_ONLY, value_bytes: int = 0, device: int | None = None):
+                 mode: int = MODE_KEYS_ONLY, value_bytes: int = 0, device: int | None = None, long_route: str = "host"):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
         if key_type not in (KEY_UINT32, KEY_INT32, KEY_FLOAT32):
             raise ValueError("the segmented sort takes 32-bit keys only")
+        if long_route not in LONG_ROUTES:
+            raise ValueError('long_route must be "host" or "device"')
         self._lib = _lib.load()
         if device is not None:
             torch.cuda.set_device(device)
@@ -94,6 +106,8 @@ class SegmentedSort:
         check(self._lib.gs_segsort_create(C.byref(h), self.max_keys, self.max_segments, mode, self.value_bytes), "gs_segsort_create")
         self._h = h
         self._alt_keys = self._alt_vals = None
+        if long_route != "host":
+            self.set_long_route(long_route)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -119,13 +133,27 @@ class SegmentedSort:
         from .onesweep import OneSweep
         return OneSweep._borrow(self._lib.gs_segsort_engine(self._h), self.max_keys, self.mode, self.value_bytes, self.key_type)
 
+    @property
+    def long_route(self) -> str:
+        """The route of the long segments: ``"host"`` or ``"device"``."""
+        r = int(self._lib.gs_segsort_get_long_route(self._h))
+        return next(name for name, code in LONG_ROUTES.items() if code == r)
+
+    def set_long_route(self, long_route: str) -> None:
+        """``gs_segsort_set_long_route``, with no call in flight and not during a capture: the first switch to ``"device"`` allocates
+        that route's buffers (synchronously); they stay until ``close``."""
+        if long_route not in LONG_ROUTES:
+            raise ValueError('long_route must be "host" or "device"')
+        check(self._lib.gs_segsort_set_long_route(self._h, LONG_ROUTES[long_route]), "gs_segsort_set_long_route")
+
     def class_of(self, length: int) -> int:
         return int(self._lib.gs_segsort_class_of(int(length), self.mode, self.value_bytes))
 
     def sort(self, keys, offsets, values=None, n: int | None = None, max_segment_len: int = 0, stream=None) -> None:
         """Sort every segment of ``keys[:n]`` (and ``values[:n]``) in place on the current stream.  ``offsets``: int32 device tensor of
         ``num_segments + 1`` CSR offsets.  ``max_segment_len``: a promise (0 = unknown); non-zero and at most ``max_lds_segment`` the
-        call never waits on the host, otherwise it waits once for the list of long segments."""
+        call never waits on the host; otherwise it waits once for the list of long segments on the ``"host"`` long route and never
+        on the ``"device"`` one."""
         import torch
         from .onesweep import _require_cuda, _require_room, _stream_ptr
         _require_cuda(keys, "keys")
@@ -174,3 +202,11 @@ class SegmentedSort:
         buf = (C.c_uint32 * (SEGSORT_CLASSES + 1))()
         check(self._lib.gs_segsort_last_classes(self._h, buf, SEGSORT_CLASSES + 1, _stream_ptr(stream)), "gs_segsort_last_classes")
         return {"counts": [int(x) for x in buf[:SEGSORT_CLASSES]], "longest": int(buf[SEGSORT_CLASSES])}
+
+    def last(self, stream=None) -> dict:
+        """``gs_segsort_last`` (synchronises): the report words of the last call as a dict: ``route``, ``units``, ``long``,
+        ``unit_cap``, ``forms`` (``GS_SEGSORT_LF_*``), ``status``, ``rank``, ``n``."""
+        from .onesweep import _stream_ptr
+        buf = (C.c_uint32 * _lib.GS_SEGSORT_REPORT_WORDS)()
+        check(self._lib.gs_segsort_last(self._h, buf, _lib.GS_SEGSORT_REPORT_WORDS, _stream_ptr(stream)), "gs_segsort_last")
+        return {name: int(buf[i]) for i, name in enumerate(_REPORT)}

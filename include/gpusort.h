@@ -475,13 +475,16 @@ gs_status gs_debug_msd_plan_device(const uint32_t* h_table, uint32_t nbins, uint
  *   2  33 .. 256: one segment per wave, sorted in LDS
  *   3 .. 7  up to 1024 / 2048 / 8192 / 16 384 / 32 768: one segment per workgroup, sorted in LDS by the single-tile sort
  *      (class 6 not with 8-byte values, class 7 keys-only: what 160 KiB of LDS hold)
- *   8  longer than gs_segsort_max_lds_segment(): sorted one by one by the handle's own gs_onesweep engine
+ *   8  longer than gs_segsort_max_lds_segment(): sorted one by one by the handle's own gs_onesweep engine (the default), or all at
+ *      once by four passes on the device (gs_segsort_set_long_route)
  *
  * max_segment_len is a promise by the caller.  Non-zero and <= gs_segsort_max_lds_segment(): the call is asynchronous on
  * `stream`, never touches the host after its launches (it can be captured into a graph) and d_alt* may be NULL; a segment
  * that breaks the promise is left unsorted — noticed on the device — and gs_segsort_check reports GS_ERR_SIZE.  0 (unknown)
- * or larger: long segments are allowed, d_alt* (n elements each, scratch) are required, and the call WAITS ON THE HOST ONCE
- * for the list of long segments (then once per long segment for its two offsets) before it enqueues their sorts.
+ * or larger: long segments are allowed, d_alt* (n elements each, scratch) are required, and on the default long route
+ * (GS_SEGSORT_LONG_HOST) the call WAITS ON THE HOST ONCE for the list of long segments (then once per long segment for its two
+ * offsets) before it enqueues their sorts.  gs_segsort_set_long_route(h, GS_SEGSORT_LONG_DEVICE) selects a route that never waits
+ * (below).
  * One in-flight call per handle. */
 #define GS_SEGSORT_CLASSES 9
 typedef struct gs_segsort gs_segsort;
@@ -512,6 +515,63 @@ gs_status gs_segsort_last_classes(gs_segsort* h, uint32_t* counts, uint32_t word
  * the one the workgroup classes run with.  For gs_onesweep_set_rank_mode / gs_onesweep_get_rank_mode / gs_onesweep_check, with no call of
  * the handle in flight; the handle destroys it. */
 gs_onesweep* gs_segsort_engine(gs_segsort* h);
+
+/* The route of the long segments (class 8), chosen per handle; the default is GS_SEGSORT_LONG_HOST, so a handle that never switches
+ * behaves as described above.
+ *
+ * GS_SEGSORT_LONG_DEVICE: GS_SEGSORT_LONG_PASSES stable 8-bit LSD passes over ALL long segments at once, ping-pong between the caller's
+ * buffers and d_alt* (the result is back in the caller's buffers).  The (segment, part) work list — parts of GS_SEGSORT_LONG_PART
+ * elements — is built on the device, and each pass is a count, a scan and a scatter launch on fixed grids sized by
+ * gs_segsort_long_units: 1 + 3 x GS_SEGSORT_LONG_PASSES launches whatever the number of long segments.  The call NEVER waits on the
+ * host, whatever the lengths: with max_segment_len = 0 it can be captured on one linear stream and every node is a kernel launch.  No
+ * kernel waits on another workgroup.  A segment starts at any element; nothing is merged or copied afterwards.
+ *
+ * Results are those of the host route bit for bit, keys and values; max_segment_len, the promise and gs_segsort_last_classes mean what
+ * they mean there.  On this route only, after the size checks: GS_ERR_ARG if any two of d_keys, d_vals, d_alt_keys, d_alt_vals (n
+ * elements each) overlap.  gs_segsort_check: GS_ERR_ARG (bad offsets), then GS_ERR_HIP if a long segment's counts did not add up (the
+ * scatters then wrote nothing), then GS_ERR_SIZE, then what it reports on the host route.
+ *
+ * It moves about 4 x (4 count + 4 read + 4 write) bytes per key where the engine's two-level plan moves 28: the host route stays the
+ * better one for a handful of huge segments (DESIGN.md 3.16 has the measured table). */
+#define GS_SEGSORT_LONG_HOST 0u   /* default: one host wait + one per long segment, the embedded engine sorts each */
+#define GS_SEGSORT_LONG_DEVICE 1u /* GS_SEGSORT_LONG_PASSES stable 8-bit LSD passes over ALL long segments at once, no host wait */
+#define GS_SEGSORT_LONG_PASSES 4u
+#define GS_SEGSORT_LONG_PART (4u * GS_SORT_ROWS_TILE) /* elements of a part of a long segment: 4 tiles (measured against 8 and 16) */
+/* With no call of the handle in flight and not while a stream is capturing.  The first switch to GS_SEGSORT_LONG_DEVICE allocates
+ * gs_segsort_long_temp_bytes(max_keys, max_segments, mode, value_bytes) of device memory, synchronously; the buffers are neither moved
+ * nor freed before gs_segsort_destroy (a captured graph stays valid), and switching back keeps them.  GS_ERR_ARG: null handle or
+ * unknown route.  GS_ERR_MODE: GS_SEGSORT_LONG_DEVICE on a build flavour without the pass kernels (the tuning and fault-injection
+ * libraries).  GS_ERR_HIP: the allocation failed; the route stays GS_SEGSORT_LONG_HOST. */
+gs_status gs_segsort_set_long_route(gs_segsort* h, uint32_t route);
+/* GS_SEGSORT_LONG_*; 0xffffffff for a null handle. */
+uint32_t gs_segsort_get_long_route(gs_segsort* h);
+/* Host only: the bound on the (segment, part) units of a device-route call, the fixed grid of its count and scatter launches.  With
+ * L = gs_segsort_max_lds_segment(mode, value_bytes), n / GS_SEGSORT_LONG_PART + min(num_segments, n / (L + 1)) — a segment of length len
+ * has at most len / GS_SEGSORT_LONG_PART + 1 parts, and at most n / (L + 1) segments are long.  0 for the arguments gs_segsort16_units
+ * refuses. */
+uint32_t gs_segsort_long_units(uint32_t n, uint32_t num_segments, gs_mode mode, uint32_t value_bytes);
+/* Host only.  With U = gs_segsort_long_units(max_keys, max_segments, ..) and G = min(max_segments, max_keys / (L + 1)): the unit
+ * descriptors (16 x U), the long-segment records (16 x G), the table and the bases (U x 256 words each), each rounded up to 256 bytes.
+ * 0 for arguments gs_segsort_long_units refuses. */
+size_t gs_segsort_long_temp_bytes(uint32_t max_keys, uint32_t max_segments, gs_mode mode, uint32_t value_bytes);
+/* gs_segsort_last: report[GS_SEGSORT_R_*].  On the host route every word but R_ROUTE, R_LONG, R_STATUS, R_RANK and R_N is 0. */
+#define GS_SEGSORT_R_ROUTE 0     /* the long route the last call was set to */
+#define GS_SEGSORT_R_UNITS 1     /* (segment, part) units claimed on the device */
+#define GS_SEGSORT_R_LONG 2      /* long segments counted on the device */
+#define GS_SEGSORT_R_UNIT_CAP 3  /* gs_segsort_long_units of the call: the fixed grid (0: the long launches were skipped) */
+#define GS_SEGSORT_R_FORMS 4     /* GS_SEGSORT_LF_*: the kernel forms of the long route the call launched */
+#define GS_SEGSORT_R_STATUS 5    /* the device status: bit 0 bad offsets, bit 1 a promise broken; bit 8: a long segment's counts did not add up */
+#define GS_SEGSORT_R_RANK 6      /* the embedded engine's rank mode */
+#define GS_SEGSORT_R_N 7
+#define GS_SEGSORT_REPORT_WORDS 8
+/* v: 0 keys only, 1 4-byte values, 2 8-byte values */
+#define GS_SEGSORT_LF_UNITS 1u
+#define GS_SEGSORT_LF_COUNT 2u
+#define GS_SEGSORT_LF_SCAN 4u
+#define GS_SEGSORT_LF_SCATTER 8u /* << (2 x v + rank mode): bits 3 .. 8 */
+#define GS_SEGSORT_LF_ALL 0x1ffu
+/* Synchronous diagnostics of the last call: report[GS_SEGSORT_R_*], words >= GS_SEGSORT_REPORT_WORDS. */
+gs_status gs_segsort_last(gs_segsort* h, uint32_t* report, uint32_t words, void* stream);
 
 /* ---- top-k selection: the first k elements of the sorted order without sorting the rest --------------------
  * No counterpart in the reference project.
