@@ -69,6 +69,19 @@ GS_SEGSORT_REPORT_WORDS = 8
 GS_SEGSORT_LF_UNITS, GS_SEGSORT_LF_COUNT, GS_SEGSORT_LF_SCAN, GS_SEGSORT_LF_SCATTER = 1, 2, 4, 8
 GS_SEGSORT_LF_ALL = 0x1FF
 
+# gs_segtopk_last: the report words and the kernel-form bits
+GS_SEGTOPK_R_CLASSES = 0
+(GS_SEGTOPK_R_LONGEST, GS_SEGTOPK_R_STATUS, GS_SEGTOPK_R_READS, GS_SEGTOPK_R_FORMS, GS_SEGTOPK_R_RANK, GS_SEGTOPK_R_K,
+ GS_SEGTOPK_R_PACKED) = range(9, 16)
+GS_SEGTOPK_REPORT_WORDS = 16
+GS_SEGTOPK_F_PACKED, GS_SEGTOPK_F_WAVE, GS_SEGTOPK_F_STREAM, GS_SEGTOPK_F_VM = 1, 2, 4, 0x10000
+
+
+def GS_SEGTOPK_F_TILE(cls: int, rank: int) -> int:
+    """The bit of a tile-class kernel (class 3 .. 7, rank mode 0 / 1) in report[GS_SEGTOPK_R_FORMS] (the macro of include/gpusort.h)."""
+    return 8 << ((cls - 3) + 5 * rank)
+
+
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
 GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
@@ -292,6 +305,15 @@ _PROTOS = [
     ("gs_segsort16_last", _int, [_vp, _u32p, _u32, _vp]),
     ("gs_segsort16_set_rank_mode", _int, [_vp, _int]),
     ("gs_segsort16_get_rank_mode", _int, [_vp]),
+    ("gs_segtopk_create", _int, [C.POINTER(_vp), _u32, _u32, _u32, _int, _u32]),
+    ("gs_segtopk_destroy", _int, [_vp]),
+    ("gs_segtopk_temp_bytes", C.c_size_t, [_u32]),
+    ("gs_segtopk_select_keys", _int, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _int, _int, _vp]),
+    ("gs_segtopk_select_pairs", _int, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _int, _int, _vp]),
+    ("gs_segtopk_check", _int, [_vp, _vp]),
+    ("gs_segtopk_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_segtopk_set_rank_mode", _int, [_vp, _int]),
+    ("gs_segtopk_get_rank_mode", _int, [_vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

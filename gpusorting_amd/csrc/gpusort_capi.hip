@@ -19,6 +19,7 @@
 #include "topk_kernels.hpp"
 #include "topk_rows_kernels.hpp"
 #include "topk_rows16_kernels.hpp"
+#include "topk_seg_kernels.hpp"
 #include "sort16_kernels.hpp"
 #include "sortrows_kernels.hpp"
 #include "sortrows16_kernels.hpp"
@@ -35,4 +36,5 @@
 #include "sortrows_host.hpp"    // gs_sort_rows: every row of a matrix sorted in one call
 #include "sortrows16_host.hpp"  // gs_sort_rows16: the same on 16-bit keys
 #include "segsort16_host.hpp"   // gs_segsort16: the segmented sort on 16-bit keys
+#include "topk_seg_host.hpp"    // gs_segtopk: the first k of every segment
 #include "gpusort_mgpu.hpp"     // gs_mgpu, gs_onesweep_sort_sharded

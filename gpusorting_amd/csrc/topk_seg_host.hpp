@@ -1,0 +1,203 @@
+// topk_seg_host.hpp — part of the gpusort_capi.hip translation unit: the gs_segtopk handle (topk_seg_kernels.hpp) and its entries.
+// No counterpart in the reference project.
+struct gs_segtopk {
+    uint32_t max_keys, max_segments, max_k;
+    gs_mode mode;
+    uint32_t value_bytes;
+    int rank_mode;               // the ranking of the tile classes: 0 ballot multi-split, 1 returning LDS atomic (probed at create)
+    uint32_t* ctl = nullptr;     // gs::SEGC_WORDS control words, then the class lists (max_segments words)
+    uint32_t* pinned = nullptr;  // read-back of the control block
+    // the last call (gs_segtopk_last)
+    uint32_t last_forms = 0, last_k = 0;
+};
+
+static_assert(GS_SEGTOPK_R_CLASSES + GS_SEGSORT_CLASSES <= GS_SEGTOPK_R_LONGEST && GS_SEGTOPK_REPORT_WORDS >= 16, "the report holds every class");
+namespace {
+inline size_t segtopk_bytes(uint32_t max_segments) { return (((size_t)gs::SEGC_WORDS + max_segments) * sizeof(uint32_t) + 255u) & ~(size_t)255u; }
+
+// the kernels are launched directly (no registry family; gs_segtopk_last's forms word accounts for them)
+using TksLauncher = void (*)(hipStream_t, uint32_t grid, const gs::TksArgs& a, uint32_t cls);
+template <int VM>
+void launch_tks_packed(hipStream_t s, uint32_t grid, const gs::TksArgs& a, uint32_t) {
+    hipLaunchKernelGGL((gs::tks_packed_kernel<VM>), dim3(grid), dim3(64), 0, s, a);
+}
+template <int VM>
+void launch_tks_wave(hipStream_t s, uint32_t grid, const gs::TksArgs& a, uint32_t) {
+    hipLaunchKernelGGL((gs::tks_wave_kernel<VM>), dim3(grid), dim3(64 * gs::TKR_WAVE_ROWS), 0, s, a);
+}
+template <int VM>
+void launch_tks_stream(hipStream_t s, uint32_t grid, const gs::TksArgs& a, uint32_t) {
+    hipLaunchKernelGGL((gs::tks_stream_kernel<VM, 0>), dim3(grid), dim3(gs::TKR_THREADS), 0, s, a);  // (RANK 0, as the row-wise stream kernel)
+}
+template <int T, int K, int VM, int RANK>
+void launch_tks_tile(hipStream_t s, uint32_t grid, const gs::TksArgs& a, uint32_t cls) {
+    hipLaunchKernelGGL((gs::tks_tile_kernel<T, K, VM, RANK, SEG_WG_LOOP(T, K)>), dim3(grid), dim3(T), 0, s, a, cls);
+}
+struct TksVmLaunchers { TksLauncher packed, wave, stream; };
+constexpr auto g_tks_vm = Table<4>::make([](auto v) -> TksVmLaunchers {  // [vm index]
+    if constexpr (TK_BUILT) return TksVmLaunchers{launch_tks_packed<VM_OF[v]>, launch_tks_wave<VM_OF[v]>, launch_tks_stream<VM_OF[v]>};
+    else return TksVmLaunchers{nullptr, nullptr, nullptr};
+});
+using TksTileTable = Table<5, 2, 4>;  // [workgroup class][rank mode][vm index]: the cells of the row-wise tile kernel (class 6 no 8-byte values, class 7 keys only)
+constexpr auto g_tks_tile = TksTileTable::make([](auto c, auto r, auto v) -> TksLauncher {
+    if constexpr (tkr_tile_built(c, VM_OF[v])) return launch_tks_tile<g_small_class[c].threads, g_small_class[c].kpt, VM_OF[v], r>;
+    else return nullptr;
+});
+
+gs_status segtopk_read_ctl(gs_segtopk* h, hipStream_t s) {
+    GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, gs::SEGC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GS_HIP(hipStreamSynchronize(s));
+    return GS_OK;
+}
+
+gs_status segtopk_impl(gs_segtopk* h, const void* d_keys, const void* d_vals, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments, uint32_t k,
+                       uint32_t max_len, void* d_out_keys, void* d_out_vals, gs_key_type kt, gs_order order, hipStream_t s, bool pairs) {
+    if (!h || !d_keys || !d_out_keys || !d_offsets || misaligned(d_keys) || misaligned(d_out_keys) || (reinterpret_cast<uintptr_t>(d_offsets) & 3u) ||
+        !is_key32_type(kt) || !valid_order(order))
+        return GS_ERR_ARG;  // (64-bit and 16-bit key types: out of scope)
+    if (pairs != (h->mode == GS_MODE_PAIRS)) return GS_ERR_MODE;
+    const uint32_t vb = h->value_bytes;
+    const bool pos = pairs && !d_vals;  // the value is the element's position in the whole array
+    if (pairs && (!d_out_vals || misaligned(d_out_vals) || (pos ? vb != 4u : misaligned(d_vals)))) return GS_ERR_ARG;
+    if (n == 0 || n > h->max_keys || num_segments == 0 || num_segments > h->max_segments || k == 0 || k > h->max_k) return GS_ERR_SIZE;
+    const unsigned long long out_elems = (unsigned long long)num_segments * k;
+    const size_t off_bytes = ((size_t)num_segments + 1u) * 4u;
+    if (buffers_overlap(d_keys, (size_t)n * 4u, d_out_keys, (size_t)out_elems * 4u) || buffers_overlap(d_offsets, off_bytes, d_out_keys, (size_t)out_elems * 4u) ||
+        (pairs && (buffers_overlap(d_offsets, off_bytes, d_out_vals, (size_t)out_elems * vb) || buffers_overlap(d_keys, (size_t)n * 4u, d_out_vals, (size_t)out_elems * vb) ||
+                   buffers_overlap(d_out_keys, (size_t)out_elems * 4u, d_out_vals, (size_t)out_elems * vb) ||
+                   (!pos && (buffers_overlap(d_vals, (size_t)n * vb, d_out_vals, (size_t)out_elems * vb) || buffers_overlap(d_vals, (size_t)n * vb, d_out_keys, (size_t)out_elems * 4u))))))
+        return GS_ERR_ARG;
+    // lengths are known on the device only: a k the stream route does not take needs the promise that no segment goes there
+    const bool allow_long = max_len == 0u || max_len > gs::seg_max_lds(vb);
+    if (allow_long && k > gs::TKR_STAGE) return GS_ERR_SIZE;
+    if (!TK_BUILT) return GS_ERR_MODE;  // this build flavour has no selection
+    const uint32_t top = allow_long ? gs::SEG_CLASS_LONG : gs::seg_class_of(max_len, vb);  // the highest class a segment can fall in
+    uint32_t* list = h->ctl + gs::SEGC_WORDS;
+    const gs::TksArgs a{static_cast<const uint32_t*>(d_keys), d_vals, static_cast<uint32_t*>(d_out_keys), d_out_vals, d_offsets, list, h->ctl,
+                        num_segments, k, (uint32_t)kt, order == GS_ORDER_DESCENDING ? 1u : 0u, max_len};
+    const uint32_t vm = !pairs ? 0u : pos ? 1u : vb, vi = (uint32_t)vm_index(vm), rank = h->rank_mode ? 1u : 0u;
+    const TksVmLaunchers& f = g_tks_vm[vi];
+    uint32_t forms = GS_SEGTOPK_F_VM << vi;
+    h->last_k = k;
+    h->last_forms = 0;
+    hipLaunchKernelGGL(gs::seg_reset_kernel, dim3(1), dim3(64), 0, s, h->ctl);
+    const uint32_t seg_blocks = div_up(num_segments, 256);
+    hipLaunchKernelGGL(gs::seg_classify_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, n, vb, max_len, h->ctl);
+    if (top >= 2) hipLaunchKernelGGL(gs::seg_fill_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, vb, max_len, h->ctl, list);
+    f.packed(s, div_up(num_segments, 64), a, 0);
+    forms |= GS_SEGTOPK_F_PACKED;
+    // a class whose shortest segment has m elements holds at most n / m segments
+    auto bound = [&](uint32_t min_len) { const uint32_t b = n / min_len; return b < num_segments ? b : num_segments; };
+    if (top >= 2 && n > gs::SEG_PACK_MAX) {
+        const uint32_t vbs = vm == 0 ? 0u : vm == 8 ? 8u : 4u;
+        f.wave(s, seg_grid(div_up(bound(gs::SEG_PACK_MAX + 1), gs::TKR_WAVE_ROWS), gs::TKR_WAVE_ROWS, (size_t)gs::TKR_WAVE_ROWS * gs::SEG_WAVE_MAX * (8 + vbs)), a, 0);
+        forms |= GS_SEGTOPK_F_WAVE;
+    }
+    for (uint32_t c = 3; c <= 7 && c <= top; ++c) {
+        const uint32_t min_len = gs::SEG_CLASS_MAX[c - 1] + 1;
+        if (n < min_len || gs::SEG_CLASS_MAX[c] > gs::seg_max_lds(vb)) continue;
+        const Shape sh = g_small_class[c - 3];
+        const TksLauncher tile = g_tks_tile[TksTileTable::index({(int)c - 3, (int)rank, (int)vi})];
+        if (!tile) return GS_ERR_MODE;
+        const size_t lds = (size_t)sh.threads * sh.kpt * (4 + (vm == 0 ? 0u : vm == 8 ? 8u : 4u)) + (size_t)sh.threads / 64 * gs::RADIX * 4 + 64;
+        tile(s, SEG_WG_LOOP(sh.threads, sh.kpt) ? seg_grid(bound(min_len), (uint32_t)sh.threads / 64, lds) : bound(min_len), a, c);
+        forms |= GS_SEGTOPK_F_TILE(c, rank);
+    }
+    if (allow_long && n > gs::seg_max_lds(vb)) {
+        f.stream(s, seg_grid(bound(gs::seg_max_lds(vb) + 1), gs::TKR_THREADS / 64, 97u * 1024u), a, 0);  // (the histogram, the staging, the staged sort's tables: 96.6 KiB)
+        forms |= GS_SEGTOPK_F_STREAM;
+    }
+    GS_HIP(hipGetLastError());
+    h->last_forms = forms;
+    return GS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t gs_segtopk_temp_bytes(uint32_t max_segments) { return segtopk_bytes(max_segments); }
+
+gs_status gs_segtopk_create(gs_segtopk** out, uint32_t max_keys, uint32_t max_segments, uint32_t max_k, gs_mode mode, uint32_t value_bytes) {
+    if (!out) return GS_ERR_ARG;
+    *out = nullptr;
+    if (max_keys == 0 || max_keys > GS_MAX_KEYS || max_segments == 0 || max_segments > GS_MAX_KEYS || max_k == 0 || max_k > GS_MAX_KEYS) return GS_ERR_SIZE;
+    if (!mode_value_ok(mode, value_bytes)) return GS_ERR_MODE;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return GS_ERR_NO_DEVICE;
+    gs_segtopk* h = new (std::nothrow) gs_segtopk();
+    if (!h) return GS_ERR_ARG;
+    h->max_keys = max_keys;
+    h->max_segments = max_segments;
+    h->max_k = max_k;
+    h->mode = mode;
+    h->value_bytes = value_bytes;
+    h->rank_mode = lds_atomic_order_ok() ? 1 : 0;  // the probe of gs_onesweep_create, once per device
+    hipError_t e = hipMalloc(&h->ctl, segtopk_bytes(max_segments));
+    if (e == hipSuccess) e = hipMemset(h->ctl, 0, gs::SEGC_WORDS * sizeof(uint32_t));  // gs_segtopk_check may run before any call
+    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, gs::SEGC_WORDS * sizeof(uint32_t), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        g_last_hip_error = (int)e;
+        (void)gs_segtopk_destroy(h);
+        return GS_ERR_HIP;
+    }
+    *out = h;
+    return GS_OK;
+}
+
+gs_status gs_segtopk_destroy(gs_segtopk* h) {
+    if (!h) return GS_ERR_ARG;
+    if (h->pinned) (void)hipHostFree(h->pinned);
+    if (h->ctl) (void)hipFree(h->ctl);
+    delete h;
+    return GS_OK;
+}
+
+gs_status gs_segtopk_select_keys(gs_segtopk* h, const void* d_keys, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments, uint32_t k,
+                                 uint32_t max_segment_len, void* d_out_keys, gs_key_type key_type, gs_order order, void* stream) {
+    return segtopk_impl(h, d_keys, nullptr, n, d_offsets, num_segments, k, max_segment_len, d_out_keys, nullptr, key_type, order,
+                        static_cast<hipStream_t>(stream), false);
+}
+
+gs_status gs_segtopk_select_pairs(gs_segtopk* h, const void* d_keys, const void* d_vals, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments,
+                                  uint32_t k, uint32_t max_segment_len, void* d_out_keys, void* d_out_vals, gs_key_type key_type, gs_order order,
+                                  void* stream) {
+    return segtopk_impl(h, d_keys, d_vals, n, d_offsets, num_segments, k, max_segment_len, d_out_keys, d_out_vals, key_type, order,
+                        static_cast<hipStream_t>(stream), true);
+}
+
+gs_status gs_segtopk_check(gs_segtopk* h, void* stream) {
+    if (!h) return GS_ERR_ARG;
+    const gs_status rd = segtopk_read_ctl(h, static_cast<hipStream_t>(stream));
+    if (rd != GS_OK) return rd;
+    const uint32_t st = h->pinned[gs::SEGC_STATUS];
+    if (st & gs::SEG_ST_ARG) return GS_ERR_ARG;
+    if (h->pinned[gs::TKSC_TKR + gs::TKC_STATUS] & gs::TK_ST_INTERNAL) return GS_ERR_HIP;
+    if (st & gs::SEG_ST_SIZE) return GS_ERR_SIZE;
+    return GS_OK;
+}
+
+gs_status gs_segtopk_last(gs_segtopk* h, uint32_t* report, uint32_t words, void* stream) {
+    if (!h || !report || words < GS_SEGTOPK_REPORT_WORDS) return GS_ERR_ARG;
+    const gs_status rd = segtopk_read_ctl(h, static_cast<hipStream_t>(stream));
+    if (rd != GS_OK) return rd;
+    for (uint32_t i = 0; i < GS_SEGTOPK_REPORT_WORDS; ++i) report[i] = 0;
+    for (uint32_t c = 0; c < GS_SEGSORT_CLASSES; ++c) report[GS_SEGTOPK_R_CLASSES + c] = h->pinned[gs::SEGC_COUNT + c];
+    report[GS_SEGTOPK_R_LONGEST] = h->pinned[gs::SEGC_MAXLEN];
+    report[GS_SEGTOPK_R_STATUS] = h->pinned[gs::SEGC_STATUS] | ((h->pinned[gs::TKSC_TKR + gs::TKC_STATUS] & gs::TK_ST_INTERNAL) ? 256u : 0u);
+    report[GS_SEGTOPK_R_READS] = h->pinned[gs::TKSC_TKR + gs::TKR_CTL_READS];
+    report[GS_SEGTOPK_R_FORMS] = h->last_forms;
+    report[GS_SEGTOPK_R_RANK] = (uint32_t)h->rank_mode;
+    report[GS_SEGTOPK_R_K] = h->last_k;
+    report[GS_SEGTOPK_R_PACKED] = h->pinned[gs::TKSC_PACKED];
+    return GS_OK;
+}
+
+gs_status gs_segtopk_set_rank_mode(gs_segtopk* h, int mode) {
+    if (!h || (mode != 0 && mode != 1)) return GS_ERR_ARG;
+    h->rank_mode = mode;
+    return GS_OK;
+}
+
+int gs_segtopk_get_rank_mode(gs_segtopk* h) { return h ? h->rank_mode : -1; }
+
+}  // extern "C"

@@ -21,6 +21,7 @@ from .segsort import SegmentedSort, segmented_sort_reference  # noqa: F401
 from .segsort16 import SegmentedSort16, segmented_sort16_reference  # noqa: F401
 from .rowsort import RowSort, sort_rows_reference  # noqa: F401
 from .rowsort16 import RowSort16, sort_rows16_reference  # noqa: F401
+from .segtopk import SegmentedTopK, segmented_topk_reference  # noqa: F401
 from .sort16 import Sort16, sort16_reference  # noqa: F401
 from .topk import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, TopK, rows_max_k, topk_reference, topk_rows_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
@@ -449,3 +450,65 @@ def _topk_rows(keys: torch.Tensor, k: int, largest: bool, values: torch.Tensor |
         s = _topk_handle(keys.device, (rows - 1) * stride + row_len, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
         s.select_rows(keys, rows, row_len, stride, k, out_k, values, out_v)
     return out_k, out_v
+
+
+# ---- segmented top-k ----------------------------------------------------------------------------------------------------------
+_segtopk_cache: dict = {}
+
+
+def _segtopk_handle(device: torch.device, n: int, num_segments: int, k: int, key_type: int, order: int, value_bytes: int) -> SegmentedTopK:
+    """One cached handle per (device, stream, type, order, value width); re-created when n, the segments or k outgrow it."""
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+    s = _segtopk_cache.get(key)
+    if s is None or s.max_keys < n or s.max_segments < num_segments or s.max_k < k:
+        if s is not None:
+            s.close()
+        cap = lambda x, low: min(1 << max(int(x - 1).bit_length(), low), (1 << 30) - 1)  # noqa: E731
+        s = SegmentedTopK(cap(n, 16), cap(num_segments, 16), cap(k, 6), order, key_type, MODE_PAIRS, value_bytes, device=device.index)
+        _segtopk_cache[key] = s
+    return s
+
+
+def segmented_topk(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor | None = None,
+                   unsigned: bool = False, max_segment_len: int = 0):
+    """The ``k`` largest (``largest=True``) or smallest elements of every segment ``keys[offsets[s]:offsets[s + 1]]`` in sorted order,
+    in one call that never waits on the host: returns ``(keys_k [S, k], indices_k [S, k], counts [S])`` (int32 positions in the whole
+    array, as ``segmented_argsort``) or, with ``values``, ``(keys_k, values_k, counts)``.  ``counts[s] = min(k, length of segment s)``
+    (int32): row ``s`` holds that many results; the slots behind them hold zero keys, ``-1`` positions and zero values.  ``offsets``:
+    int32 tensor of ``num_segments + 1`` on the device (CSR).  ``max_segment_len``: an upper bound on the segment length if the caller
+    knows one, 0 = unknown; a segment longer than LDS holds takes ``k <= rows_max_k`` (4096), so a larger ``k`` needs a bound that
+    fits LDS (``ValueError`` otherwise).  The result is the head of ``segmented_sort``: floats by the order-preserving bit flip, ties
+    by position (smallest: lowest positions first; largest: highest positions first).  The inputs are not written."""
+    if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+    if keys.dtype not in _KEY_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
+    _require_offsets(keys, offsets)
+    n, k, segs = keys.numel(), int(k), offsets.numel() - 1
+    if k < 1:
+        raise ValueError("k >= 1")
+    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    vb = 4
+    if values is not None:
+        if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:
+            raise ValueError("values must match keys in shape and device and be contiguous")
+        vb = values.element_size()
+        if vb not in (4, 8):
+            raise TypeError("values must be 4 or 8 bytes wide")
+    max_segment_len = int(max_segment_len)
+    lds_len, max_k = _lib.load().gs_segsort_max_lds_segment(MODE_PAIRS, vb), rows_max_k(MODE_PAIRS, vb)
+    if k > max_k and not 0 < max_segment_len <= lds_len:
+        # GS_ERR_SIZE of gs_segtopk_select_*, stated here: lengths are known on the device only
+        raise ValueError(f"k = {k} is above {max_k}: it needs max_segment_len <= {lds_len} (with {vb}-byte values), got {max_segment_len}")
+    out_k = torch.zeros((segs, k), dtype=keys.dtype, device=keys.device)
+    if values is None:
+        out_v = torch.full((segs, k), -1, dtype=torch.int32, device=keys.device)
+    else:
+        out_v = torch.zeros((segs, k), dtype=values.dtype, device=keys.device)
+    counts = torch.diff(offsets.view(torch.int32)).clamp(max=k)
+    if n == 0:
+        return out_k, out_v, counts
+    with torch.cuda.device(keys.device):
+        s = _segtopk_handle(keys.device, n, segs, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
+        s.select(keys, offsets, k, out_k, values, out_v, n=n, max_segment_len=max_segment_len)
+    return out_k, out_v, counts

@@ -1034,6 +1034,81 @@ gs_status gs_segsort16_last(gs_segsort16* h, uint32_t* report, uint32_t words, v
 gs_status gs_segsort16_set_rank_mode(gs_segsort16* h, int mode);
 int gs_segsort16_get_rank_mode(gs_segsort16* h);
 
+/* ---- segmented top-k: the first k of every segment of one array in one call -------------------------------------------------------
+ * No counterpart in the reference project.  Segment s is keys[off[s] .. off[s + 1]) (CSR offsets d_offsets[0 .. num_segments], as
+ * gs_segsort_*; elements outside [off[0], off[num_segments]) belong to no segment).  With m_s = min(k, len_s), output row s is
+ * out[s * k .. s * k + m_s): bit for bit the first m_s elements that gs_segsort_sort_keys / _sort_pairs would leave in that segment —
+ * for len_s >= k what gs_topk_select_keys / _pairs delivers for that slice.  Sorted, floats by the order-preserving bit flip, ties by
+ * position (ascending the lowest positions, in rising position; descending the exact reverse of the stable ascending result), values
+ * bit-copied.  The output is dense, [num_segments, k] with row stride k.  Slots m_s .. k of a short or empty segment's row are NOT
+ * WRITTEN; nothing behind element num_segments * k is touched; the inputs are not written.
+ *
+ * d_vals == NULL on a handle with 4-byte values: the value is the element's position in the WHOLE ARRAY, off[s] plus the position in
+ * the segment (the convention of the segmented argsort).  The kernels produce it themselves: no n-sized index array exists.
+ *
+ * Key types: GS_KEY_UINT32 / INT32 / FLOAT32; the 64-bit and 16-bit ones return GS_ERR_ARG.
+ *
+ * The offsets are validated on the device before anything is loaded through them (non-decreasing, last <= n); with bad offsets no
+ * output is written and gs_segtopk_check reports GS_ERR_ARG.  max_segment_len is the promise of gs_segsort_*: 0 = unknown; a segment
+ * longer than a non-zero promise gets no output row — noticed on the device — and gs_segtopk_check reports GS_ERR_SIZE.
+ *
+ * THE CALL NEVER WAITS ON THE HOST, whatever the lengths and whatever max_segment_len is: every launch is enqueued up front on fixed
+ * grids (reset, classify, fill, then one kernel per length class that can occur), no kernel waits on another workgroup, nothing is
+ * allocated after create, and a call can be captured on one linear stream with every node a kernel launch.
+ * Kernels by segment length (the classes of gs_segsort_class_of):
+ *   1 .. 32      packed: 64 consecutive segments per wave, a counting rank inside the segment (length 1 is emitted here)
+ *   33 .. 256    one wave per segment, the segment sorted in LDS, its head written
+ *   classes 3 .. 7, up to gs_segsort_max_lds_segment(): one workgroup per segment, the single-tile sort, its head written; every k
+ *   longer       one workgroup per segment, the radix select of GS_TOPK_ROWS_ROUTE_STREAM: k <= gs_topk_rows_max_k (4096)
+ * Lengths are known on the device only, so the rule for k is one the host can check: k > gs_topk_rows_max_k is accepted only with a
+ * non-zero promise max_segment_len <= gs_segsort_max_lds_segment(mode, value_bytes); otherwise the call returns GS_ERR_SIZE before
+ * anything is launched.  There is no row-by-row route and no embedded engine.
+ *
+ * GS_ERR_ARG: null handle (before anything else is looked at), a null or not 16-byte aligned base pointer (d_offsets: 4-byte aligned),
+ * a key type other than the three above, an output ([num_segments * k] elements, computed in 64 bits) overlapping an input or the
+ * other output.  GS_ERR_MODE: a keys call on a pairs handle or the reverse; every call on the build flavours without the selection
+ * kernels (the tuning and fault-injection libraries).  GS_ERR_SIZE: n, num_segments or k zero or above the handle's maxima, and the
+ * rule for k above. */
+typedef struct gs_segtopk gs_segtopk;
+/* value_bytes 0 (keys only), 4 or 8, as gs_onesweep_create.  Synchronous (allocates gs_segtopk_temp_bytes of device memory).
+ * GS_ERR_SIZE: max_keys, max_segments or max_k zero or above GS_MAX_KEYS.  GS_ERR_MODE: mode and value_bytes do not fit. */
+gs_status gs_segtopk_create(gs_segtopk** out, uint32_t max_keys, uint32_t max_segments, uint32_t max_k, gs_mode mode, uint32_t value_bytes);
+gs_status gs_segtopk_destroy(gs_segtopk* h);
+/* Host only: the control block (64 words) and the class lists (max_segments words), 4 bytes each, rounded up to 256 bytes:
+ * ((64 + max_segments) * 4 + 255) & ~255.  Independent of max_keys and max_k: no n-sized scratch exists. */
+size_t gs_segtopk_temp_bytes(uint32_t max_segments);
+gs_status gs_segtopk_select_keys(gs_segtopk* h, const void* d_keys, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments, uint32_t k,
+                                 uint32_t max_segment_len, void* d_out_keys, gs_key_type key_type, gs_order order, void* stream);
+gs_status gs_segtopk_select_pairs(gs_segtopk* h, const void* d_keys, const void* d_vals, uint32_t n, const uint32_t* d_offsets,
+                                  uint32_t num_segments, uint32_t k, uint32_t max_segment_len, void* d_out_keys, void* d_out_vals,
+                                  gs_key_type key_type, gs_order order, void* stream);
+/* Synchronises `stream` and reports the last call: GS_OK, GS_ERR_ARG (bad offsets: nothing was written), GS_ERR_HIP (a count did not
+ * add up in a long segment — cannot happen; that row is unwritten), GS_ERR_SIZE (a segment longer than promised: that row is unwritten,
+ * every other one is right), in that order.  Every call resets the status itself. */
+gs_status gs_segtopk_check(gs_segtopk* h, void* stream);
+/* gs_segtopk_last: report[GS_SEGTOPK_R_*] */
+#define GS_SEGTOPK_R_CLASSES 0  /* [GS_SEGSORT_CLASSES] words: segments per class of gs_segsort_class_of (class 0: empty, length 1, and longer than promised) */
+#define GS_SEGTOPK_R_LONGEST 9  /* the longest segment seen */
+#define GS_SEGTOPK_R_STATUS 10  /* the device status: bit 0 bad offsets, bit 1 a promise broken; bit 8: a count did not add up */
+#define GS_SEGTOPK_R_READS 11   /* the most reads of its segment any long segment took (2 .. 4, as GS_TOPK_ROWS_R_READS); 0 without long segments */
+#define GS_SEGTOPK_R_FORMS 12   /* GS_SEGTOPK_F_*: the kernel forms the call launched */
+#define GS_SEGTOPK_R_RANK 13    /* the rank mode of the tile classes */
+#define GS_SEGTOPK_R_K 14
+#define GS_SEGTOPK_R_PACKED 15  /* segments the packed kernel emitted: those of length 1 .. 32 within the promise */
+#define GS_SEGTOPK_REPORT_WORDS 16
+/* the kernel forms of a call, one bit each */
+#define GS_SEGTOPK_F_PACKED 1u
+#define GS_SEGTOPK_F_WAVE 2u
+#define GS_SEGTOPK_F_STREAM 4u
+#define GS_SEGTOPK_F_TILE(cls, rank) (8u << (((cls) - 3u) + 5u * (rank))) /* class 3 .. 7, rank mode 0 / 1: bits 3 .. 12 */
+#define GS_SEGTOPK_F_VM 0x10000u /* << (0 keys only, 1 positions, 2 4-byte values, 3 8-byte values): the value mode every kernel of the call ran in */
+/* Synchronous diagnostics of the last call: report[GS_SEGTOPK_R_*], words >= GS_SEGTOPK_REPORT_WORDS. */
+gs_status gs_segtopk_last(gs_segtopk* h, uint32_t* report, uint32_t words, void* stream);
+/* The ranking inside a tile (classes 3 .. 7), as gs_sort16_set_rank_mode: 0 = 64-lane ballot multi-split, 1 = returning LDS atomic;
+ * probed at create.  With no call of the handle in flight.  get: -1 for a null handle. */
+gs_status gs_segtopk_set_rank_mode(gs_segtopk* h, int mode);
+int gs_segtopk_get_rank_mode(gs_segtopk* h);
+
 #ifdef __cplusplus
 }
 #endif
