@@ -2,17 +2,21 @@
 // 2-byte elements in d_keys and d_out_keys, read once at their own width instead of being widened to 32 bits by the caller.  No
 // counterpart in the reference project.
 //
-// Same selection space, same rules, same three kernels by row length as the 32-bit file; what differs:
+// Same selection space, same rules, same three kernels by row length as the 32-bit file.  The wave and the tile kernel are that
+// file's bodies (tkr_wave_row, tkr_tile_row behind tkr_matrix_wave, tkr_matrix_tile) on the key traits TkrKey16 below; what differs:
 //   - TkrArgs::keys / out_keys point at 2-byte elements (row_stride, row_len, k and positions keep counting elements; values stay
 //     4 or 8 bytes under the same index).  Rows start at 2-byte alignment only; the base pointers are 16-byte aligned.
 //   - the sortable 16 bits sit in the low half of the 32-bit word the passes rank, the high half is 0, and only the passes for
-//     shift 0 and 8 run (BITS = 16 of seg_wave_sort_passes / tkr_tile_sort_passes).  The all-one dummies of the slots >= n tie
-//     with a real key 0xFFFF on those two bytes: they stay behind it only because the passes are stable and the dummies start in
-//     the highest slots (in the RANK 1 form they take no part at all).  Whoever changes the dummies' place or the passes' stability
-//     breaks that.
+//     shift 0 and 8 run (TkrKey16::RANKED_BITS).
 //   - tkr16_stream_kernel: 16-byte loads of eight elements behind a scalar peel of up to seven; the radix select is exact after two
 //     levels (12 + 4 bits), so a row is read 2 or 3 times, never 4; a tile is 32 768 elements, and its front and equal counts, packed
 //     into 16 bits each, stay below 65 536 (asserted).
+// tkr16_stream_kernel keeps a body of its own: tkr_stream_row (topk_rows_kernels.hpp) with other constants (8 elements per load, the
+// 12 + 4 level schedule, a 16-bit flip mask, mask bits at 8 + j, 512 in the one-add shortcut).  Written as one function of key traits
+// and called from a wrapper, the select kept the 32-bit and the segmented kernels' resources but spilled one more SGPR in every
+// tkr16_stream_kernel<VM, 0> (VM 0 / 1 / 4 / 8: 100 / 102 / 106 / 106 -> 101 / 103 / 107 / 107, to VGPR lanes, everything else equal),
+// with the early-outs in a wrapper in front of the body in whatever form; DESIGN.md 3.17 has the table.  Resources were to stay what
+// they were, so a fix to the select belongs in both: there and here.
 // Every LDS and global store index is checked against its buffer's length; a count that does not add up sets TK_ST_INTERNAL.  No
 // kernel waits on another workgroup.  Registers, LDS and scratch per kernel: DESIGN.md 3.11.
 #pragma once
@@ -35,85 +39,23 @@ __device__ __forceinline__ uint32_t tkr16_from_bits(uint32_t u, uint32_t kt) {
     return kt == KEY_U16 ? u : kt == KEY_I16 ? u ^ 0x8000u : u ^ ((u & 0x8000u) ? 0x8000u : 0xffffu);
 }
 
-// element `o` of row r's head (o < k is the caller's check); bits: the low 16, whatever the high half holds
-template <int VM>
-__device__ __forceinline__ void tkr16_emit(const TkrArgs& a, uint32_t r, uint32_t o, uint32_t bits, typename TkrVal<VM>::type val) {
-    using V = typename TkrVal<VM>::type;
-    const size_t dst = (size_t)r * a.k + o;
-    reinterpret_cast<uint16_t*>(a.out_keys)[dst] = (uint16_t)tkr16_from_bits(bits, a.kt);  // (the store keeps the low half)
-    if constexpr (VM != 0) static_cast<V*>(a.out_vals)[dst] = val;
-}
+// the row bodies' key traits for 2-byte keys (TkrKey32, topk_rows_kernels.hpp)
+struct TkrKey16 {
+    using elem = uint16_t;
+    // Two passes.  The all-one dummies of the slots >= n tie with a real key 0xFFFF on those two bytes: they stay behind it only
+    // because the passes are stable and the dummies start in the highest slots (in the RANK 1 form they take no part at all).
+    // Whoever changes the dummies' place or the passes' stability breaks that.
+    static constexpr uint32_t RANKED_BITS = 16u;
+    static __device__ __forceinline__ uint32_t to_bits(uint32_t u, uint32_t kt) { return tkr16_to_bits(u, kt); }
+    static __device__ __forceinline__ uint32_t from_bits(uint32_t u, uint32_t kt) { return tkr16_from_bits(u, kt); }  // (the low 16 bits count)
+};
 
-// ---- wave kernel: row_len <= SEG_WAVE_MAX (tkr_wave_kernel on 2-byte elements, two passes) --------------------------------------
 template <int VM>
-__global__ __launch_bounds__(64 * TKR_WAVE_ROWS) void tkr16_wave_kernel(const TkrArgs a) {
-    using V = typename TkrVal<VM>::type;
-    constexpr int VB = TkrVal<VM>::VB, KPT = SEG_WAVE_MAX / 64;
-    __shared__ __attribute__((aligned(16))) uint32_t s_hist[TKR_WAVE_ROWS][RADIX];
-    __shared__ uint32_t s_stage[TKR_WAVE_ROWS][SEG_WAVE_MAX];
-    __shared__ V s_vstage[VB != 0 ? TKR_WAVE_ROWS : 1][VB != 0 ? SEG_WAVE_MAX : 1];
-    const uint16_t* keys = reinterpret_cast<const uint16_t*>(a.keys);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t r = blockIdx.x * TKR_WAVE_ROWS + wave;
-    const bool live = r < a.rows && a.row_len <= SEG_WAVE_MAX;
-    const uint32_t len = live ? a.row_len : 0u;
-    const size_t base = live ? (size_t)r * a.row_stride : 0;
-    uint32_t key[KPT];
-    V val[VB != 0 ? KPT : 1];
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-        const uint32_t idx = lane + i * 64u, ci = idx < len ? idx : (len ? len - 1u : 0u);
-        key[i] = keys[base + ci];
-        if constexpr (VM == 1) val[i] = ci;
-        else if constexpr (VM != 0) val[i] = static_cast<const V*>(a.vals)[base + ci];
-    }
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) key[i] = lane + i * 64u < len ? tkr16_to_bits(key[i], a.kt) : 0xffffffffu;
-    seg_wave_sort_passes<VB, 16u>(key, val, (len + 63u) >> 6, lane, s_hist[wave], s_stage[wave], s_vstage[VB != 0 ? wave : 0]);
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-        const uint32_t idx = lane + i * 64u;
-        if (idx < len) {
-            const uint32_t o = a.descending ? len - 1u - idx : idx;
-            if (o < a.k) tkr16_emit<VM>(a, r, o, key[i], val[VB != 0 ? i : 0]);
-        }
-    }
-}
-
-// ---- tile kernel: one workgroup per row (tkr_tile_kernel on 2-byte elements, two passes) -----------------------------------------
+__global__ __launch_bounds__(64 * TKR_WAVE_ROWS) void tkr16_wave_kernel(const TkrArgs a) { tkr_matrix_wave<TkrKey16, VM>(a); }
 template <int THREADS, int KPT, int VM, int RANK>
-__global__ __launch_bounds__(THREADS) void tkr16_tile_kernel(const TkrArgs a) {
-    using V = typename TkrVal<VM>::type;
-    constexpr int VB = TkrVal<VM>::VB;
-    const uint32_t r = blockIdx.x, n = a.row_len;
-    if (r >= a.rows || n == 0u || n > (uint32_t)(THREADS * KPT)) return;  // (uniform)
-    const uint16_t* keys = reinterpret_cast<const uint16_t*>(a.keys);
-    const size_t base = (size_t)r * a.row_stride;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t my_base = wave * (64u * KPT) + lane;
-    uint32_t key[KPT];
-    V val[VB != 0 ? KPT : 1];
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-        const uint32_t idx = my_base + i * 64u, ci = idx < n ? idx : n - 1u;
-        key[i] = keys[base + ci];
-        if constexpr (VM == 1) val[i] = ci;
-        else if constexpr (VM != 0) val[i] = static_cast<const V*>(a.vals)[base + ci];
-    }
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) key[i] = my_base + i * 64u < n ? tkr16_to_bits(key[i], a.kt) : 0xffffffffu;
-    tkr_tile_sort_passes<THREADS, KPT, VB, RANK, 16u>(key, val, n);
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-        const uint32_t idx = my_base + i * 64u;
-        if (idx < n) {
-            const uint32_t o = a.descending ? n - 1u - idx : idx;
-            if (o < a.k) tkr16_emit<VM>(a, r, o, key[i], val[VB != 0 ? i : 0]);
-        }
-    }
-}
+__global__ __launch_bounds__(THREADS) void tkr16_tile_kernel(const TkrArgs a) { tkr_matrix_tile<TkrKey16, THREADS, KPT, VM, RANK>(a); }
 
-// ---- stream kernel ----------------------------------------------------------------------------------------------------------------
+// ---- stream kernel: its own body (the header says why) ----------------------------------------------------------------------------
 // The row as the index range [lo, hi) of the 16-byte aligned pointer q (lo <= 7: the peel).  Eight elements of thread `tid` in the
 // chunk at c, two to a word, the lower index in the low half; mask: which of them lie in the row.  A chunk inside the row is one
 // 16-byte load per thread, the first and the last chunk are loaded element by element.
@@ -134,6 +76,7 @@ __device__ __forceinline__ uint4 tkr16_load_chunk(const uint16_t* q, uint32_t c,
     }
     return uint4{e[0], e[1], e[2], e[3]};
 }
+
 // element j (0 .. 7) of a loaded chunk, in the low half of the result
 __device__ __forceinline__ uint32_t tkr16_elem(const uint32_t (&w)[4], uint32_t j) { return (j & 1u) ? w[j >> 1] >> 16 : w[j >> 1] & 0xffffu; }
 
@@ -317,8 +260,8 @@ __global__ __launch_bounds__(TKR_THREADS) void tkr16_stream_kernel(const TkrArgs
     for (int i = 0; i < TKR_SORT_KPT; ++i) {
         const uint32_t idx = my_base + i * 64u;
         if (idx < k && pos[i] < a.row_len) {  // (idx < k <= G)
-            if constexpr (VM == 0 || VM == 1) tkr16_emit<VM>(a, r, idx, key[i] ^ flip, pos[i]);
-            else tkr16_emit<VM>(a, r, idx, key[i] ^ flip, static_cast<const V*>(a.vals)[row_base + pos[i]]);
+            if constexpr (VM == 0 || VM == 1) tkr_emit<TkrKey16, VM>(a, r, idx, key[i] ^ flip, pos[i]);
+            else tkr_emit<TkrKey16, VM>(a, r, idx, key[i] ^ flip, static_cast<const V*>(a.vals)[row_base + pos[i]]);
         }
     }
 }

@@ -5,7 +5,11 @@
 // Everything runs in the selection space of topk_kernels.hpp: sel = to_bits(key) ^ (descending ? ~0 : 0), both orders look for the
 // k smallest sel, ties by position (ascending: lowest positions first; descending: the exact reverse of the stable ascending
 // order).  Rows start at 4-byte alignment only (odd strides); only the base pointers are 16-byte aligned.  Three kernels by row
-// length, VM as in tk_scatter_kernel (0 keys only, 1 the value is the position in the row, 4 / 8 value bytes):
+// length, VM as in tk_scatter_kernel (0 keys only, 1 the value is the position in the row, 4 / 8 value bytes).  Each is a wrapper that
+// finds its row in the matrix and calls the one body of its shape, tkr_wave_row / tkr_tile_row / tkr_stream_row: functions of a
+// resolved row (output row, element offset, length, the position its first element counts as), which the segmented top-k
+// (topk_seg_kernels.hpp) calls on its segments.  The wave and the tile body are also functions of the key width (TkrKey32 here,
+// TkrKey16 in topk_rows16_kernels.hpp) and serve the 16-bit kernels; the 16-bit stream kernel has a body of its own (said there):
 //   tkr_wave_kernel    row_len <= 256: one wave per row, TKR_WAVE_ROWS rows per workgroup, the wave class's four ranking passes
 //                      (seg_wave_sort_passes) on the row in registers; the head is written.
 //   tkr_tile_kernel    row_len <= seg_max_lds(value bytes): one workgroup per row on the single-tile shape of the length's class
@@ -75,47 +79,62 @@ __global__ __launch_bounds__(64) void tkr_status_kernel(uint32_t* __restrict__ c
     }
 }
 
-// element `o` of row r's head (o < k is the caller's check)
-template <int VM>
+// ---- what the key width decides ------------------------------------------------------------------------------------------------
+// The wave and the tile body take one of these (the 2-byte one: TkrKey16, topk_rows16_kernels.hpp).  A key travels through the passes
+// as a 32-bit word whose low RANKED_BITS hold its sortable bits and whose other bits are 0.
+struct TkrKey32 {
+    using elem = uint32_t;                        // what keys and out_keys point at
+    static constexpr uint32_t RANKED_BITS = 32u;  // the bits seg_wave_sort_passes / tkr_tile_sort_passes rank
+    static __device__ __forceinline__ uint32_t to_bits(uint32_t u, uint32_t kt) { return seg_to_bits(u, kt); }
+    static __device__ __forceinline__ uint32_t from_bits(uint32_t u, uint32_t kt) { return seg_from_bits(u, kt); }
+};
+
+// element `o` of row r's head (o < k is the caller's check); bits: the low RANKED_BITS count
+template <class K, int VM>
 __device__ __forceinline__ void tkr_emit(const TkrArgs& a, uint32_t r, uint32_t o, uint32_t bits, typename TkrVal<VM>::type val) {
     using V = typename TkrVal<VM>::type;
+    using E = typename K::elem;
     const size_t dst = (size_t)r * a.k + o;
-    a.out_keys[dst] = seg_from_bits(bits, a.kt);
+    reinterpret_cast<E*>(a.out_keys)[dst] = (E)K::from_bits(bits, a.kt);  // (a 2-byte store keeps the low half)
     if constexpr (VM != 0) static_cast<V*>(a.out_vals)[dst] = val;
 }
 
-// ---- wave kernel: row_len <= SEG_WAVE_MAX ------------------------------------------------------------------------------------
-// Waves beyond the last row run the passes on no rows of slots: the passes' barriers are the workgroup's.
-template <int VM>
-__global__ __launch_bounds__(64 * TKR_WAVE_ROWS) void tkr_wave_kernel(const TkrArgs a) {
+// ---- the row bodies ---------------------------------------------------------------------------------------------------------------
+// Each works on a resolved row: keys[base .. base + len), its head to output row r, pos0 what the row's first element counts as in
+// the position mode (VM 1).  The row-wise kernels below and in topk_rows16_kernels.hpp find the row as r * row_stride with pos0 = 0,
+// the segmented ones (topk_seg_kernels.hpp) take it from a class list with pos0 = the segment's start.  The LDS is each body's own.
+
+// One row on the calling wave, len <= SEG_WAVE_MAX: sorted by the wave class's ranking passes in registers, the head written.  The
+// tables are the calling wave's own; the passes' barriers are the workgroup's: every wave of the workgroup calls this, and equally
+// often.  A wave without a row passes len 0: the passes run on no rows of slots and nothing is written, but the clamped loads still
+// read keys[base] (and vals[base], VM 4 / 8), so such a caller passes a readable base (both callers pass 0).
+template <class K, int VM>
+__device__ __forceinline__ void tkr_wave_row(const TkrArgs& a, uint32_t r, size_t base, uint32_t len, uint32_t pos0) {
     using V = typename TkrVal<VM>::type;
     constexpr int VB = TkrVal<VM>::VB, KPT = SEG_WAVE_MAX / 64;
     __shared__ __attribute__((aligned(16))) uint32_t s_hist[TKR_WAVE_ROWS][RADIX];
     __shared__ uint32_t s_stage[TKR_WAVE_ROWS][SEG_WAVE_MAX];
     __shared__ V s_vstage[VB != 0 ? TKR_WAVE_ROWS : 1][VB != 0 ? SEG_WAVE_MAX : 1];
+    const typename K::elem* keys = reinterpret_cast<const typename K::elem*>(a.keys);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t r = blockIdx.x * TKR_WAVE_ROWS + wave;
-    const bool live = r < a.rows && a.row_len <= SEG_WAVE_MAX;
-    const uint32_t len = live ? a.row_len : 0u;
-    const size_t base = live ? (size_t)r * a.row_stride : 0;
     uint32_t key[KPT];
     V val[VB != 0 ? KPT : 1];
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
         const uint32_t idx = lane + i * 64u, ci = idx < len ? idx : (len ? len - 1u : 0u);
-        key[i] = a.keys[base + ci];
-        if constexpr (VM == 1) val[i] = ci;
+        key[i] = keys[base + ci];
+        if constexpr (VM == 1) val[i] = pos0 + ci;
         else if constexpr (VM != 0) val[i] = static_cast<const V*>(a.vals)[base + ci];
     }
 #pragma unroll
-    for (int i = 0; i < KPT; ++i) key[i] = lane + i * 64u < len ? seg_to_bits(key[i], a.kt) : 0xffffffffu;
-    seg_wave_sort_passes<VB>(key, val, (len + 63u) >> 6, lane, s_hist[wave], s_stage[wave], s_vstage[VB != 0 ? wave : 0]);
+    for (int i = 0; i < KPT; ++i) key[i] = lane + i * 64u < len ? K::to_bits(key[i], a.kt) : 0xffffffffu;
+    seg_wave_sort_passes<VB, K::RANKED_BITS>(key, val, (len + 63u) >> 6, lane, s_hist[wave], s_stage[wave], s_vstage[VB != 0 ? wave : 0]);
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
         const uint32_t idx = lane + i * 64u;
         if (idx < len) {
             const uint32_t o = a.descending ? len - 1u - idx : idx;
-            if (o < a.k) tkr_emit<VM>(a, r, o, key[i], val[VB != 0 ? i : 0]);
+            if (o < a.k) tkr_emit<K, VM>(a, r, o, key[i], val[VB != 0 ? i : 0]);
         }
     }
 }
@@ -217,14 +236,14 @@ __device__ __forceinline__ void tkr_tile_sort_passes(uint32_t (&key)[SMALL_KPT],
     }
 }
 
-// ---- tile kernel: one workgroup per row, the single-tile sort's passes ---------------------------------------------------------
-template <int THREADS, int KPT, int VM, int RANK>
-__global__ __launch_bounds__(THREADS) void tkr_tile_kernel(const TkrArgs a) {
+// One row on the calling workgroup of THREADS threads, 1 <= n <= THREADS * KPT (the caller's check): read once into registers, the
+// single-tile sort's passes, the head written.  Called or not is uniform over the workgroup; a caller that goes on to another row
+// puts a barrier in between (the passes' LDS is read after their last barrier).
+template <class K, int THREADS, int KPT, int VM, int RANK>
+__device__ __forceinline__ void tkr_tile_row(const TkrArgs& a, uint32_t r, size_t base, uint32_t n, uint32_t pos0) {
     using V = typename TkrVal<VM>::type;
     constexpr int VB = TkrVal<VM>::VB;
-    const uint32_t r = blockIdx.x, n = a.row_len;
-    if (r >= a.rows || n == 0u || n > (uint32_t)(THREADS * KPT)) return;  // (uniform)
-    const size_t base = (size_t)r * a.row_stride;
+    const typename K::elem* keys = reinterpret_cast<const typename K::elem*>(a.keys);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t my_base = wave * (64u * KPT) + lane;
     uint32_t key[KPT];
@@ -233,24 +252,23 @@ __global__ __launch_bounds__(THREADS) void tkr_tile_kernel(const TkrArgs a) {
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
         const uint32_t idx = my_base + i * 64u, ci = idx < n ? idx : n - 1u;
-        key[i] = a.keys[base + ci];
-        if constexpr (VM == 1) val[i] = ci;
+        key[i] = keys[base + ci];
+        if constexpr (VM == 1) val[i] = pos0 + ci;
         else if constexpr (VM != 0) val[i] = static_cast<const V*>(a.vals)[base + ci];
     }
 #pragma unroll
-    for (int i = 0; i < KPT; ++i) key[i] = my_base + i * 64u < n ? seg_to_bits(key[i], a.kt) : 0xffffffffu;
-    tkr_tile_sort_passes<THREADS, KPT, VB, RANK>(key, val, n);
+    for (int i = 0; i < KPT; ++i) key[i] = my_base + i * 64u < n ? K::to_bits(key[i], a.kt) : 0xffffffffu;
+    tkr_tile_sort_passes<THREADS, KPT, VB, RANK, K::RANKED_BITS>(key, val, n);
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
         const uint32_t idx = my_base + i * 64u;
         if (idx < n) {
             const uint32_t o = a.descending ? n - 1u - idx : idx;
-            if (o < a.k) tkr_emit<VM>(a, r, o, key[i], val[VB != 0 ? i : 0]);
+            if (o < a.k) tkr_emit<K, VM>(a, r, o, key[i], val[VB != 0 ? i : 0]);
         }
     }
 }
 
-// ---- stream kernel ----------------------------------------------------------------------------------------------------------------
 // The row as the index range [lo, hi) of the 16-byte aligned pointer q (lo <= 3: the peel).  Four elements of thread `tid` in the
 // chunk at c; mask: which of them lie in the row.  A chunk inside the row is one 16-byte load per thread, the first and the last
 // chunk are loaded element by element.
@@ -272,8 +290,11 @@ __device__ __forceinline__ uint4 tkr_load_chunk(const uint32_t* q, uint32_t c, u
     return uint4{e[0], e[1], e[2], e[3]};
 }
 
+// One row on the calling workgroup of TKR_THREADS threads, 32-bit keys, k <= TKR_STAGE and k <= row_len (the caller's checks): the
+// radix select of the header, the first k to output row r.  Every return is uniform over the workgroup; a caller that goes on to
+// another row puts a barrier in between.  (tkr16_stream_kernel, topk_rows16_kernels.hpp, has its own body; its header says why.)
 template <int VM, int RANK>
-__global__ __launch_bounds__(TKR_THREADS) void tkr_stream_kernel(const TkrArgs a) {
+__device__ __forceinline__ void tkr_stream_row(const TkrArgs& a, const uint32_t r, const size_t row_base, const uint32_t row_len, const uint32_t pos0) {
     using V = typename TkrVal<VM>::type;
     constexpr uint32_t T = TKR_THREADS, W = T / 64, SLOTS = TKR_UNROLL * W;
     static_assert(SLOTS == 64, "the tile's wave totals are scanned by one wave");
@@ -282,17 +303,15 @@ __global__ __launch_bounds__(TKR_THREADS) void tkr_stream_kernel(const TkrArgs a
     __shared__ uint32_t s_skey[TKR_STAGE], s_spos[TKR_STAGE];
     __shared__ uint32_t s_w[2][SLOTS + 1];  // packed: front | equal << 16 (a tile holds 16 384 elements)
     __shared__ uint32_t s_ws[W], s_bc[4];
-    const uint32_t r = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t k = a.k, kt = a.kt, flip = a.descending ? 0xffffffffu : 0u;
-    if (r >= a.rows || k == 0u || k > TKR_STAGE || k > a.row_len) return;  // (uniform; the host's checks)
-    const size_t row_base = (size_t)r * a.row_stride;
     const uint32_t* p = a.keys + row_base;
-    const uint32_t lo = (uint32_t)((reinterpret_cast<uintptr_t>(p) >> 2) & 3u), hi = lo + a.row_len;
+    const uint32_t lo = (uint32_t)((reinterpret_cast<uintptr_t>(p) >> 2) & 3u), hi = lo + row_len;
     const uint32_t* q = p - lo;  // (the base pointer is 16-byte aligned: q never lies in front of it)
     auto fail = [&]() { if (tid == 0) atomicOr(&a.ctl[TKC_STATUS], TK_ST_INTERNAL); };
 
     // ---- narrow: pfx = the bits of P found so far, front = elements in front of it, equal = elements in it
-    uint32_t pfx = 0, front = 0, equal = a.row_len, level = 0, sh = 0;
+    uint32_t pfx = 0, front = 0, equal = row_len, level = 0, sh = 0;
     for (;; ++level) {
         sh = level == 0u ? 20u : level == 1u ? 8u : 0u;
         const uint32_t nbits = level == 2u ? 8u : 12u, above = sh + nbits;
@@ -449,11 +468,41 @@ __global__ __launch_bounds__(TKR_THREADS) void tkr_stream_kernel(const TkrArgs a
 #pragma unroll
     for (int i = 0; i < TKR_SORT_KPT; ++i) {
         const uint32_t idx = my_base + i * 64u;
-        if (idx < k && pos[i] < a.row_len) {  // (idx < k <= G)
-            if constexpr (VM == 0 || VM == 1) tkr_emit<VM>(a, r, idx, key[i] ^ flip, pos[i]);
-            else tkr_emit<VM>(a, r, idx, key[i] ^ flip, static_cast<const V*>(a.vals)[row_base + pos[i]]);
+        if (idx < k && pos[i] < row_len) {  // (idx < k <= G)
+            if constexpr (VM == 0 || VM == 1) tkr_emit<TkrKey32, VM>(a, r, idx, key[i] ^ flip, pos0 + pos[i]);
+            else tkr_emit<TkrKey32, VM>(a, r, idx, key[i] ^ flip, static_cast<const V*>(a.vals)[row_base + pos[i]]);
         }
     }
+}
+
+// ---- the row-wise kernels: the row is r * row_stride of a [rows, row_len] matrix ----------------------------------------------------
+// (the wave and the tile one as functions of the key traits: topk_rows16_kernels.hpp wraps the same two on TkrKey16)
+
+// row_len <= SEG_WAVE_MAX: one wave per row.  Waves beyond the last row run the passes on no rows of slots.
+template <class K, int VM>
+__device__ __forceinline__ void tkr_matrix_wave(const TkrArgs& a) {
+    const uint32_t r = blockIdx.x * TKR_WAVE_ROWS + (threadIdx.x >> 6);
+    const bool live = r < a.rows && a.row_len <= SEG_WAVE_MAX;
+    tkr_wave_row<K, VM>(a, r, live ? (size_t)r * a.row_stride : 0, live ? a.row_len : 0u, 0u);
+}
+// row_len <= THREADS * KPT, the single-tile shape of the length's class: one workgroup per row
+template <class K, int THREADS, int KPT, int VM, int RANK>
+__device__ __forceinline__ void tkr_matrix_tile(const TkrArgs& a) {
+    const uint32_t r = blockIdx.x, n = a.row_len;
+    if (r >= a.rows || n == 0u || n > (uint32_t)(THREADS * KPT)) return;  // (uniform)
+    tkr_tile_row<K, THREADS, KPT, VM, RANK>(a, r, (size_t)r * a.row_stride, n, 0u);
+}
+
+template <int VM>
+__global__ __launch_bounds__(64 * TKR_WAVE_ROWS) void tkr_wave_kernel(const TkrArgs a) { tkr_matrix_wave<TkrKey32, VM>(a); }
+template <int THREADS, int KPT, int VM, int RANK>
+__global__ __launch_bounds__(THREADS) void tkr_tile_kernel(const TkrArgs a) { tkr_matrix_tile<TkrKey32, THREADS, KPT, VM, RANK>(a); }
+// longer rows: one workgroup of TKR_THREADS per row
+template <int VM, int RANK>
+__global__ __launch_bounds__(TKR_THREADS) void tkr_stream_kernel(const TkrArgs a) {
+    const uint32_t r = blockIdx.x;
+    if (r >= a.rows || a.k == 0u || a.k > TKR_STAGE || a.k > a.row_len) return;  // (uniform; the host's checks)
+    tkr_stream_row<VM, RANK>(a, r, (size_t)r * a.row_stride, a.row_len, 0u);
 }
 
 }  // namespace gs
