@@ -12,8 +12,10 @@ Only the hot path of b0nes164/GPUSorting named by BASELINE.json is here:
   sort16     sort of 16-bit keys (float16, bfloat16, int16, uint16) at their own width over gs_sort16_*, and its numpy reference
   topk       top-k selection (the head of the sort without the sort) over gs_topk_*, and its numpy reference
   segtopk    segmented top-k (the first k of every CSR segment) over gs_segtopk_*, and its numpy reference
-  functional sort / sort_ / argsort / sort_rows / argsort_rows / segmented_sort / topk / segmented_topk on torch tensors (plumbing over
-             OneSweep / RowSort / RowSort16 / SegmentedSort / SegmentedSort16 / TopK / SegmentedTopK)
+  segtopk16  segmented top-k of 16-bit keys at their own width over gs_segtopk16_*
+  functional sort / sort_ / argsort / sort_rows / argsort_rows / segmented_sort / topk / segmented_topk / segmented_topk16 on torch
+             tensors (plumbing over OneSweep / RowSort / RowSort16 / SegmentedSort / SegmentedSort16 / TopK / SegmentedTopK /
+             SegmentedTopK16)
 """
 from .onesweep import (  # noqa: F401
     ENTROPY_PRESET_1, ENTROPY_PRESET_2, ENTROPY_PRESET_3, ENTROPY_PRESET_4, ENTROPY_PRESET_5,
@@ -21,11 +23,14 @@ from .onesweep import (  # noqa: F401
     GPUSortingConfig, OneSweep, OneSweepDispatcher, init_random, validate,
 )
 from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, GpuSortError  # noqa: F401
-from .functional import argsort, argsort_rows, segmented_argsort, segmented_sort, segmented_sort_, segmented_topk, sort, sort_, sort_rows, sort_rows_, topk  # noqa: F401
+from .functional import (  # noqa: F401
+    argsort, argsort_rows, segmented_argsort, segmented_sort, segmented_sort_, segmented_topk, segmented_topk16, sort, sort_, sort_rows, sort_rows_, topk,
+)
 from .rowsort import RowSort, sort_rows_plan, sort_rows_reference  # noqa: F401
 from .rowsort16 import SORT_ROWS16_FORMS, RowSort16, sort_rows16_plan, sort_rows16_reference  # noqa: F401
 from .segsort import SegmentedSort, segmented_sort_reference, segsort_long_units  # noqa: F401
 from .segsort16 import SEGSORT16_FORMS, SegmentedSort16, segmented_sort16_reference, segsort16_units  # noqa: F401
 from .segtopk import SegmentedTopK, segmented_topk_reference  # noqa: F401
+from .segtopk16 import SegmentedTopK16  # noqa: F401
 from .sort16 import Sort16, sort16_plan, sort16_reference  # noqa: F401
 from .topk import TopK, topk_reference, topk_rows_reference  # noqa: F401

@@ -314,6 +314,15 @@ _PROTOS = [
     ("gs_segtopk_last", _int, [_vp, _u32p, _u32, _vp]),
     ("gs_segtopk_set_rank_mode", _int, [_vp, _int]),
     ("gs_segtopk_get_rank_mode", _int, [_vp]),
+    ("gs_segtopk16_create", _int, [C.POINTER(_vp), _u32, _u32, _u32, _int, _u32]),
+    ("gs_segtopk16_destroy", _int, [_vp]),
+    ("gs_segtopk16_temp_bytes", C.c_size_t, [_u32]),
+    ("gs_segtopk16_select_keys", _int, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _int, _int, _vp]),
+    ("gs_segtopk16_select_pairs", _int, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _int, _int, _vp]),
+    ("gs_segtopk16_check", _int, [_vp, _vp]),
+    ("gs_segtopk16_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_segtopk16_set_rank_mode", _int, [_vp, _int]),
+    ("gs_segtopk16_get_rank_mode", _int, [_vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

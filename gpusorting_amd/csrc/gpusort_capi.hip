@@ -20,6 +20,7 @@
 #include "topk_rows_kernels.hpp"
 #include "topk_rows16_kernels.hpp"
 #include "topk_seg_kernels.hpp"
+#include "topk_seg16_kernels.hpp"
 #include "sort16_kernels.hpp"
 #include "sortrows_kernels.hpp"
 #include "sortrows16_kernels.hpp"
@@ -37,4 +38,5 @@
 #include "sortrows16_host.hpp"  // gs_sort_rows16: the same on 16-bit keys
 #include "segsort16_host.hpp"   // gs_segsort16: the segmented sort on 16-bit keys
 #include "topk_seg_host.hpp"    // gs_segtopk: the first k of every segment
+#include "topk_seg16_host.hpp"  // gs_segtopk16: the same on 16-bit keys
 #include "gpusort_mgpu.hpp"     // gs_mgpu, gs_onesweep_sort_sharded

@@ -16,7 +16,8 @@
 // and called from a wrapper, the select kept the 32-bit and the segmented kernels' resources but spilled one more SGPR in every
 // tkr16_stream_kernel<VM, 0> (VM 0 / 1 / 4 / 8: 100 / 102 / 106 / 106 -> 101 / 103 / 107 / 107, to VGPR lanes, everything else equal),
 // with the early-outs in a wrapper in front of the body in whatever form; DESIGN.md 3.17 has the table.  Resources were to stay what
-// they were, so a fix to the select belongs in both: there and here.
+// they were, so a fix to the select belongs in both: there and here — and in tks16_stream_row (topk_seg16_kernels.hpp), the copy of
+// this kernel's body that the segmented top-k runs on a list entry (the same rule decided it).
 // Every LDS and global store index is checked against its buffer's length; a count that does not add up sets TK_ST_INTERNAL.  No
 // kernel waits on another workgroup.  Registers, LDS and scratch per kernel: DESIGN.md 3.11.
 #pragma once

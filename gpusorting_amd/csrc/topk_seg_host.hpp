@@ -44,28 +44,40 @@ constexpr auto g_tks_tile = TksTileTable::make([](auto c, auto r, auto v) -> Tks
     else return nullptr;
 });
 
+// what the key width decides in a call: the element size, the accepted key types, the kernels (topk_seg16_host.hpp has the 2-byte set)
+struct TksRoutes {
+    uint32_t key_bytes;
+    const TksVmLaunchers* vm;  // [vm index]
+    const TksLauncher* tile;   // TksTileTable
+    // whether a tile shape's kernel walks its class list by grid stride on seg_grid's grid, or takes one workgroup per slot the class
+    // can have; and the same for the stream kernel
+    bool (*tile_loops)(int threads, int kpt);
+    bool stream_loops;
+};
+constexpr TksRoutes g_tks_routes32{4u, g_tks_vm.data(), g_tks_tile.data(), SEG_WG_LOOP, true};
+
 gs_status segtopk_read_ctl(gs_segtopk* h, hipStream_t s) {
     GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, gs::SEGC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     GS_HIP(hipStreamSynchronize(s));
     return GS_OK;
 }
 
-gs_status segtopk_impl(gs_segtopk* h, const void* d_keys, const void* d_vals, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments, uint32_t k,
+gs_status segtopk_impl(const TksRoutes& routes, gs_segtopk* h, const void* d_keys, const void* d_vals, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments, uint32_t k,
                        uint32_t max_len, void* d_out_keys, void* d_out_vals, gs_key_type kt, gs_order order, hipStream_t s, bool pairs) {
     if (!h || !d_keys || !d_out_keys || !d_offsets || misaligned(d_keys) || misaligned(d_out_keys) || (reinterpret_cast<uintptr_t>(d_offsets) & 3u) ||
-        !is_key32_type(kt) || !valid_order(order))
-        return GS_ERR_ARG;  // (64-bit and 16-bit key types: out of scope)
+        !(routes.key_bytes == 2u ? is_key16(kt) : is_key32_type(kt)) || !valid_order(order))
+        return GS_ERR_ARG;  // (64-bit key types: out of scope; the 16-bit ones: gs_segtopk16_*)
     if (pairs != (h->mode == GS_MODE_PAIRS)) return GS_ERR_MODE;
-    const uint32_t vb = h->value_bytes;
+    const uint32_t vb = h->value_bytes, kb = routes.key_bytes;
     const bool pos = pairs && !d_vals;  // the value is the element's position in the whole array
     if (pairs && (!d_out_vals || misaligned(d_out_vals) || (pos ? vb != 4u : misaligned(d_vals)))) return GS_ERR_ARG;
     if (n == 0 || n > h->max_keys || num_segments == 0 || num_segments > h->max_segments || k == 0 || k > h->max_k) return GS_ERR_SIZE;
     const unsigned long long out_elems = (unsigned long long)num_segments * k;
     const size_t off_bytes = ((size_t)num_segments + 1u) * 4u;
-    if (buffers_overlap(d_keys, (size_t)n * 4u, d_out_keys, (size_t)out_elems * 4u) || buffers_overlap(d_offsets, off_bytes, d_out_keys, (size_t)out_elems * 4u) ||
-        (pairs && (buffers_overlap(d_offsets, off_bytes, d_out_vals, (size_t)out_elems * vb) || buffers_overlap(d_keys, (size_t)n * 4u, d_out_vals, (size_t)out_elems * vb) ||
-                   buffers_overlap(d_out_keys, (size_t)out_elems * 4u, d_out_vals, (size_t)out_elems * vb) ||
-                   (!pos && (buffers_overlap(d_vals, (size_t)n * vb, d_out_vals, (size_t)out_elems * vb) || buffers_overlap(d_vals, (size_t)n * vb, d_out_keys, (size_t)out_elems * 4u))))))
+    if (buffers_overlap(d_keys, (size_t)n * kb, d_out_keys, (size_t)out_elems * kb) || buffers_overlap(d_offsets, off_bytes, d_out_keys, (size_t)out_elems * kb) ||
+        (pairs && (buffers_overlap(d_offsets, off_bytes, d_out_vals, (size_t)out_elems * vb) || buffers_overlap(d_keys, (size_t)n * kb, d_out_vals, (size_t)out_elems * vb) ||
+                   buffers_overlap(d_out_keys, (size_t)out_elems * kb, d_out_vals, (size_t)out_elems * vb) ||
+                   (!pos && (buffers_overlap(d_vals, (size_t)n * vb, d_out_vals, (size_t)out_elems * vb) || buffers_overlap(d_vals, (size_t)n * vb, d_out_keys, (size_t)out_elems * kb))))))
         return GS_ERR_ARG;
     // lengths are known on the device only: a k the stream route does not take needs the promise that no segment goes there
     const bool allow_long = max_len == 0u || max_len > gs::seg_max_lds(vb);
@@ -76,7 +88,7 @@ gs_status segtopk_impl(gs_segtopk* h, const void* d_keys, const void* d_vals, ui
     const gs::TksArgs a{static_cast<const uint32_t*>(d_keys), d_vals, static_cast<uint32_t*>(d_out_keys), d_out_vals, d_offsets, list, h->ctl,
                         num_segments, k, (uint32_t)kt, order == GS_ORDER_DESCENDING ? 1u : 0u, max_len};
     const uint32_t vm = !pairs ? 0u : pos ? 1u : vb, vi = (uint32_t)vm_index(vm), rank = h->rank_mode ? 1u : 0u;
-    const TksVmLaunchers& f = g_tks_vm[vi];
+    const TksVmLaunchers& f = routes.vm[vi];
     uint32_t forms = GS_SEGTOPK_F_VM << vi;
     h->last_k = k;
     h->last_forms = 0;
@@ -97,14 +109,15 @@ gs_status segtopk_impl(gs_segtopk* h, const void* d_keys, const void* d_vals, ui
         const uint32_t min_len = gs::SEG_CLASS_MAX[c - 1] + 1;
         if (n < min_len || gs::SEG_CLASS_MAX[c] > gs::seg_max_lds(vb)) continue;
         const Shape sh = g_small_class[c - 3];
-        const TksLauncher tile = g_tks_tile[TksTileTable::index({(int)c - 3, (int)rank, (int)vi})];
+        const TksLauncher tile = routes.tile[TksTileTable::index({(int)c - 3, (int)rank, (int)vi})];
         if (!tile) return GS_ERR_MODE;
         const size_t lds = (size_t)sh.threads * sh.kpt * (4 + (vm == 0 ? 0u : vm == 8 ? 8u : 4u)) + (size_t)sh.threads / 64 * gs::RADIX * 4 + 64;
-        tile(s, SEG_WG_LOOP(sh.threads, sh.kpt) ? seg_grid(bound(min_len), (uint32_t)sh.threads / 64, lds) : bound(min_len), a, c);
+        tile(s, routes.tile_loops(sh.threads, sh.kpt) ? seg_grid(bound(min_len), (uint32_t)sh.threads / 64, lds) : bound(min_len), a, c);
         forms |= GS_SEGTOPK_F_TILE(c, rank);
     }
     if (allow_long && n > gs::seg_max_lds(vb)) {
-        f.stream(s, seg_grid(bound(gs::seg_max_lds(vb) + 1), gs::TKR_THREADS / 64, 97u * 1024u), a, 0);  // (the histogram, the staging, the staged sort's tables: 96.6 KiB)
+        const uint32_t longs = bound(gs::seg_max_lds(vb) + 1);
+        f.stream(s, routes.stream_loops ? seg_grid(longs, gs::TKR_THREADS / 64, 97u * 1024u) : longs, a, 0);  // (the histogram, the staging, the staged sort's tables: 96.6 KiB)
         forms |= GS_SEGTOPK_F_STREAM;
     }
     GS_HIP(hipGetLastError());
@@ -154,14 +167,14 @@ gs_status gs_segtopk_destroy(gs_segtopk* h) {
 
 gs_status gs_segtopk_select_keys(gs_segtopk* h, const void* d_keys, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments, uint32_t k,
                                  uint32_t max_segment_len, void* d_out_keys, gs_key_type key_type, gs_order order, void* stream) {
-    return segtopk_impl(h, d_keys, nullptr, n, d_offsets, num_segments, k, max_segment_len, d_out_keys, nullptr, key_type, order,
+    return segtopk_impl(g_tks_routes32, h, d_keys, nullptr, n, d_offsets, num_segments, k, max_segment_len, d_out_keys, nullptr, key_type, order,
                         static_cast<hipStream_t>(stream), false);
 }
 
 gs_status gs_segtopk_select_pairs(gs_segtopk* h, const void* d_keys, const void* d_vals, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments,
                                   uint32_t k, uint32_t max_segment_len, void* d_out_keys, void* d_out_vals, gs_key_type key_type, gs_order order,
                                   void* stream) {
-    return segtopk_impl(h, d_keys, d_vals, n, d_offsets, num_segments, k, max_segment_len, d_out_keys, d_out_vals, key_type, order,
+    return segtopk_impl(g_tks_routes32, h, d_keys, d_vals, n, d_offsets, num_segments, k, max_segment_len, d_out_keys, d_out_vals, key_type, order,
                         static_cast<hipStream_t>(stream), true);
 }
 

@@ -22,6 +22,7 @@ from .segsort16 import SegmentedSort16, segmented_sort16_reference  # noqa: F401
 from .rowsort import RowSort, sort_rows_reference  # noqa: F401
 from .rowsort16 import RowSort16, sort_rows16_reference  # noqa: F401
 from .segtopk import SegmentedTopK, segmented_topk_reference  # noqa: F401
+from .segtopk16 import SegmentedTopK16  # noqa: F401
 from .sort16 import Sort16, sort16_reference  # noqa: F401
 from .topk import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, TopK, rows_max_k, topk_reference, topk_rows_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
@@ -457,14 +458,16 @@ _segtopk_cache: dict = {}
 
 
 def _segtopk_handle(device: torch.device, n: int, num_segments: int, k: int, key_type: int, order: int, value_bytes: int) -> SegmentedTopK:
-    """One cached handle per (device, stream, type, order, value width); re-created when n, the segments or k outgrow it."""
+    """One cached handle per (device, stream, type, order, value width); re-created when n, the segments or k outgrow it.  A 16-bit
+    key type gets a ``SegmentedTopK16``."""
     key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
     s = _segtopk_cache.get(key)
     if s is None or s.max_keys < n or s.max_segments < num_segments or s.max_k < k:
         if s is not None:
             s.close()
         cap = lambda x, low: min(1 << max(int(x - 1).bit_length(), low), (1 << 30) - 1)  # noqa: E731
-        s = SegmentedTopK(cap(n, 16), cap(num_segments, 16), cap(k, 6), order, key_type, MODE_PAIRS, value_bytes, device=device.index)
+        cls = SegmentedTopK16 if key_type in _KEY16_TYPE.values() else SegmentedTopK
+        s = cls(cap(n, 16), cap(num_segments, 16), cap(k, 6), order, key_type, MODE_PAIRS, value_bytes, device=device.index)
         _segtopk_cache[key] = s
     return s
 
@@ -482,12 +485,33 @@ def segmented_topk(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: b
     if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
         raise ValueError("keys must be a contiguous 1-D device tensor")
     if keys.dtype not in _KEY_TYPE:
-        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
+        raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32); "
+                        "float16, bfloat16, int16 and uint16 keys: segmented_topk16")
+    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    return _segmented_topk(keys, offsets, k, largest, values, kt, max_segment_len)
+
+
+def segmented_topk16(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor | None = None,
+                     unsigned: bool = False, max_segment_len: int = 0):
+    """``segmented_topk`` on 2-byte keys (float16, bfloat16, int16, and uint16 where torch has it; ``unsigned=True`` treats int16
+    storage as uint16), read at their own width by ``gs_segtopk16_*``: the same arguments, the same result ``(keys_k, indices_k |
+    values_k, counts)``, the same filling (zero keys, ``-1`` positions, zero values) and the same rule for ``k`` above 4096.  The result
+    is the head of ``segmented_sort`` on the same tensor."""
+    if keys.dtype not in _KEY16_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: 16-bit keys only (float16, bfloat16, int16, uint16); "
+                        "int32, uint32 and float32 keys: segmented_topk")
+    if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    return _segmented_topk(keys, offsets, k, largest, values, kt, max_segment_len)
+
+
+def _segmented_topk(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: bool, values: torch.Tensor | None, kt: int, max_segment_len: int):
+    """``segmented_topk`` / ``segmented_topk16`` behind their checks of the keys: ``kt`` is the key type of ``keys.dtype``."""
     _require_offsets(keys, offsets)
     n, k, segs = keys.numel(), int(k), offsets.numel() - 1
     if k < 1:
         raise ValueError("k >= 1")
-    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
     vb = 4
     if values is not None:
         if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:

@@ -64,13 +64,21 @@ class SegmentedTopK:
     ``value_bytes`` 0 selects keys only; 4 or 8 carries values; on a 4-byte handle ``select(keys, offsets, k, out_keys, None,
     out_values)`` delivers the positions in the whole array as values."""
 
+    # what the key width decides (SegmentedTopK16, segtopk16.py, overrides the three)
+    _ENTRY = "gs_segtopk"
+    _KEY_TYPES = (KEY_UINT32, KEY_INT32, KEY_FLOAT32)
+    _KEY_BYTES = 4
+
+    def _fn(self, name: str):
+        return getattr(self._lib, f"{self._ENTRY}_{name}")
+
     def __init__(self, max_keys: int, max_segments: int, max_k: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT32,
                  mode: int = MODE_KEYS_ONLY, value_bytes: int = 0, device: int | None = None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type not in (KEY_UINT32, KEY_INT32, KEY_FLOAT32):
-            raise ValueError("the segmented top-k takes 32-bit keys only")
+        if key_type not in self._KEY_TYPES:
+            raise ValueError(f"{type(self).__name__} takes {8 * self._KEY_BYTES}-bit keys only")
         self._lib = _lib.load()
         if device is not None:
             torch.cuda.set_device(device)
@@ -79,12 +87,12 @@ class SegmentedTopK:
         self.order, self.key_type, self.mode = order, key_type, mode
         self.value_bytes = (value_bytes or 4) if mode == MODE_PAIRS else 0
         h = C.c_void_p()
-        check(self._lib.gs_segtopk_create(C.byref(h), self.max_keys, self.max_segments, self.max_k, mode, self.value_bytes), "gs_segtopk_create")
+        check(self._fn("create")(C.byref(h), self.max_keys, self.max_segments, self.max_k, mode, self.value_bytes), f"{self._ENTRY}_create")
         self._h = h
 
     def close(self) -> None:
         if getattr(self, "_h", None):
-            self._lib.gs_segtopk_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -95,7 +103,7 @@ class SegmentedTopK:
 
     @property
     def temp_bytes(self) -> int:
-        return int(self._lib.gs_segtopk_temp_bytes(self.max_segments))
+        return int(self._fn("temp_bytes")(self.max_segments))
 
     @property
     def max_lds_segment(self) -> int:
@@ -104,11 +112,11 @@ class SegmentedTopK:
 
     @property
     def rank_mode(self) -> int:
-        return int(self._lib.gs_segtopk_get_rank_mode(self._h))
+        return int(self._fn("get_rank_mode")(self._h))
 
     def set_rank_mode(self, mode: int) -> None:
         """``gs_segtopk_set_rank_mode``: the ranking inside a tile (0 ballot multi-split, 1 returning LDS atomic), with no call in flight."""
-        check(self._lib.gs_segtopk_set_rank_mode(self._h, int(mode)), "gs_segtopk_set_rank_mode")
+        check(self._fn("set_rank_mode")(self._h, int(mode)), f"{self._ENTRY}_set_rank_mode")
 
     def class_of(self, length: int) -> int:
         return int(self._lib.gs_segsort_class_of(int(length), self.mode, self.value_bytes))
@@ -124,8 +132,9 @@ class SegmentedTopK:
         _require_cuda(keys, "keys")
         _require_cuda(offsets, "offsets")
         _require_cuda(out_keys, "out_keys")
-        if keys.element_size() != 4 or out_keys.element_size() != 4 or offsets.element_size() != 4 or offsets.dim() != 1 or offsets.numel() < 2:
-            raise ValueError("keys must be 32-bit and offsets a 1-D tensor of num_segments + 1 32-bit words")
+        kb = self._KEY_BYTES
+        if keys.element_size() != kb or out_keys.element_size() != kb or offsets.element_size() != 4 or offsets.dim() != 1 or offsets.numel() < 2:
+            raise ValueError(f"keys must be {8 * kb}-bit and offsets a 1-D tensor of num_segments + 1 32-bit words")
         if (out_values is not None) != (self.mode == MODE_PAIRS):
             raise ValueError("out_values must be given exactly when the handle was built with MODE_PAIRS")
         n = keys.numel() if n is None else int(n)
@@ -142,22 +151,22 @@ class SegmentedTopK:
                     raise ValueError(f"{name} must be {self.value_bytes} bytes wide for this handle")
         s = _stream_ptr(stream)
         if out_values is None:
-            st = self._lib.gs_segtopk_select_keys(self._h, keys.data_ptr(), n, offsets.data_ptr(), num_segments, k, int(max_segment_len),
-                                                  out_keys.data_ptr(), self.key_type, self.order, s)
+            st = self._fn("select_keys")(self._h, keys.data_ptr(), n, offsets.data_ptr(), num_segments, k, int(max_segment_len),
+                                         out_keys.data_ptr(), self.key_type, self.order, s)
         else:
-            st = self._lib.gs_segtopk_select_pairs(self._h, keys.data_ptr(), None if values is None else values.data_ptr(), n,
-                                                   offsets.data_ptr(), num_segments, k, int(max_segment_len), out_keys.data_ptr(),
-                                                   out_values.data_ptr(), self.key_type, self.order, s)
-        check(st, "gs_segtopk_select")
+            st = self._fn("select_pairs")(self._h, keys.data_ptr(), None if values is None else values.data_ptr(), n,
+                                          offsets.data_ptr(), num_segments, k, int(max_segment_len), out_keys.data_ptr(),
+                                          out_values.data_ptr(), self.key_type, self.order, s)
+        check(st, f"{self._ENTRY}_select")
 
     def status(self, stream=None) -> int:
         """``gs_segtopk_check`` as a status code (synchronises): GS_OK, GS_ERR_ARG (bad offsets), GS_ERR_HIP, GS_ERR_SIZE (promise broken)."""
         from .onesweep import _stream_ptr
-        return int(self._lib.gs_segtopk_check(self._h, _stream_ptr(stream)))
+        return int(self._fn("check")(self._h, _stream_ptr(stream)))
 
     def check(self, stream=None) -> None:
         """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
-        check(self.status(stream), "gs_segtopk_check")
+        check(self.status(stream), f"{self._ENTRY}_check")
 
     def last(self, stream=None) -> dict:
         """``gs_segtopk_last`` (synchronises): ``counts`` (segments per class of ``class_of``), ``longest``, ``status``, ``reads`` (the
@@ -165,7 +174,7 @@ class SegmentedTopK:
         packed kernel emitted: length 1 .. 32)."""
         from .onesweep import _stream_ptr
         buf = (C.c_uint32 * _lib.GS_SEGTOPK_REPORT_WORDS)()
-        check(self._lib.gs_segtopk_last(self._h, buf, _lib.GS_SEGTOPK_REPORT_WORDS, _stream_ptr(stream)), "gs_segtopk_last")
+        check(self._fn("last")(self._h, buf, _lib.GS_SEGTOPK_REPORT_WORDS, _stream_ptr(stream)), f"{self._ENTRY}_last")
         out = {"counts": [int(buf[_lib.GS_SEGTOPK_R_CLASSES + c]) for c in range(_lib.GS_SEGSORT_CLASSES)]}
         out.update({name: int(buf[_lib.GS_SEGTOPK_R_LONGEST + i]) for i, name in enumerate(_SCALARS)})
         return out

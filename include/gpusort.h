@@ -1046,7 +1046,7 @@ int gs_segsort16_get_rank_mode(gs_segsort16* h);
  * d_vals == NULL on a handle with 4-byte values: the value is the element's position in the WHOLE ARRAY, off[s] plus the position in
  * the segment (the convention of the segmented argsort).  The kernels produce it themselves: no n-sized index array exists.
  *
- * Key types: GS_KEY_UINT32 / INT32 / FLOAT32; the 64-bit and 16-bit ones return GS_ERR_ARG.
+ * Key types: GS_KEY_UINT32 / INT32 / FLOAT32; the 64-bit and 16-bit ones return GS_ERR_ARG (16-bit keys: gs_segtopk16_* below).
  *
  * The offsets are validated on the device before anything is loaded through them (non-decreasing, last <= n); with bad offsets no
  * output is written and gs_segtopk_check reports GS_ERR_ARG.  max_segment_len is the promise of gs_segsort_*: 0 = unknown; a segment
@@ -1108,6 +1108,50 @@ gs_status gs_segtopk_last(gs_segtopk* h, uint32_t* report, uint32_t words, void*
  * probed at create.  With no call of the handle in flight.  get: -1 for a null handle. */
 gs_status gs_segtopk_set_rank_mode(gs_segtopk* h, int mode);
 int gs_segtopk_get_rank_mode(gs_segtopk* h);
+
+/* ---- segmented top-k on 16-bit keys: GS_KEY_UINT16 / INT16 / FLOAT16 / BFLOAT16 -----------------------------------------------------
+ * No counterpart in the reference project.  gs_segtopk_* on 2-BYTE ELEMENTS in d_keys and d_out_keys, read once at their own width:
+ * row s of the dense [num_segments, k] output holds the first m_s = min(k, len_s) elements that gs_segsort16_sort_keys / _sort_pairs
+ * would leave in segment s; slots m_s .. k are NOT WRITTEN — the key stores are 2-byte stores, so an unwritten slot keeps its content
+ * even where it shares a 32-bit word with a written one (odd k).  Keys are ordered by the 16-bit order-preserving flip (unsigned as
+ * they are, signed with the sign bit flipped, both float formats with all bits of negatives flipped too: -0 < +0, NaNs by bit
+ * pattern); ties by position, descending the exact reverse of the stable ascending result.  Offsets, n, k, max_segment_len and the
+ * positions count elements; values are 4 or 8 bytes wide under the same index; d_vals == NULL on a 4-byte handle delivers the position
+ * in the whole array.  Everything else is what the section above says of gs_segtopk_*: the offsets are validated on the device (bad
+ * offsets: nothing written, GS_ERR_ARG at check), a segment longer than a non-zero promise gets no output row (GS_ERR_SIZE at check),
+ * the call never waits on the host, allocates nothing after create, needs no n-sized scratch and can be captured on one linear stream
+ * with every node a kernel launch; k > gs_topk_rows_max_k (4096) is accepted only with a non-zero promise max_segment_len <=
+ * gs_segsort_max_lds_segment(mode, value_bytes) and returns GS_ERR_SIZE before anything is launched otherwise.
+ * Kernels by segment length, the classes and the LDS limit of gs_segsort_class_of as in the 32-bit call: packed (1 .. 32), one wave
+ * per segment (33 .. 256), one workgroup per segment (classes 3 .. 7), and for longer segments the 16-bit radix select of the row-wise
+ * top-k (12 + 4 bits: a segment is read 2 or 3 times, never 4).
+ *
+ * GS_ERR_ARG: null handle, a null or not 16-byte aligned base pointer (d_offsets: 4-byte aligned; segments and output rows start at
+ * 2-byte alignment only), a key type other than the four 16-bit ones, an output overlapping an input or the other output — in 2-byte
+ * key sizes, so an output at d_keys + 2 * n bytes is legal.  GS_ERR_MODE and GS_ERR_SIZE as gs_segtopk_select_*. */
+typedef struct gs_segtopk16 gs_segtopk16;
+/* No counterpart in the reference project.  As gs_segtopk_create; the handle holds nothing that depends on the key width. */
+gs_status gs_segtopk16_create(gs_segtopk16** out, uint32_t max_keys, uint32_t max_segments, uint32_t max_k, gs_mode mode, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_segtopk16_destroy(gs_segtopk16* h);
+/* No counterpart in the reference project.  Host only: gs_segtopk_temp_bytes(max_segments), ((64 + max_segments) * 4 + 255) & ~255. */
+size_t gs_segtopk16_temp_bytes(uint32_t max_segments);
+/* No counterpart in the reference project. */
+gs_status gs_segtopk16_select_keys(gs_segtopk16* h, const void* d_keys, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments, uint32_t k,
+                                   uint32_t max_segment_len, void* d_out_keys, gs_key_type key_type, gs_order order, void* stream);
+/* No counterpart in the reference project. */
+gs_status gs_segtopk16_select_pairs(gs_segtopk16* h, const void* d_keys, const void* d_vals, uint32_t n, const uint32_t* d_offsets,
+                                    uint32_t num_segments, uint32_t k, uint32_t max_segment_len, void* d_out_keys, void* d_out_vals,
+                                    gs_key_type key_type, gs_order order, void* stream);
+/* No counterpart in the reference project.  As gs_segtopk_check: GS_OK, GS_ERR_ARG, GS_ERR_HIP, GS_ERR_SIZE, in that order. */
+gs_status gs_segtopk16_check(gs_segtopk16* h, void* stream);
+/* No counterpart in the reference project.  The 16-word report of gs_segtopk_last in the same layout: the GS_SEGTOPK_R_* words and
+ * GS_SEGTOPK_F_* bits above are reused, there is no second set; words >= GS_SEGTOPK_REPORT_WORDS.  report[GS_SEGTOPK_R_READS] is 2 or
+ * 3 here (0 without long segments), never 4. */
+gs_status gs_segtopk16_last(gs_segtopk16* h, uint32_t* report, uint32_t words, void* stream);
+/* No counterpart in the reference project.  As gs_segtopk_set_rank_mode / _get_rank_mode. */
+gs_status gs_segtopk16_set_rank_mode(gs_segtopk16* h, int mode);
+int gs_segtopk16_get_rank_mode(gs_segtopk16* h);
 
 #ifdef __cplusplus
 }
