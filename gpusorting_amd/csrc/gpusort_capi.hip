@@ -30,6 +30,8 @@
 // One translation unit; one host file per concern, in this order (each may use what stands above it):
 #include "host_common.hpp"      // GS_HIP, argument predicates, div_up, cu_count, DeviceScratch
 #include "kernel_registry.hpp"  // launcher templates, which kernels a build flavour compiles
+#include "handle_core.hpp"      // what the handles below share: layout arena, workspace + control read-back, create/destroy frame, rank mode,
+                                // alternate-buffer predicates, pass ping-pong, the head of a segmented call (gs_onesweep and gs_mgpu do not use it)
 #include "onesweep_host.hpp"    // gs_onesweep: slab sizing, prologue, routing, sort_impl; every gs_onesweep_* / gs_selftest_* / gs_debug_* entry
 #include "segsort_host.hpp"     // gs_segsort
 #include "topk_host.hpp"        // gs_topk: the 1-D selection and the row-wise one

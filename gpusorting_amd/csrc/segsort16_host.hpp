@@ -1,12 +1,13 @@
 // segsort16_host.hpp — part of the gpusort_capi.hip translation unit: the gs_segsort16 handle (segsort16_kernels.hpp) and its
-// entries.  No counterpart in the reference project.
+// entries: the layout, the launchers, every launch of a call and the reports.  Allocation, create/destroy, the control read-back, the
+// rank mode, the buffer predicate, the ping-pong and the head of a segmented call are handle_core.hpp's.  No counterpart in the
+// reference project.
 struct gs_segsort16 {
     uint32_t max_keys, max_segments;
     gs_mode mode;
     uint32_t value_bytes;
     int rank_mode;               // the ranking of the workgroup classes and of the long route's scatter (probed at create)
-    char* dev = nullptr;         // one allocation: see segsort16_layout
-    uint32_t* pinned = nullptr;  // read-back of the control block
+    Workspace ws;                // one allocation: see segsort16_layout
     // the last call (gs_segsort16_last)
     uint32_t last_forms = 0, last_wg_forms = 0, last_unit_cap = 0, last_n = 0;
 };
@@ -28,15 +29,14 @@ struct SegSort16Layout {
 // table, bases: units x 256 words each
 SegSort16Layout segsort16_layout(uint32_t max_keys, uint32_t max_segments, uint32_t vb) {
     SegSort16Layout l{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t a = at; at += (bytes + 255u) & ~(size_t)255u; return a; };
+    Arena a;
     const size_t units = segsort16_units(max_keys, max_segments, vb), longs = segsort16_long_cap(max_keys, max_segments, vb);
-    l.ctl = take(((size_t)gs::SEGC_WORDS + max_segments) * 4u);
-    l.desc = take(units * 16u);
-    l.rec = take(longs * 16u);
-    l.table = take(units * gs::RADIX * 4u);
-    l.bases = take(units * gs::RADIX * 4u);
-    l.total = at;
+    l.ctl = a.take(((size_t)gs::SEGC_WORDS + max_segments) * 4u);
+    l.desc = a.take(units * 16u);
+    l.rec = a.take(longs * 16u);
+    l.table = a.take(units * gs::RADIX * 4u);
+    l.bases = a.take(units * gs::RADIX * 4u);
+    l.total = a.total();
     return l;
 }
 
@@ -91,25 +91,18 @@ gs_status segsort16_enqueue(gs_segsort16* h, const SegSort16Layout& l, uint16_t*
                             const uint32_t* d_offsets, uint32_t num_segments, uint32_t max_len, uint32_t top, bool allow_long, uint32_t kt, bool descending,
                             uint32_t vm, hipStream_t s) {
     const uint32_t vb = h->value_bytes, v = (uint32_t)vm_index(vm), desc = descending ? 1u : 0u, rank = h->rank_mode ? 1u : 0u;
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->dev + l.ctl);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->ws.dev + l.ctl);
     uint32_t* list = ctl + gs::SEGC_WORDS;
-    hipLaunchKernelGGL(gs::seg_reset_kernel, dim3(1), dim3(64), 0, s, ctl);
-    const uint32_t seg_blocks = div_up(num_segments, 256);
-    hipLaunchKernelGGL(gs::seg_classify_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, n, vb, max_len, ctl);
-    h->last_forms = GS_SEGSORT16_F_CLASSIFY;
-    if (top >= 2) {
-        hipLaunchKernelGGL(gs::seg_fill_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, vb, max_len, ctl, list);
-        h->last_forms |= GS_SEGSORT16_F_FILL;
-    }
+    seg_enqueue_head(ctl, d_offsets, num_segments, n, vb, max_len, top, s);
+    h->last_forms = GS_SEGSORT16_F_CLASSIFY | (top >= 2 ? GS_SEGSORT16_F_FILL : 0u);
     const Seg16VmLaunchers& f = g_seg16_vm[v];
     if (top >= 1 || vm == 1u) {  // (the argsort form writes the position of a segment of one element)
         f.packed(s, div_up(num_segments, 64), keys, vals, d_offsets, num_segments, max_len, kt, desc, ctl);
         h->last_forms |= GS_SEGSORT16_F_PACKED << v;
     }
-    // a class whose shortest segment has m elements holds at most n / m segments
-    auto bound = [&](uint32_t min_len) { const uint32_t b = n / min_len; return b < num_segments ? b : num_segments; };
     if (top >= 2 && n > gs::SEG_PACK_MAX) {
-        f.wave(s, seg_grid(bound(gs::SEG_PACK_MAX + 1), 1, gs::SEG_WAVE_MAX * (8 + (vm == 1u ? 4u : vm))), keys, vals, d_offsets, list, ctl, num_segments, kt, desc);
+        f.wave(s, seg_grid(seg_class_bound(n, num_segments, gs::SEG_PACK_MAX + 1), 1, gs::SEG_WAVE_MAX * (8 + (vm == 1u ? 4u : vm))), keys, vals, d_offsets, list,
+               ctl, num_segments, kt, desc);
         h->last_forms |= GS_SEGSORT16_F_WAVE << v;
     }
     for (uint32_t c = 3; c <= 7 && c <= top; ++c) {
@@ -118,32 +111,29 @@ gs_status segsort16_enqueue(gs_segsort16* h, const SegSort16Layout& l, uint16_t*
         const Shape sh = g_small_class[c - 3];
         const Seg16WgLauncher wg = g_seg16_wg[Seg16WgTable::index({(int)c - 3, (int)rank, (int)v})];
         if (!wg) return GS_ERR_MODE;
-        const size_t lds = (size_t)sh.threads * sh.kpt * (4 + vb) + (size_t)sh.threads / 64 * gs::RADIX * 4 + 64;
-        wg(s, SEG_WG_LOOP(sh.threads, sh.kpt) ? seg_grid(bound(min_len), (uint32_t)sh.threads / 64, lds) : bound(min_len), keys, vals, d_offsets, list, ctl,
+        const uint32_t bound = seg_class_bound(n, num_segments, min_len);
+        wg(s, SEG_WG_LOOP(sh.threads, sh.kpt) ? seg_grid(bound, (uint32_t)sh.threads / 64, seg_wg_lds_bytes(sh, vb)) : bound, keys, vals, d_offsets, list, ctl,
            num_segments, c, kt, desc);
         h->last_wg_forms |= GS_SEGSORT16_WG_FORM(c, v, rank);
     }
     // ---- long segments: the work list, then two passes, the low byte into the alternates, the high byte back ----
     if (allow_long && n > gs::seg_max_lds(vb)) {
         const uint32_t unit_cap = segsort16_units(n, num_segments, vb), long_cap = segsort16_long_cap(n, num_segments, vb);
-        uint4* desc4 = reinterpret_cast<uint4*>(h->dev + l.desc);
-        uint4* rec = reinterpret_cast<uint4*>(h->dev + l.rec);
-        uint32_t* table = reinterpret_cast<uint32_t*>(h->dev + l.table);
-        uint32_t* bases = reinterpret_cast<uint32_t*>(h->dev + l.bases);
+        uint4* desc4 = reinterpret_cast<uint4*>(h->ws.dev + l.desc);
+        uint4* rec = reinterpret_cast<uint4*>(h->ws.dev + l.rec);
+        uint32_t* table = reinterpret_cast<uint32_t*>(h->ws.dev + l.table);
+        uint32_t* bases = reinterpret_cast<uint32_t*>(h->ws.dev + l.bases);
         h->last_unit_cap = unit_cap;
         hipLaunchKernelGGL(gs::seg16_units_kernel, dim3(div_up(long_cap, 256)), dim3(256), 0, s, d_offsets, list, ctl, num_segments, GS_SEGSORT16_PART, unit_cap,
                            long_cap, desc4, rec);
         h->last_forms |= GS_SEGSORT16_F_UNITS | GS_SEGSORT16_F_COUNT | GS_SEGSORT16_F_SCAN;
         for (uint32_t pass = 0; pass < gs::SR16_PASSES; ++pass) {
             const bool fwd = pass == 0u;
-            const uint16_t* kin = fwd ? keys : alt_keys;
-            uint16_t* kout = fwd ? alt_keys : keys;
-            const void* vin = fwd ? vals : alt_vals;
-            void* vout = fwd ? alt_vals : vals;
+            const PingPong<uint16_t> b = ping_pong(pass, keys, vals, alt_keys, alt_vals);
             const uint32_t pv = (uint32_t)vm_index((vm == 1u && !fwd) ? 4u : vm);  // the argsort's second pass carries the positions as 4-byte values
-            hipLaunchKernelGGL(gs::seg16_count_kernel, dim3(unit_cap), dim3(gs::SR_THREADS), 0, s, kin, desc4, ctl, unit_cap, kt, pass * 8u, table);
+            hipLaunchKernelGGL(gs::seg16_count_kernel, dim3(unit_cap), dim3(gs::SR_THREADS), 0, s, b.kin, desc4, ctl, unit_cap, kt, pass * 8u, table);
             hipLaunchKernelGGL(gs::seg16_scan_kernel, dim3(long_cap), dim3(gs::RADIX), 0, s, table, bases, rec, ctl, unit_cap, long_cap);
-            g_seg16_scatter[Table<2, 4>::index({(int)rank, (int)pv})](s, unit_cap, kin, vin, kout, vout, desc4, unit_cap, kt, pass * 8u,
+            g_seg16_scatter[Table<2, 4>::index({(int)rank, (int)pv})](s, unit_cap, b.kin, b.vin, b.kout, b.vout, desc4, unit_cap, kt, pass * 8u,
                                                                      (descending && !fwd) ? 1u : 0u, bases, ctl);
             h->last_forms |= GS_SEGSORT16_F_SCATTER << (2u * pv + rank);
         }
@@ -164,13 +154,7 @@ gs_status segsort16_impl(gs_segsort16* h, void* d_keys, void* d_vals, void* d_al
     if (n == 0 || n > h->max_keys || num_segments == 0 || num_segments > h->max_segments) return GS_ERR_SIZE;
     const uint32_t vb = h->value_bytes;
     const bool allow_long = max_len == 0u || max_len > gs::seg_max_lds(vb);
-    if (allow_long) {
-        if (!d_alt_keys || misaligned(d_alt_keys) || (pairs && (!d_alt_vals || misaligned(d_alt_vals)))) return GS_ERR_ARG;
-        const size_t kb = (size_t)n * 2u, vbytes = (size_t)n * vb;
-        const void* p[4] = {d_keys, d_alt_keys, d_vals, d_alt_vals};
-        const size_t b[4] = {kb, kb, vbytes, vbytes};
-        if (any_overlap(p, b, pairs ? 4 : 2)) return GS_ERR_ARG;
-    }
+    if (allow_long && !alt_buffers_ok(d_keys, d_alt_keys, d_vals, d_alt_vals, n, 2u, vb, pairs)) return GS_ERR_ARG;
     if (!SR_BUILT) return GS_ERR_MODE;  // this build flavour has no segmented sort
 #if GS_SORT_ROWS_BUILT
     const uint32_t top = allow_long ? gs::SEG_CLASS_LONG : gs::seg_class_of(max_len, vb);  // the highest class a segment can fall in
@@ -183,14 +167,6 @@ gs_status segsort16_impl(gs_segsort16* h, void* d_keys, void* d_vals, void* d_al
     (void)s; (void)d_alt_keys; (void)d_alt_vals; (void)d_vals; (void)max_len; (void)allow_long;
     return GS_ERR_MODE;
 #endif
-}
-
-// the control block -> h->pinned (synchronises)
-gs_status segsort16_read_ctl(gs_segsort16* h, hipStream_t s) {
-    GS_HIP(hipMemcpyAsync(h->pinned, h->dev + segsort16_layout(h->max_keys, h->max_segments, h->value_bytes).ctl, gs::SEGC_WORDS * sizeof(uint32_t),
-                          hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));
-    return GS_OK;
 }
 }  // namespace
 
@@ -205,39 +181,16 @@ size_t gs_segsort16_temp_bytes(uint32_t max_keys, uint32_t max_segments, gs_mode
 }
 
 gs_status gs_segsort16_create(gs_segsort16** out, uint32_t max_keys, uint32_t max_segments, gs_mode mode, uint32_t value_bytes) {
-    if (!out) return GS_ERR_ARG;
-    *out = nullptr;
-    if (max_keys == 0 || max_keys > GS_MAX_KEYS || max_segments == 0 || max_segments > GS_MAX_KEYS) return GS_ERR_SIZE;
-    if (!mode_value_ok(mode, value_bytes)) return GS_ERR_MODE;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return GS_ERR_NO_DEVICE;
-    gs_segsort16* h = new (std::nothrow) gs_segsort16();
-    if (!h) return GS_ERR_ARG;
-    h->max_keys = max_keys;
-    h->max_segments = max_segments;
-    h->mode = mode;
-    h->value_bytes = value_bytes;
-    h->rank_mode = lds_atomic_order_ok() ? 1 : 0;  // the probe of gs_onesweep_create, once per device
-    const SegSort16Layout l = segsort16_layout(max_keys, max_segments, value_bytes);
-    hipError_t e = hipMalloc(&h->dev, l.total);
-    if (e == hipSuccess) e = hipMemset(h->dev + l.ctl, 0, gs::SEGC_WORDS * sizeof(uint32_t));  // gs_segsort16_check may run before any call
-    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, gs::SEGC_WORDS * sizeof(uint32_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)gs_segsort16_destroy(h);
-        return GS_ERR_HIP;
-    }
-    *out = h;
-    return GS_OK;
+    const bool sizes_ok = max_keys != 0 && max_keys <= GS_MAX_KEYS && max_segments != 0 && max_segments <= GS_MAX_KEYS;
+    return handle_create(out, sizes_ok, mode, value_bytes, [&](gs_segsort16* h) {
+        h->max_keys = max_keys;
+        h->max_segments = max_segments;
+        const SegSort16Layout l = segsort16_layout(max_keys, max_segments, value_bytes);
+        return h->ws.alloc(l.total, l.ctl, gs::SEGC_WORDS, gs::SEGC_WORDS);
+    });
 }
 
-gs_status gs_segsort16_destroy(gs_segsort16* h) {
-    if (!h) return GS_ERR_ARG;
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->dev) (void)hipFree(h->dev);
-    delete h;
-    return GS_OK;
-}
+gs_status gs_segsort16_destroy(gs_segsort16* h) { return handle_destroy(h); }
 
 gs_status gs_segsort16_sort_keys(gs_segsort16* h, void* d_keys, void* d_alt, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments,
                                  uint32_t max_segment_len, gs_key_type key_type, gs_order order, void* stream) {
@@ -258,46 +211,42 @@ gs_status gs_segsort16_argsort(gs_segsort16* h, void* d_keys, void* d_pos, void*
 
 gs_status gs_segsort16_check(gs_segsort16* h, void* stream) {
     if (!h) return GS_ERR_ARG;
-    const gs_status rd = segsort16_read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
-    const uint32_t st = h->pinned[gs::SEGC_STATUS];
+    const uint32_t st = h->ws.pinned[gs::SEGC_STATUS];
     if (st & gs::SEG_ST_ARG) return GS_ERR_ARG;
-    if (h->pinned[gs::SEG16C_INTERNAL] != 0u) return GS_ERR_HIP;
+    if (h->ws.pinned[gs::SEG16C_INTERNAL] != 0u) return GS_ERR_HIP;
     if (st & gs::SEG_ST_SIZE) return GS_ERR_SIZE;
     return GS_OK;
 }
 
 gs_status gs_segsort16_last_classes(gs_segsort16* h, uint32_t* counts, uint32_t words, void* stream) {
     if (!h || !counts || words < GS_SEGSORT_CLASSES + 1) return GS_ERR_ARG;
-    const gs_status rd = segsort16_read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
-    for (uint32_t c = 0; c < GS_SEGSORT_CLASSES; ++c) counts[c] = h->pinned[gs::SEGC_COUNT + c];
-    counts[GS_SEGSORT_CLASSES] = h->pinned[gs::SEGC_MAXLEN];
+    for (uint32_t c = 0; c < GS_SEGSORT_CLASSES; ++c) counts[c] = h->ws.pinned[gs::SEGC_COUNT + c];
+    counts[GS_SEGSORT_CLASSES] = h->ws.pinned[gs::SEGC_MAXLEN];
     return GS_OK;
 }
 
 gs_status gs_segsort16_last(gs_segsort16* h, uint32_t* report, uint32_t words, void* stream) {
     if (!h || !report || words < GS_SEGSORT16_REPORT_WORDS) return GS_ERR_ARG;
-    const gs_status rd = segsort16_read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
     for (uint32_t i = 0; i < GS_SEGSORT16_REPORT_WORDS; ++i) report[i] = 0;
-    report[GS_SEGSORT16_R_UNITS] = h->pinned[gs::SEG16C_UNITS];
+    report[GS_SEGSORT16_R_UNITS] = h->ws.pinned[gs::SEG16C_UNITS];
     report[GS_SEGSORT16_R_FORMS] = h->last_forms;
     report[GS_SEGSORT16_R_WG_FORMS] = h->last_wg_forms;
-    report[GS_SEGSORT16_R_STATUS] = h->pinned[gs::SEGC_STATUS] | (h->pinned[gs::SEG16C_INTERNAL] != 0u ? 256u : 0u);
+    report[GS_SEGSORT16_R_STATUS] = h->ws.pinned[gs::SEGC_STATUS] | (h->ws.pinned[gs::SEG16C_INTERNAL] != 0u ? 256u : 0u);
     report[GS_SEGSORT16_R_RANK] = (uint32_t)h->rank_mode;
-    report[GS_SEGSORT16_R_LONG] = h->pinned[gs::SEGC_COUNT + gs::SEG_CLASS_LONG];
+    report[GS_SEGSORT16_R_LONG] = h->ws.pinned[gs::SEGC_COUNT + gs::SEG_CLASS_LONG];
     report[GS_SEGSORT16_R_UNIT_CAP] = h->last_unit_cap;
     report[GS_SEGSORT16_R_N] = h->last_n;
     return GS_OK;
 }
 
-gs_status gs_segsort16_set_rank_mode(gs_segsort16* h, int mode) {
-    if (!h || (mode != 0 && mode != 1)) return GS_ERR_ARG;
-    h->rank_mode = mode;
-    return GS_OK;
-}
+gs_status gs_segsort16_set_rank_mode(gs_segsort16* h, int mode) { return handle_set_rank_mode(h, mode); }
 
-int gs_segsort16_get_rank_mode(gs_segsort16* h) { return h ? h->rank_mode : -1; }
+int gs_segsort16_get_rank_mode(gs_segsort16* h) { return handle_get_rank_mode(h); }
 
 }  // extern "C"

@@ -1,12 +1,15 @@
 // segsort_host.hpp — part of the gpusort_capi.hip translation unit: the gs_segsort handle (segsort_kernels.hpp) and its entries.
 // Replaces SplitSortAllocateTempMemory / SplitSortPairs / SplitSortFreeTempMemory (GPUSortingCUDA/SegSort/SplitSort/SplitSort.cuh:674-709).
+// The handle's own: the engine, the two long routes and their buffers, the launches of the LDS classes (shared with the row-wise sort).
+// The control block's allocation and read-back, the buffer predicates, the ping-pong and the head of a segmented call are
+// handle_core.hpp's.
 struct gs_segsort {
     uint32_t max_keys, max_segments;
     gs_mode mode;
     uint32_t value_bytes;
     gs_onesweep* engine = nullptr;  // long segments (and the rank mode of the workgroup classes)
-    uint32_t* ctl = nullptr;        // gs::SEGC_WORDS control words, then the class lists (max_segments words)
-    uint32_t* pinned = nullptr;     // read-backs: control block + SEG_LONG_CHUNK list entries
+    Workspace ws;                   // device: gs::SEGC_WORDS control words, then the class lists (max_segments words);
+                                    // pinned: the control block + SEG_LONG_CHUNK list entries + a segment's two offsets (the host long route)
     bool long_failed = false;       // a long segment's engine call failed on the host side
     uint32_t long_route = GS_SEGSORT_LONG_HOST;
     char* long_dev = nullptr;       // the device route's buffers (seg_long_layout), from the first switch to it until destroy
@@ -20,13 +23,7 @@ static_assert(GS_SEGSORT_LONG_PASSES == gs::SR_PASSES && GS_SEGSORT_LONG_PASSES 
               "header and kernels agree on the plan: a part is whole tiles, and an even number of passes ends in the caller's buffers");
 namespace {
 constexpr uint32_t SEG_LONG_CHUNK = 1024;  // long-list entries per read-back
-inline uint32_t* seg_list(const gs_segsort* h) { return h->ctl + gs::SEGC_WORDS; }
-// the control block -> h->pinned (synchronises)
-gs_status read_ctl(gs_segsort* h, hipStream_t s) {
-    GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, gs::SEGC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));
-    return GS_OK;
-}
+inline uint32_t* seg_list(const gs_segsort* h) { return h->ws.ctl() + gs::SEGC_WORDS; }
 
 // workgroups of a fixed-grid class kernel: what the chip holds at once (waves and LDS), never more than the class can have segments
 uint32_t seg_grid(uint32_t bound, uint32_t waves, size_t lds_bytes) {
@@ -44,24 +41,21 @@ uint32_t seg_grid(uint32_t bound, uint32_t waves, size_t lds_bytes) {
 gs_status seg_enqueue_lds(uint32_t* ctl, int rank_mode, uint32_t vb, uint32_t* keys, void* d_vals, uint32_t n, const uint32_t* d_offsets,
                           uint32_t num_segments, uint32_t max_len, uint32_t top, gs_key_type kt, uint32_t desc, hipStream_t s) {
     uint32_t* list = ctl + gs::SEGC_WORDS;
-    hipLaunchKernelGGL(gs::seg_reset_kernel, dim3(1), dim3(64), 0, s, ctl);
-    const uint32_t seg_blocks = div_up(num_segments, 256);
-    hipLaunchKernelGGL(gs::seg_classify_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, n, vb, max_len, ctl);
-    if (top >= 2) hipLaunchKernelGGL(gs::seg_fill_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, vb, max_len, ctl, list);
+    seg_enqueue_head(ctl, d_offsets, num_segments, n, vb, max_len, top, s);
     const SegVbLaunchers& f = seg_vb(vb);
     if (top >= 1) f.packed(s, div_up(num_segments, 64), keys, d_vals, d_offsets, num_segments, max_len, (uint32_t)kt, desc, ctl);
-    // a class whose shortest segment has m elements holds at most n / m segments
-    auto bound = [&](uint32_t min_len) { const uint32_t b = n / min_len; return b < num_segments ? b : num_segments; };
     if (top >= 2 && n > gs::SEG_PACK_MAX)
-        f.wave(s, seg_grid(bound(gs::SEG_PACK_MAX + 1), 1, gs::SEG_WAVE_MAX * (8 + vb)), keys, d_vals, d_offsets, list, ctl, num_segments, (uint32_t)kt, desc);
+        f.wave(s, seg_grid(seg_class_bound(n, num_segments, gs::SEG_PACK_MAX + 1), 1, gs::SEG_WAVE_MAX * (8 + vb)), keys, d_vals, d_offsets, list, ctl, num_segments,
+               (uint32_t)kt, desc);
     for (uint32_t c = 3; c <= 7 && c <= top; ++c) {
         const uint32_t min_len = gs::SEG_CLASS_MAX[c - 1] + 1;
         if (n < min_len || gs::SEG_CLASS_MAX[c] > gs::seg_max_lds(vb)) continue;
         const Shape sh = g_small_class[c - 3];
         const SegWgLauncher wg = seg_wg_launcher((int)c - 3, rank_mode, vb, (int)kt);
         if (!wg) return GS_ERR_MODE;
-        const size_t lds = (size_t)sh.threads * sh.kpt * (4 + vb) + (size_t)sh.threads / 64 * gs::RADIX * 4 + 64;
-        wg(s, SEG_WG_LOOP(sh.threads, sh.kpt) ? seg_grid(bound(min_len), (uint32_t)sh.threads / 64, lds) : bound(min_len), keys, d_vals, d_offsets, list, ctl, num_segments, c, desc);
+        const uint32_t bound = seg_class_bound(n, num_segments, min_len);
+        wg(s, SEG_WG_LOOP(sh.threads, sh.kpt) ? seg_grid(bound, (uint32_t)sh.threads / 64, seg_wg_lds_bytes(sh, vb)) : bound, keys, d_vals, d_offsets, list, ctl,
+           num_segments, c, desc);
     }
     GS_HIP(hipGetLastError());
     return GS_OK;
@@ -84,14 +78,13 @@ struct SegLongLayout {
 // desc: one uint4 per unit; rec: one uint4 per long segment; table, bases: units x 256 words each
 SegLongLayout seg_long_layout(uint32_t max_keys, uint32_t max_segments, uint32_t vb) {
     SegLongLayout l{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t a = at; at += (bytes + 255u) & ~(size_t)255u; return a; };
+    Arena a;
     const size_t units = seg_long_units(max_keys, max_segments, vb, GS_SEGSORT_LONG_PART), longs = seg_long_cap(max_keys, max_segments, vb);
-    l.desc = take(units * 16u);
-    l.rec = take(longs * 16u);
-    l.table = take(units * gs::RADIX * 4u);
-    l.bases = take(units * gs::RADIX * 4u);
-    l.total = at;
+    l.desc = a.take(units * 16u);
+    l.rec = a.take(longs * 16u);
+    l.table = a.take(units * gs::RADIX * 4u);
+    l.bases = a.take(units * gs::RADIX * 4u);
+    l.total = a.total();
     return l;
 }
 
@@ -114,7 +107,7 @@ gs_status seg_enqueue_long(gs_segsort* h, uint32_t* keys, void* vals, uint32_t* 
     const uint32_t vb = h->value_bytes, v = vb / 4u, rank = h->engine->rank_mode ? 1u : 0u;
     const SegLongLayout l = seg_long_layout(h->max_keys, h->max_segments, vb);
     const uint32_t unit_cap = seg_long_units(n, num_segments, vb, GS_SEGSORT_LONG_PART), long_cap = seg_long_cap(n, num_segments, vb);
-    uint32_t* ctl = h->ctl;
+    uint32_t* ctl = h->ws.ctl();
     uint4* desc4 = reinterpret_cast<uint4*>(h->long_dev + l.desc);
     uint4* rec = reinterpret_cast<uint4*>(h->long_dev + l.rec);
     uint32_t* table = reinterpret_cast<uint32_t*>(h->long_dev + l.table);
@@ -124,14 +117,11 @@ gs_status seg_enqueue_long(gs_segsort* h, uint32_t* keys, void* vals, uint32_t* 
                        unit_cap, long_cap, desc4, rec);
     h->last_forms |= GS_SEGSORT_LF_UNITS | GS_SEGSORT_LF_COUNT | GS_SEGSORT_LF_SCAN;
     for (uint32_t pass = 0; pass < GS_SEGSORT_LONG_PASSES; ++pass) {
-        const bool fwd = (pass & 1u) == 0u, last = pass + 1u == GS_SEGSORT_LONG_PASSES;
-        const uint32_t* kin = fwd ? keys : alt_keys;
-        uint32_t* kout = fwd ? alt_keys : keys;
-        const void* vin = fwd ? vals : alt_vals;
-        void* vout = fwd ? alt_vals : vals;
-        hipLaunchKernelGGL(gs::segl_count_kernel, dim3(unit_cap), dim3(gs::SR_THREADS), 0, s, kin, desc4, ctl, unit_cap, kt, pass * 8u, table);
+        const bool last = pass + 1u == GS_SEGSORT_LONG_PASSES;
+        const PingPong<uint32_t> b = ping_pong(pass, keys, vals, alt_keys, alt_vals);
+        hipLaunchKernelGGL(gs::segl_count_kernel, dim3(unit_cap), dim3(gs::SR_THREADS), 0, s, b.kin, desc4, ctl, unit_cap, kt, pass * 8u, table);
         hipLaunchKernelGGL(gs::seg16_scan_kernel, dim3(long_cap), dim3(gs::RADIX), 0, s, table, bases, rec, ctl, unit_cap, long_cap);
-        g_segl_scatter[Table<2, 3>::index({(int)rank, (int)v})](s, unit_cap, kin, vin, kout, vout, desc4, unit_cap, kt, pass * 8u,
+        g_segl_scatter[Table<2, 3>::index({(int)rank, (int)v})](s, unit_cap, b.kin, b.vin, b.kout, b.vout, desc4, unit_cap, kt, pass * 8u,
                                                                (descending && last) ? 1u : 0u, bases, ctl);
     }
     h->last_forms |= GS_SEGSORT_LF_SCATTER << (2u * v + rank);
@@ -149,13 +139,9 @@ gs_status segsort_impl(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_ke
     if (n == 0 || n > h->max_keys || num_segments == 0 || num_segments > h->max_segments) return GS_ERR_SIZE;
     const uint32_t vb = h->value_bytes;
     const bool allow_long = max_len == 0u || max_len > gs::seg_max_lds(vb);
-    if (allow_long && (!d_alt_keys || misaligned(d_alt_keys) || (pairs && (!d_alt_vals || misaligned(d_alt_vals))))) return GS_ERR_ARG;
-    if (allow_long && h->long_route == GS_SEGSORT_LONG_DEVICE) {  // the passes read one buffer while they write the other
-        const size_t kb = (size_t)n * 4u, vbytes = (size_t)n * vb;
-        const void* p[4] = {d_keys, d_alt_keys, d_vals, d_alt_vals};
-        const size_t b[4] = {kb, kb, vbytes, vbytes};
-        if (any_overlap(p, b, pairs ? 4 : 2)) return GS_ERR_ARG;
-    }
+    if (allow_long && !alt_buffers_present(d_alt_keys, d_alt_vals, pairs)) return GS_ERR_ARG;
+    if (allow_long && h->long_route == GS_SEGSORT_LONG_DEVICE && !alt_buffers_disjoint(d_keys, d_alt_keys, d_vals, d_alt_vals, n, 4u, vb, pairs))
+        return GS_ERR_ARG;  // (the device route's passes read one buffer while they write the other)
     if (!SEG_BUILT) return GS_ERR_MODE;  // this build flavour has no segmented-sort kernels
     const uint32_t top = allow_long ? gs::SEG_CLASS_LONG : gs::seg_class_of(max_len, vb);  // the highest class a segment can fall in
     const uint32_t desc = order == GS_ORDER_DESCENDING ? 1u : 0u;
@@ -164,7 +150,7 @@ gs_status segsort_impl(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_ke
     h->last_route = h->long_route;
     h->last_forms = h->last_unit_cap = 0;
     h->last_n = n;
-    const gs_status lds = seg_enqueue_lds(h->ctl, h->engine->rank_mode, vb, keys, d_vals, n, d_offsets, num_segments, max_len, top, kt, desc, s);
+    const gs_status lds = seg_enqueue_lds(h->ws.ctl(), h->engine->rank_mode, vb, keys, d_vals, n, d_offsets, num_segments, max_len, top, kt, desc, s);
     if (lds != GS_OK) return lds;
     if (!allow_long || n <= gs::seg_max_lds(vb)) return GS_OK;
 #if GS_SORT_ROWS_BUILT
@@ -174,11 +160,11 @@ gs_status segsort_impl(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_ke
     // ---- long segments: the one host wait.  Control block + the head of the long list (it starts the list array) ----
     const SegVbLaunchers& f = seg_vb(vb);
     const uint32_t by_len = n / (gs::seg_max_lds(vb) + 1), most = by_len < num_segments ? by_len : num_segments;  // long segments at most
-    uint32_t got = most < SEG_LONG_CHUNK ? most : SEG_LONG_CHUNK;
-    GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, (gs::SEGC_WORDS + got) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));
-    if (h->pinned[gs::SEGC_STATUS] & gs::SEG_ST_ARG) return GS_OK;  // reported by gs_segsort_check; nothing was sorted
-    const uint32_t count = h->pinned[gs::SEGC_COUNT + gs::SEG_CLASS_LONG];
+    uint32_t* pinned = h->ws.pinned;
+    const gs_status rd = h->ws.read_ctl(s, gs::SEGC_WORDS + (most < SEG_LONG_CHUNK ? most : SEG_LONG_CHUNK));
+    if (rd != GS_OK) return rd;
+    if (pinned[gs::SEGC_STATUS] & gs::SEG_ST_ARG) return GS_OK;  // reported by gs_segsort_check; nothing was sorted
+    const uint32_t count = pinned[gs::SEGC_COUNT + gs::SEG_CLASS_LONG];
     if (count > most) return GS_ERR_HIP;  // (cannot happen: the classify kernel counted more long segments than n holds)
     char* vals = static_cast<char*>(d_vals);
     char* alt_vals = static_cast<char*>(d_alt_vals);
@@ -186,13 +172,13 @@ gs_status segsort_impl(gs_segsort* h, void* d_keys, void* d_vals, void* d_alt_ke
     for (uint32_t first = 0; first < count; first += SEG_LONG_CHUNK) {
         const uint32_t chunk = count - first < SEG_LONG_CHUNK ? count - first : SEG_LONG_CHUNK;
         if (first != 0) {
-            GS_HIP(hipMemcpyAsync(h->pinned + gs::SEGC_WORDS, seg_list(h) + first, chunk * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            GS_HIP(hipMemcpyAsync(pinned + gs::SEGC_WORDS, seg_list(h) + first, chunk * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             GS_HIP(hipStreamSynchronize(s));
         }
         // the chunk's offsets: segment numbers come from the device's own (validated) classification
-        uint32_t* bounds = h->pinned + gs::SEGC_WORDS + SEG_LONG_CHUNK;
+        uint32_t* bounds = pinned + gs::SEGC_WORDS + SEG_LONG_CHUNK;
         for (uint32_t i = 0; i < chunk; ++i) {
-            const uint32_t seg = h->pinned[gs::SEGC_WORDS + i];
+            const uint32_t seg = pinned[gs::SEGC_WORDS + i];
             if (seg >= num_segments) return GS_ERR_HIP;
             GS_HIP(hipMemcpyAsync(bounds, d_offsets + seg, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             GS_HIP(hipStreamSynchronize(s));
@@ -245,13 +231,10 @@ gs_status gs_segsort_create(gs_segsort** out, uint32_t max_keys, uint32_t max_se
     h->mode = mode;
     h->value_bytes = value_bytes;
     h->engine = engine;
-    hipError_t e = hipMalloc(&h->ctl, ((size_t)gs::SEGC_WORDS + max_segments) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(h->ctl, 0, gs::SEGC_WORDS * sizeof(uint32_t));  // gs_segsort_check may run before any sort
-    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, (gs::SEGC_WORDS + SEG_LONG_CHUNK + 2) * sizeof(uint32_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)gs_segsort_destroy(h);
-        return GS_ERR_HIP;
+    const gs_status ws = h->ws.alloc(((size_t)gs::SEGC_WORDS + max_segments) * sizeof(uint32_t), 0, gs::SEGC_WORDS, gs::SEGC_WORDS + SEG_LONG_CHUNK + 2);
+    if (ws != GS_OK) {
+        (void)gs_segsort_destroy(h);  // the engine with it
+        return ws;
     }
     *out = h;
     return GS_OK;
@@ -259,8 +242,7 @@ gs_status gs_segsort_create(gs_segsort** out, uint32_t max_keys, uint32_t max_se
 
 gs_status gs_segsort_destroy(gs_segsort* h) {
     if (!h) return GS_ERR_ARG;
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->ctl) (void)hipFree(h->ctl);
+    h->ws.release();
     if (h->long_dev) (void)hipFree(h->long_dev);
     if (h->engine) (void)gs_onesweep_destroy(h->engine);
     delete h;
@@ -282,11 +264,11 @@ gs_status gs_segsort_sort_pairs(gs_segsort* h, void* d_keys, void* d_vals, void*
 
 gs_status gs_segsort_check(gs_segsort* h, void* stream) {
     if (!h) return GS_ERR_ARG;
-    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
-    const uint32_t st = h->pinned[gs::SEGC_STATUS];
+    const uint32_t st = h->ws.pinned[gs::SEGC_STATUS];
     if (st & gs::SEG_ST_ARG) return GS_ERR_ARG;
-    if (h->long_failed || h->pinned[gs::SEG16C_INTERNAL] != 0u) return GS_ERR_HIP;  // (the word is the device route's: a long segment's counts did not add up)
+    if (h->long_failed || h->ws.pinned[gs::SEG16C_INTERNAL] != 0u) return GS_ERR_HIP;  // (the word is the device route's: a long segment's counts did not add up)
     if (st & gs::SEG_ST_SIZE) return GS_ERR_SIZE;
     return gs_onesweep_check(h->engine, stream);  // the long segments' sorts
 }
@@ -314,17 +296,17 @@ uint32_t gs_segsort_get_long_route(gs_segsort* h) { return h ? h->long_route : 0
 
 gs_status gs_segsort_last(gs_segsort* h, uint32_t* report, uint32_t words, void* stream) {
     if (!h || !report || words < GS_SEGSORT_REPORT_WORDS) return GS_ERR_ARG;
-    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
     for (uint32_t i = 0; i < GS_SEGSORT_REPORT_WORDS; ++i) report[i] = 0;
     report[GS_SEGSORT_R_ROUTE] = h->last_route;
     if (h->last_route == GS_SEGSORT_LONG_DEVICE) {
-        report[GS_SEGSORT_R_UNITS] = h->pinned[gs::SEG16C_UNITS];
+        report[GS_SEGSORT_R_UNITS] = h->ws.pinned[gs::SEG16C_UNITS];
         report[GS_SEGSORT_R_UNIT_CAP] = h->last_unit_cap;
         report[GS_SEGSORT_R_FORMS] = h->last_forms;
     }
-    report[GS_SEGSORT_R_LONG] = h->pinned[gs::SEGC_COUNT + gs::SEG_CLASS_LONG];
-    report[GS_SEGSORT_R_STATUS] = h->pinned[gs::SEGC_STATUS] | (h->pinned[gs::SEG16C_INTERNAL] != 0u ? 256u : 0u);
+    report[GS_SEGSORT_R_LONG] = h->ws.pinned[gs::SEGC_COUNT + gs::SEG_CLASS_LONG];
+    report[GS_SEGSORT_R_STATUS] = h->ws.pinned[gs::SEGC_STATUS] | (h->ws.pinned[gs::SEG16C_INTERNAL] != 0u ? 256u : 0u);
     report[GS_SEGSORT_R_RANK] = (uint32_t)h->engine->rank_mode;
     report[GS_SEGSORT_R_N] = h->last_n;
     return GS_OK;
@@ -332,10 +314,10 @@ gs_status gs_segsort_last(gs_segsort* h, uint32_t* report, uint32_t words, void*
 
 gs_status gs_segsort_last_classes(gs_segsort* h, uint32_t* counts, uint32_t words, void* stream) {
     if (!h || !counts || words < GS_SEGSORT_CLASSES + 1) return GS_ERR_ARG;
-    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
-    for (uint32_t c = 0; c < GS_SEGSORT_CLASSES; ++c) counts[c] = h->pinned[gs::SEGC_COUNT + c];
-    counts[GS_SEGSORT_CLASSES] = h->pinned[gs::SEGC_MAXLEN];
+    for (uint32_t c = 0; c < GS_SEGSORT_CLASSES; ++c) counts[c] = h->ws.pinned[gs::SEGC_COUNT + c];
+    counts[GS_SEGSORT_CLASSES] = h->ws.pinned[gs::SEGC_MAXLEN];
     return GS_OK;
 }
 

@@ -1,12 +1,12 @@
-// sort16_host.hpp — part of the gpusort_capi.hip translation unit: the gs_sort16 handle (sort16_kernels.hpp) and its entries.
-// No counterpart in the reference project.
+// sort16_host.hpp — part of the gpusort_capi.hip translation unit: the gs_sort16 handle (sort16_kernels.hpp) and its entries: the
+// layout, the plan, the launches of the two routes and the report.  Allocation, create/destroy, the control read-back, the rank mode
+// and the buffer predicates are handle_core.hpp's.  No counterpart in the reference project.
 struct gs_sort16 {
     uint32_t max_keys;
     gs_mode mode;
     uint32_t value_bytes;
     int rank_mode;               // the scatter's ranking: 0 ballot multi-split, 1 returning LDS atomic (probed at create)
-    char* dev = nullptr;         // one allocation: see sort16_layout
-    uint32_t* pinned = nullptr;  // read-back of the control block
+    Workspace ws;                // one allocation: see sort16_layout; the control block lies at its start
     // the last call (gs_sort16_last)
     uint32_t last_route = GS_SORT16_ROUTE_NONE, last_n = 0, last_forms = 0, last_plan[4] = {0u, 0u, 0u, 0u};
 };
@@ -20,14 +20,13 @@ struct Sort16Layout {
 // keys only: the 65 536-bin histogram and its prefix; pairs: the per-range digit table and its bases.  Independent of max_keys.
 Sort16Layout sort16_layout(bool pairs) {
     Sort16Layout l{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t a = at; at += (bytes + 255u) & ~(size_t)255u; return a; };
-    l.ctl = take(gs::S16C_WORDS * 4u);
-    l.hist = take(pairs ? 0u : gs::S16_BINS * 4u);
-    l.prefix = take(pairs ? 0u : (gs::S16_BINS + 1u) * 4u);
-    l.table = take(pairs ? (size_t)gs::S16_PCAP * gs::RADIX * 4u : 0u);
-    l.bases = take(pairs ? (size_t)gs::S16_PCAP * gs::RADIX * 4u : 0u);
-    l.total = at;
+    Arena a;
+    l.ctl = a.take(gs::S16C_WORDS * 4u);
+    l.hist = a.take(pairs ? 0u : gs::S16_BINS * 4u);
+    l.prefix = a.take(pairs ? 0u : (gs::S16_BINS + 1u) * 4u);
+    l.table = a.take(pairs ? (size_t)gs::S16_PCAP * gs::RADIX * 4u : 0u);
+    l.bases = a.take(pairs ? (size_t)gs::S16_PCAP * gs::RADIX * 4u : 0u);
+    l.total = a.total();
     return l;
 }
 
@@ -59,13 +58,13 @@ inline S16Scatter s16_scatter(uint32_t vm, int rank, uint32_t* form) {
 
 gs_status sort16_run_keys(gs_sort16* h, uint16_t* keys, uint32_t n, uint32_t kt, uint32_t flip, hipStream_t s) {
     const Sort16Layout l = sort16_layout(false);
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->dev + l.ctl);
-    uint32_t* hist = reinterpret_cast<uint32_t*>(h->dev + l.hist);
-    uint32_t* prefix = reinterpret_cast<uint32_t*>(h->dev + l.prefix);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->ws.dev + l.ctl);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(h->ws.dev + l.hist);
+    uint32_t* prefix = reinterpret_cast<uint32_t*>(h->ws.dev + l.prefix);
     const uint32_t* plan = h->last_plan;
     // the clear: status word and histogram lie side by side (ctl, hist)
     const uint32_t groups = (uint32_t)((l.prefix - l.ctl) / 16u);
-    hipLaunchKernelGGL(gs::s16_clear_kernel, dim3(div_up(groups, 256u)), dim3(256), 0, s, reinterpret_cast<uint4*>(h->dev + l.ctl), groups);
+    hipLaunchKernelGGL(gs::s16_clear_kernel, dim3(div_up(groups, 256u)), dim3(256), 0, s, reinterpret_cast<uint4*>(h->ws.dev + l.ctl), groups);
     hipLaunchKernelGGL(gs::s16_hist_kernel, dim3(2u * plan[0]), dim3(gs::S16_KTHREADS), 0, s, keys, n, plan[1], kt, flip, hist);
     hipLaunchKernelGGL(gs::s16_scan_kernel, dim3(1), dim3(gs::S16_KTHREADS), 0, s, hist, prefix, n, ctl);
     hipLaunchKernelGGL(gs::s16_fill_kernel, dim3(div_up(n, gs::S16_KTILE)), dim3(gs::S16_KTHREADS), 0, s, keys, prefix, n, kt, flip, ctl);
@@ -78,23 +77,20 @@ gs_status sort16_run_keys(gs_sort16* h, uint16_t* keys, uint32_t n, uint32_t kt,
 gs_status sort16_run_pairs(gs_sort16* h, uint16_t* keys, void* vals, uint16_t* alt_keys, void* alt_vals, uint32_t n, uint32_t kt, bool descending,
                            bool positions, hipStream_t s) {
     const Sort16Layout l = sort16_layout(true);
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->dev + l.ctl);
-    uint32_t* table = reinterpret_cast<uint32_t*>(h->dev + l.table);
-    uint32_t* bases = reinterpret_cast<uint32_t*>(h->dev + l.bases);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->ws.dev + l.ctl);
+    uint32_t* table = reinterpret_cast<uint32_t*>(h->ws.dev + l.table);
+    uint32_t* bases = reinterpret_cast<uint32_t*>(h->ws.dev + l.bases);
     const uint32_t ranges = h->last_plan[0], per = h->last_plan[1];
-    hipLaunchKernelGGL(gs::s16_clear_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<uint4*>(h->dev + l.ctl), gs::S16C_WORDS / 4u);
+    hipLaunchKernelGGL(gs::s16_clear_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<uint4*>(h->ws.dev + l.ctl), gs::S16C_WORDS / 4u);
     uint32_t forms = GS_SORT16_F_COUNT | GS_SORT16_F_PSCAN;
     for (uint32_t pass = 0; pass < 2; ++pass) {
-        const uint16_t* kin = pass == 0 ? keys : alt_keys;
-        uint16_t* kout = pass == 0 ? alt_keys : keys;
-        const void* vin = pass == 0 ? vals : alt_vals;
-        void* vout = pass == 0 ? alt_vals : vals;
+        const PingPong<uint16_t> b = ping_pong(pass, keys, vals, alt_keys, alt_vals);
         const uint32_t vm = (positions && pass == 0) ? 1u : h->value_bytes;
         uint32_t form = 0;
         const S16Scatter scatter = s16_scatter(vm, h->rank_mode, &form);
-        hipLaunchKernelGGL(gs::s16_count_kernel, dim3(ranges), dim3(gs::S16_PTHREADS), 0, s, kin, n, per, kt, pass * 8u, table);
+        hipLaunchKernelGGL(gs::s16_count_kernel, dim3(ranges), dim3(gs::S16_PTHREADS), 0, s, b.kin, n, per, kt, pass * 8u, table);
         hipLaunchKernelGGL(gs::s16_pscan_kernel, dim3(1), dim3(gs::RADIX), 0, s, table, bases, ranges, n, ctl);
-        scatter(s, ranges, kin, vin, kout, vout, n, per, kt, pass * 8u, (descending && pass == 1) ? 1u : 0u, bases, ctl);
+        scatter(s, ranges, b.kin, b.vin, b.kout, b.vout, n, per, kt, pass * 8u, (descending && pass == 1) ? 1u : 0u, bases, ctl);
         forms |= form;
     }
     GS_HIP(hipGetLastError());
@@ -109,14 +105,9 @@ gs_status sort16_impl(gs_sort16* h, void* d_keys, void* d_vals, void* d_alt_keys
     if (!h || !d_keys || misaligned(d_keys) || !is_key16(kt) || !valid_order(order)) return GS_ERR_ARG;
     const bool pairs = what != 0;
     if (pairs != (h->mode == GS_MODE_PAIRS) || (what == 2 && h->value_bytes != 4u)) return GS_ERR_MODE;
-    if (pairs && (!d_vals || misaligned(d_vals) || !d_alt_keys || misaligned(d_alt_keys) || !d_alt_vals || misaligned(d_alt_vals))) return GS_ERR_ARG;
+    if (pairs && (!d_vals || misaligned(d_vals) || !alt_buffers_present(d_alt_keys, d_alt_vals, true))) return GS_ERR_ARG;
     if (n == 0 || n > h->max_keys) return GS_ERR_SIZE;
-    if (pairs) {
-        const size_t kb = (size_t)n * 2u, vb = (size_t)n * h->value_bytes;
-        const void* p[4] = {d_keys, d_alt_keys, d_vals, d_alt_vals};
-        const size_t b[4] = {kb, kb, vb, vb};
-        if (any_overlap(p, b, 4)) return GS_ERR_ARG;
-    }
+    if (pairs && !alt_buffers_disjoint(d_keys, d_alt_keys, d_vals, d_alt_vals, n, 2u, h->value_bytes, true)) return GS_ERR_ARG;
     if (!S16_BUILT) return GS_ERR_MODE;  // this build flavour has no 16-bit sort
 #if GS_SORT16_BUILT
     h->last_route = GS_SORT16_ROUTE_NONE;
@@ -152,38 +143,14 @@ gs_status gs_sort16_plan(uint32_t n, gs_mode mode, uint32_t value_bytes, uint32_
 }
 
 gs_status gs_sort16_create(gs_sort16** out, uint32_t max_keys, gs_mode mode, uint32_t value_bytes) {
-    if (!out) return GS_ERR_ARG;
-    *out = nullptr;
-    if (max_keys == 0 || max_keys > GS_MAX_KEYS) return GS_ERR_SIZE;
-    if (!mode_value_ok(mode, value_bytes)) return GS_ERR_MODE;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return GS_ERR_NO_DEVICE;
-    gs_sort16* h = new (std::nothrow) gs_sort16();
-    if (!h) return GS_ERR_ARG;
-    h->max_keys = max_keys;
-    h->mode = mode;
-    h->value_bytes = value_bytes;
-    h->rank_mode = lds_atomic_order_ok() ? 1 : 0;  // the probe of gs_onesweep_create, once per device
-    const Sort16Layout l = sort16_layout(mode == GS_MODE_PAIRS);
-    hipError_t e = hipMalloc(&h->dev, l.total);
-    if (e == hipSuccess) e = hipMemset(h->dev + l.ctl, 0, gs::S16C_WORDS * sizeof(uint32_t));  // gs_sort16_check may run before any call
-    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, gs::S16C_WORDS * sizeof(uint32_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)gs_sort16_destroy(h);
-        return GS_ERR_HIP;
-    }
-    *out = h;
-    return GS_OK;
+    return handle_create(out, max_keys != 0 && max_keys <= GS_MAX_KEYS, mode, value_bytes, [&](gs_sort16* h) {
+        h->max_keys = max_keys;
+        const Sort16Layout l = sort16_layout(mode == GS_MODE_PAIRS);
+        return h->ws.alloc(l.total, l.ctl, gs::S16C_WORDS, gs::S16C_WORDS);
+    });
 }
 
-gs_status gs_sort16_destroy(gs_sort16* h) {
-    if (!h) return GS_ERR_ARG;
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->dev) (void)hipFree(h->dev);
-    delete h;
-    return GS_OK;
-}
+gs_status gs_sort16_destroy(gs_sort16* h) { return handle_destroy(h); }
 
 gs_status gs_sort16_sort_keys(gs_sort16* h, void* d_keys, uint32_t n, gs_key_type key_type, gs_order order, void* stream) {
     return sort16_impl(h, d_keys, nullptr, nullptr, nullptr, n, key_type, order, static_cast<hipStream_t>(stream), 0);
@@ -201,35 +168,29 @@ gs_status gs_sort16_argsort(gs_sort16* h, void* d_keys, void* d_pos, void* d_alt
 
 gs_status gs_sort16_check(gs_sort16* h, void* stream) {
     if (!h) return GS_ERR_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    GS_HIP(hipMemcpyAsync(h->pinned, h->dev, gs::S16C_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));
-    return h->pinned[gs::S16C_STATUS] != 0u ? GS_ERR_HIP : GS_OK;
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
+    if (rd != GS_OK) return rd;
+    return h->ws.pinned[gs::S16C_STATUS] != 0u ? GS_ERR_HIP : GS_OK;
 }
 
 gs_status gs_sort16_last(gs_sort16* h, uint32_t* report, uint32_t words, void* stream) {
     if (!h || !report || words < GS_SORT16_REPORT_WORDS) return GS_ERR_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    GS_HIP(hipMemcpyAsync(h->pinned, h->dev, gs::S16C_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
+    if (rd != GS_OK) return rd;
     for (uint32_t i = 0; i < GS_SORT16_REPORT_WORDS; ++i) report[i] = 0;
     report[GS_SORT16_R_ROUTE] = h->last_route;
     report[GS_SORT16_R_RANGES] = h->last_plan[0];
     report[GS_SORT16_R_PER_RANGE] = h->last_plan[1];
     report[GS_SORT16_R_TILE] = h->last_plan[2];
     report[GS_SORT16_R_FORMS] = h->last_forms;
-    report[GS_SORT16_R_STATUS] = h->pinned[gs::S16C_STATUS];
+    report[GS_SORT16_R_STATUS] = h->ws.pinned[gs::S16C_STATUS];
     report[GS_SORT16_R_N] = h->last_n;
     report[GS_SORT16_R_RANK] = (uint32_t)h->rank_mode;
     return GS_OK;
 }
 
-gs_status gs_sort16_set_rank_mode(gs_sort16* h, int mode) {
-    if (!h || (mode != 0 && mode != 1)) return GS_ERR_ARG;
-    h->rank_mode = mode;
-    return GS_OK;
-}
+gs_status gs_sort16_set_rank_mode(gs_sort16* h, int mode) { return handle_set_rank_mode(h, mode); }
 
-int gs_sort16_get_rank_mode(gs_sort16* h) { return h ? h->rank_mode : -1; }
+int gs_sort16_get_rank_mode(gs_sort16* h) { return handle_get_rank_mode(h); }
 
 }  // extern "C"

@@ -1,12 +1,12 @@
 // sortrows16_host.hpp — part of the gpusort_capi.hip translation unit: the gs_sort_rows16 handle (sortrows16_kernels.hpp) and its
-// entries.  No counterpart in the reference project.
+// entries: the layout, the plan, the launches of the two routes and the report.  Allocation, create/destroy, the control read-back, the
+// rank mode, the buffer predicate and the ping-pong are handle_core.hpp's.  No counterpart in the reference project.
 struct gs_sort_rows16 {
     uint32_t max_keys;
     gs_mode mode;
     uint32_t value_bytes;
     int rank_mode;               // the scatter's ranking and that of the LDS route's workgroup classes (probed at create)
-    char* dev = nullptr;         // one allocation: see sort_rows16_layout
-    uint32_t* pinned = nullptr;  // read-back of the control block
+    Workspace ws;                // one allocation: see sort_rows16_layout
     // the last call (gs_sort_rows16_last)
     uint32_t last_route = GS_SORT_ROWS_ROUTE_NONE, last_rows = 0, last_row_len = 0, last_forms = 0, last_parts = 0, last_per_part = 0;
 };
@@ -23,13 +23,12 @@ struct SortRows16Layout {
 // ctl: the handle's control block; table, bases: sort_rows16_units x 256 words each
 SortRows16Layout sort_rows16_layout(uint32_t max_keys, uint32_t vb) {
     SortRows16Layout l{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t a = at; at += (bytes + 255u) & ~(size_t)255u; return a; };
+    Arena a;
     const size_t units = sort_rows16_units(max_keys, vb);
-    l.ctl = take(gs::SRC_WORDS * 4u);
-    l.table = take(units * gs::RADIX * 4u);
-    l.bases = take(units * gs::RADIX * 4u);
-    l.total = at;
+    l.ctl = a.take(gs::SRC_WORDS * 4u);
+    l.table = a.take(units * gs::RADIX * 4u);
+    l.bases = a.take(units * gs::RADIX * 4u);
+    l.total = a.total();
     return l;
 }
 
@@ -77,22 +76,19 @@ gs_status sort_rows16_run_lds(gs_sort_rows16* h, uint32_t* ctl, void* keys, void
 // two passes: the low byte from the caller's buffers into the alternate ones, the high byte back.  positions: the first pass makes the value
 gs_status sort_rows16_run_passes(gs_sort_rows16* h, const SortRows16Layout& l, uint16_t* keys, void* vals, uint16_t* alt_keys, void* alt_vals, uint32_t rows,
                                  uint32_t row_len, uint32_t kt, bool descending, bool positions, hipStream_t s) {
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->dev + l.ctl);
-    uint32_t* table = reinterpret_cast<uint32_t*>(h->dev + l.table);
-    uint32_t* bases = reinterpret_cast<uint32_t*>(h->dev + l.bases);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->ws.dev + l.ctl);
+    uint32_t* table = reinterpret_cast<uint32_t*>(h->ws.dev + l.table);
+    uint32_t* bases = reinterpret_cast<uint32_t*>(h->ws.dev + l.bases);
     const uint32_t parts = h->last_parts, per = h->last_per_part, grid = rows * parts;
     uint32_t forms = GS_SORT_ROWS16_F_COUNT | GS_SORT_ROWS16_F_SCAN;
     for (uint32_t pass = 0; pass < gs::SR16_PASSES; ++pass) {
         const bool fwd = pass == 0u;
-        const uint16_t* kin = fwd ? keys : alt_keys;
-        uint16_t* kout = fwd ? alt_keys : keys;
-        const void* vin = fwd ? vals : alt_vals;
-        void* vout = fwd ? alt_vals : vals;
+        const PingPong<uint16_t> b = ping_pong(pass, keys, vals, alt_keys, alt_vals);
         uint32_t form = 0;
         const Sr16Scatter scatter = sr16_scatter((positions && fwd) ? 1u : h->value_bytes, h->rank_mode, &form);
-        hipLaunchKernelGGL(gs::sr16_count_kernel, dim3(grid), dim3(gs::SR_THREADS), 0, s, kin, row_len, parts, per, kt, pass * 8u, table);
+        hipLaunchKernelGGL(gs::sr16_count_kernel, dim3(grid), dim3(gs::SR_THREADS), 0, s, b.kin, row_len, parts, per, kt, pass * 8u, table);
         hipLaunchKernelGGL(gs::sr_scan_kernel, dim3(rows), dim3(gs::RADIX), 0, s, table, bases, parts, row_len, ctl);
-        scatter(s, grid, kin, vin, kout, vout, row_len, parts, per, kt, pass * 8u, (descending && !fwd) ? 1u : 0u, bases, ctl);
+        scatter(s, grid, b.kin, b.vin, b.kout, b.vout, row_len, parts, per, kt, pass * 8u, (descending && !fwd) ? 1u : 0u, bases, ctl);
         forms |= form;
     }
     GS_HIP(hipGetLastError());
@@ -113,13 +109,7 @@ gs_status sort_rows16_impl(gs_sort_rows16* h, void* d_keys, void* d_vals, void* 
     uint32_t plan[GS_SORT_ROWS_PLAN_WORDS];
     sort_rows16_plan(rows, row_len, vb, plan);
     const bool passes = plan[GS_SORT_ROWS_P_ROUTE] == GS_SORT_ROWS_ROUTE_PASSES;
-    if (passes) {
-        if (!d_alt_keys || misaligned(d_alt_keys) || (pairs && (!d_alt_vals || misaligned(d_alt_vals)))) return GS_ERR_ARG;
-        const size_t kb = (size_t)n * 2u, vbytes = (size_t)n * vb;
-        const void* p[4] = {d_keys, d_alt_keys, d_vals, d_alt_vals};
-        const size_t b[4] = {kb, kb, vbytes, vbytes};
-        if (any_overlap(p, b, pairs ? 4 : 2)) return GS_ERR_ARG;
-    }
+    if (passes && !alt_buffers_ok(d_keys, d_alt_keys, d_vals, d_alt_vals, n, 2u, vb, pairs)) return GS_ERR_ARG;
     if (!SR_BUILT) return GS_ERR_MODE;  // this build flavour has no row-wise sort
 #if GS_SORT_ROWS_BUILT
     const SortRows16Layout l = sort_rows16_layout(h->max_keys, vb);
@@ -129,7 +119,7 @@ gs_status sort_rows16_impl(gs_sort_rows16* h, void* d_keys, void* d_vals, void* 
     h->last_row_len = row_len;
     h->last_parts = plan[GS_SORT_ROWS_P_PARTS];
     h->last_per_part = plan[GS_SORT_ROWS_P_PER_PART];
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->dev + l.ctl);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->ws.dev + l.ctl);
     hipLaunchKernelGGL(gs::s16_clear_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<uint4*>(ctl), gs::SRC_WORDS / 4u);
     h->last_forms = GS_SORT_ROWS16_F_CLEAR;
     const bool desc = order == GS_ORDER_DESCENDING;
@@ -142,13 +132,6 @@ gs_status sort_rows16_impl(gs_sort_rows16* h, void* d_keys, void* d_vals, void* 
     (void)s; (void)d_alt_keys; (void)d_alt_vals; (void)d_vals; (void)n;
     return GS_ERR_MODE;
 #endif
-}
-
-// the control block -> h->pinned (synchronises)
-gs_status sort_rows16_read_ctl(gs_sort_rows16* h, hipStream_t s) {
-    GS_HIP(hipMemcpyAsync(h->pinned, h->dev + sort_rows16_layout(h->max_keys, h->value_bytes).ctl, gs::SRC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));
-    return GS_OK;
 }
 }  // namespace
 
@@ -168,38 +151,14 @@ gs_status gs_sort_rows16_plan(uint32_t rows, uint32_t row_len, gs_mode mode, uin
 }
 
 gs_status gs_sort_rows16_create(gs_sort_rows16** out, uint32_t max_keys, gs_mode mode, uint32_t value_bytes) {
-    if (!out) return GS_ERR_ARG;
-    *out = nullptr;
-    if (max_keys == 0 || max_keys > GS_MAX_KEYS) return GS_ERR_SIZE;
-    if (!mode_value_ok(mode, value_bytes)) return GS_ERR_MODE;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return GS_ERR_NO_DEVICE;
-    gs_sort_rows16* h = new (std::nothrow) gs_sort_rows16();
-    if (!h) return GS_ERR_ARG;
-    h->max_keys = max_keys;
-    h->mode = mode;
-    h->value_bytes = value_bytes;
-    h->rank_mode = lds_atomic_order_ok() ? 1 : 0;  // the probe of gs_onesweep_create, once per device
-    const SortRows16Layout l = sort_rows16_layout(max_keys, value_bytes);
-    hipError_t e = hipMalloc(&h->dev, l.total);
-    if (e == hipSuccess) e = hipMemset(h->dev + l.ctl, 0, gs::SRC_WORDS * sizeof(uint32_t));  // gs_sort_rows16_check may run before any call
-    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, gs::SRC_WORDS * sizeof(uint32_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)gs_sort_rows16_destroy(h);
-        return GS_ERR_HIP;
-    }
-    *out = h;
-    return GS_OK;
+    return handle_create(out, max_keys != 0 && max_keys <= GS_MAX_KEYS, mode, value_bytes, [&](gs_sort_rows16* h) {
+        h->max_keys = max_keys;
+        const SortRows16Layout l = sort_rows16_layout(max_keys, value_bytes);
+        return h->ws.alloc(l.total, l.ctl, gs::SRC_WORDS, gs::SRC_WORDS);
+    });
 }
 
-gs_status gs_sort_rows16_destroy(gs_sort_rows16* h) {
-    if (!h) return GS_ERR_ARG;
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->dev) (void)hipFree(h->dev);
-    delete h;
-    return GS_OK;
-}
+gs_status gs_sort_rows16_destroy(gs_sort_rows16* h) { return handle_destroy(h); }
 
 gs_status gs_sort_rows16_keys(gs_sort_rows16* h, void* d_keys, void* d_alt, uint32_t rows, uint32_t row_len, gs_key_type key_type, gs_order order,
                               void* stream) {
@@ -218,14 +177,14 @@ gs_status gs_sort_rows16_argsort(gs_sort_rows16* h, void* d_keys, void* d_pos, v
 
 gs_status gs_sort_rows16_check(gs_sort_rows16* h, void* stream) {
     if (!h) return GS_ERR_ARG;
-    const gs_status rd = sort_rows16_read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
-    return h->pinned[gs::SRC_STATUS] != 0u ? GS_ERR_HIP : GS_OK;
+    return h->ws.pinned[gs::SRC_STATUS] != 0u ? GS_ERR_HIP : GS_OK;
 }
 
 gs_status gs_sort_rows16_last(gs_sort_rows16* h, uint32_t* report, uint32_t words, void* stream) {
     if (!h || !report || words < GS_SORT_ROWS_REPORT_WORDS) return GS_ERR_ARG;
-    const gs_status rd = sort_rows16_read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
     for (uint32_t i = 0; i < GS_SORT_ROWS_REPORT_WORDS; ++i) report[i] = 0;
     report[GS_SORT_ROWS_R_ROUTE] = h->last_route;
@@ -233,18 +192,14 @@ gs_status gs_sort_rows16_last(gs_sort_rows16* h, uint32_t* report, uint32_t word
     report[GS_SORT_ROWS_R_ROW_LEN] = h->last_row_len;
     report[GS_SORT_ROWS_R_PARTS] = h->last_parts;
     report[GS_SORT_ROWS_R_FORMS] = h->last_forms;
-    report[GS_SORT_ROWS_R_STATUS] = h->pinned[gs::SRC_STATUS];
+    report[GS_SORT_ROWS_R_STATUS] = h->ws.pinned[gs::SRC_STATUS];
     report[GS_SORT_ROWS_R_RANK] = (uint32_t)h->rank_mode;
     report[GS_SORT_ROWS_R_PER_PART] = h->last_per_part;
     return GS_OK;
 }
 
-gs_status gs_sort_rows16_set_rank_mode(gs_sort_rows16* h, int mode) {
-    if (!h || (mode != 0 && mode != 1)) return GS_ERR_ARG;
-    h->rank_mode = mode;
-    return GS_OK;
-}
+gs_status gs_sort_rows16_set_rank_mode(gs_sort_rows16* h, int mode) { return handle_set_rank_mode(h, mode); }
 
-int gs_sort_rows16_get_rank_mode(gs_sort_rows16* h) { return h ? h->rank_mode : -1; }
+int gs_sort_rows16_get_rank_mode(gs_sort_rows16* h) { return handle_get_rank_mode(h); }
 
 }  // extern "C"

@@ -1,12 +1,12 @@
-// sortrows_host.hpp — part of the gpusort_capi.hip translation unit: the gs_sort_rows handle (sortrows_kernels.hpp) and its entries.
-// No counterpart in the reference project.
+// sortrows_host.hpp — part of the gpusort_capi.hip translation unit: the gs_sort_rows handle (sortrows_kernels.hpp) and its entries:
+// the layout, the plan, the launches of the two routes and the report.  Allocation, create/destroy, the control read-back, the rank
+// mode, the buffer predicate and the ping-pong are handle_core.hpp's.  No counterpart in the reference project.
 struct gs_sort_rows {
     uint32_t max_keys;
     gs_mode mode;
     uint32_t value_bytes;
     int rank_mode;               // the scatter's ranking and that of the LDS route's workgroup classes (probed at create)
-    char* dev = nullptr;         // one allocation: see sort_rows_layout
-    uint32_t* pinned = nullptr;  // read-back of the two control blocks
+    Workspace ws;                // one allocation: see sort_rows_layout; its control block is the two control blocks, read back as one
     // the last call (gs_sort_rows_last)
     uint32_t last_route = GS_SORT_ROWS_ROUTE_NONE, last_rows = 0, last_row_len = 0, last_forms = 0, last_parts = 0, last_per_part = 0;
 };
@@ -34,15 +34,14 @@ struct SortRowsLayout {
 // packed class); offsets: rows + 1 words; table, bases: sort_rows_units x 256 words each
 SortRowsLayout sort_rows_layout(uint32_t max_keys, uint32_t vb) {
     SortRowsLayout l{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t a = at; at += (bytes + 255u) & ~(size_t)255u; return a; };
+    Arena a;
     const size_t units = sort_rows_units(max_keys, vb);
-    l.ctl = take(gs::SRC_WORDS * 4u);
-    l.seg = take(((size_t)gs::SEGC_WORDS + max_keys / (gs::SEG_PACK_MAX + 1u) + 1u) * 4u);
-    l.offsets = take(((size_t)max_keys + 1u) * 4u);
-    l.table = take(units * gs::RADIX * 4u);
-    l.bases = take(units * gs::RADIX * 4u);
-    l.total = at;
+    l.ctl = a.take(gs::SRC_WORDS * 4u);
+    l.seg = a.take(((size_t)gs::SEGC_WORDS + max_keys / (gs::SEG_PACK_MAX + 1u) + 1u) * 4u);
+    l.offsets = a.take(((size_t)max_keys + 1u) * 4u);
+    l.table = a.take(units * gs::RADIX * 4u);
+    l.bases = a.take(units * gs::RADIX * 4u);
+    l.total = a.total();
     return l;
 }
 
@@ -88,31 +87,27 @@ inline SrScatter sr_scatter(uint32_t vb, int rank, uint32_t* form) {
 // short rows: the segmented sort's LDS classes on uniform offsets, max_segment_len = row_len (its asynchronous path)
 gs_status sort_rows_run_lds(gs_sort_rows* h, const SortRowsLayout& l, uint32_t* keys, void* vals, uint32_t rows, uint32_t row_len, gs_key_type kt, uint32_t desc,
                             hipStream_t s) {
-    uint32_t* offsets = reinterpret_cast<uint32_t*>(h->dev + l.offsets);
+    uint32_t* offsets = reinterpret_cast<uint32_t*>(h->ws.dev + l.offsets);
     hipLaunchKernelGGL(gs::sr_offsets_kernel, dim3(div_up(rows + 1u, 256u)), dim3(256), 0, s, offsets, rows, row_len);
     h->last_forms |= GS_SORT_ROWS_F_OFFSETS | GS_SORT_ROWS_F_LDS;
-    return seg_enqueue_lds(reinterpret_cast<uint32_t*>(h->dev + l.seg), h->rank_mode, h->value_bytes, keys, vals, rows * row_len, offsets, rows, row_len,
+    return seg_enqueue_lds(reinterpret_cast<uint32_t*>(h->ws.dev + l.seg), h->rank_mode, h->value_bytes, keys, vals, rows * row_len, offsets, rows, row_len,
                            gs::seg_class_of(row_len, h->value_bytes), kt, desc, s);
 }
 
 // four passes: bytes 0 and 2 from the caller's buffers into the alternate ones, bytes 1 and 3 back
 gs_status sort_rows_run_passes(gs_sort_rows* h, const SortRowsLayout& l, uint32_t* keys, void* vals, uint32_t* alt_keys, void* alt_vals, uint32_t rows,
                                uint32_t row_len, uint32_t kt, bool descending, hipStream_t s) {
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->dev + l.ctl);
-    uint32_t* table = reinterpret_cast<uint32_t*>(h->dev + l.table);
-    uint32_t* bases = reinterpret_cast<uint32_t*>(h->dev + l.bases);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->ws.dev + l.ctl);
+    uint32_t* table = reinterpret_cast<uint32_t*>(h->ws.dev + l.table);
+    uint32_t* bases = reinterpret_cast<uint32_t*>(h->ws.dev + l.bases);
     const uint32_t parts = h->last_parts, per = h->last_per_part, grid = rows * parts;
     uint32_t form = 0;
     const SrScatter scatter = sr_scatter(h->value_bytes, h->rank_mode, &form);
     for (uint32_t pass = 0; pass < gs::SR_PASSES; ++pass) {
-        const bool fwd = (pass & 1u) == 0u;
-        const uint32_t* kin = fwd ? keys : alt_keys;
-        uint32_t* kout = fwd ? alt_keys : keys;
-        const void* vin = fwd ? vals : alt_vals;
-        void* vout = fwd ? alt_vals : vals;
-        hipLaunchKernelGGL(gs::sr_count_kernel, dim3(grid), dim3(gs::SR_THREADS), 0, s, kin, row_len, parts, per, kt, pass * 8u, table);
+        const PingPong<uint32_t> b = ping_pong(pass, keys, vals, alt_keys, alt_vals);
+        hipLaunchKernelGGL(gs::sr_count_kernel, dim3(grid), dim3(gs::SR_THREADS), 0, s, b.kin, row_len, parts, per, kt, pass * 8u, table);
         hipLaunchKernelGGL(gs::sr_scan_kernel, dim3(rows), dim3(gs::RADIX), 0, s, table, bases, parts, row_len, ctl);
-        scatter(s, grid, kin, vin, kout, vout, row_len, parts, per, kt, pass * 8u, (descending && pass == gs::SR_PASSES - 1u) ? 1u : 0u, bases, ctl);
+        scatter(s, grid, b.kin, b.vin, b.kout, b.vout, row_len, parts, per, kt, pass * 8u, (descending && pass == gs::SR_PASSES - 1u) ? 1u : 0u, bases, ctl);
     }
     GS_HIP(hipGetLastError());
     h->last_forms |= GS_SORT_ROWS_F_COUNT | GS_SORT_ROWS_F_SCAN | form;
@@ -130,13 +125,7 @@ gs_status sort_rows_impl(gs_sort_rows* h, void* d_keys, void* d_vals, void* d_al
     uint32_t plan[GS_SORT_ROWS_PLAN_WORDS];
     sort_rows_plan(rows, row_len, vb, plan);
     const bool passes = plan[GS_SORT_ROWS_P_ROUTE] == GS_SORT_ROWS_ROUTE_PASSES;
-    if (passes) {
-        if (!d_alt_keys || misaligned(d_alt_keys) || (pairs && (!d_alt_vals || misaligned(d_alt_vals)))) return GS_ERR_ARG;
-        const size_t kb = (size_t)n * 4u, vbytes = (size_t)n * vb;
-        const void* p[4] = {d_keys, d_alt_keys, d_vals, d_alt_vals};
-        const size_t b[4] = {kb, kb, vbytes, vbytes};
-        if (any_overlap(p, b, pairs ? 4 : 2)) return GS_ERR_ARG;
-    }
+    if (passes && !alt_buffers_ok(d_keys, d_alt_keys, d_vals, d_alt_vals, n, 4u, vb, pairs)) return GS_ERR_ARG;
     if (!SR_BUILT) return GS_ERR_MODE;  // this build flavour has no row-wise sort
 #if GS_SORT_ROWS_BUILT
     const SortRowsLayout l = sort_rows_layout(h->max_keys, vb);
@@ -147,7 +136,7 @@ gs_status sort_rows_impl(gs_sort_rows* h, void* d_keys, void* d_vals, void* d_al
     h->last_parts = plan[GS_SORT_ROWS_P_PARTS];
     h->last_per_part = plan[GS_SORT_ROWS_P_PER_PART];
     // the clear: both control blocks (they lie side by side), so that neither route reports an earlier call's status
-    hipLaunchKernelGGL(gs::s16_clear_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<uint4*>(h->dev + l.ctl), SR_CTL_WORDS / 4u);
+    hipLaunchKernelGGL(gs::s16_clear_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<uint4*>(h->ws.dev + l.ctl), SR_CTL_WORDS / 4u);
     h->last_forms = GS_SORT_ROWS_F_CLEAR;
     const bool desc = order == GS_ORDER_DESCENDING;
     const gs_status st = passes ? sort_rows_run_passes(h, l, static_cast<uint32_t*>(d_keys), d_vals, static_cast<uint32_t*>(d_alt_keys), d_alt_vals, rows,
@@ -161,15 +150,9 @@ gs_status sort_rows_impl(gs_sort_rows* h, void* d_keys, void* d_vals, void* d_al
 #endif
 }
 
-// both control blocks -> h->pinned (synchronises): the handle's own, then the segmented sort's
-gs_status sort_rows_read_ctl(gs_sort_rows* h, hipStream_t s) {
-    const SortRowsLayout l = sort_rows_layout(h->max_keys, h->value_bytes);
-    GS_HIP(hipMemcpyAsync(h->pinned, h->dev + l.ctl, SR_CTL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));
-    return GS_OK;
-}
-// the status word of the report: the pass route's bits, the LDS route's (gs::SEG_ST_*) shifted by 8
-inline uint32_t sort_rows_status(const gs_sort_rows* h) { return h->pinned[gs::SRC_STATUS] | (h->pinned[gs::SRC_WORDS + gs::SEGC_STATUS] << 8); }
+// the status word of the report, from both control blocks in h->ws.pinned (the handle's own, then the segmented sort's): the pass
+// route's bits, the LDS route's (gs::SEG_ST_*) shifted by 8
+inline uint32_t sort_rows_status(const gs_sort_rows* h) { return h->ws.pinned[gs::SRC_STATUS] | (h->ws.pinned[gs::SRC_WORDS + gs::SEGC_STATUS] << 8); }
 }  // namespace
 
 extern "C" {
@@ -188,38 +171,14 @@ gs_status gs_sort_rows_plan(uint32_t rows, uint32_t row_len, gs_mode mode, uint3
 }
 
 gs_status gs_sort_rows_create(gs_sort_rows** out, uint32_t max_keys, gs_mode mode, uint32_t value_bytes) {
-    if (!out) return GS_ERR_ARG;
-    *out = nullptr;
-    if (max_keys == 0 || max_keys > GS_MAX_KEYS) return GS_ERR_SIZE;
-    if (!mode_value_ok(mode, value_bytes)) return GS_ERR_MODE;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return GS_ERR_NO_DEVICE;
-    gs_sort_rows* h = new (std::nothrow) gs_sort_rows();
-    if (!h) return GS_ERR_ARG;
-    h->max_keys = max_keys;
-    h->mode = mode;
-    h->value_bytes = value_bytes;
-    h->rank_mode = lds_atomic_order_ok() ? 1 : 0;  // the probe of gs_onesweep_create, once per device
-    const SortRowsLayout l = sort_rows_layout(max_keys, value_bytes);
-    hipError_t e = hipMalloc(&h->dev, l.total);
-    if (e == hipSuccess) e = hipMemset(h->dev + l.ctl, 0, SR_CTL_WORDS * sizeof(uint32_t));  // gs_sort_rows_check may run before any call
-    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, SR_CTL_WORDS * sizeof(uint32_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)gs_sort_rows_destroy(h);
-        return GS_ERR_HIP;
-    }
-    *out = h;
-    return GS_OK;
+    return handle_create(out, max_keys != 0 && max_keys <= GS_MAX_KEYS, mode, value_bytes, [&](gs_sort_rows* h) {
+        h->max_keys = max_keys;
+        const SortRowsLayout l = sort_rows_layout(max_keys, value_bytes);
+        return h->ws.alloc(l.total, l.ctl, SR_CTL_WORDS, SR_CTL_WORDS);
+    });
 }
 
-gs_status gs_sort_rows_destroy(gs_sort_rows* h) {
-    if (!h) return GS_ERR_ARG;
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->dev) (void)hipFree(h->dev);
-    delete h;
-    return GS_OK;
-}
+gs_status gs_sort_rows_destroy(gs_sort_rows* h) { return handle_destroy(h); }
 
 gs_status gs_sort_rows_keys(gs_sort_rows* h, void* d_keys, void* d_alt, uint32_t rows, uint32_t row_len, gs_key_type key_type, gs_order order, void* stream) {
     return sort_rows_impl(h, d_keys, nullptr, d_alt, nullptr, rows, row_len, key_type, order, static_cast<hipStream_t>(stream), false);
@@ -232,14 +191,14 @@ gs_status gs_sort_rows_pairs(gs_sort_rows* h, void* d_keys, void* d_vals, void* 
 
 gs_status gs_sort_rows_check(gs_sort_rows* h, void* stream) {
     if (!h) return GS_ERR_ARG;
-    const gs_status rd = sort_rows_read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
     return sort_rows_status(h) != 0u ? GS_ERR_HIP : GS_OK;
 }
 
 gs_status gs_sort_rows_last(gs_sort_rows* h, uint32_t* report, uint32_t words, void* stream) {
     if (!h || !report || words < GS_SORT_ROWS_REPORT_WORDS) return GS_ERR_ARG;
-    const gs_status rd = sort_rows_read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
     for (uint32_t i = 0; i < GS_SORT_ROWS_REPORT_WORDS; ++i) report[i] = 0;
     report[GS_SORT_ROWS_R_ROUTE] = h->last_route;
@@ -253,12 +212,8 @@ gs_status gs_sort_rows_last(gs_sort_rows* h, uint32_t* report, uint32_t words, v
     return GS_OK;
 }
 
-gs_status gs_sort_rows_set_rank_mode(gs_sort_rows* h, int mode) {
-    if (!h || (mode != 0 && mode != 1)) return GS_ERR_ARG;
-    h->rank_mode = mode;
-    return GS_OK;
-}
+gs_status gs_sort_rows_set_rank_mode(gs_sort_rows* h, int mode) { return handle_set_rank_mode(h, mode); }
 
-int gs_sort_rows_get_rank_mode(gs_sort_rows* h) { return h ? h->rank_mode : -1; }
+int gs_sort_rows_get_rank_mode(gs_sort_rows* h) { return handle_get_rank_mode(h); }
 
 }  // extern "C"

@@ -1,12 +1,12 @@
 // topk_host.hpp — part of the gpusort_capi.hip translation unit: the gs_topk handle (topk_kernels.hpp) and its entries.
-// No counterpart in the reference project.
+// The handle's own: the engine, the 1-D routes, the row-wise routes and the LOOP route's staging.  The layout arena and the control
+// block's allocation and read-back are handle_core.hpp's.  No counterpart in the reference project.
 struct gs_topk {
     uint32_t max_keys, max_k, sort_cap;
     gs_mode mode;
     uint32_t value_bytes;
     gs_onesweep* engine = nullptr;  // the final sort of the k selected elements (and the single-tile route's sort)
-    char* dev = nullptr;            // one allocation: see topk_layout
-    uint32_t* pinned = nullptr;     // read-back of the control block
+    Workspace ws;                   // one allocation: see topk_layout
     uint32_t last_route = GS_TOPK_ROUTE_NONE, last_flip = 0;
     bool sort_failed = false;       // the engine refused a call on the host side
     // the last row-wise call (gs_topk_rows_last)
@@ -25,7 +25,6 @@ constexpr uint32_t TOPK_SINGLE_MAX_ANY = 32768;  // the largest of them (keys on
 struct TopkLayout {
     size_t ctl, extra, sums, rc, slices, cand_keys, cand_vals, alt_keys, alt_vals, total;
 };
-inline size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
 inline uint32_t topk_sort_cap(uint32_t max_keys, uint32_t max_k) {
     const uint32_t small = max_keys < TOPK_SINGLE_MAX_ANY ? max_keys : TOPK_SINGLE_MAX_ANY;
@@ -34,18 +33,17 @@ inline uint32_t topk_sort_cap(uint32_t max_keys, uint32_t max_k) {
 TopkLayout topk_layout(uint32_t max_keys, uint32_t max_k, uint32_t vb) {
     TopkLayout l{};
     const size_t cap = topk_sort_cap(max_keys, max_k);
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t a = at; at += up256(bytes); return a; };
-    l.ctl = take(gs::TKC_WORDS * 4u);
-    l.extra = take(2u * gs::TK_BINS * 4u);
-    l.sums = take(gs::TK_BINS * 4u);
-    l.rc = take(2u * 2u * gs::TK_MAX_RANGES * 4u);
-    l.slices = take((size_t)gs::TK_MAX_RANGES * gs::TK_SLICE_WORDS * 4u);
-    l.cand_keys = take((size_t)max_keys * 4u);
-    l.cand_vals = take((size_t)max_keys * vb);
-    l.alt_keys = take(cap * 4u);
-    l.alt_vals = take(cap * vb);
-    l.total = at;
+    Arena a;
+    l.ctl = a.take(gs::TKC_WORDS * 4u);
+    l.extra = a.take(2u * gs::TK_BINS * 4u);
+    l.sums = a.take(gs::TK_BINS * 4u);
+    l.rc = a.take(2u * 2u * gs::TK_MAX_RANGES * 4u);
+    l.slices = a.take((size_t)gs::TK_MAX_RANGES * gs::TK_SLICE_WORDS * 4u);
+    l.cand_keys = a.take((size_t)max_keys * 4u);
+    l.cand_vals = a.take((size_t)max_keys * vb);
+    l.alt_keys = a.take(cap * 4u);
+    l.alt_vals = a.take(cap * vb);
+    l.total = a.total();
     return l;
 }
 
@@ -61,18 +59,6 @@ inline TkScatter tk_scatter(uint32_t vm) {
     return vm == 0 ? launch_tk_scatter<0> : vm == 1 ? launch_tk_scatter<1> : vm == 4 ? launch_tk_scatter<4> : launch_tk_scatter<8>;
 }
 
-// the control block -> h->pinned (synchronises)
-gs_status read_ctl(gs_topk* h, hipStream_t s) {
-    GS_HIP(hipMemcpyAsync(h->pinned, h->dev, gs::TKC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));
-    return GS_OK;
-}
-
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-
 gs_status topk_run(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t n, uint32_t k, void* d_out_keys, void* d_out_vals,
                    gs_key_type kt, gs_order order, hipStream_t s, bool pairs);
 
@@ -85,8 +71,8 @@ gs_status topk_impl(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t
     const bool pos = pairs && !d_vals;  // the value is the element's position
     if (pairs && (!d_out_vals || misaligned(d_out_vals) || (pos ? vb != 4u : misaligned(d_vals)))) return GS_ERR_ARG;
     if (n == 0 || n > h->max_keys || k == 0 || k > n || k > h->max_k) return GS_ERR_SIZE;
-    if (overlaps(d_keys, (size_t)n * 4u, d_out_keys, (size_t)k * 4u) ||
-        (pairs && !pos && overlaps(d_vals, (size_t)n * vb, d_out_vals, (size_t)k * vb)))
+    if (buffers_overlap(d_keys, (size_t)n * 4u, d_out_keys, (size_t)k * 4u) ||
+        (pairs && !pos && buffers_overlap(d_vals, (size_t)n * vb, d_out_vals, (size_t)k * vb)))
         return GS_ERR_ARG;
     if (!TK_BUILT) return GS_ERR_MODE;  // this build flavour has no selection
     return topk_run(h, d_keys, d_vals, n, k, d_out_keys, d_out_vals, kt, order, s, pairs);
@@ -98,11 +84,11 @@ gs_status topk_run(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t 
     const uint32_t vb = h->value_bytes;
     const bool pos = pairs && !d_vals;
     const TopkLayout l = topk_layout(h->max_keys, h->max_k, vb);
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->dev + l.ctl);
-    uint32_t* cand_keys = reinterpret_cast<uint32_t*>(h->dev + l.cand_keys);
-    void* cand_vals = h->dev + l.cand_vals;
-    uint32_t* alt_keys = reinterpret_cast<uint32_t*>(h->dev + l.alt_keys);
-    void* alt_vals = h->dev + l.alt_vals;
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->ws.dev + l.ctl);
+    uint32_t* cand_keys = reinterpret_cast<uint32_t*>(h->ws.dev + l.cand_keys);
+    void* cand_vals = h->ws.dev + l.cand_vals;
+    uint32_t* alt_keys = reinterpret_cast<uint32_t*>(h->ws.dev + l.alt_keys);
+    void* alt_vals = h->ws.dev + l.alt_vals;
     const uint32_t* keys = static_cast<const uint32_t*>(d_keys);
     uint32_t* out = static_cast<uint32_t*>(d_out_keys);
     h->sort_failed = false;
@@ -124,10 +110,10 @@ gs_status topk_run(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t 
         h->last_route = GS_TOPK_ROUTE_SINGLE_TILE;
         return GS_OK;
     }
-    uint32_t* extra = reinterpret_cast<uint32_t*>(h->dev + l.extra);
-    uint32_t* sums = reinterpret_cast<uint32_t*>(h->dev + l.sums);
-    uint32_t* rc = reinterpret_cast<uint32_t*>(h->dev + l.rc);
-    uint32_t* slices = reinterpret_cast<uint32_t*>(h->dev + l.slices);
+    uint32_t* extra = reinterpret_cast<uint32_t*>(h->ws.dev + l.extra);
+    uint32_t* sums = reinterpret_cast<uint32_t*>(h->ws.dev + l.sums);
+    uint32_t* rc = reinterpret_cast<uint32_t*>(h->ws.dev + l.rc);
+    uint32_t* slices = reinterpret_cast<uint32_t*>(h->ws.dev + l.slices);
     const uint32_t flip = order == GS_ORDER_DESCENDING ? 0xffffffffu : 0u, ktu = (uint32_t)kt;
     hipLaunchKernelGGL(gs::tk_init_kernel, dim3(2u * gs::TK_BINS / 4u / 256u), dim3(256), 0, s, ctl, extra, n, k);
     for (uint32_t level = 0; level < 2; ++level) {
@@ -182,7 +168,7 @@ gs_status rows_loop(gs_topk* h, const uint32_t* keys, const char* vals, uint32_t
         if (cap != hipStreamCaptureStatusNone) return GS_ERR_MODE;
         GS_HIP(hipMalloc(&h->loop_stage, l.total));
     }
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->dev + topk_layout(h->max_keys, h->max_k, vb).ctl);
+    uint32_t* ctl = h->ws.ctl();
     hipLaunchKernelGGL(gs::tkr_reset_kernel, dim3(1), dim3(64), 0, s, ctl);  // (the status gathered over the rows starts at 0)
     char* st_in = h->loop_stage;
     char* st_outk = h->loop_stage + l.outk;
@@ -222,8 +208,8 @@ gs_status rows_impl(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t
     const unsigned long long extent = (unsigned long long)(rows - 1u) * row_stride + row_len;
     if (extent > h->max_keys) return GS_ERR_SIZE;
     const size_t out_elems = (size_t)rows * k;
-    if (overlaps(d_keys, (size_t)extent * kb, d_out_keys, out_elems * kb) ||
-        (pairs && !pos && overlaps(d_vals, (size_t)extent * vb, d_out_vals, out_elems * vb)))
+    if (buffers_overlap(d_keys, (size_t)extent * kb, d_out_keys, out_elems * kb) ||
+        (pairs && !pos && buffers_overlap(d_vals, (size_t)extent * vb, d_out_vals, out_elems * vb)))
         return GS_ERR_ARG;
     if (!TK_BUILT) return GS_ERR_MODE;  // this build flavour has no selection
     h->sort_failed = false;
@@ -232,7 +218,7 @@ gs_status rows_impl(gs_topk* h, const void* d_keys, const void* d_vals, uint32_t
     h->rows_rows = rows;
     h->rows_len = row_len;
     h->rows_k = k;
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(h->dev + topk_layout(h->max_keys, h->max_k, vb).ctl);
+    uint32_t* ctl = h->ws.ctl();
     // few, very long rows: one workgroup per row leaves the other CUs idle, and the 1-D route row by row is faster.  Measured (DESIGN.md
     // 3.10): STREAM costs 0.415 ms per 2^20 elements of a row, LOOP 0.078 ms + 0.022 ms per 2^20 elements for every row; LOOP where
     // rows * (0.078 + 0.022 L) <= 0.415 L, in integers below, for the row lengths that were measured (2^19 and up)
@@ -290,13 +276,10 @@ gs_status gs_topk_create(gs_topk** out, uint32_t max_keys, uint32_t max_k, gs_mo
     h->value_bytes = mode == GS_MODE_PAIRS ? value_bytes : 0u;
     h->engine = engine;
     const TopkLayout l = topk_layout(max_keys, max_k, h->value_bytes);
-    hipError_t e = hipMalloc(&h->dev, l.total);
-    if (e == hipSuccess) e = hipMemset(h->dev + l.ctl, 0, gs::TKC_WORDS * sizeof(uint32_t));  // gs_topk_check may run before any call
-    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, gs::TKC_WORDS * sizeof(uint32_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)gs_topk_destroy(h);
-        return GS_ERR_HIP;
+    const gs_status ws = h->ws.alloc(l.total, l.ctl, gs::TKC_WORDS, gs::TKC_WORDS);
+    if (ws != GS_OK) {
+        (void)gs_topk_destroy(h);  // the engine with it
+        return ws;
     }
     *out = h;
     return GS_OK;
@@ -304,8 +287,7 @@ gs_status gs_topk_create(gs_topk** out, uint32_t max_keys, uint32_t max_k, gs_mo
 
 gs_status gs_topk_destroy(gs_topk* h) {
     if (!h) return GS_ERR_ARG;
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->dev) (void)hipFree(h->dev);
+    h->ws.release();
     if (h->loop_stage) (void)hipFree(h->loop_stage);
     if (h->engine) (void)gs_onesweep_destroy(h->engine);
     delete h;
@@ -339,15 +321,15 @@ uint32_t gs_topk_rows_max_k(gs_mode mode, uint32_t value_bytes) {
 
 gs_status gs_topk_rows_last(gs_topk* h, uint32_t* report, uint32_t words, void* stream) {
     if (!h || !report || words < GS_TOPK_ROWS_REPORT_WORDS) return GS_ERR_ARG;
-    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
     for (uint32_t i = 0; i < GS_TOPK_ROWS_REPORT_WORDS; ++i) report[i] = 0;
     report[GS_TOPK_ROWS_R_ROUTE] = h->rows_route;
     report[GS_TOPK_ROWS_R_ROWS] = h->rows_rows;
     report[GS_TOPK_ROWS_R_ROW_LEN] = h->rows_len;
     report[GS_TOPK_ROWS_R_K] = h->rows_k;
-    report[GS_TOPK_ROWS_R_STATUS] = h->pinned[gs::TKC_STATUS];
-    if (h->rows_route == GS_TOPK_ROWS_ROUTE_STREAM) report[GS_TOPK_ROWS_R_READS] = h->pinned[gs::TKR_CTL_READS];
+    report[GS_TOPK_ROWS_R_STATUS] = h->ws.pinned[gs::TKC_STATUS];
+    if (h->rows_route == GS_TOPK_ROWS_ROUTE_STREAM) report[GS_TOPK_ROWS_R_READS] = h->ws.pinned[gs::TKR_CTL_READS];
     return GS_OK;
 }
 
@@ -355,20 +337,20 @@ gs_onesweep* gs_topk_engine(gs_topk* h) { return h ? h->engine : nullptr; }
 
 gs_status gs_topk_check(gs_topk* h, void* stream) {
     if (!h) return GS_ERR_ARG;
-    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
-    if (h->sort_failed || (h->pinned[gs::TKC_STATUS] & gs::TK_ST_INTERNAL)) return GS_ERR_HIP;
+    if (h->sort_failed || (h->ws.pinned[gs::TKC_STATUS] & gs::TK_ST_INTERNAL)) return GS_ERR_HIP;
     return gs_onesweep_check(h->engine, stream);  // the final sort
 }
 
 gs_status gs_topk_last(gs_topk* h, uint32_t* report, uint32_t words, void* stream) {
     if (!h || !report || words < GS_TOPK_REPORT_WORDS) return GS_ERR_ARG;
-    const gs_status rd = read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
     for (uint32_t i = 0; i < GS_TOPK_REPORT_WORDS; ++i) report[i] = 0;
     report[GS_TOPK_R_ROUTE] = h->last_route;
     if (h->last_route != GS_TOPK_ROUTE_SELECT) return GS_OK;
-    const uint32_t* l1 = h->pinned + gs::TKC_LEVEL;
+    const uint32_t* l1 = h->ws.pinned + gs::TKC_LEVEL;
     const uint32_t* l2 = l1 + gs::TKL_WORDS;
     report[GS_TOPK_R_THRESHOLD] = ((l1[gs::TKL_BIN] << 16) | l2[gs::TKL_BIN]) ^ h->last_flip;
     report[GS_TOPK_R_IN_FRONT] = l1[gs::TKL_FRONT] + l2[gs::TKL_FRONT];

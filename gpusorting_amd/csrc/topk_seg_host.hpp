@@ -1,19 +1,23 @@
 // topk_seg_host.hpp — part of the gpusort_capi.hip translation unit: the gs_segtopk handle (topk_seg_kernels.hpp) and its entries.
-// No counterpart in the reference project.
+// The handle's own: the launchers, the per-class launches of a call and the report.  Allocation, create/destroy, the control
+// read-back, the rank mode and the head of a segmented call are handle_core.hpp's.  No counterpart in the reference project.
 struct gs_segtopk {
     uint32_t max_keys, max_segments, max_k;
     gs_mode mode;
     uint32_t value_bytes;
     int rank_mode;               // the ranking of the tile classes: 0 ballot multi-split, 1 returning LDS atomic (probed at create)
-    uint32_t* ctl = nullptr;     // gs::SEGC_WORDS control words, then the class lists (max_segments words)
-    uint32_t* pinned = nullptr;  // read-back of the control block
+    Workspace ws;                // gs::SEGC_WORDS control words, then the class lists (max_segments words)
     // the last call (gs_segtopk_last)
     uint32_t last_forms = 0, last_k = 0;
 };
 
 static_assert(GS_SEGTOPK_R_CLASSES + GS_SEGSORT_CLASSES <= GS_SEGTOPK_R_LONGEST && GS_SEGTOPK_REPORT_WORDS >= 16, "the report holds every class");
 namespace {
-inline size_t segtopk_bytes(uint32_t max_segments) { return (((size_t)gs::SEGC_WORDS + max_segments) * sizeof(uint32_t) + 255u) & ~(size_t)255u; }
+inline size_t segtopk_bytes(uint32_t max_segments) {
+    Arena a;
+    a.take(((size_t)gs::SEGC_WORDS + max_segments) * sizeof(uint32_t));
+    return a.total();
+}
 
 // the kernels are launched directly (no registry family; gs_segtopk_last's forms word accounts for them)
 using TksLauncher = void (*)(hipStream_t, uint32_t grid, const gs::TksArgs& a, uint32_t cls);
@@ -56,12 +60,6 @@ struct TksRoutes {
 };
 constexpr TksRoutes g_tks_routes32{4u, g_tks_vm.data(), g_tks_tile.data(), SEG_WG_LOOP, true};
 
-gs_status segtopk_read_ctl(gs_segtopk* h, hipStream_t s) {
-    GS_HIP(hipMemcpyAsync(h->pinned, h->ctl, gs::SEGC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));
-    return GS_OK;
-}
-
 gs_status segtopk_impl(const TksRoutes& routes, gs_segtopk* h, const void* d_keys, const void* d_vals, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments, uint32_t k,
                        uint32_t max_len, void* d_out_keys, void* d_out_vals, gs_key_type kt, gs_order order, hipStream_t s, bool pairs) {
     if (!h || !d_keys || !d_out_keys || !d_offsets || misaligned(d_keys) || misaligned(d_out_keys) || (reinterpret_cast<uintptr_t>(d_offsets) & 3u) ||
@@ -84,25 +82,21 @@ gs_status segtopk_impl(const TksRoutes& routes, gs_segtopk* h, const void* d_key
     if (allow_long && k > gs::TKR_STAGE) return GS_ERR_SIZE;
     if (!TK_BUILT) return GS_ERR_MODE;  // this build flavour has no selection
     const uint32_t top = allow_long ? gs::SEG_CLASS_LONG : gs::seg_class_of(max_len, vb);  // the highest class a segment can fall in
-    uint32_t* list = h->ctl + gs::SEGC_WORDS;
-    const gs::TksArgs a{static_cast<const uint32_t*>(d_keys), d_vals, static_cast<uint32_t*>(d_out_keys), d_out_vals, d_offsets, list, h->ctl,
+    uint32_t* ctl = h->ws.ctl();
+    const gs::TksArgs a{static_cast<const uint32_t*>(d_keys), d_vals, static_cast<uint32_t*>(d_out_keys), d_out_vals, d_offsets, ctl + gs::SEGC_WORDS, ctl,
                         num_segments, k, (uint32_t)kt, order == GS_ORDER_DESCENDING ? 1u : 0u, max_len};
     const uint32_t vm = !pairs ? 0u : pos ? 1u : vb, vi = (uint32_t)vm_index(vm), rank = h->rank_mode ? 1u : 0u;
     const TksVmLaunchers& f = routes.vm[vi];
     uint32_t forms = GS_SEGTOPK_F_VM << vi;
     h->last_k = k;
     h->last_forms = 0;
-    hipLaunchKernelGGL(gs::seg_reset_kernel, dim3(1), dim3(64), 0, s, h->ctl);
-    const uint32_t seg_blocks = div_up(num_segments, 256);
-    hipLaunchKernelGGL(gs::seg_classify_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, n, vb, max_len, h->ctl);
-    if (top >= 2) hipLaunchKernelGGL(gs::seg_fill_kernel, dim3(seg_blocks), dim3(256), 0, s, d_offsets, num_segments, vb, max_len, h->ctl, list);
+    seg_enqueue_head(ctl, d_offsets, num_segments, n, vb, max_len, top, s);
     f.packed(s, div_up(num_segments, 64), a, 0);
     forms |= GS_SEGTOPK_F_PACKED;
-    // a class whose shortest segment has m elements holds at most n / m segments
-    auto bound = [&](uint32_t min_len) { const uint32_t b = n / min_len; return b < num_segments ? b : num_segments; };
+    const uint32_t vbs = vm == 0 ? 0u : vm == 8 ? 8u : 4u;  // the bytes a value takes in LDS: positions are 4-byte values
     if (top >= 2 && n > gs::SEG_PACK_MAX) {
-        const uint32_t vbs = vm == 0 ? 0u : vm == 8 ? 8u : 4u;
-        f.wave(s, seg_grid(div_up(bound(gs::SEG_PACK_MAX + 1), gs::TKR_WAVE_ROWS), gs::TKR_WAVE_ROWS, (size_t)gs::TKR_WAVE_ROWS * gs::SEG_WAVE_MAX * (8 + vbs)), a, 0);
+        f.wave(s, seg_grid(div_up(seg_class_bound(n, num_segments, gs::SEG_PACK_MAX + 1), gs::TKR_WAVE_ROWS), gs::TKR_WAVE_ROWS,
+                           (size_t)gs::TKR_WAVE_ROWS * gs::SEG_WAVE_MAX * (8 + vbs)), a, 0);
         forms |= GS_SEGTOPK_F_WAVE;
     }
     for (uint32_t c = 3; c <= 7 && c <= top; ++c) {
@@ -111,12 +105,12 @@ gs_status segtopk_impl(const TksRoutes& routes, gs_segtopk* h, const void* d_key
         const Shape sh = g_small_class[c - 3];
         const TksLauncher tile = routes.tile[TksTileTable::index({(int)c - 3, (int)rank, (int)vi})];
         if (!tile) return GS_ERR_MODE;
-        const size_t lds = (size_t)sh.threads * sh.kpt * (4 + (vm == 0 ? 0u : vm == 8 ? 8u : 4u)) + (size_t)sh.threads / 64 * gs::RADIX * 4 + 64;
-        tile(s, routes.tile_loops(sh.threads, sh.kpt) ? seg_grid(bound(min_len), (uint32_t)sh.threads / 64, lds) : bound(min_len), a, c);
+        const uint32_t bound = seg_class_bound(n, num_segments, min_len);
+        tile(s, routes.tile_loops(sh.threads, sh.kpt) ? seg_grid(bound, (uint32_t)sh.threads / 64, seg_wg_lds_bytes(sh, vbs)) : bound, a, c);
         forms |= GS_SEGTOPK_F_TILE(c, rank);
     }
     if (allow_long && n > gs::seg_max_lds(vb)) {
-        const uint32_t longs = bound(gs::seg_max_lds(vb) + 1);
+        const uint32_t longs = seg_class_bound(n, num_segments, gs::seg_max_lds(vb) + 1);
         f.stream(s, routes.stream_loops ? seg_grid(longs, gs::TKR_THREADS / 64, 97u * 1024u) : longs, a, 0);  // (the histogram, the staging, the staged sort's tables: 96.6 KiB)
         forms |= GS_SEGTOPK_F_STREAM;
     }
@@ -131,39 +125,16 @@ extern "C" {
 size_t gs_segtopk_temp_bytes(uint32_t max_segments) { return segtopk_bytes(max_segments); }
 
 gs_status gs_segtopk_create(gs_segtopk** out, uint32_t max_keys, uint32_t max_segments, uint32_t max_k, gs_mode mode, uint32_t value_bytes) {
-    if (!out) return GS_ERR_ARG;
-    *out = nullptr;
-    if (max_keys == 0 || max_keys > GS_MAX_KEYS || max_segments == 0 || max_segments > GS_MAX_KEYS || max_k == 0 || max_k > GS_MAX_KEYS) return GS_ERR_SIZE;
-    if (!mode_value_ok(mode, value_bytes)) return GS_ERR_MODE;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return GS_ERR_NO_DEVICE;
-    gs_segtopk* h = new (std::nothrow) gs_segtopk();
-    if (!h) return GS_ERR_ARG;
-    h->max_keys = max_keys;
-    h->max_segments = max_segments;
-    h->max_k = max_k;
-    h->mode = mode;
-    h->value_bytes = value_bytes;
-    h->rank_mode = lds_atomic_order_ok() ? 1 : 0;  // the probe of gs_onesweep_create, once per device
-    hipError_t e = hipMalloc(&h->ctl, segtopk_bytes(max_segments));
-    if (e == hipSuccess) e = hipMemset(h->ctl, 0, gs::SEGC_WORDS * sizeof(uint32_t));  // gs_segtopk_check may run before any call
-    if (e == hipSuccess) e = hipHostMalloc(&h->pinned, gs::SEGC_WORDS * sizeof(uint32_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)gs_segtopk_destroy(h);
-        return GS_ERR_HIP;
-    }
-    *out = h;
-    return GS_OK;
+    const bool sizes_ok = max_keys != 0 && max_keys <= GS_MAX_KEYS && max_segments != 0 && max_segments <= GS_MAX_KEYS && max_k != 0 && max_k <= GS_MAX_KEYS;
+    return handle_create(out, sizes_ok, mode, value_bytes, [&](gs_segtopk* h) {
+        h->max_keys = max_keys;
+        h->max_segments = max_segments;
+        h->max_k = max_k;
+        return h->ws.alloc(segtopk_bytes(max_segments), 0, gs::SEGC_WORDS, gs::SEGC_WORDS);
+    });
 }
 
-gs_status gs_segtopk_destroy(gs_segtopk* h) {
-    if (!h) return GS_ERR_ARG;
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->ctl) (void)hipFree(h->ctl);
-    delete h;
-    return GS_OK;
-}
+gs_status gs_segtopk_destroy(gs_segtopk* h) { return handle_destroy(h); }
 
 gs_status gs_segtopk_select_keys(gs_segtopk* h, const void* d_keys, uint32_t n, const uint32_t* d_offsets, uint32_t num_segments, uint32_t k,
                                  uint32_t max_segment_len, void* d_out_keys, gs_key_type key_type, gs_order order, void* stream) {
@@ -180,37 +151,33 @@ gs_status gs_segtopk_select_pairs(gs_segtopk* h, const void* d_keys, const void*
 
 gs_status gs_segtopk_check(gs_segtopk* h, void* stream) {
     if (!h) return GS_ERR_ARG;
-    const gs_status rd = segtopk_read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
-    const uint32_t st = h->pinned[gs::SEGC_STATUS];
+    const uint32_t st = h->ws.pinned[gs::SEGC_STATUS];
     if (st & gs::SEG_ST_ARG) return GS_ERR_ARG;
-    if (h->pinned[gs::TKSC_TKR + gs::TKC_STATUS] & gs::TK_ST_INTERNAL) return GS_ERR_HIP;
+    if (h->ws.pinned[gs::TKSC_TKR + gs::TKC_STATUS] & gs::TK_ST_INTERNAL) return GS_ERR_HIP;
     if (st & gs::SEG_ST_SIZE) return GS_ERR_SIZE;
     return GS_OK;
 }
 
 gs_status gs_segtopk_last(gs_segtopk* h, uint32_t* report, uint32_t words, void* stream) {
     if (!h || !report || words < GS_SEGTOPK_REPORT_WORDS) return GS_ERR_ARG;
-    const gs_status rd = segtopk_read_ctl(h, static_cast<hipStream_t>(stream));
+    const gs_status rd = h->ws.read_ctl(static_cast<hipStream_t>(stream));
     if (rd != GS_OK) return rd;
     for (uint32_t i = 0; i < GS_SEGTOPK_REPORT_WORDS; ++i) report[i] = 0;
-    for (uint32_t c = 0; c < GS_SEGSORT_CLASSES; ++c) report[GS_SEGTOPK_R_CLASSES + c] = h->pinned[gs::SEGC_COUNT + c];
-    report[GS_SEGTOPK_R_LONGEST] = h->pinned[gs::SEGC_MAXLEN];
-    report[GS_SEGTOPK_R_STATUS] = h->pinned[gs::SEGC_STATUS] | ((h->pinned[gs::TKSC_TKR + gs::TKC_STATUS] & gs::TK_ST_INTERNAL) ? 256u : 0u);
-    report[GS_SEGTOPK_R_READS] = h->pinned[gs::TKSC_TKR + gs::TKR_CTL_READS];
+    for (uint32_t c = 0; c < GS_SEGSORT_CLASSES; ++c) report[GS_SEGTOPK_R_CLASSES + c] = h->ws.pinned[gs::SEGC_COUNT + c];
+    report[GS_SEGTOPK_R_LONGEST] = h->ws.pinned[gs::SEGC_MAXLEN];
+    report[GS_SEGTOPK_R_STATUS] = h->ws.pinned[gs::SEGC_STATUS] | ((h->ws.pinned[gs::TKSC_TKR + gs::TKC_STATUS] & gs::TK_ST_INTERNAL) ? 256u : 0u);
+    report[GS_SEGTOPK_R_READS] = h->ws.pinned[gs::TKSC_TKR + gs::TKR_CTL_READS];
     report[GS_SEGTOPK_R_FORMS] = h->last_forms;
     report[GS_SEGTOPK_R_RANK] = (uint32_t)h->rank_mode;
     report[GS_SEGTOPK_R_K] = h->last_k;
-    report[GS_SEGTOPK_R_PACKED] = h->pinned[gs::TKSC_PACKED];
+    report[GS_SEGTOPK_R_PACKED] = h->ws.pinned[gs::TKSC_PACKED];
     return GS_OK;
 }
 
-gs_status gs_segtopk_set_rank_mode(gs_segtopk* h, int mode) {
-    if (!h || (mode != 0 && mode != 1)) return GS_ERR_ARG;
-    h->rank_mode = mode;
-    return GS_OK;
-}
+gs_status gs_segtopk_set_rank_mode(gs_segtopk* h, int mode) { return handle_set_rank_mode(h, mode); }
 
-int gs_segtopk_get_rank_mode(gs_segtopk* h) { return h ? h->rank_mode : -1; }
+int gs_segtopk_get_rank_mode(gs_segtopk* h) { return handle_get_rank_mode(h); }
 
 }  // extern "C"
