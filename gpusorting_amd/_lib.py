@@ -27,6 +27,13 @@ GS_SORT16_ROUTE_NONE, GS_SORT16_ROUTE_KEYS, GS_SORT16_ROUTE_PAIRS = 0, 1, 2
  GS_SORT16_R_RANK) = range(8)
 GS_SORT16_F_HIST, GS_SORT16_F_SCAN, GS_SORT16_F_FILL, GS_SORT16_F_COUNT, GS_SORT16_F_PSCAN, GS_SORT16_F_SCATTER = 1, 2, 4, 8, 16, 32
 GS_SORT16_F_ALL = 0x7FF
+# gs_topk16_last: routes and report words
+GS_TOPK16_ROUTE_NONE, GS_TOPK16_ROUTE_TILE, GS_TOPK16_ROUTE_COUNT, GS_TOPK16_ROUTE_SELECT = 0, 1, 2, 3
+(GS_TOPK16_R_ROUTE, GS_TOPK16_R_THRESHOLD, GS_TOPK16_R_IN_FRONT, GS_TOPK16_R_EQUAL, GS_TOPK16_R_TAKEN, GS_TOPK16_R_RANGES, GS_TOPK16_R_STATUS,
+ GS_TOPK16_R_PER_RANGE, GS_TOPK16_R_HIST) = range(9)
+GS_TOPK16_REPORT_WORDS = 9
+GS_TOPK16_HIST_AUTO, GS_TOPK16_HIST_SLICES, GS_TOPK16_HIST_GLOBAL = 0, 1, 2
+GS_TOPK16_COUNT_SLICES_MIN = 1 << 27
 # gs_sort_rows_plan / gs_sort_rows_last: plan and report words, routes and the kernel-form bits
 GS_SORT_ROWS_PLAN_WORDS = GS_SORT_ROWS_REPORT_WORDS = 8
 GS_SORT_ROWS_ROUTE_NONE, GS_SORT_ROWS_ROUTE_LDS, GS_SORT_ROWS_ROUTE_PASSES = 0, 1, 2
@@ -87,7 +94,7 @@ GS_ROUTE_NONE = 0xFFFFFFFF
 GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
 (GS_KF_BIN, GS_KF_POS, GS_KF_PERSIST, GS_KF_SMALL, GS_KF_MID, GS_KF_SEG_WG, GS_KF_SEG_VB, GS_KF_TKR_TILE, GS_KF_TKR_VM, GS_KF_HIST,
  GS_KF_HY_HIST, GS_KF_HY_LOCAL, GS_KF_HY_LOCAL_PAIRS, GS_KF_COUNT) = range(14)
-# gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs, gs_sort16_*, gs_sort_rows16_* and gs_segsort16_*
+# gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs, gs_topk16_*, gs_sort16_*, gs_sort_rows16_* and gs_segsort16_*
 KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16 = 6, 7, 8, 9
 
 # every symbol include/gpusort.h declares: (name, restype, argtypes)
@@ -272,6 +279,14 @@ _PROTOS = [
     ("gs_sort16_plan", _int, [_u32, _int, _u32, _u32p]),
     ("gs_sort16_set_rank_mode", _int, [_vp, _int]),
     ("gs_sort16_get_rank_mode", _int, [_vp]),
+    ("gs_topk16_create", _int, [C.POINTER(_vp), _u32, _u32, _int, _u32]),
+    ("gs_topk16_destroy", _int, [_vp]),
+    ("gs_topk16_temp_bytes", C.c_size_t, [_u32, _u32, _int, _u32]),
+    ("gs_topk16_select_keys", _int, [_vp, _vp, _u32, _u32, _vp, _int, _int, _vp]),
+    ("gs_topk16_select_pairs", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _int, _int, _vp]),
+    ("gs_topk16_check", _int, [_vp, _vp]),
+    ("gs_topk16_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_topk16_set_count_histogram", _int, [_vp, _u32]),
     ("gs_sort_rows_create", _int, [C.POINTER(_vp), _u32, _int, _u32]),
     ("gs_sort_rows_destroy", _int, [_vp]),
     ("gs_sort_rows_temp_bytes", C.c_size_t, [_u32, _int, _u32]),

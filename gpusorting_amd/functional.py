@@ -25,6 +25,7 @@ from .segtopk import SegmentedTopK, segmented_topk_reference  # noqa: F401
 from .segtopk16 import SegmentedTopK16  # noqa: F401
 from .sort16 import Sort16, sort16_reference  # noqa: F401
 from .topk import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, TopK, rows_max_k, topk_reference, topk_rows_reference  # noqa: F401
+from .topk16 import TopK16  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
 
 _KEY_TYPE = {torch.int32: KEY_INT32, torch.float32: KEY_FLOAT32, torch.uint32: KEY_UINT32}
@@ -390,7 +391,8 @@ def topk(keys: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor 
     if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
         raise ValueError("keys must be a contiguous 1-D device tensor")
     if keys.dtype in _KEY16_TYPE:
-        raise TypeError(f"a 1-D {keys.dtype} tensor is not taken: 16-bit keys are selected row-wise, pass the 2-D form x[None, :]")
+        raise TypeError(f"a 1-D {keys.dtype} tensor is not taken: 16-bit keys are selected row-wise, pass the 2-D form x[None, :] "
+                        "(or call topk16, the 1-D selection on 16-bit keys)")
     if keys.dtype not in _KEY_TYPE:
         raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
     n, k = keys.numel(), int(k)
@@ -450,6 +452,50 @@ def _topk_rows(keys: torch.Tensor, k: int, largest: bool, values: torch.Tensor |
     with torch.cuda.device(keys.device):
         s = _topk_handle(keys.device, (rows - 1) * stride + row_len, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
         s.select_rows(keys, rows, row_len, stride, k, out_k, values, out_v)
+    return out_k, out_v
+
+
+def _topk16_handle(device: torch.device, n: int, k: int, key_type: int, order: int, value_bytes: int) -> TopK16:
+    """The cache rule of ``_topk_handle`` for the 1-D selection on 16-bit keys."""
+    key = (16, device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+    s = _topk_cache.get(key)
+    if s is None or s.max_keys < n or s.max_k < k:
+        if s is not None:
+            s.close()
+        cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
+        s = TopK16(cap(n), min(cap(k), cap(n)), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes, device=device.index)
+        _topk_cache[key] = s
+    return s
+
+
+def topk16(keys: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor | None = None, unsigned: bool = False):
+    """``topk`` for a 1-D contiguous tensor of 16-bit keys (float16, bfloat16, int16, uint16; ``unsigned=True`` on int16 storage selects
+    uint16 keys), read at their own width by ``gs_topk16_*``: returns ``(keys_k, indices_k)`` (int32 input positions) or, with
+    ``values``, ``(keys_k, values_k)``; every ``1 <= k <= n``.  The result is the head of this library's 16-bit sort: floats by the
+    order-preserving bit flip (-0 < +0, NaNs by bit pattern), ties by position (smallest: lowest positions first; largest: highest
+    positions first).  A 2-D tensor is forwarded to ``topk``'s row-wise call; other dtypes are a ``TypeError``: see ``topk``."""
+    if keys.dim() == 2:
+        return _topk_rows(keys, int(k), largest, values, unsigned)
+    if keys.dtype not in _KEY16_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: topk16 takes 16-bit keys (float16, bfloat16, int16, uint16); 32-bit keys go to topk")
+    if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+    n, k = keys.numel(), int(k)
+    if not 1 <= k <= n:
+        raise ValueError("1 <= k <= n")
+    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    vb = 4
+    if values is not None:
+        if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:
+            raise ValueError("values must match keys in shape and device and be contiguous")
+        vb = values.element_size()
+        if vb not in (4, 8):
+            raise TypeError("values must be 4 or 8 bytes wide")
+    out_k = torch.empty(k, dtype=keys.dtype, device=keys.device)
+    out_v = torch.empty(k, dtype=torch.int32 if values is None else values.dtype, device=keys.device)
+    with torch.cuda.device(keys.device):
+        s = _topk16_handle(keys.device, n, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
+        s.select(keys, k, out_k, values, out_v, n=n)
     return out_k, out_v
 
 

@@ -784,6 +784,102 @@ gs_status gs_sort16_plan(uint32_t n, gs_mode mode, uint32_t value_bytes, uint32_
 gs_status gs_sort16_set_rank_mode(gs_sort16* h, int mode);
 int gs_sort16_get_rank_mode(gs_sort16* h);
 
+/* ---- 1-D top-k on 16-bit keys: GS_KEY_UINT16 / INT16 / FLOAT16 / BFLOAT16 at their own width, keys, pairs and positions -------------
+ * No counterpart in the reference project.  gs_topk_select_* on 2-BYTE ELEMENTS in d_keys and d_out_keys, with a handle of its own.
+ *
+ * Result.  For 1 <= k <= n the output is, bit for bit, the first k elements of what gs_sort16_sort_keys / _sort_pairs / _argsort with
+ * the same key type and order leaves for that input: ordered by the sortable 16 bits (uint16 as it is, int16 with the sign bit
+ * flipped, float16 and bfloat16 by the order-preserving flip: -0 < +0, NaNs by bit pattern); ties ascending: the LOWEST positions are
+ * taken and equal keys come out in rising position; descending is the exact reverse of the stable ascending result, so the HIGHEST
+ * positions are taken and equal keys come out in falling position.  Every key bit pattern is preserved, values are bit-copied.  On a
+ * handle with 4-byte values d_vals == NULL means "the value is the element's input position" (uint32): the positions are made in
+ * registers, no index array exists anywhere.
+ *
+ * Buffers.  The inputs are not written.  Key elements are 2 bytes; nothing at or behind element k of an output is written, at 2-byte
+ * granularity for the keys (an odd k is legal).  Base pointers are 16-byte aligned.  No output may overlap an input or the other output;
+ * the extents are counted in 2-byte elements for the keys, so an output at d_keys + 2 * n bytes is legal.
+ *
+ * Errors, in this order.  GS_ERR_ARG: null handle (before anything else is looked at), null or misaligned d_keys / d_out_keys, a key type
+ * outside 6 .. 9 (the 32-bit key types go to gs_topk_select_*, the 64-bit ones nowhere), a bad order.  GS_ERR_MODE: a keys call on a pairs
+ * handle or the reverse.  GS_ERR_ARG: null or misaligned d_out_vals, misaligned d_vals, d_vals == NULL on a handle whose value_bytes is not
+ * 4.  GS_ERR_SIZE: n == 0, n > max_keys, k == 0, k > n, k > max_k.  GS_ERR_ARG: overlapping buffers (the test needs valid sizes).
+ * GS_ERR_MODE: every select call on a build flavour without these kernels (the tuning and fault-injection libraries).  A refused call
+ * launches nothing, writes nothing and leaves GS_TOPK16_ROUTE_NONE in the report.
+ *
+ * Execution.  Asynchronous on `stream`; every launch is enqueued up front (the output count is k whatever the data), there is no host
+ * round trip and every node is a kernel launch, so a call can be captured into a graph.  No kernel waits on another workgroup.  One call
+ * in flight per handle.
+ *
+ * Routes (gs_topk16_last).  bin = sortable bits ^ (descending ? 0xFFFF : 0), so both orders look for the k smallest bins:
+ *   GS_TOPK16_ROUTE_TILE    n <= gs_segsort_max_lds_segment(mode, value_bytes): one launch of the row-wise 16-bit wave / tile kernel of
+ *                           gs_topk_select_rows_* on the one row.
+ *   GS_TOPK16_ROUTE_COUNT   keys only, longer arrays: a histogram of all 65 536 bins, a scan to prefix[65 537], and a fill of outputs
+ *                           [0, k) FROM THE PREFIX: the keys are read by the histogram only.  Two histograms (gs_topk16_set_count_histogram;
+ *                           measured): from GS_TOPK16_COUNT_SLICES_MIN elements on GS_TOPK16_HIST_SLICES, the per-range
+ *                           slices of the SELECT route and their sum (one read of the keys, 2 bytes per key, and a fixed 64 MiB of
+ *                           slice traffic); below it GS_TOPK16_HIST_GLOBAL, the histogram kernel of gs_sort16_sort_keys (every range read
+ *                           by two workgroups, one per half of the bin space: 4 bytes per key, no slices).
+ *   GS_TOPK16_ROUTE_SELECT  pairs and positions, longer arrays: the same histograms and their sum, the threshold bin P with
+ *                           in_front < k <= in_front + equal, per-range counts from the histograms, and an ordered scatter (second
+ *                           read: 4 bytes per key in total) that puts the elements in front of P and, by position rank, the wanted share
+ *                           of those in P into the output in input order; the handle's embedded gs_sort16 pairs handle then sorts
+ *                           those k in place.
+ * The 16 bits are one level of gs_topk's two-level select: the histogram is exact, there is no second level and no candidate buffer. */
+typedef struct gs_topk16 gs_topk16;
+#define GS_TOPK16_ROUTE_NONE 0u
+#define GS_TOPK16_ROUTE_TILE 1u
+#define GS_TOPK16_ROUTE_COUNT 2u
+#define GS_TOPK16_ROUTE_SELECT 3u
+/* gs_topk16_last report words */
+#define GS_TOPK16_R_ROUTE 0      /* GS_TOPK16_ROUTE_* of the last call; words 1 .. 5, 7 and 8 are zero unless it is COUNT or SELECT */
+#define GS_TOPK16_R_THRESHOLD 1  /* T: the k-th element's key as sortable 16 bits (unsigned order = key order) */
+#define GS_TOPK16_R_IN_FRONT 2   /* elements strictly in front of T in the requested order (< k) */
+#define GS_TOPK16_R_EQUAL 3      /* elements equal to T (in_front + equal >= k) */
+#define GS_TOPK16_R_TAKEN 4      /* how many of those are in the output: k - in_front */
+#define GS_TOPK16_R_RANGES 5     /* workgroup ranges of the histogram: ceil(n / per-range) */
+#define GS_TOPK16_R_STATUS 6     /* the device status word: 0, or 1 if a count did not add up (gs_topk16_check: GS_ERR_HIP) */
+#define GS_TOPK16_R_PER_RANGE 7  /* elements per range: max(32 768, ceil(ceil(n / 256) / 8192) x 8192); GS_TOPK16_HIST_GLOBAL: as gs_sort16_plan */
+#define GS_TOPK16_R_HIST 8       /* GS_TOPK16_ROUTE_COUNT: the histogram that ran, GS_TOPK16_HIST_SLICES or _GLOBAL; SELECT: _SLICES; otherwise 0 */
+#define GS_TOPK16_REPORT_WORDS 9
+/* the COUNT route's histogram */
+#define GS_TOPK16_HIST_AUTO 0u    /* by n: GS_TOPK16_HIST_GLOBAL below GS_TOPK16_COUNT_SLICES_MIN elements, GS_TOPK16_HIST_SLICES from there on */
+#define GS_TOPK16_HIST_SLICES 1u
+#define GS_TOPK16_HIST_GLOBAL 2u
+#define GS_TOPK16_COUNT_SLICES_MIN 134217728u  /* 2^27 */
+/* No counterpart in the reference project.  value_bytes 0 (keys only), 4 or 8, as gs_onesweep_create (GS_ERR_MODE);
+ * 1 <= max_k <= max_keys <= GS_MAX_KEYS (GS_ERR_SIZE).  Synchronous (allocates gs_topk16_temp_bytes of device memory). */
+gs_status gs_topk16_create(gs_topk16** out, uint32_t max_keys, uint32_t max_k, gs_mode mode, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_topk16_destroy(gs_topk16* h);
+/* No counterpart in the reference project.  Host only; 0 for invalid sizes, mode or value width.  NO TERM GROWS WITH max_keys.  Every
+ * term rounded up to 256 bytes:
+ *     256                     control block
+ *   + 2 x 262 144             the recount histogram and the summed histogram
+ *   + 256 x 131 088           histogram slices: 256 workgroup ranges x (65 536 packed 16-bit counters + 16 bytes)
+ * keys only:
+ *   + 262 148                 prefix[65 537]
+ * pairs:
+ *   + 2048                    per-range counts
+ *   + max_k x 2 + max_k x value_bytes   the final sort's second buffers
+ *   + gs_sort16_temp_bytes(max_k, GS_MODE_PAIRS, value_bytes)   the embedded sorter */
+size_t gs_topk16_temp_bytes(uint32_t max_keys, uint32_t max_k, gs_mode mode, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_topk16_select_keys(gs_topk16* h, const void* d_keys, uint32_t n, uint32_t k, void* d_out_keys, gs_key_type key_type,
+                                gs_order order, void* stream);
+/* No counterpart in the reference project.  d_vals == NULL on a handle with 4-byte values: the values are the input positions 0 .. n - 1. */
+gs_status gs_topk16_select_pairs(gs_topk16* h, const void* d_keys, const void* d_vals, uint32_t n, uint32_t k, void* d_out_keys,
+                                 void* d_out_vals, gs_key_type key_type, gs_order order, void* stream);
+/* No counterpart in the reference project.  Synchronises `stream` and reports the last call: GS_OK, GS_ERR_HIP (a count did not add up —
+ * cannot happen; no store leaves its buffer — or the embedded sorter refused the final sort), or what gs_sort16_check says about the
+ * final sort of a SELECT call. */
+gs_status gs_topk16_check(gs_topk16* h, void* stream);
+/* No counterpart in the reference project.  Synchronous diagnostics of the last call: report[GS_TOPK16_R_*], words >= GS_TOPK16_REPORT_WORDS. */
+gs_status gs_topk16_last(gs_topk16* h, uint32_t* report, uint32_t words, void* stream);
+/* No counterpart in the reference project.  Which histogram the COUNT route runs from the next call on: GS_TOPK16_HIST_AUTO (the
+ * default), _SLICES or _GLOBAL; the result is the same bit for bit.  With no call of the handle in flight.  GS_ERR_ARG: null handle, any
+ * other value. */
+gs_status gs_topk16_set_count_histogram(gs_topk16* h, uint32_t which);
+
 /* ---- row-wise sort: every row of a contiguous [rows, row_len] matrix of 32-bit keys sorted on its own, in one call ------------------
  * No counterpart in the reference project.  Row r is elements [r * row_len, (r + 1) * row_len) of the array; after the call every row
  * holds exactly what gs_onesweep_sort_keys / _sort_pairs leaves for that slice, bit for bit: stable by key, descending = the exact
