@@ -14,9 +14,11 @@ Only the hot path of b0nes164/GPUSorting named by BASELINE.json is here:
   segtopk    segmented top-k (the first k of every CSR segment) over gs_segtopk_*, and its numpy reference
   segtopk16  segmented top-k of 16-bit keys at their own width over gs_segtopk16_*
   topk16     1-D top-k of 16-bit keys at their own width over gs_topk16_*
-  functional sort / sort_ / argsort / sort_rows / argsort_rows / segmented_sort / topk / topk16 / segmented_topk / segmented_topk16 on torch
-             tensors (plumbing over OneSweep / RowSort / RowSort16 / SegmentedSort / SegmentedSort16 / TopK / SegmentedTopK /
-             SegmentedTopK16 / TopK16)
+  unique     distinct keys, counts, first positions and the inverse map (the sort plus a run-length stage, or that stage alone) over
+             gs_unique_*, and its numpy reference
+  functional sort / sort_ / argsort / sort_rows / argsort_rows / segmented_sort / topk / topk16 / segmented_topk / segmented_topk16 /
+             unique / unique_consecutive on torch tensors (plumbing over OneSweep / RowSort / RowSort16 / SegmentedSort /
+             SegmentedSort16 / TopK / SegmentedTopK / SegmentedTopK16 / TopK16 / Unique)
 """
 from .onesweep import (  # noqa: F401
     ENTROPY_PRESET_1, ENTROPY_PRESET_2, ENTROPY_PRESET_3, ENTROPY_PRESET_4, ENTROPY_PRESET_5,
@@ -26,7 +28,7 @@ from .onesweep import (  # noqa: F401
 from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, GpuSortError  # noqa: F401
 from .functional import (  # noqa: F401
     argsort, argsort_rows, segmented_argsort, segmented_sort, segmented_sort_, segmented_topk, segmented_topk16, sort, sort_, sort_rows, sort_rows_, topk,
-    topk16,
+    topk16, unique, unique_consecutive,
 )
 from .rowsort import RowSort, sort_rows_plan, sort_rows_reference  # noqa: F401
 from .rowsort16 import SORT_ROWS16_FORMS, RowSort16, sort_rows16_plan, sort_rows16_reference  # noqa: F401
@@ -37,3 +39,4 @@ from .segtopk16 import SegmentedTopK16  # noqa: F401
 from .sort16 import Sort16, sort16_plan, sort16_reference  # noqa: F401
 from .topk import TopK, topk_reference, topk_rows_reference  # noqa: F401
 from .topk16 import TopK16  # noqa: F401
+from .unique import Unique, unique_plan, unique_reference  # noqa: F401

@@ -89,6 +89,12 @@ def GS_SEGTOPK_F_TILE(cls: int, rank: int) -> int:
     return 8 << ((cls - 3) + 5 * rank)
 
 
+# gs_unique_last: routes and report words
+GS_UNIQUE_ROUTE_NONE, GS_UNIQUE_ROUTE_KEYS, GS_UNIQUE_ROUTE_POSITIONS, GS_UNIQUE_ROUTE_CONSECUTIVE = 0, 1, 2, 3
+(GS_UNIQUE_R_ROUTE, GS_UNIQUE_R_N, GS_UNIQUE_R_U, GS_UNIQUE_R_RANGES, GS_UNIQUE_R_PER_RANGE, GS_UNIQUE_R_TILE, GS_UNIQUE_R_STATUS,
+ GS_UNIQUE_R_RANK) = range(8)
+GS_UNIQUE_REPORT_WORDS = 8
+
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
 GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
@@ -338,6 +344,15 @@ _PROTOS = [
     ("gs_segtopk16_last", _int, [_vp, _u32p, _u32, _vp]),
     ("gs_segtopk16_set_rank_mode", _int, [_vp, _int]),
     ("gs_segtopk16_get_rank_mode", _int, [_vp]),
+    ("gs_unique_create", _int, [C.POINTER(_vp), _u32, _int, _u32]),
+    ("gs_unique_destroy", _int, [_vp]),
+    ("gs_unique_temp_bytes", C.c_size_t, [_u32, _int, _u32]),
+    ("gs_unique_keys", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _int, _int, _vp]),
+    ("gs_unique_positions", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    ("gs_unique_consecutive", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("gs_unique_plan", _int, [_u32, _u32p]),
+    ("gs_unique_check", _int, [_vp, _vp]),
+    ("gs_unique_last", _int, [_vp, _u32p, _u32, _vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

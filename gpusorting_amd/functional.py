@@ -8,6 +8,8 @@ handle cache, buffers).  The reference has no such layer; it is what a torch use
     sorted_rows = gpusorting_amd.sort(matrix)                                # 2-D: every row on its own, torch.sort(x, dim=-1) (RowSort)
     sorted_rows = gpusorting_amd.sort_rows(half_matrix, descending=True)     # 2-D, 16- and 32-bit keys (RowSort16 / RowSort)
     positions = gpusorting_amd.argsort_rows(half_matrix)                     # int32 positions within the row
+    distinct, inverse, counts = gpusorting_amd.unique(keys, return_inverse=True, return_counts=True)   # torch.unique (Unique)
+    runs, counts = gpusorting_amd.unique_consecutive(keys, return_counts=True)                         # torch.unique_consecutive
 
 Semantics are the library's: stable LSD radix sort; descending = exact reverse of the stable ascending result;
 float keys ordered by the order-preserving bit flip (-0 < +0, NaNs by bit pattern); values bit-copied.
@@ -26,6 +28,7 @@ from .segtopk16 import SegmentedTopK16  # noqa: F401
 from .sort16 import Sort16, sort16_reference  # noqa: F401
 from .topk import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, TopK, rows_max_k, topk_reference, topk_rows_reference  # noqa: F401
 from .topk16 import TopK16  # noqa: F401
+from .unique import Unique, unique_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
 
 _KEY_TYPE = {torch.int32: KEY_INT32, torch.float32: KEY_FLOAT32, torch.uint32: KEY_UINT32}
@@ -582,3 +585,78 @@ def _segmented_topk(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: 
         s = _segtopk_handle(keys.device, n, segs, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
         s.select(keys, offsets, k, out_k, values, out_v, n=n, max_segment_len=max_segment_len)
     return out_k, out_v, counts
+
+
+# ---- unique / run-length encode -------------------------------------------------------------------------------------------------
+_unique_cache: dict = {}
+
+
+def _unique_handle(device: torch.device, n: int, key_type: int, order: int, positions: bool) -> Unique:
+    """The cache rule of ``_sorter``: one ``Unique`` handle per (device, stream, type, order, with positions); re-created when the
+    size outgrows it."""
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, positions)
+    s = _unique_cache.get(key)
+    if s is None or s.max_keys < n:
+        if s is not None:
+            s.close()
+        cap = 1 << max(int(n - 1).bit_length(), 16)
+        s = Unique(min(cap, (1 << 30) - 1), order, key_type, positions=positions, device=device.index)
+        _unique_cache[key] = s
+    return s
+
+
+def _require_unique_keys(keys: torch.Tensor) -> None:
+    if keys.dim() != 1:
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+    if keys.dtype not in _KEY_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: unique takes 32-bit keys (int32, uint32, float32)")
+    if not keys.is_contiguous() or keys.device.type != "cuda":
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+
+
+def unique(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False, return_index: bool = False, descending: bool = False,
+           unsigned: bool = False):
+    """The distinct elements of a 1-D contiguous int32 / uint32 / float32 tensor in sorted order, as ``torch.unique(keys, sorted=True)``:
+    returns ``output`` or the tuple ``(output[, inverse][, counts][, index])``.  ``inverse`` (int32) maps every input to its place in
+    ``output``, ``counts`` (int32) is each element's multiplicity, ``index`` (int32) the lowest input position that holds it (numpy's
+    ``return_index``).  ``descending=True`` returns the distinct elements in falling order; ``unsigned=True`` treats int32 storage as
+    uint32 keys.  Equality is BITWISE and the order is this library's sort: on floats ``-0.0`` and ``+0.0`` are two elements
+    (``-0.0`` first) and every NaN bit pattern is an element of its own, placed by its bits — unlike ``torch.unique``, which compares
+    values.  On integers the result equals ``torch.unique``'s.  Slicing the outputs to their length is the one wait on the host, as in
+    ``torch.unique``.  ``keys`` is not written."""
+    _require_unique_keys(keys)
+    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    n = keys.numel()
+    positions = return_inverse or return_index
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=keys.device)
+        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ()) + ((e.clone(),) if return_index else ())
+        return out[0] if len(out) == 1 else out
+    with torch.cuda.device(keys.device):
+        s = _unique_handle(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, positions)
+        if positions:
+            out_k, out_c, out_f, out_i, num = s.unique_positions(keys, n, counts=return_counts, first=return_index, inverse=return_inverse)
+        else:
+            out_k, out_c, num = s.unique(keys, n, counts=return_counts)
+            out_f = out_i = None
+    u = int(num.item())
+    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ()) + ((out_f[:u],) if return_index else ())
+    return out[0] if len(out) == 1 else out
+
+
+def unique_consecutive(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False):
+    """``torch.unique_consecutive`` on a 1-D contiguous int32 / uint32 / float32 tensor: one element per run of BITWISE-equal neighbours of
+    the input as it lies (no sort): returns ``output`` or ``(output[, inverse][, counts])`` with int32 ``inverse`` (the run of every
+    input) and ``counts`` (the runs' lengths).  One wait on the host, for the length.  ``keys`` is not written."""
+    _require_unique_keys(keys)
+    n = keys.numel()
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=keys.device)
+        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ())
+        return out[0] if len(out) == 1 else out
+    with torch.cuda.device(keys.device):
+        s = _unique_handle(keys.device, n, KEY_UINT32, ORDER_ASCENDING, False)
+        out_k, out_c, out_i, num = s.unique_consecutive(keys, n, counts=return_counts, inverse=return_inverse)
+    u = int(num.item())
+    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ())
+    return out[0] if len(out) == 1 else out

@@ -1249,6 +1249,93 @@ gs_status gs_segtopk16_last(gs_segtopk16* h, uint32_t* report, uint32_t words, v
 gs_status gs_segtopk16_set_rank_mode(gs_segtopk16* h, int mode);
 int gs_segtopk16_get_rank_mode(gs_segtopk16* h);
 
+/* ---- unique / run-length encode: the distinct keys of an array, their counts, first positions and the inverse map ------------------
+ * No counterpart in the reference project.  For n keys of GS_KEY_UINT32 / INT32 / FLOAT32 and an order, with u distinct keys:
+ *   out_keys[0 .. u)    the distinct key BIT PATTERNS in the order gs_onesweep_sort_keys would leave them (floats by the order-preserving
+ *                       flip).  Equality is BITWISE: -0.0 and +0.0 are two keys and every NaN pattern is a key of its own — unlike
+ *                       torch.unique / numpy.unique, which compare values (-0.0 == +0.0 there, and NaNs are placed by their own rules).
+ *   out_counts[j]       (uint32) how many inputs equal out_keys[j]; the counts add up to n.
+ *   out_first[j]        (uint32) the LOWEST input position that holds out_keys[j], in either order (numpy's return_index).  Descending
+ *                       is the exact reverse of the stable ascending sort, so there the lowest position lies at the run's tail.
+ *   out_inverse[i]      (uint32, n entries) the j with out_keys[j] bitwise equal to keys[i].
+ *   *d_out_num          u, one uint32 ON THE DEVICE, so that a following kernel can use it without a host wait; gs_unique_last reports
+ *                       it too.
+ * The input is not written.  Every output pointer but d_out_keys may be NULL: not wanted.  The caller provides n elements for each of
+ * out_keys, out_counts, out_first and out_inverse and one word at d_out_num; NOTHING AT OR BEHIND ELEMENT u of out_keys, out_counts or
+ * out_first IS WRITTEN, and nothing intermediate passes through them.  Base pointers are 16-byte aligned (d_out_num: 4-byte); no
+ * buffer of the call overlaps another.  The call is asynchronous on `stream`: every launch is enqueued up front with no host round
+ * trip, every node is a kernel launch, and every grid is fixed by n, never by u — a call can be captured into a graph and replayed on
+ * new data with another u.  No kernel waits on another workgroup.  One call in flight per handle.  The 64-bit and 16-bit key types
+ * return GS_ERR_ARG (a 65 536-bin histogram answers the 16-bit case; not built).
+ *
+ * Handles: (GS_MODE_KEYS_ONLY, 0) for keys and counts; (GS_MODE_PAIRS, 4) adds first and inverse — its embedded gs_onesweep sorts
+ * (key, position) pairs.  Anything else: GS_ERR_MODE.
+ *   gs_unique_keys         either handle: copies the keys into the workspace, sorts them there, then the run-length stage.
+ *   gs_unique_positions    the pairs handle only: one kernel copies the keys and writes the positions 0 .. n - 1 beside them, the
+ *                          engine's pairs sort, then the run-length stage with the sorted positions as a second input.
+ *   gs_unique_consecutive  either handle: the run-length encode of the input AS IT LIES, no sort, no key type: runs of bitwise-equal
+ *                          neighbours (torch.unique_consecutive); out_inverse[i] is the index of the run that holds i.  It is the second
+ *                          half of the two calls above.
+ * The result does not depend on the route the engine takes (single tile, mid, two-level, LSD passes).  The keys-only handle's engine
+ * is created with position_chains = 0 (gs_onesweep_options): DESIGN.md 3.21 says why.
+ * The run-length stage: the array is cut into gs_unique_plan's ranges of whole tiles; count (one workgroup per range: the heads of the
+ * range — element i is a head when i == 0 or key[i] != key[i - 1] — and its last head's position), scan (one workgroup: heads and last
+ * head in front of every range, u), compact (the head of rank r writes out_keys[r] and closes run r - 1: out_counts[r - 1] = its
+ * position - the previous head's; the workgroup that holds element n - 1 closes the last run).
+ *
+ * Errors, in this order.  GS_ERR_ARG: null handle (before anything else is looked at), null or misaligned d_keys / d_out_keys, a key type
+ * outside 0 .. 2, a bad order (gs_unique_consecutive has neither).  GS_ERR_MODE: gs_unique_positions on a keys-only handle.
+ * GS_ERR_ARG: a misaligned d_out_counts / d_out_first / d_out_inverse / d_out_num.  GS_ERR_SIZE: n == 0 or n > max_keys.  GS_ERR_ARG:
+ * any two of the call's buffers overlapping (outputs at their capacity of n elements).  GS_ERR_MODE: every call on a build flavour
+ * without these kernels (the tuning and fault-injection libraries).  A refused call launches nothing and leaves route NONE. */
+typedef struct gs_unique gs_unique;
+#define GS_UNIQUE_ROUTE_NONE 0
+#define GS_UNIQUE_ROUTE_KEYS 1
+#define GS_UNIQUE_ROUTE_POSITIONS 2
+#define GS_UNIQUE_ROUTE_CONSECUTIVE 3
+/* gs_unique_last report words */
+#define GS_UNIQUE_R_ROUTE 0
+#define GS_UNIQUE_R_N 1
+#define GS_UNIQUE_R_U 2          /* distinct keys (runs) of the last call */
+#define GS_UNIQUE_R_RANGES 3     /* the run-length stage's plan: gs_unique_plan(n) */
+#define GS_UNIQUE_R_PER_RANGE 4
+#define GS_UNIQUE_R_TILE 5
+#define GS_UNIQUE_R_STATUS 6     /* the device status word: 0, or 1 if a count did not add up (gs_unique_check: GS_ERR_HIP) */
+#define GS_UNIQUE_R_RANK 7       /* the embedded engine's rank mode (gs_onesweep_get_rank_mode) */
+#define GS_UNIQUE_REPORT_WORDS 8
+/* No counterpart in the reference project.  1 <= max_keys <= GS_MAX_KEYS (GS_ERR_SIZE), then (mode, value_bytes) as above (GS_ERR_MODE),
+ * both answered before a device is looked for.  Synchronous (allocates gs_unique_temp_bytes of device memory). */
+gs_status gs_unique_create(gs_unique** out, uint32_t max_keys, gs_mode mode, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_unique_destroy(gs_unique* h);
+/* No counterpart in the reference project.  Host only.  With A(x) = (x + 255) & ~255:
+ *     A(64 * 4)                            the control block
+ *   + 4 * A(1024 * 4)                      per range: heads, last head, heads in front, last head in front
+ *   + 2 * A(4 * max_keys)                  the copy of the keys the engine sorts, and its alternate buffer
+ *   + 2 * A(4 * max_keys)  pairs only      the positions and their alternate buffer
+ *   + gs_onesweep_temp_bytes(max_keys)     the embedded engine
+ * 0 for invalid sizes, mode or value width. */
+size_t gs_unique_temp_bytes(uint32_t max_keys, gs_mode mode, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_unique_keys(gs_unique* h, const void* d_keys, uint32_t n, void* d_out_keys, void* d_out_counts, void* d_out_num, gs_key_type key_type,
+                         gs_order order, void* stream);
+/* No counterpart in the reference project. */
+gs_status gs_unique_positions(gs_unique* h, const void* d_keys, uint32_t n, void* d_out_keys, void* d_out_counts, void* d_out_first,
+                              void* d_out_inverse, void* d_out_num, gs_key_type key_type, gs_order order, void* stream);
+/* No counterpart in the reference project. */
+gs_status gs_unique_consecutive(gs_unique* h, const void* d_keys, uint32_t n, void* d_out_keys, void* d_out_counts, void* d_out_inverse,
+                                void* d_out_num, void* stream);
+/* No counterpart in the reference project.  Host only: the run-length stage's plan for n elements: plan[0] ranges (at most 1024),
+ * [1] elements per range = ceil(ceil(n / 1024) / tile) * tile, [2] tile (4096).  ranges x per-range >= n.  GS_ERR_ARG for a null plan,
+ * GS_ERR_SIZE for n == 0 or n > GS_MAX_KEYS. */
+gs_status gs_unique_plan(uint32_t n, uint32_t plan[3]);
+/* No counterpart in the reference project.  Synchronises `stream` and reports the last call: GS_ERR_HIP if the heads counted and the
+ * heads written disagree (cannot happen; the compact then wrote nothing or stopped) or the engine refused its sort; otherwise, after
+ * gs_unique_keys / _positions, what gs_onesweep_check says of the engine (GS_ERR_TIMEOUT); GS_OK. */
+gs_status gs_unique_check(gs_unique* h, void* stream);
+/* No counterpart in the reference project.  Synchronous diagnostics of the last call: report[GS_UNIQUE_R_*], words >= GS_UNIQUE_REPORT_WORDS. */
+gs_status gs_unique_last(gs_unique* h, uint32_t* report, uint32_t words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
