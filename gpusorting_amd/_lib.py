@@ -94,6 +94,14 @@ GS_UNIQUE_ROUTE_NONE, GS_UNIQUE_ROUTE_KEYS, GS_UNIQUE_ROUTE_POSITIONS, GS_UNIQUE
 (GS_UNIQUE_R_ROUTE, GS_UNIQUE_R_N, GS_UNIQUE_R_U, GS_UNIQUE_R_RANGES, GS_UNIQUE_R_PER_RANGE, GS_UNIQUE_R_TILE, GS_UNIQUE_R_STATUS,
  GS_UNIQUE_R_RANK) = range(8)
 GS_UNIQUE_REPORT_WORDS = 8
+# gs_unique16_last: routes, report words, the optional-kernel bits; gs_unique16_set_inverse_form
+GS_UNIQUE16_ROUTE_NONE, GS_UNIQUE16_ROUTE_HISTOGRAM, GS_UNIQUE16_ROUTE_CONSECUTIVE = 0, 1, 2
+(GS_UNIQUE16_R_ROUTE, GS_UNIQUE16_R_N, GS_UNIQUE16_R_U, GS_UNIQUE16_R_STATUS, GS_UNIQUE16_R_RAN, GS_UNIQUE16_R_RANGES, GS_UNIQUE16_R_PER_RANGE,
+ GS_UNIQUE16_R_TILE, GS_UNIQUE16_R_FIRST_RANGES, GS_UNIQUE16_R_INVERSE_RANGES) = range(10)
+GS_UNIQUE16_REPORT_WORDS = 10
+GS_UNIQUE16_K_FIRST, GS_UNIQUE16_K_INVERSE_LDS, GS_UNIQUE16_K_INVERSE_GATHER = 1, 2, 4
+GS_UNIQUE16_INVERSE_AUTO, GS_UNIQUE16_INVERSE_LDS, GS_UNIQUE16_INVERSE_GATHER = 0, 1, 2
+GS_UNIQUE16_INVERSE_LDS_MIN = 1 << 22
 
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
@@ -353,6 +361,14 @@ _PROTOS = [
     ("gs_unique_plan", _int, [_u32, _u32p]),
     ("gs_unique_check", _int, [_vp, _vp]),
     ("gs_unique_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_unique16_create", _int, [C.POINTER(_vp), _u32]),
+    ("gs_unique16_destroy", _int, [_vp]),
+    ("gs_unique16_temp_bytes", C.c_size_t, [_u32]),
+    ("gs_unique16_unique", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    ("gs_unique16_consecutive", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("gs_unique16_check", _int, [_vp, _vp]),
+    ("gs_unique16_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_unique16_set_inverse_form", _int, [_vp, _u32]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

@@ -10,6 +10,7 @@ handle cache, buffers).  The reference has no such layer; it is what a torch use
     positions = gpusorting_amd.argsort_rows(half_matrix)                     # int32 positions within the row
     distinct, inverse, counts = gpusorting_amd.unique(keys, return_inverse=True, return_counts=True)   # torch.unique (Unique)
     runs, counts = gpusorting_amd.unique_consecutive(keys, return_counts=True)                         # torch.unique_consecutive
+    distinct, index = gpusorting_amd.unique16(half_keys, return_index=True)  # float16 / bfloat16 / int16 / uint16: one histogram (Unique16)
 
 Semantics are the library's: stable LSD radix sort; descending = exact reverse of the stable ascending result;
 float keys ordered by the order-preserving bit flip (-0 < +0, NaNs by bit pattern); values bit-copied.
@@ -29,6 +30,7 @@ from .sort16 import Sort16, sort16_reference  # noqa: F401
 from .topk import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, TopK, rows_max_k, topk_reference, topk_rows_reference  # noqa: F401
 from .topk16 import TopK16  # noqa: F401
 from .unique import Unique, unique_reference  # noqa: F401
+from .unique16 import Unique16, unique16_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
 
 _KEY_TYPE = {torch.int32: KEY_INT32, torch.float32: KEY_FLOAT32, torch.uint32: KEY_UINT32}
@@ -656,6 +658,75 @@ def unique_consecutive(keys: torch.Tensor, return_inverse: bool = False, return_
         return out[0] if len(out) == 1 else out
     with torch.cuda.device(keys.device):
         s = _unique_handle(keys.device, n, KEY_UINT32, ORDER_ASCENDING, False)
+        out_k, out_c, out_i, num = s.unique_consecutive(keys, n, counts=return_counts, inverse=return_inverse)
+    u = int(num.item())
+    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ())
+    return out[0] if len(out) == 1 else out
+
+
+# ---- unique / run-length encode on 16-bit keys -----------------------------------------------------------------------------------
+_unique16_cache: dict = {}
+
+
+def _unique16_handle(device: torch.device, n: int, key_type: int, order: int) -> Unique16:
+    """The cache rule of ``_unique_handle`` for the 16-bit keys: one ``Unique16`` handle per (device, stream, type, order); re-created
+    when the size outgrows it (its scratch does not grow with the size)."""
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order)
+    s = _unique16_cache.get(key)
+    if s is None or s.max_keys < n:
+        if s is not None:
+            s.close()
+        cap = 1 << max(int(n - 1).bit_length(), 16)
+        s = Unique16(min(cap, (1 << 30) - 1), order, key_type, device=device.index)
+        _unique16_cache[key] = s
+    return s
+
+
+def _require_unique16_keys(keys: torch.Tensor, name: str) -> None:
+    if keys.dim() != 1:
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+    if keys.dtype not in _KEY16_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: {name} takes 16-bit keys (float16, bfloat16, int16, uint16); 32-bit keys go to "
+                        f"{'unique_consecutive' if 'consecutive' in name else 'unique'}")
+    if not keys.is_contiguous() or keys.device.type != "cuda":
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+
+
+def unique16(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False, return_index: bool = False, descending: bool = False,
+             unsigned: bool = False):
+    """``unique`` for a 1-D contiguous tensor of 16-bit keys (float16, bfloat16, int16, uint16; ``unsigned=True`` on int16 storage treats
+    it as uint16 keys), read at their own width by ``gs_unique16_*``: one 65 536-bin histogram, no sort.  Returns ``output`` or the tuple
+    ``(output[, inverse][, counts][, index])`` with int32 ``inverse``, ``counts`` and ``index`` (the lowest input position of each
+    element), as ``unique`` does.  Equality is BITWISE and the order is this library's 16-bit sort: ``-0.0`` and ``+0.0`` are two
+    elements (``-0.0`` first) and every NaN bit pattern is an element of its own.  Slicing the outputs to their length is the one wait
+    on the host.  ``keys`` is not written.  Other dtypes are a ``TypeError``: see ``unique``."""
+    _require_unique16_keys(keys, "unique16")
+    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    n = keys.numel()
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=keys.device)
+        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ()) + ((e.clone(),) if return_index else ())
+        return out[0] if len(out) == 1 else out
+    with torch.cuda.device(keys.device):
+        s = _unique16_handle(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING)
+        out_k, out_c, out_f, out_i, num = s.unique(keys, n, counts=return_counts, first=return_index, inverse=return_inverse)
+    u = int(num.item())
+    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ()) + ((out_f[:u],) if return_index else ())
+    return out[0] if len(out) == 1 else out
+
+
+def unique_consecutive16(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False):
+    """``unique_consecutive`` for a 1-D contiguous tensor of 16-bit keys: one element per run of BITWISE-equal neighbours of the input as
+    it lies (no sort): returns ``output`` or ``(output[, inverse][, counts])`` with int32 ``inverse`` and ``counts``.  One wait on the
+    host, for the length.  ``keys`` is not written.  Other dtypes are a ``TypeError``: see ``unique_consecutive``."""
+    _require_unique16_keys(keys, "unique_consecutive16")
+    n = keys.numel()
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=keys.device)
+        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ())
+        return out[0] if len(out) == 1 else out
+    with torch.cuda.device(keys.device):
+        s = _unique16_handle(keys.device, n, KEY_UINT16, ORDER_ASCENDING)
         out_k, out_c, out_i, num = s.unique_consecutive(keys, n, counts=return_counts, inverse=return_inverse)
     u = int(num.item())
     out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ())

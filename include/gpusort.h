@@ -1266,7 +1266,7 @@ int gs_segtopk16_get_rank_mode(gs_segtopk16* h);
  * buffer of the call overlaps another.  The call is asynchronous on `stream`: every launch is enqueued up front with no host round
  * trip, every node is a kernel launch, and every grid is fixed by n, never by u — a call can be captured into a graph and replayed on
  * new data with another u.  No kernel waits on another workgroup.  One call in flight per handle.  The 64-bit and 16-bit key types
- * return GS_ERR_ARG (a 65 536-bin histogram answers the 16-bit case; not built).
+ * return GS_ERR_ARG (a 65 536-bin histogram answers the 16-bit case: gs_unique16_* below).
  *
  * Handles: (GS_MODE_KEYS_ONLY, 0) for keys and counts; (GS_MODE_PAIRS, 4) adds first and inverse — its embedded gs_onesweep sorts
  * (key, position) pairs.  Anything else: GS_ERR_MODE.
@@ -1335,6 +1335,94 @@ gs_status gs_unique_plan(uint32_t n, uint32_t plan[3]);
 gs_status gs_unique_check(gs_unique* h, void* stream);
 /* No counterpart in the reference project.  Synchronous diagnostics of the last call: report[GS_UNIQUE_R_*], words >= GS_UNIQUE_REPORT_WORDS. */
 gs_status gs_unique_last(gs_unique* h, uint32_t* report, uint32_t words, void* stream);
+
+/* ---- unique / run-length encode on 16-bit keys: one histogram, no sort ------------------------------------------------------------------
+ * No counterpart in the reference project.  gs_unique_positions restated for n keys of GS_KEY_UINT16 / INT16 / FLOAT16 / BFLOAT16 at
+ * their own width, with u distinct keys:
+ *   out_keys[0 .. u)    (2-byte elements) the distinct key BIT PATTERNS in the order gs_sort16_sort_keys would leave them.  Equality is
+ *                       BITWISE: -0.0 and +0.0 are two keys and every NaN pattern is a key of its own.
+ *   out_counts[j]       (uint32) how many inputs equal out_keys[j]; the counts add up to n.
+ *   out_first[j]        (uint32) the LOWEST input position that holds out_keys[j], in either order.
+ *   out_inverse[i]      (uint32, n entries) the j with out_keys[j] bitwise equal to keys[i].
+ *   *d_out_num          u, one uint32 ON THE DEVICE; gs_unique16_last reports it too.
+ * The input is not written.  Every output pointer but d_out_keys may be NULL: not wanted (d_out_num as well, as in gs_unique_*).
+ * gs_unique16_unique: the caller provides min(n, 65 536) elements for each of out_keys, out_counts and out_first (u cannot be larger)
+ * and n for out_inverse; gs_unique16_consecutive: n elements each (u can reach n).  NOTHING AT OR BEHIND ELEMENT u of out_keys,
+ * out_counts or out_first IS WRITTEN, and out_keys is written with 2-byte stores: an unwritten 2-byte neighbour of a written element
+ * survives.  Base pointers are 16-byte aligned (d_out_num: 4-byte); no buffer of the call overlaps another.  The call is asynchronous
+ * on `stream`: every launch is enqueued up front, every node is a kernel launch, every grid is fixed by n, never by u — a call can be
+ * captured into a graph and replayed on new data with another u.  No kernel waits on another workgroup.  One call in flight per handle.
+ *
+ * One handle kind: there is no sorter to choose.
+ *   gs_unique16_unique       A 16-bit key has 65 536 patterns, so one histogram of bin = sortable bits ^ (descending ? 0xFFFF : 0) is the
+ *                            exact answer: a clear; the histogram kernel of gs_sort16 on gs_sort16_plan's ranges; with d_out_first the
+ *                            lowest position per bin (a filtered atomic minimum into a 65 536-word table); one workgroup that scans the
+ *                            non-empty bins, writes u, the table of the bins' ranks, out_keys, out_counts and out_first; with
+ *                            d_out_inverse the lookup out_inverse[i] = rank[bin(keys[i])].  No sort, no scratch that grows with n.
+ *                            The lookup has two forms, chosen by n (GS_UNIQUE16_INVERSE_LDS_MIN; gs_unique16_set_inverse_form): the
+ *                            rank table in LDS (one workgroup per range of at most 256), or gathered from global memory.
+ *   gs_unique16_consecutive  the run-length encode of the input AS IT LIES (torch.unique_consecutive): no key type, no order.  The
+ *                            count / scan / compact stage of gs_unique_consecutive on 2-byte loads, on gs_unique_plan's ranges.
+ *
+ * Errors, in this order.  GS_ERR_ARG: null handle (before anything else is looked at); null or misaligned d_keys / d_out_keys, a key
+ * type outside the four 16-bit ones, a bad order (gs_unique16_consecutive has neither); a misaligned d_out_counts / d_out_first /
+ * d_out_inverse / d_out_num.  GS_ERR_SIZE: n == 0 or n > max_keys.  GS_ERR_ARG: any two of the call's buffers overlapping (outputs at
+ * the capacities above).  GS_ERR_MODE: every call on a build flavour without these kernels (the tuning and fault-injection
+ * libraries).  A refused call launches nothing and leaves route NONE. */
+typedef struct gs_unique16 gs_unique16;
+#define GS_UNIQUE16_ROUTE_NONE 0
+#define GS_UNIQUE16_ROUTE_HISTOGRAM 1
+#define GS_UNIQUE16_ROUTE_CONSECUTIVE 2
+/* gs_unique16_last report words */
+#define GS_UNIQUE16_R_ROUTE 0
+#define GS_UNIQUE16_R_N 1
+#define GS_UNIQUE16_R_U 2          /* distinct keys (runs) of the last call */
+#define GS_UNIQUE16_R_STATUS 3     /* the device status word: 0, or 1 if a count did not add up (gs_unique16_check: GS_ERR_HIP) */
+#define GS_UNIQUE16_R_RAN 4        /* GS_UNIQUE16_K_* bits: the optional kernels the last call launched */
+#define GS_UNIQUE16_R_RANGES 5     /* HISTOGRAM: gs_sort16_plan(n) of the histogram; CONSECUTIVE: gs_unique_plan(n) */
+#define GS_UNIQUE16_R_PER_RANGE 6
+#define GS_UNIQUE16_R_TILE 7
+#define GS_UNIQUE16_R_FIRST_RANGES 8    /* workgroups of the first-position kernel: ranges of max(4, ceil(ceil(n / 256) / 8192)) tiles of 8192 */
+#define GS_UNIQUE16_R_INVERSE_RANGES 9  /* workgroups of the inverse: LDS ranges of max(8, ceil(ceil(n / 256) / 8192)) tiles; GATHER one tile each */
+#define GS_UNIQUE16_REPORT_WORDS 10
+#define GS_UNIQUE16_K_FIRST 1u           /* the first-position kernel (d_out_first given) */
+#define GS_UNIQUE16_K_INVERSE_LDS 2u     /* the inverse with the rank table in LDS */
+#define GS_UNIQUE16_K_INVERSE_GATHER 4u  /* the inverse gathering from the global rank table */
+/* gs_unique16_set_inverse_form */
+#define GS_UNIQUE16_INVERSE_AUTO 0
+#define GS_UNIQUE16_INVERSE_LDS 1
+#define GS_UNIQUE16_INVERSE_GATHER 2
+/* AUTO: the gather below this many keys, the LDS table from there on (measured: DESIGN.md 3.22) */
+#define GS_UNIQUE16_INVERSE_LDS_MIN (1u << 22)
+/* No counterpart in the reference project.  1 <= max_keys <= GS_MAX_KEYS (GS_ERR_SIZE), answered before a device is looked for.
+ * Synchronous (allocates gs_unique16_temp_bytes of device memory). */
+gs_status gs_unique16_create(gs_unique16** out, uint32_t max_keys);
+/* No counterpart in the reference project. */
+gs_status gs_unique16_destroy(gs_unique16* h);
+/* No counterpart in the reference project.  Host only.  With A(x) = (x + 255) & ~255:
+ *     A(64 * 4)            the control block
+ *   + A(65536 * 4)         the histogram (directly behind the control block: one clear)
+ *   + A(65536 * 4)         the first position per bin
+ *   + A(65536 * 2)         the rank per bin
+ *   + 4 * A(1024 * 4)      the run-length stage, per range: heads, last head, heads in front, last head in front
+ * = 672 000 bytes whatever max_keys is.  0 for max_keys == 0 or above GS_MAX_KEYS. */
+size_t gs_unique16_temp_bytes(uint32_t max_keys);
+/* No counterpart in the reference project. */
+gs_status gs_unique16_unique(gs_unique16* h, const void* d_keys, uint32_t n, void* d_out_keys, void* d_out_counts, void* d_out_first,
+                             void* d_out_inverse, void* d_out_num, gs_key_type key_type, gs_order order, void* stream);
+/* No counterpart in the reference project. */
+gs_status gs_unique16_consecutive(gs_unique16* h, const void* d_keys, uint32_t n, void* d_out_keys, void* d_out_counts, void* d_out_inverse,
+                                  void* d_out_num, void* stream);
+/* No counterpart in the reference project.  Synchronises `stream` and reports the last call: GS_ERR_HIP if a count did not add up
+ * (cannot happen; the kernels behind then wrote nothing); GS_OK. */
+gs_status gs_unique16_check(gs_unique16* h, void* stream);
+/* No counterpart in the reference project.  Synchronous diagnostics of the last call: report[GS_UNIQUE16_R_*], words >=
+ * GS_UNIQUE16_REPORT_WORDS. */
+gs_status gs_unique16_last(gs_unique16* h, uint32_t* report, uint32_t words, void* stream);
+/* No counterpart in the reference project.  Which form of the inverse lookup gs_unique16_unique runs from the next call on:
+ * GS_UNIQUE16_INVERSE_AUTO (by n, the default), _LDS or _GATHER; the result is the same bit for bit.  GS_ERR_ARG for a null handle
+ * or another value. */
+gs_status gs_unique16_set_inverse_form(gs_unique16* h, uint32_t which);
 
 #ifdef __cplusplus
 }
