@@ -102,6 +102,13 @@ GS_UNIQUE16_REPORT_WORDS = 10
 GS_UNIQUE16_K_FIRST, GS_UNIQUE16_K_INVERSE_LDS, GS_UNIQUE16_K_INVERSE_GATHER = 1, 2, 4
 GS_UNIQUE16_INVERSE_AUTO, GS_UNIQUE16_INVERSE_LDS, GS_UNIQUE16_INVERSE_GATHER = 0, 1, 2
 GS_UNIQUE16_INVERSE_LDS_MIN = 1 << 22
+# gs_reduce_*: value types, operations, routes and report words
+GS_VALUE_INT32, GS_VALUE_UINT32, GS_VALUE_FLOAT32, GS_VALUE_INT64, GS_VALUE_UINT64, GS_VALUE_FLOAT64 = range(6)
+GS_REDUCE_SUM, GS_REDUCE_MIN, GS_REDUCE_MAX = 0, 1, 2
+GS_REDUCE_ROUTE_NONE, GS_REDUCE_ROUTE_SORTED, GS_REDUCE_ROUTE_CONSECUTIVE = 0, 1, 2
+(GS_REDUCE_R_ROUTE, GS_REDUCE_R_N, GS_REDUCE_R_U, GS_REDUCE_R_RANGES, GS_REDUCE_R_PER_RANGE, GS_REDUCE_R_TILE, GS_REDUCE_R_STATUS, GS_REDUCE_R_RANK,
+ GS_REDUCE_R_VALUE_TYPE, GS_REDUCE_R_OP) = range(10)
+GS_REDUCE_REPORT_WORDS = 10
 
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
@@ -369,6 +376,13 @@ _PROTOS = [
     ("gs_unique16_check", _int, [_vp, _vp]),
     ("gs_unique16_last", _int, [_vp, _u32p, _u32, _vp]),
     ("gs_unique16_set_inverse_form", _int, [_vp, _u32]),
+    ("gs_reduce_create", _int, [C.POINTER(_vp), _u32, _u32]),
+    ("gs_reduce_destroy", _int, [_vp]),
+    ("gs_reduce_temp_bytes", C.c_size_t, [_u32, _u32]),
+    ("gs_reduce_by_key", _int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
+    ("gs_reduce_by_key_consecutive", _int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    ("gs_reduce_check", _int, [_vp, _vp]),
+    ("gs_reduce_last", _int, [_vp, _u32p, _u32, _vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

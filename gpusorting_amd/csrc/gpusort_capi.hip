@@ -25,6 +25,7 @@
 #include "topk16_kernels.hpp"
 #include "unique_kernels.hpp"
 #include "unique16_kernels.hpp"
+#include "reduce_kernels.hpp"
 #include "sortrows_kernels.hpp"
 #include "sortrows16_kernels.hpp"
 #include "segsort16_kernels.hpp"
@@ -42,6 +43,7 @@
 #include "topk16_host.hpp"      // gs_topk16: the 1-D selection on 16-bit keys
 #include "unique_host.hpp"      // gs_unique: distinct keys, counts, first positions, inverse (behind onesweep_host and sort16_host)
 #include "unique16_host.hpp"    // gs_unique16: the same on 16-bit keys, from one histogram (behind sort16_host and unique_host)
+#include "reduce_host.hpp"      // gs_reduce: one sum, minimum or maximum per distinct key (behind onesweep_host and unique_host)
 #include "sortrows_host.hpp"    // gs_sort_rows: every row of a matrix sorted in one call
 #include "sortrows16_host.hpp"  // gs_sort_rows16: the same on 16-bit keys
 #include "segsort16_host.hpp"   // gs_segsort16: the segmented sort on 16-bit keys

@@ -10,6 +10,7 @@ handle cache, buffers).  The reference has no such layer; it is what a torch use
     positions = gpusorting_amd.argsort_rows(half_matrix)                     # int32 positions within the row
     distinct, inverse, counts = gpusorting_amd.unique(keys, return_inverse=True, return_counts=True)   # torch.unique (Unique)
     runs, counts = gpusorting_amd.unique_consecutive(keys, return_counts=True)                         # torch.unique_consecutive
+    distinct, sums = gpusorting_amd.reduce_by_key(keys, values, op="sum")   # unique + index_add_ in one call, no atomics (ReduceByKey)
     distinct, index = gpusorting_amd.unique16(half_keys, return_index=True)  # float16 / bfloat16 / int16 / uint16: one histogram (Unique16)
 
 Semantics are the library's: stable LSD radix sort; descending = exact reverse of the stable ascending result;
@@ -29,6 +30,7 @@ from .segtopk16 import SegmentedTopK16  # noqa: F401
 from .sort16 import Sort16, sort16_reference  # noqa: F401
 from .topk import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, TopK, rows_max_k, topk_reference, topk_rows_reference  # noqa: F401
 from .topk16 import TopK16  # noqa: F401
+from .reduce import OPS as _REDUCE_OPS, ReduceByKey, _torch_value_types, reduce_by_key_reference  # noqa: F401
 from .unique import Unique, unique_reference  # noqa: F401
 from .unique16 import Unique16, unique16_reference  # noqa: F401
 from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
@@ -662,6 +664,77 @@ def unique_consecutive(keys: torch.Tensor, return_inverse: bool = False, return_
     u = int(num.item())
     out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ())
     return out[0] if len(out) == 1 else out
+
+
+# ---- reduce by key ------------------------------------------------------------------------------------------------------------------
+_reduce_cache: dict = {}
+
+
+def _reduce_handle(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> ReduceByKey:
+    """The cache rule of ``_unique_handle``: one ``ReduceByKey`` handle per (device, stream, type, order, value width); re-created when
+    the size outgrows it."""
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+    s = _reduce_cache.get(key)
+    if s is None or s.max_keys < n:
+        if s is not None:
+            s.close()
+        cap = 1 << max(int(n - 1).bit_length(), 16)
+        s = ReduceByKey(min(cap, (1 << 30) - 1), order, key_type, value_bytes, device=device.index)
+        _reduce_cache[key] = s
+    return s
+
+
+def _require_reduce_args(keys: torch.Tensor, values: torch.Tensor, op: str):
+    if keys.dim() != 1 or values.dim() != 1 or keys.numel() != values.numel():
+        raise ValueError("keys and values must be contiguous 1-D device tensors of one length")
+    if keys.dtype not in _KEY_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: reduce_by_key takes 32-bit keys (int32, uint32, float32)")
+    vt = _torch_value_types().get(values.dtype)
+    if vt is None:
+        raise TypeError(f"unsupported value dtype {values.dtype}: reduce_by_key takes int32, uint32, float32, int64, uint64 or float64 values")
+    if op not in _REDUCE_OPS:
+        raise ValueError('op is "sum", "min" or "max"')
+    if not keys.is_contiguous() or not values.is_contiguous() or keys.device.type != "cuda" or values.device != keys.device:
+        raise ValueError("keys and values must be contiguous 1-D device tensors of one length")
+    return vt, _REDUCE_OPS[op]
+
+
+def reduce_by_key(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", descending: bool = False, return_counts: bool = False,
+                  unsigned: bool = False):
+    """One ``op`` ("sum", "min", "max") of ``values`` per distinct element of ``keys``: returns ``(distinct, reduced[, counts])`` with
+    ``distinct`` as ``unique(keys, descending=descending, unsigned=unsigned)`` delivers it, ``reduced[j]`` the reduction of all values
+    whose key is ``distinct[j]`` (the values' dtype) and ``counts`` (int32) the multiplicities — ``unique(return_inverse=True)`` followed
+    by ``index_add_`` / ``scatter_reduce`` in one call, with no inverse, no gather and no atomics.  1-D contiguous tensors: keys int32 /
+    uint32 / float32, values int32 / float32 / int64 / float64 (uint32, uint64 where torch has them).  Key equality is BITWISE.  Integer
+    sums wrap.  "min" / "max" on floats use this library's total order (``-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN``) and
+    return one of the inputs bit for bit — UNLIKE ``torch.amin`` / ``amax``, which propagate NaNs, and ``fmin`` / ``fmax``, which drop
+    them.  A float "sum" is combined in an order fixed by the data: two calls give bitwise identical results (``index_add_`` does not),
+    but not the left-to-right sum.  One wait on the host, for the length.  Neither input is written."""
+    vt, opc = _require_reduce_args(keys, values, op)
+    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    n = keys.numel()
+    if n == 0:
+        out = (keys.clone(), values.clone()) + ((torch.empty(0, dtype=torch.int32, device=keys.device),) if return_counts else ())
+        return out
+    with torch.cuda.device(keys.device):
+        s = _reduce_handle(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, values.element_size())
+        out_k, out_v, out_c, num = s.reduce_by_key(keys, values, opc, vt, n, counts=return_counts)
+    u = int(num.item())
+    return (out_k[:u], out_v[:u]) + ((out_c[:u],) if return_counts else ())
+
+
+def reduce_by_key_consecutive(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", return_counts: bool = False):
+    """``reduce_by_key`` on the input as it lies (no sort): one ``op`` of ``values`` per run of BITWISE-equal neighbouring keys, as thrust's
+    ``reduce_by_key``: ``(runs, reduced[, counts])``.  One wait on the host, for the length.  Neither input is written."""
+    vt, opc = _require_reduce_args(keys, values, op)
+    n = keys.numel()
+    if n == 0:
+        return (keys.clone(), values.clone()) + ((torch.empty(0, dtype=torch.int32, device=keys.device),) if return_counts else ())
+    with torch.cuda.device(keys.device):
+        s = _reduce_handle(keys.device, n, KEY_UINT32, ORDER_ASCENDING, values.element_size())
+        out_k, out_v, out_c, num = s.reduce_by_key_consecutive(keys, values, opc, vt, n, counts=return_counts)
+    u = int(num.item())
+    return (out_k[:u], out_v[:u]) + ((out_c[:u],) if return_counts else ())
 
 
 # ---- unique / run-length encode on 16-bit keys -----------------------------------------------------------------------------------

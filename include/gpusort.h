@@ -1424,6 +1424,110 @@ gs_status gs_unique16_last(gs_unique16* h, uint32_t* report, uint32_t words, voi
  * or another value. */
 gs_status gs_unique16_set_inverse_form(gs_unique16* h, uint32_t which);
 
+/* ---- reduce by key: one sum, minimum or maximum per distinct key ----------------------------------------------------------------------
+ * No counterpart in the reference project.  For n keys of GS_KEY_UINT32 / INT32 / FLOAT32, n values of one gs_value_type and an order,
+ * with u distinct keys:
+ *   out_keys[0 .. u)    exactly what gs_unique_keys delivers: the distinct key BIT PATTERNS in the engine's order.  Equality is BITWISE.
+ *   out_values[j]       (the value type) the reduction, by one gs_reduce_op, of all values whose key equals out_keys[j].
+ *   out_counts[j]       (uint32) how many inputs equal out_keys[j]; the counts add up to n.
+ *   *d_out_num          u, one uint32 ON THE DEVICE; gs_reduce_last reports it too.
+ * It is what unique(return_inverse) + index_add_ / scatter_reduce computes, without the inverse, without a gather and without atomics
+ * on the values: a stable sort of (key, value) pairs followed by one segmented reduction.
+ *
+ * The operations.
+ *   GS_REDUCE_SUM on integers wraps modulo 2^32 / 2^64 (signed and unsigned are the same bits).
+ *   GS_REDUCE_MIN / _MAX on integers are the usual ones.
+ *   GS_REDUCE_MIN / _MAX on floats use this library's TOTAL ORDER of float keys, the sortable-bits order
+ *       -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN
+ *     They return one of the inputs bit for bit and are exact and independent of the order of the inputs.  THIS DIFFERS from torch.amin /
+ *     amax (a NaN in the run makes the result NaN) and from fmin / fmax (NaNs are dropped): here a negative NaN is the smallest value, a
+ *     positive NaN the largest, and -0.0 lies below +0.0.
+ *   GS_REDUCE_SUM on floats is the fold of the run's values in the STABLE SORTED ORDER: for ascending the order of the input, for
+ *     descending its exact reverse (descending is the reverse of the stable ascending sort, as for gs_unique_positions).  The values
+ *     are combined in a tree fixed by n and the run's place in the sorted array (eight values per thread left to right, the threads of
+ *     a wave by a scan of distances 1 .. 32, then waves, tiles and ranges left to right); the tree never depends on timing, on how the
+ *     grid is scheduled or on the route the engine takes.  No identity element is combined in anywhere: a run of length 1 returns its
+ *     value bit for bit (NaN payloads included) and a run of -0.0s returns -0.0.  Consequences: two calls on the same input give
+ *     bitwise identical output; the result is NOT the left-to-right sequential sum; ascending and descending may differ in the last bits.
+ *
+ * The inputs are not written.  d_out_counts and d_out_num may be NULL: not wanted.  The caller provides n elements for each of
+ * out_keys, out_values and out_counts and one word at d_out_num; NOTHING AT OR BEHIND ELEMENT u of out_keys, out_values or out_counts IS
+ * WRITTEN, and nothing intermediate passes through them.  Base pointers are 16-byte aligned (d_out_num: 4-byte); no two of the call's
+ * buffers overlap (keys, values, the three outputs, d_out_num, and the handle's own workspace: seven, pairwise).  The call is
+ * asynchronous on `stream`: every launch is enqueued up front with no host round trip, every node is a kernel launch, and every grid
+ * is fixed by n, never by u — a call can be captured into a graph and replayed on new data with another u.  No kernel waits on
+ * another workgroup and no value goes through an atomic.  One call in flight per handle.
+ *
+ * A handle is made for one value WIDTH (4 or 8 bytes); its embedded gs_onesweep sorts (key, value) pairs of that width.
+ *   gs_reduce_by_key              one kernel copies keys and values into the workspace, gs_onesweep_sort_pairs runs on the copy, then
+ *                                 the reduce stage.
+ *   gs_reduce_by_key_consecutive  the stage alone on the input AS IT LIES: runs of bitwise-equal neighbouring keys are reduced (thrust's
+ *                                 reduce_by_key); no key type, no order.
+ * The stage works on gs_unique_plan's ranges of whole tiles, in three launches: count (one workgroup per range: its heads, its last
+ * head's position and its open partial — the reduction from its last head to its end, or of the whole range if it holds no head),
+ * scan (one workgroup: heads and last head in front of every range, u, and the carry into every range), reduce (a segmented scan per
+ * tile; the head of rank r writes out_keys[r] and closes run r - 1: its count and its total, each written exactly once; the thread
+ * that holds element n - 1 closes the last run).
+ *
+ * Errors, in this order.  GS_ERR_ARG: null handle (before anything else is looked at); null or misaligned d_keys / d_values / d_out_keys
+ * / d_out_values; a key type outside 0 .. 2, a bad order (gs_reduce_by_key_consecutive has neither); a value type outside 0 .. 5, an
+ * op outside 0 .. 2.  GS_ERR_MODE: a value type whose width is not the handle's.  GS_ERR_ARG: a misaligned d_out_counts / d_out_num.
+ * GS_ERR_SIZE: n == 0 or n > max_keys.  GS_ERR_ARG: any two of the seven buffers overlapping (outputs at their capacity of n elements).
+ * GS_ERR_MODE: every call on a build flavour without these kernels (the tuning and fault-injection libraries).  A refused call
+ * launches nothing and leaves route NONE. */
+typedef struct gs_reduce gs_reduce;
+typedef enum gs_value_type {
+    GS_VALUE_INT32 = 0,
+    GS_VALUE_UINT32 = 1,
+    GS_VALUE_FLOAT32 = 2,
+    GS_VALUE_INT64 = 3,
+    GS_VALUE_UINT64 = 4,
+    GS_VALUE_FLOAT64 = 5
+} gs_value_type;
+typedef enum gs_reduce_op { GS_REDUCE_SUM = 0, GS_REDUCE_MIN = 1, GS_REDUCE_MAX = 2 } gs_reduce_op;
+#define GS_REDUCE_ROUTE_NONE 0
+#define GS_REDUCE_ROUTE_SORTED 1
+#define GS_REDUCE_ROUTE_CONSECUTIVE 2
+/* gs_reduce_last report words */
+#define GS_REDUCE_R_ROUTE 0
+#define GS_REDUCE_R_N 1
+#define GS_REDUCE_R_U 2           /* distinct keys (runs) of the last call */
+#define GS_REDUCE_R_RANGES 3      /* the stage's plan: gs_unique_plan(n) */
+#define GS_REDUCE_R_PER_RANGE 4
+#define GS_REDUCE_R_TILE 5
+#define GS_REDUCE_R_STATUS 6      /* the device status word: 0, or 1 if a count did not add up (gs_reduce_check: GS_ERR_HIP) */
+#define GS_REDUCE_R_RANK 7        /* the embedded engine's rank mode (gs_onesweep_get_rank_mode) */
+#define GS_REDUCE_R_VALUE_TYPE 8  /* the gs_value_type of the last call */
+#define GS_REDUCE_R_OP 9          /* its gs_reduce_op */
+#define GS_REDUCE_REPORT_WORDS 10
+/* No counterpart in the reference project.  1 <= max_keys <= GS_MAX_KEYS (GS_ERR_SIZE), then value_bytes 4 or 8 (GS_ERR_MODE), both
+ * answered before a device is looked for.  Synchronous (allocates gs_reduce_temp_bytes of device memory). */
+gs_status gs_reduce_create(gs_reduce** out, uint32_t max_keys, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_reduce_destroy(gs_reduce* h);
+/* No counterpart in the reference project.  Host only.  With A(x) = (x + 255) & ~255:
+ *     A(64 * 4)                            the control block
+ *   + 4 * A(1024 * 4)                      per range: heads, last head, heads in front, last head in front
+ *   + 2 * A(1024 * 8)                      per range: the open partial and the carry (8 bytes each, whatever the width)
+ *   + 2 * A(4 * max_keys)                  the copy of the keys the engine sorts, and its alternate buffer
+ *   + 2 * A(value_bytes * max_keys)        the copy of the values, and its alternate buffer
+ *   + gs_onesweep_temp_bytes(max_keys)     the embedded engine
+ * 0 for invalid sizes or value width. */
+size_t gs_reduce_temp_bytes(uint32_t max_keys, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_reduce_by_key(gs_reduce* h, const void* d_keys, const void* d_values, uint32_t n, void* d_out_keys, void* d_out_values,
+                           void* d_out_counts, void* d_out_num, gs_key_type key_type, gs_order order, gs_value_type value_type, gs_reduce_op op,
+                           void* stream);
+/* No counterpart in the reference project. */
+gs_status gs_reduce_by_key_consecutive(gs_reduce* h, const void* d_keys, const void* d_values, uint32_t n, void* d_out_keys, void* d_out_values,
+                                       void* d_out_counts, void* d_out_num, gs_value_type value_type, gs_reduce_op op, void* stream);
+/* No counterpart in the reference project.  Synchronises `stream` and reports the last call: GS_ERR_HIP if the heads counted and the
+ * heads written disagree (cannot happen; the reduce then wrote nothing or stopped) or the engine refused its sort; otherwise, after
+ * gs_reduce_by_key, what gs_onesweep_check says of the engine (GS_ERR_TIMEOUT); GS_OK. */
+gs_status gs_reduce_check(gs_reduce* h, void* stream);
+/* No counterpart in the reference project.  Synchronous diagnostics of the last call: report[GS_REDUCE_R_*], words >= GS_REDUCE_REPORT_WORDS. */
+gs_status gs_reduce_last(gs_reduce* h, uint32_t* report, uint32_t words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
