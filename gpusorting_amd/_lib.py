@@ -112,7 +112,7 @@ GS_REDUCE_REPORT_WORDS = 10
 
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
-GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS = 1, 2, 4, 8, 16
+GS_PF_SKEW, GS_PF_SKIP, GS_PF_SRC_ALT, GS_PF_LAST, GS_PF_POS, GS_PF_HALF16 = 1, 2, 4, 8, 16, 32
 (GS_KF_BIN, GS_KF_POS, GS_KF_PERSIST, GS_KF_SMALL, GS_KF_MID, GS_KF_SEG_WG, GS_KF_SEG_VB, GS_KF_TKR_TILE, GS_KF_TKR_VM, GS_KF_HIST,
  GS_KF_HY_HIST, GS_KF_HY_LOCAL, GS_KF_HY_LOCAL_PAIRS, GS_KF_COUNT) = range(14)
 # gs_key_type behind the 64-bit ones: 2-byte keys, accepted by gs_topk_select_rows_keys / _pairs, gs_topk16_*, gs_sort16_*, gs_sort_rows16_* and gs_segsort16_*
@@ -228,6 +228,7 @@ _PROTOS = [
     ("gs_debug_sort_route", _int, [_vp, _u32, _int, _u32p]),
     ("gs_debug_set_hy_class", _int, [_vp, _int]),
     ("gs_debug_pass_flags", _int, [_vp, _u32p, _vp]),
+    ("gs_debug_hy_half_slot", _u32, [_u32, _u32, _u32, _u32, _u32]),
     ("gs_debug_registry_dims", _int, [_u32, C.POINTER(C.c_int32)]),
     ("gs_debug_registry_cell", _int, [_u32, C.POINTER(C.c_int32)]),
     ("gs_onesweep_global_histogram", _int, [_vp, _vp, _u32, _int, C.POINTER(_u32), _vp]),

@@ -1,4 +1,5 @@
-// hybrid_kernels.hpp — the TWO-LEVEL plan of large sorts of 32-bit keys (round 5): 28 bytes of HBM traffic per key instead of 36.
+// hybrid_kernels.hpp — the TWO-LEVEL plan of large sorts of 32-bit keys (round 5): 28 bytes of HBM traffic per key instead of 36
+// (keys only: 24 — pass B hands the bucket-local sort 16-bit halves, hy_half_slot below).
 //
 // The reference's OneSweep (GPUSortingCUDA/Sort/OneSweep.cu:44-600; dispatch OneSweepDispatcher.cuh:311-363) is one histogram
 // sweep + four 8-bit LSD passes: 4 + 4 x 8 = 36 B/key.  On MI355X each pass already runs at the floor of its access shape
@@ -21,6 +22,8 @@
 //   hy_local_sort_kernel  one workgroup per 16-bit-prefix bucket (n / 65 536 keys on average): loads the bucket, sorts it on the low
 //                         16 bits by two 8-bit passes in LDS, and writes it back IN PLACE — sequential reads and writes
 //                         (hy_local_sort_pairs_kernel: the same with values, which move once, behind the keys).
+//                         Keys only: the bucket's top 16 bits are its number, so pass B writes (4 + 2 B/key) and this kernel reads
+//                         (2 + 4 B/key) the low halves alone — PF_HALF16, hy_half_slot.  Pairs hand over whole keys.
 // (stable by byte 3) o (stable by byte 2 inside each byte-3 bucket) o (stable by the low 16 bits inside each 16-bit bucket) is
 // the stable sort by the whole key: the result is bit-identical to the four LSD passes, values included.
 //
@@ -46,6 +49,21 @@ constexpr uint32_t HYT_BASE = HY_BINS;                  // base[65 536 + 1]: sta
 constexpr uint32_t HYT_T = HYT_BASE + HY_BINS + 64;     // T[NCH][256]: keys of position segment x whose top byte is d
 constexpr uint32_t HYT_WORDS = HYT_T + NCH * RADIX;
 static_assert(HYT_BASE % 4 == 0 && HYT_T % 4 == 0, "16-byte accesses");
+
+// ---------------------------------------------------------------------------
+// The hand-over from pass B to the bucket-local sort, keys only (PF_HALF16).  Behind pass B every key of bucket p — a 16-bit prefix in
+// radix-sortable bits, count = base_p1 - base_p keys — shares its top 16 bits with the bucket's number, so pass B writes the low 16
+// bits alone, as a uint16, and the bucket-local sort puts the prefix back from blockIdx.x: 2 bytes per key less written, 2 less read.
+// The bucket's final range starts at key index `at` = base_p (ascending) or n - base_p1 (descending: the mirrored range).  With the key
+// buffer viewed as uint16[2 n], the key pass B ranks `rank` = (ascending output position) - base_p inside its bucket goes to halfword
+// 2 at + rank: the halfwords fill the first half of the bucket's own bytes, [2 at, 2 at + count) — 4-byte aligned, no extra memory,
+// nothing outside [0, 4 n) bytes, buckets disjoint.  (Any bijection onto those slots would do — keys alone carry no order — and this
+// one costs pass B nothing: the addend 2 at - base_p joins the digit's base.)  n <= GS_MAX_KEYS < 2^30: 2 at + rank < 2^31.
+// ---------------------------------------------------------------------------
+__host__ __device__ inline uint32_t hy_half_slot(uint32_t base_p, uint32_t base_p1, uint32_t n, uint32_t descending, uint32_t rank) {
+    const uint32_t at = descending ? n - base_p1 : base_p;
+    return 2u * at + rank;
+}
 
 constexpr int HY_HIST_THREADS = 1024;
 constexpr uint32_t HY_FOLD_CHUNKS = 256;  // the digit-0 replicas are folded at least this often (see global_histogram_kernel)
@@ -313,7 +331,8 @@ __global__ __launch_bounds__(256) void hy_reduce_kernel(const uint32_t* __restri
 __global__ __launch_bounds__(1024) void hy_scan_kernel(uint32_t* slab, uint32_t* tab, uint32_t n, uint32_t seg_len0, uint32_t desc_stride,
                                                         uint32_t cap, uint32_t tile, uint32_t pregrouped /*the input is already grouped by
                                                         its top byte and lies in the ALTERNATE buffer (multi-GPU: the bucket exchange landed it
-                                                        there bin by bin): pass A has nothing to do*/) {
+                                                        there bin by bin): pass A has nothing to do*/,
+                                                        uint32_t keys_only /*pass B hands the bucket-local sort 16-bit halves (PF_HALF16)*/) {
     // Row i (16 rows) = prefixes [4096 i, 4096 (i + 1)); thread t holds prefixes 4096 i + 4 t .. + 3 of every row: all global
     // accesses are coalesced 16-byte ones (64 consecutive prefixes per thread, the first form, made every access of a wave touch 64
     // cache lines: 30 us for 256 KiB).  Wave w of row i = the 256 prefixes of top byte 16 i + w.
@@ -432,7 +451,7 @@ __global__ __launch_bounds__(1024) void hy_scan_kernel(uint32_t* slab, uint32_t*
         info0[I_NEXT_SHIFT] = 0xffffffffu;
         info0[I_SHIFT] = 24u;
         info0[I_MODE] = 0xffffffffu;
-        info1[PASS_FLAGS] = PF_SRC_ALT | PF_LAST;
+        info1[PASS_FLAGS] = PF_SRC_ALT | PF_LAST | (keys_only ? PF_HALF16 : 0u);
         info1[I_NCH] = CHMAX;
         info1[I_NEXT_SHIFT] = 0xffffffffu;
         info1[I_SHIFT] = 16u;
@@ -448,9 +467,10 @@ static_assert(CHMAX == RADIX, "pass B: one chain per top-byte value");
 // ---------------------------------------------------------------------------
 // One workgroup per 16-bit prefix: the bucket's keys (all share their top 16 bits) sorted on the low 16 bits by two stable
 // 8-bit passes in LDS (the machinery of bucket_sort_kernel / small_sort_kernel), IN PLACE: the bucket is in registers before
-// anything is written, and no other workgroup touches its range.  Descending: pass B wrote to mirrored positions (index
-// n - 1 - o), so the bucket lies at [n - start - count, n - start) and is written back in reverse (keys only: equal keys
-// are indistinguishable, the reverse of the stable ascending order is any descending order).
+// anything is written, and no other workgroup touches its range.  Pass B left the keys' low halves in the first half of that range
+// (PF_HALF16, hy_half_slot); the top 16 bits are the bucket's number, blockIdx.x, in radix-sortable form already.  Descending: the
+// bucket's range is the mirrored one, [n - start - count, n - start), and the sorted keys are written back in reverse (keys only:
+// equal keys are indistinguishable, the reverse of the stable ascending order is any descending order).
 // ---------------------------------------------------------------------------
 template <int KT, int THREADS_, int KPT_>
 __global__ __launch_bounds__(THREADS_) void hy_local_sort_kernel(uint32_t* keys, const uint32_t* __restrict__ tab, uint32_t* __restrict__ slab,
@@ -470,20 +490,35 @@ __global__ __launch_bounds__(THREADS_) void hy_local_sort_kernel(uint32_t* keys,
     if (__builtin_amdgcn_readfirstlane((int)valid) == 0) return;  // the sort runs on the LSD passes
     const uint32_t start = b_lo, count = b_hi - b_lo;
     if (count == 0u || count > TILE || start > n || count > n - start) return;  // (the last three cannot happen with a valid plan)
-    const uint32_t at = descending ? n - start - count : start;
+    // first key of the bucket's range = first dword of its halfwords (hy_half_slot: rank r lies in half r & 1 of dword at + r / 2)
+    const uint32_t at = hy_half_slot(start, b_hi, n, descending, 0u) >> 1;
     const uint32_t kpt = (uint32_t)__builtin_amdgcn_readfirstlane((int)((count + THREADS - 1u) / THREADS));  // uniform, 1 .. KPT
     const uint32_t my_base = wave * (64u * kpt) + lane;
+    // The load: (count + 1) / 2 dwords, kp2 = ceil(kpt / 2) per thread, wave-striped like the slots (256 bytes per wave-instruction);
+    // dword j of a thread becomes key[2 j] and key[2 j + 1].  Pass 1 is not stable, so the keys need not sit in the slot order the
+    // rest of the kernel uses (my_base + i * 64): pass 1 takes them as they come — its own mask below — and leaves them in the stage,
+    // from where every thread picks up the keys of its slots: no second remapping.  An odd count's last dword has a stale upper half:
+    // halfword `count`, masked like every halfword at or behind it.
+    const uint32_t kp2 = (kpt + 1u) >> 1, ndw = (count + 1u) >> 1;  // uniform
+    const uint32_t my_half = 2u * (wave * (64u * kp2) + lane);     // halfword index of key[0]; key[i]: my_half + (i >> 1) * 128 + (i & 1)
+    const uint32_t top = blockIdx.x << 16;
     uint32_t key[KPT];
+    // (all loads are issued before the first is consumed: split in the loop that loads, every load waited for its own round trip —
+    //  0.65 ms for the kernel instead of 0.51, profiles/half16_headline_ab.txt)
 #pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-        if ((uint32_t)i >= kpt) continue;  // uniform
-        const uint32_t slot = my_base + i * 64u;
-        key[i] = keys[at + (slot < count ? slot : count - 1u)];
+    for (int j = 0; j < KPT / 2; ++j) {
+        if ((uint32_t)j >= kp2) continue;  // uniform
+        const uint32_t q = (my_half >> 1) + j * 64u;
+        key[2 * j] = keys[at + (q < ndw ? q : ndw - 1u)];
     }
     if (tid < RADIX) s_cnt[tid] = 0;
 #pragma unroll
-    for (int i = 0; i < KPT; ++i)
-        if ((uint32_t)i < kpt) key[i] = to_bits<KT>(key[i]);
+    for (int j = 0; j < KPT / 2; ++j) {
+        if ((uint32_t)j >= kp2) continue;
+        const uint32_t w = key[2 * j];
+        key[2 * j] = top | (w & 0xffffu);
+        key[2 * j + 1] = top | (w >> 16);
+    }
     __syncthreads();
     // The kernel is bound by its LDS instructions (two passes x rank / base / stage / read back, profiles/r05_*): whatever is not
     // per key is kept small.
@@ -494,8 +529,8 @@ __global__ __launch_bounds__(THREADS_) void hy_local_sort_kernel(uint32_t* keys,
     for (int i = 0; i < KPT / 2; ++i) off[i] = 0;
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
-        if ((uint32_t)i >= kpt) continue;
-        if (my_base + i * 64u < count)
+        if ((uint32_t)(i >> 1) >= kp2) continue;  // uniform
+        if (my_half + (i >> 1) * 128u + (i & 1) < count)
             off[i >> 1] |= __hip_atomic_fetch_add(&s_cnt[key[i] & 255u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) << (16 * (i & 1));
     }
     __syncthreads();
@@ -514,8 +549,8 @@ __global__ __launch_bounds__(THREADS_) void hy_local_sort_kernel(uint32_t* keys,
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
-        if ((uint32_t)i >= kpt) continue;
-        if (my_base + i * 64u < count) s_stage[((off[i >> 1] >> (16 * (i & 1))) & 0xffffu) + s_cnt[key[i] & 255u]] = key[i];
+        if ((uint32_t)(i >> 1) >= kp2) continue;
+        if (my_half + (i >> 1) * 128u + (i & 1) < count) s_stage[((off[i >> 1] >> (16 * (i & 1))) & 0xffffu) + s_cnt[key[i] & 255u]] = key[i];
     }
     __syncthreads();
 #pragma unroll

@@ -168,6 +168,7 @@ struct PrologueIn {
     bool hy = false;               // the sort may run on the two-level plan (hybrid_kernels.hpp): its histogram sweep replaces GlobalHistogram,
                                    // its scan runs in front of the ordinary one, and both plans' launches follow (sort_impl)
     bool pregrouped = false;       // ... and its input is already grouped by its top byte (sort_impl)
+    bool keys_only = false;        // ... and it carries no values: pass B hands the bucket-local sort 16-bit halves (PF_HALF16)
 };
 gs_status prologue(gs_onesweep* h, const void* d_keys, uint32_t n, gs_key_type kt, hipStream_t s, const PrologueIn& in, PassPlan* plan) {
     const uint32_t p0 = in.first_pass, np = in.num_passes, scan_plan = in.scan_plan, word = in.word, pos_tile = in.pos_tile;
@@ -210,7 +211,8 @@ gs_status prologue(gs_onesweep* h, const void* d_keys, uint32_t n, gs_key_type k
         hy_hist_launcher(kt)(s, G, static_cast<const uint32_t*>(d_keys), h->slab, used_words, n, seg_len0, per_wg, wg_per_seg, h->partials, cap);
         hipLaunchKernelGGL(gs::hy_reduce_kernel, dim3(gs::RADIX + gs::NCH), dim3(256), 0, s, h->partials, G, wg_per_seg, h->hy_tab, h->slab + SLAB_HIST);
         if (rec) GS_HIP(hipEventRecord(h->ev[2], s));
-        hipLaunchKernelGGL(gs::hy_scan_kernel, dim3(1), dim3(1024), 0, s, h->slab, h->hy_tab, n, seg_len0, desc_stride, cap, tile, pregrouped ? 1u : 0u);
+        hipLaunchKernelGGL(gs::hy_scan_kernel, dim3(1), dim3(1024), 0, s, h->slab, h->hy_tab, n, seg_len0, desc_stride, cap, tile, pregrouped ? 1u : 0u,
+                           in.keys_only ? 1u : 0u);
     } else {
     hist_launcher(kt)(s, hist_blocks(n, h->hist_blocks_opt), static_cast<const uint32_t*>(d_keys), h->slab, used_words, n, seg_len0, p0, np, word,
                (scan_plan & 4u) ? (h->pos_chains == 2 ? 3u : 1u) : 0u, h->partials);
@@ -392,6 +394,7 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
         in.pos_tile = pos_tile_for(vb);
         in.hy = hy;
         in.pregrouped = pregrouped;
+        in.keys_only = vb == 0;
         gs_status st = prologue(h, pregrouped ? d_alt_keys : d_keys, n, kt, s, in, &plan);
         if (st != GS_OK) return st;
         if (values_ready && word == 0) GS_HIP(hipStreamWaitEvent(s, values_ready, 0));  // histogram + scan ran on the keys meanwhile
@@ -409,7 +412,7 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
         auto launch = [&](BinLauncher f, uint32_t grid, uint32_t p, uint32_t a, uint32_t shift, uint32_t mode) {
             launch_pass(h, f, s, grid, p, plan.desc_stride, k[a], k[a ^ 1u], v[a], v[a ^ 1u], n, shift, mode);
         };
-        const bool skip_local = (h->debug_flags & 0x40000000u) != 0u;  // (tuning builds, tools/hy_bringup.py: pass B's output stays as it is)
+        const bool skip_local = (h->debug_flags & 0x40000000u) != 0u;  // (tuning builds, tools/hy_bringup.py: pass B's output stays as it is — keys only: 16-bit halves)
         for (uint32_t p = 0; p < NP; ++p) {
             const uint32_t a = dyn ? 0u : (p & 1u);
             const uint32_t mode = (dyn ? (desc_bit | gs::BM_PLANNED) : ((desc_bit && p == NP - 1) ? gs::BM_REVERSE : 0u)) | (p == 0 ? gs::BM_ZERO_HIST : 0u);
@@ -644,7 +647,10 @@ gs_status gs_debug_sort_route(gs_onesweep* h, uint32_t n, gs_key_type kt, uint32
 }
 
 static_assert(GS_PF_SKEW == gs::PF_SKEW && GS_PF_SKIP == gs::PF_SKIP && GS_PF_SRC_ALT == gs::PF_SRC_ALT && GS_PF_LAST == gs::PF_LAST &&
-              GS_PF_POS == gs::PF_POS, "header and kernels agree on the pass flags");
+              GS_PF_POS == gs::PF_POS && GS_PF_HALF16 == gs::PF_HALF16, "header and kernels agree on the pass flags");
+uint32_t gs_debug_hy_half_slot(uint32_t base_p, uint32_t base_p1, uint32_t n, uint32_t descending, uint32_t rank) {
+    return gs::hy_half_slot(base_p, base_p1, n, descending, rank);
+}
 gs_status gs_debug_pass_flags(gs_onesweep* h, uint32_t flags[8], void* stream) {
     if (!h || !flags) return GS_ERR_ARG;
     for (uint32_t q = 0; q < gs::MAX_PASSES; ++q) flags[q] = 0;

@@ -136,6 +136,10 @@ constexpr uint32_t PF_POS = 16;     // the sort runs on position chains in EVERY
                                     // upfront: each pass counts the next pass's digit per output position segment while it
                                     // scatters (CNEXT), every workgroup of the next pass derives digit starts / skew / mode digit
                                     // from those counts when it starts, and tile 0 of each chain seeds the chain's row 0
+constexpr uint32_t PF_HALF16 = 32;  // pass B of a keys-only two-level sort (set by hy_scan_kernel alone): the pass writes the low 16 bits
+                                    // of every key, as a uint16, to the slot hy_half_slot names (hybrid_kernels.hpp)
+// halfword index of the key ranked `rank` in the bucket [base_p, base_p1) of a sort of n keys: defined in hybrid_kernels.hpp
+__host__ __device__ inline uint32_t hy_half_slot(uint32_t base_p, uint32_t base_p1, uint32_t n, uint32_t descending, uint32_t rank);
 
 // ---- state slab layout (uint32 words), shared by host and kernels -------------
 //  COUNTERS  tile tickets, [pass][chain]                       (reference m_index)
@@ -1288,6 +1292,7 @@ __device__ __forceinline__ void binning_body(
     uint32_t mode /*BM_* bits, above*/) {
     constexpr int KW = KeyWords<KT>::value;
     using Cfg = BinCfg<THREADS, KPT, VB, KW, VR, POS>;
+    constexpr bool HALF16_FORM = POS == 0 && VB == 0 && KW == 1 && PERSIST;  // the form that may be told PF_HALF16 (the dual kernel's plain one)
     if (mode & BM_INFO_SHIFT) shift_full = (uint32_t)__builtin_amdgcn_readfirstlane((int)info[I_SHIFT]);
     // Chain a workgroup asks first: blockIdx modulo NCH, in chain GROUP `group`.  The LSD plans have one group (NCH chains).  A pass on
     // CHMAX chains (the two-level plan's second pass: one chain per top-byte bucket) is walked group by group — NCH chains at a time,
@@ -1431,7 +1436,11 @@ __device__ __forceinline__ void binning_body(
     uint32_t* keys_out = swapped ? keys_a : keys_b;
     const void* vals_in_ = swapped ? vals_b : vals_a;
     void* vals_out_ = swapped ? vals_a : vals_b;
-    const bool reverse = (mode & BM_REVERSE) && (!(mode & BM_PLANNED) || (pflags & PF_LAST));
+    const bool descending = (mode & BM_REVERSE) && (!(mode & BM_PLANNED) || (pflags & PF_LAST));
+    // PF_HALF16 (uniform per launch; the plain keys-only form as persistent workgroups: pass B of the two-level plan): the scatter
+    // stores halfwords, and hy_half_slot's addend — folded into s_gbase below — carries the order: no index reversal
+    const bool half16 = HALF16_FORM && (pflags & PF_HALF16) != 0u;
+    const bool reverse = descending && !half16;
     const uint32_t nch = uni(s_misc[10]);                                 // chains of this pass
     // POS: bit position of the next running pass's digit (~0: nothing to count) and log2 of its position segments
     const uint32_t next_shift = (POS == 1 && (mode & BM_PLANNED)) ? uni(s_misc[11]) : 0xffffffffu, seglog = uni(s_misc[12]);
@@ -1599,6 +1608,16 @@ __device__ __forceinline__ void binning_body(
     // rows requested before the staging phase, rows through the scalar data path, larger batches in crowded chains
     // (profiles/r02_ab_early_lookback_rows.txt, r02_ab_scalar_lookback.txt).
     uint32_t prev = 0, spins = 0;
+    // PF_HALF16: digit d of this chain is the 16-bit prefix (chain, d), a bucket of the bucket-local sort.  Its bounds are the chain's
+    // seed row (row 0: written by hy_scan_kernel, never again) — the last digit's upper one is the chain's end — requested here, in
+    // flight beside the walk's rows, and folded into the digit's base: the key at output position o goes to halfword o + half_add.
+    uint32_t half_add = 0;
+    if constexpr (HALF16_FORM) {
+        if (half16 && tid < RADIX) {
+            const uint32_t base_p = cdesc[tid] >> 2, base_p1 = tid == RADIX - 1u ? seg_end : cdesc[(tid + 1u) & (RADIX - 1u)] >> 2;
+            half_add = hy_half_slot(base_p, base_p1, n, descending ? 1u : 0u, 0u) - base_p;
+        }
+    }
     int32_t k = (int32_t)tile;
     bool done = false, poisoned = false, finished = tid >= RADIX;
     auto walk = [&]() {
@@ -1651,7 +1670,7 @@ __device__ __forceinline__ void binning_body(
                 if (!GS_FAULT_TILE(chain, tile))
                     st_agent(&cdesc[(size_t)(tile + 1u) * RADIX + tid],
                              poisoned ? FLAG_POISON : (((prev + tile_total) << 2) | FLAG_INCLUSIVE));
-                s_gbase[tid] = prev - dpre - (tid == 0 ? head : 0u);  // digit 0's real keys start `head` slots into its run
+                s_gbase[tid] = prev - dpre - (tid == 0 ? head : 0u) + half_add;  // digit 0's real keys start `head` slots into its run
             }
         }
         __syncthreads();
@@ -1814,13 +1833,20 @@ __device__ __forceinline__ void binning_body(
             uint32_t kb[KPT];
 #pragma unroll
             for (int j = 0; j < KPT; ++j) kb[j] = s_stage[tid + j * THREADS];
+            if (half16) {  // uniform (false at compile time outside HALF16_FORM): the low halves, in bits form, to their halfword slots
+                uint16_t* half_out = reinterpret_cast<uint16_t*>(keys_out);
 #pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                const uint32_t d = (kb[j] >> shift) & 255u;
-                const uint32_t opos = s_gbase[d] + tid + j * THREADS;
-                st_stream(keys_out + ((opos ^ rev_xor) + rev_add), from_bits<KT>(kb[j]));
-                if constexpr (POS == 1) { if (counting) count_next(kb[j], opos, true); }
-                if constexpr (VB != 0) digs[j >> 2] |= d << (8 * (j & 3));
+                for (int j = 0; j < KPT; ++j)
+                    st_stream(half_out + (s_gbase[(kb[j] >> shift) & 255u] + tid + j * THREADS), (uint16_t)(kb[j] & 0xffffu));
+            } else {
+#pragma unroll
+                for (int j = 0; j < KPT; ++j) {
+                    const uint32_t d = (kb[j] >> shift) & 255u;
+                    const uint32_t opos = s_gbase[d] + tid + j * THREADS;
+                    st_stream(keys_out + ((opos ^ rev_xor) + rev_add), from_bits<KT>(kb[j]));
+                    if constexpr (POS == 1) { if (counting) count_next(kb[j], opos, true); }
+                    if constexpr (VB != 0) digs[j >> 2] |= d << (8 * (j & 3));
+                }
             }
         }
     } else {
@@ -1837,6 +1863,8 @@ __device__ __forceinline__ void binning_body(
             if (full || (i >= head && i < head + count)) {
                 if constexpr (KW == 2)
                     st_stream(reinterpret_cast<uint2*>(keys_out) + o, from_bits2<KT>(hi_word ? uint2{kb2.y, kb2.x} : kb2));
+                else if (half16)  // (o is the halfword slot: `reverse` is off)
+                    st_stream(reinterpret_cast<uint16_t*>(keys_out) + o, (uint16_t)(kb & 0xffffu));
                 else
                     st_stream(keys_out + o, from_bits<KT>(kb));
             }

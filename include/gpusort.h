@@ -257,7 +257,15 @@ gs_status gs_debug_set_hy_class(gs_onesweep* h, int cls);
 #define GS_PF_SRC_ALT 4u  /* an odd number of earlier passes ran: this pass reads the alternate buffers */
 #define GS_PF_LAST 8u     /* the last pass that runs */
 #define GS_PF_POS 16u     /* the sort runs on position chains: the position-chain form of the pass works */
+#define GS_PF_HALF16 32u  /* the second pass of a keys-only sort on the two-level plan: it hands the bucket-local sort the keys' low 16 bits
+                             alone, two bytes per key (gs_debug_hy_half_slot); never set for pairs or on the LSD passes */
 gs_status gs_debug_pass_flags(gs_onesweep* h, uint32_t flags[8], void* stream);
+/* Test hook, host only (no device work): where the second pass of a keys-only sort on the two-level plan puts the low 16 bits of a key.
+ * The bucket of a 16-bit prefix holds the keys whose sorted ascending positions are [base_p, base_p1); its final range starts at key
+ * index at = base_p (ascending) or n - base_p1 (descending != 0).  With the key buffer viewed as uint16[2 n], the key that pass ranks
+ * `rank` (0 .. base_p1 - base_p - 1) inside the bucket goes to halfword 2 at + rank — the value returned: the first half of the bucket's
+ * own bytes.  The kernels compute their addresses with the same function. */
+uint32_t gs_debug_hy_half_slot(uint32_t base_p, uint32_t base_p1, uint32_t n, uint32_t descending, uint32_t rank);
 /* Test hooks, host only (they work without a GPU): the kernel registry of this build — one launcher table per kernel family
  * (GS_KF_*), indexed by tile shape or size class, rank mode, value width and key type.  gs_debug_registry_dims: dims[0 .. r) = the
  * table's extents, the rest 1; returns r, -1 for an unknown family or null dims.  gs_debug_registry_cell: 1 if this build compiled
