@@ -19,10 +19,13 @@ Only the hot path of b0nes164/GPUSorting named by BASELINE.json is here:
   unique16   the same on 16-bit keys at their own width, from one 65 536-bin histogram, over gs_unique16_*, and its numpy reference
   reduce     reduce by key: one sum, minimum or maximum per distinct key (the pairs sort plus one segmented reduction, or that stage alone
              on runs of equal neighbours) over gs_reduce_*, and its numpy reference
+  unique64   unique on 64-bit keys (uint64, int64, float64) over gs_unique64_*, and its numpy reference
+  reduce64   reduce by key on 64-bit keys over gs_reduce64_*, and its numpy reference
   functional sort / sort_ / argsort / sort_rows / argsort_rows / segmented_sort / topk / topk16 / segmented_topk / segmented_topk16 /
-             unique / unique_consecutive / unique16 / unique_consecutive16 / reduce_by_key / reduce_by_key_consecutive on torch tensors (plumbing
+             unique / unique_consecutive / unique16 / unique_consecutive16 / reduce_by_key / reduce_by_key_consecutive / unique64 /
+             unique_consecutive64 / reduce_by_key64 / reduce_by_key_consecutive64 on torch tensors (plumbing
              over OneSweep / RowSort / RowSort16 / SegmentedSort / SegmentedSort16 / TopK / SegmentedTopK / SegmentedTopK16 / TopK16 /
-             Unique / Unique16 / ReduceByKey)
+             Unique / Unique16 / ReduceByKey / Unique64 / ReduceByKey64)
 """
 from .onesweep import (  # noqa: F401
     ENTROPY_PRESET_1, ENTROPY_PRESET_2, ENTROPY_PRESET_3, ENTROPY_PRESET_4, ENTROPY_PRESET_5,
@@ -33,8 +36,10 @@ from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, GpuSortError
 from .functional import (  # noqa: F401
     argsort, argsort_rows, reduce_by_key, reduce_by_key_consecutive, segmented_argsort, segmented_sort, segmented_sort_, segmented_topk, segmented_topk16, sort, sort_, sort_rows, sort_rows_, topk,
     topk16, unique, unique16, unique_consecutive, unique_consecutive16,
+    reduce_by_key64, reduce_by_key_consecutive64, unique64, unique_consecutive64,
 )
 from .reduce import ReduceByKey, reduce_by_key_reference  # noqa: F401
+from .reduce64 import ReduceByKey64, reduce_by_key64_reference  # noqa: F401
 from .rowsort import RowSort, sort_rows_plan, sort_rows_reference  # noqa: F401
 from .rowsort16 import SORT_ROWS16_FORMS, RowSort16, sort_rows16_plan, sort_rows16_reference  # noqa: F401
 from .segsort import SegmentedSort, segmented_sort_reference, segsort_long_units  # noqa: F401
@@ -46,3 +51,4 @@ from .topk import TopK, topk_reference, topk_rows_reference  # noqa: F401
 from .topk16 import TopK16  # noqa: F401
 from .unique import Unique, unique_plan, unique_reference  # noqa: F401
 from .unique16 import Unique16, unique16_reference  # noqa: F401
+from .unique64 import Unique64, unique64_reference  # noqa: F401

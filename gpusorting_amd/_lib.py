@@ -109,6 +109,15 @@ GS_REDUCE_ROUTE_NONE, GS_REDUCE_ROUTE_SORTED, GS_REDUCE_ROUTE_CONSECUTIVE = 0, 1
 (GS_REDUCE_R_ROUTE, GS_REDUCE_R_N, GS_REDUCE_R_U, GS_REDUCE_R_RANGES, GS_REDUCE_R_PER_RANGE, GS_REDUCE_R_TILE, GS_REDUCE_R_STATUS, GS_REDUCE_R_RANK,
  GS_REDUCE_R_VALUE_TYPE, GS_REDUCE_R_OP) = range(10)
 GS_REDUCE_REPORT_WORDS = 10
+# gs_unique64_* / gs_reduce64_*: the routes and report words of the 32-bit families under their own names
+GS_UNIQUE64_ROUTE_NONE, GS_UNIQUE64_ROUTE_KEYS, GS_UNIQUE64_ROUTE_POSITIONS, GS_UNIQUE64_ROUTE_CONSECUTIVE = 0, 1, 2, 3
+(GS_UNIQUE64_R_ROUTE, GS_UNIQUE64_R_N, GS_UNIQUE64_R_U, GS_UNIQUE64_R_RANGES, GS_UNIQUE64_R_PER_RANGE, GS_UNIQUE64_R_TILE, GS_UNIQUE64_R_STATUS,
+ GS_UNIQUE64_R_RANK) = range(8)
+GS_UNIQUE64_REPORT_WORDS = 8
+GS_REDUCE64_ROUTE_NONE, GS_REDUCE64_ROUTE_SORTED, GS_REDUCE64_ROUTE_CONSECUTIVE = 0, 1, 2
+(GS_REDUCE64_R_ROUTE, GS_REDUCE64_R_N, GS_REDUCE64_R_U, GS_REDUCE64_R_RANGES, GS_REDUCE64_R_PER_RANGE, GS_REDUCE64_R_TILE, GS_REDUCE64_R_STATUS,
+ GS_REDUCE64_R_RANK, GS_REDUCE64_R_VALUE_TYPE, GS_REDUCE64_R_OP) = range(10)
+GS_REDUCE64_REPORT_WORDS = 10
 
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
@@ -384,6 +393,21 @@ _PROTOS = [
     ("gs_reduce_by_key_consecutive", _int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     ("gs_reduce_check", _int, [_vp, _vp]),
     ("gs_reduce_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_unique64_create", _int, [C.POINTER(_vp), _u32, _int, _u32]),
+    ("gs_unique64_destroy", _int, [_vp]),
+    ("gs_unique64_temp_bytes", C.c_size_t, [_u32, _int, _u32]),
+    ("gs_unique64_keys", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _int, _int, _vp]),
+    ("gs_unique64_positions", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    ("gs_unique64_consecutive", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("gs_unique64_check", _int, [_vp, _vp]),
+    ("gs_unique64_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_reduce64_create", _int, [C.POINTER(_vp), _u32, _u32]),
+    ("gs_reduce64_destroy", _int, [_vp]),
+    ("gs_reduce64_temp_bytes", C.c_size_t, [_u32, _u32]),
+    ("gs_reduce64_by_key", _int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
+    ("gs_reduce64_by_key_consecutive", _int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    ("gs_reduce64_check", _int, [_vp, _vp]),
+    ("gs_reduce64_last", _int, [_vp, _u32p, _u32, _vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

@@ -44,6 +44,8 @@
 #include "unique_host.hpp"      // gs_unique: distinct keys, counts, first positions, inverse (behind onesweep_host and sort16_host)
 #include "unique16_host.hpp"    // gs_unique16: the same on 16-bit keys, from one histogram (behind sort16_host and unique_host)
 #include "reduce_host.hpp"      // gs_reduce: one sum, minimum or maximum per distinct key (behind onesweep_host and unique_host)
+#include "unique64_host.hpp"    // gs_unique64: gs_unique on 8-byte keys (behind unique_host)
+#include "reduce64_host.hpp"    // gs_reduce64: gs_reduce on 8-byte keys (behind reduce_host)
 #include "sortrows_host.hpp"    // gs_sort_rows: every row of a matrix sorted in one call
 #include "sortrows16_host.hpp"  // gs_sort_rows16: the same on 16-bit keys
 #include "segsort16_host.hpp"   // gs_segsort16: the segmented sort on 16-bit keys

@@ -141,13 +141,15 @@ __device__ __forceinline__ void rd_block_scan(bool f, typename Op::V v, uint32_t
 }
 
 // src -> keys, vals -> values (W: a value's word): the engine sorts the copies, the caller's arrays are not written
-template <class W>
-__global__ __launch_bounds__(UQ_PREP_THREADS) void rd_prepare_kernel(const uint32_t* __restrict__ src, const W* __restrict__ vals, uint32_t n,
-                                                                     uint32_t* __restrict__ keys, W* __restrict__ values) {
+template <class K, class W>
+__global__ __launch_bounds__(UQ_PREP_THREADS) void rd_prepare_kernel(const K* __restrict__ src, const W* __restrict__ vals, uint32_t n,
+                                                                     K* __restrict__ keys, W* __restrict__ values) {
     const uint32_t i = (blockIdx.x * UQ_PREP_THREADS + threadIdx.x) * 4u;
     if (i >= n) return;
     if (GS_LIKELY(i + 4u <= n)) {
-        *reinterpret_cast<uint4*>(keys + i) = *reinterpret_cast<const uint4*>(src + i);
+        constexpr uint32_t KPER = 16u / sizeof(K);  // keys per 16-byte move
+#pragma unroll
+        for (uint32_t g = 0; g < 4u / KPER; ++g) *reinterpret_cast<uint4*>(keys + i + g * KPER) = *reinterpret_cast<const uint4*>(src + i + g * KPER);
         constexpr uint32_t PER = 16u / sizeof(W);
 #pragma unroll
         for (uint32_t g = 0; g < 4u / PER; ++g) *reinterpret_cast<uint4*>(values + i + g * PER) = *reinterpret_cast<const uint4*>(vals + i + g * PER);
@@ -161,8 +163,8 @@ __global__ __launch_bounds__(UQ_PREP_THREADS) void rd_prepare_kernel(const uint3
 
 // rc[r] = heads of range r, rl[r] = position + 1 of its last head (0: the range holds none), part[r] = its open partial (what the
 // range that holds element n - 1 leaves there is read by nobody)
-template <class Op>
-__global__ __launch_bounds__(UQ_THREADS) void rd_count_kernel(const uint32_t* __restrict__ keys, const typename Op::V* __restrict__ vals, uint32_t n,
+template <class K, class Op>
+__global__ __launch_bounds__(UQ_THREADS) void rd_count_kernel(const K* __restrict__ keys, const typename Op::V* __restrict__ vals, uint32_t n,
                                                               uint32_t per_range, uint32_t xform, uint32_t* __restrict__ rc, uint32_t* __restrict__ rl,
                                                               typename Op::V* __restrict__ part) {
     typedef typename Op::V V;
@@ -177,7 +179,7 @@ __global__ __launch_bounds__(UQ_THREADS) void rd_count_kernel(const uint32_t* __
     uint32_t par = 0;
     for (uint32_t t0 = lo; t0 < hi; t0 += UQ_TILE, par ^= 1u) {
         const uint32_t i = t0 + tid * UQ_KPT;
-        uint32_t k[UQ_KPT];
+        K k[UQ_KPT];
         V v[UQ_KPT];
         uq_load8(keys, i, n, k);
         rd_load8(vals, i, n, xform, v);
@@ -256,11 +258,11 @@ __global__ __launch_bounds__(UQ_CAP) void rd_scan_kernel(const uint32_t* __restr
 }
 
 // One workgroup per range, its tiles in order.  out_counts may be null.
-template <class Op>
-__global__ __launch_bounds__(UQ_THREADS) void rd_reduce_kernel(const uint32_t* __restrict__ keys, const typename Op::V* __restrict__ vals, uint32_t n,
+template <class K, class Op>
+__global__ __launch_bounds__(UQ_THREADS) void rd_reduce_kernel(const K* __restrict__ keys, const typename Op::V* __restrict__ vals, uint32_t n,
                                                                uint32_t per_range, uint32_t xform, const uint32_t* __restrict__ base,
                                                                const uint32_t* __restrict__ prev, const typename Op::V* __restrict__ carry,
-                                                               const uint32_t* __restrict__ rc, uint32_t* __restrict__ out_keys,
+                                                               const uint32_t* __restrict__ rc, K* __restrict__ out_keys,
                                                                typename Op::V* __restrict__ out_values, uint32_t* __restrict__ out_counts,
                                                                uint32_t* __restrict__ ctl) {
     typedef typename Op::V V;
@@ -279,7 +281,7 @@ __global__ __launch_bounds__(UQ_THREADS) void rd_reduce_kernel(const uint32_t* _
     uint32_t par = 0;
     for (uint32_t t0 = lo; t0 < hi; t0 += UQ_TILE, par ^= 1u) {
         const uint32_t i = t0 + tid * UQ_KPT;
-        uint32_t k[UQ_KPT];
+        K k[UQ_KPT];
         V v[UQ_KPT];
         uq_load8(keys, i, n, k);
         rd_load8(vals, i, n, xform, v);

@@ -35,6 +35,9 @@ static_assert(UQ_KPT == 8 && UQ_TILE == 4096 && UQ_CAP % 64u == 0 && UQ_CAP <= 1
 
 #if GS_SORT16_BUILT  // the product build only, as the 16-bit sort
 
+// The kernels below are written once over the key word K: uint32_t (gs_unique_*, gs_reduce_*) or uint64_t (gs_unique64_*,
+// gs_reduce64_*: an 8-byte key is one element, compared and moved as both of its words).  Positions, counts and ranks are uint32_t.
+
 // eight words from index i of the 16-byte aligned array q (i a multiple of 8); what lies at or behind n reads as 0 and is not loaded
 __device__ __forceinline__ void uq_load8(const uint32_t* __restrict__ q, uint32_t i, uint32_t n, uint32_t (&k)[UQ_KPT]) {
     if (GS_LIKELY(i + UQ_KPT <= n)) {
@@ -46,21 +49,37 @@ __device__ __forceinline__ void uq_load8(const uint32_t* __restrict__ q, uint32_
 #pragma unroll
     for (uint32_t j = 0; j < UQ_KPT; ++j) k[j] = i + j < n ? q[i + j] : 0u;
 }
+// the same for 8-byte keys: four 16-byte loads of two keys each
+__device__ __forceinline__ void uq_load8(const uint64_t* __restrict__ q, uint32_t i, uint32_t n, uint64_t (&k)[UQ_KPT]) {
+    if (GS_LIKELY(i + UQ_KPT <= n)) {
+#pragma unroll
+        for (uint32_t g = 0; g < UQ_KPT / 2u; ++g) {
+            const uint4 a = *reinterpret_cast<const uint4*>(q + i + 2u * g);
+            k[2u * g] = (uint64_t)a.x | ((uint64_t)a.y << 32);
+            k[2u * g + 1u] = (uint64_t)a.z | ((uint64_t)a.w << 32);
+        }
+        return;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < UQ_KPT; ++j) k[j] = i + j < n ? q[i + j] : 0ull;
+}
 
-// the word left of this thread's eight: the lane below holds it; lane 0 (a wave, tile or range edge) reads it from global memory.
-// Every lane of the wave calls this.
-__device__ __forceinline__ uint32_t uq_left(const uint32_t* __restrict__ q, const uint32_t (&k)[UQ_KPT], uint32_t i, uint32_t n, uint32_t lane) {
-    uint32_t left = __shfl_up(k[UQ_KPT - 1u], 1, 64);
+// the word left of this thread's eight: the lane below holds it (an 8-byte key: both words); lane 0 (a wave, tile or range edge) reads
+// it from global memory.  Every lane of the wave calls this.
+template <class K>
+__device__ __forceinline__ K uq_left(const K* __restrict__ q, const K (&k)[UQ_KPT], uint32_t i, uint32_t n, uint32_t lane) {
+    K left = __shfl_up(k[UQ_KPT - 1u], 1, 64);
     if (lane == 0u && i != 0u && i < n) left = q[i - 1u];
     return left;
 }
 
-// bit j: element i + j (< n) starts a run
-__device__ __forceinline__ uint32_t uq_heads(const uint32_t (&k)[UQ_KPT], uint32_t left, uint32_t i, uint32_t n) {
+// bit j: element i + j (< n) starts a run (an 8-byte key: it differs from its left neighbour in either word)
+template <class K>
+__device__ __forceinline__ uint32_t uq_heads(const K (&k)[UQ_KPT], K left, uint32_t i, uint32_t n) {
     uint32_t h = 0;
 #pragma unroll
     for (uint32_t j = 0; j < UQ_KPT; ++j) {
-        const uint32_t before = j ? k[j ? j - 1u : 0u] : left;
+        const K before = j ? k[j ? j - 1u : 0u] : left;
         if (i + j < n && (i + j == 0u || k[j] != before)) h |= 1u << j;
     }
     return h;
@@ -70,13 +89,15 @@ __device__ __forceinline__ uint32_t uq_heads(const uint32_t (&k)[UQ_KPT], uint32
 __device__ __forceinline__ uint32_t uq_last_head(uint32_t h, uint32_t i) { return h ? i + 32u - (uint32_t)__clz((int)h) : 0u; }
 
 // src[0 .. n) -> keys, and with POS the positions 0 .. n - 1 beside them: the engine sorts the copy, the caller's keys are not written
-template <bool POS>
-__global__ __launch_bounds__(UQ_PREP_THREADS) void uq_prepare_kernel(const uint32_t* __restrict__ src, uint32_t n, uint32_t* __restrict__ keys,
+template <class K, bool POS>
+__global__ __launch_bounds__(UQ_PREP_THREADS) void uq_prepare_kernel(const K* __restrict__ src, uint32_t n, K* __restrict__ keys,
                                                                      uint32_t* __restrict__ pos) {
     const uint32_t i = (blockIdx.x * UQ_PREP_THREADS + threadIdx.x) * 4u;
     if (i >= n) return;
     if (GS_LIKELY(i + 4u <= n)) {
-        *reinterpret_cast<uint4*>(keys + i) = *reinterpret_cast<const uint4*>(src + i);
+        constexpr uint32_t PER = 16u / sizeof(K);  // keys per 16-byte move
+#pragma unroll
+        for (uint32_t g = 0; g < 4u / PER; ++g) *reinterpret_cast<uint4*>(keys + i + g * PER) = *reinterpret_cast<const uint4*>(src + i + g * PER);
         if (POS) *reinterpret_cast<uint4*>(pos + i) = uint4{i, i + 1u, i + 2u, i + 3u};
         return;
     }
@@ -87,7 +108,8 @@ __global__ __launch_bounds__(UQ_PREP_THREADS) void uq_prepare_kernel(const uint3
 }
 
 // rc[r] = heads of range r, rl[r] = position + 1 of its last head (0: the range holds none)
-__global__ __launch_bounds__(UQ_THREADS) void uq_count_kernel(const uint32_t* __restrict__ keys, uint32_t n, uint32_t per_range, uint32_t* __restrict__ rc,
+template <class K>
+__global__ __launch_bounds__(UQ_THREADS) void uq_count_kernel(const K* __restrict__ keys, uint32_t n, uint32_t per_range, uint32_t* __restrict__ rc,
                                                               uint32_t* __restrict__ rl) {
     __shared__ uint32_t s_c[UQ_WAVES], s_l[UQ_WAVES];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -96,7 +118,7 @@ __global__ __launch_bounds__(UQ_THREADS) void uq_count_kernel(const uint32_t* __
     uint32_t heads = 0, last = 0;  // heads: the wave's (uniform); last: this thread's (positions rise from tile to tile)
     for (uint32_t t0 = lo; t0 < hi; t0 += UQ_TILE) {
         const uint32_t i = t0 + tid * UQ_KPT;
-        uint32_t k[UQ_KPT];
+        K k[UQ_KPT];
         uq_load8(keys, i, n, k);
         const uint32_t h = uq_heads(k, uq_left(keys, k, i, n, lane), i, n);
 #pragma unroll
@@ -160,11 +182,11 @@ __global__ __launch_bounds__(UQ_CAP) void uq_scan_kernel(const uint32_t* __restr
 // One workgroup per range, its tiles in order.  POS: perm[i] is the input position of element i (the engine's sorted values) and the
 // inverse is scattered through it; without, the inverse is written in place (gs_unique_consecutive).  tail_first != 0 (descending):
 // a run's lowest position is stored at its tail.  out_counts, out_first and out_inverse may be null.
-template <bool POS>
-__global__ __launch_bounds__(UQ_THREADS) void uq_compact_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ perm, uint32_t n,
+template <class K, bool POS>
+__global__ __launch_bounds__(UQ_THREADS) void uq_compact_kernel(const K* __restrict__ keys, const uint32_t* __restrict__ perm, uint32_t n,
                                                                 uint32_t per_range, uint32_t tail_first, const uint32_t* __restrict__ base,
                                                                 const uint32_t* __restrict__ prev, const uint32_t* __restrict__ rc,
-                                                                uint32_t* __restrict__ out_keys, uint32_t* __restrict__ out_counts,
+                                                                K* __restrict__ out_keys, uint32_t* __restrict__ out_counts,
                                                                 uint32_t* __restrict__ out_first, uint32_t* __restrict__ out_inverse,
                                                                 uint32_t* __restrict__ ctl) {
     __shared__ uint32_t s_c[2][UQ_WAVES], s_l[2][UQ_WAVES];  // by tile parity: one barrier per tile
@@ -180,7 +202,8 @@ __global__ __launch_bounds__(UQ_THREADS) void uq_compact_kernel(const uint32_t* 
     uint32_t par = 0;
     for (uint32_t t0 = lo; t0 < hi; t0 += UQ_TILE, par ^= 1u) {
         const uint32_t i = t0 + tid * UQ_KPT;
-        uint32_t k[UQ_KPT], v[UQ_KPT];
+        K k[UQ_KPT];
+        uint32_t v[UQ_KPT];
         uq_load8(keys, i, n, k);
         const uint32_t h = uq_heads(k, uq_left(keys, k, i, n, lane), i, n);
         uint32_t vleft = 0;

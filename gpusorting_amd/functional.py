@@ -33,7 +33,10 @@ from .topk16 import TopK16  # noqa: F401
 from .reduce import OPS as _REDUCE_OPS, ReduceByKey, _torch_value_types, reduce_by_key_reference  # noqa: F401
 from .unique import Unique, unique_reference  # noqa: F401
 from .unique16 import Unique16, unique16_reference  # noqa: F401
-from .onesweep import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, OneSweep
+from .unique64 import Unique64, unique64_reference  # noqa: F401
+from .reduce64 import ReduceByKey64, reduce_by_key64_reference  # noqa: F401
+from .onesweep import (KEY_FLOAT32, KEY_FLOAT64, KEY_INT32, KEY_INT64, KEY_UINT32, KEY_UINT64, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING,
+                       ORDER_DESCENDING, OneSweep)
 
 _KEY_TYPE = {torch.int32: KEY_INT32, torch.float32: KEY_FLOAT32, torch.uint32: KEY_UINT32}
 # 2-byte keys: sort / sort_ / argsort (Sort16) and the row-wise top-k (torch.uint16 where this torch has it)
@@ -804,3 +807,146 @@ def unique_consecutive16(keys: torch.Tensor, return_inverse: bool = False, retur
     u = int(num.item())
     out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ())
     return out[0] if len(out) == 1 else out
+
+
+# ---- unique / run-length encode and reduce by key on 64-bit keys ------------------------------------------------------------------
+_KEY64_TYPE = {torch.int64: KEY_INT64, torch.float64: KEY_FLOAT64}
+if hasattr(torch, "uint64"):
+    _KEY64_TYPE[torch.uint64] = KEY_UINT64
+_unique64_cache: dict = {}
+_reduce64_cache: dict = {}
+
+
+def _unique64_handle(device: torch.device, n: int, key_type: int, order: int, positions: bool) -> Unique64:
+    """The cache rule of ``_unique_handle`` for the 64-bit keys: one ``Unique64`` handle per (device, stream, type, order, with
+    positions); re-created when the size outgrows it."""
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, positions)
+    s = _unique64_cache.get(key)
+    if s is None or s.max_keys < n:
+        if s is not None:
+            s.close()
+        cap = 1 << max(int(n - 1).bit_length(), 16)
+        s = Unique64(min(cap, (1 << 30) - 1), order, key_type, positions=positions, device=device.index)
+        _unique64_cache[key] = s
+    return s
+
+
+def _reduce64_handle(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> ReduceByKey64:
+    """The cache rule of ``_reduce_handle`` for the 64-bit keys."""
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
+    s = _reduce64_cache.get(key)
+    if s is None or s.max_keys < n:
+        if s is not None:
+            s.close()
+        cap = 1 << max(int(n - 1).bit_length(), 16)
+        s = ReduceByKey64(min(cap, (1 << 30) - 1), order, key_type, value_bytes, device=device.index)
+        _reduce64_cache[key] = s
+    return s
+
+
+def _require_unique64_keys(keys: torch.Tensor, name: str) -> None:
+    if keys.dim() != 1:
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+    if keys.dtype not in _KEY64_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: {name} takes 64-bit keys (int64, uint64, float64); 32-bit keys go to "
+                        f"{name[:-2]}")
+    if not keys.is_contiguous() or keys.device.type != "cuda":
+        raise ValueError("keys must be a contiguous 1-D device tensor")
+
+
+def unique64(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False, return_index: bool = False, descending: bool = False,
+             unsigned: bool = False):
+    """``unique`` for a 1-D contiguous tensor of 64-bit keys (int64, float64, uint64 where torch has it; ``unsigned=True`` reads int64
+    storage as uint64 keys), as ``torch.unique(keys, sorted=True)``: returns ``output`` or the tuple
+    ``(output[, inverse][, counts][, index])`` with int32 ``inverse``, ``counts`` and ``index`` (the lowest input position of each
+    element), as ``unique`` does.  Equality is BITWISE on all 64 bits and the order is this library's sort: on floats ``-0.0`` and
+    ``+0.0`` are two elements (``-0.0`` first) and every NaN bit pattern is an element of its own; on integers the result equals
+    ``torch.unique``'s.  Keys below 2^32 (ids) cost the sort four passes, not eight.  Slicing the outputs to their length is the one wait
+    on the host.  ``keys`` is not written.  Other dtypes are a ``TypeError``: see ``unique``."""
+    _require_unique64_keys(keys, "unique64")
+    kt = KEY_UINT64 if (unsigned and keys.dtype == torch.int64) else _KEY64_TYPE[keys.dtype]
+    n = keys.numel()
+    positions = return_inverse or return_index
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=keys.device)
+        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ()) + ((e.clone(),) if return_index else ())
+        return out[0] if len(out) == 1 else out
+    with torch.cuda.device(keys.device):
+        s = _unique64_handle(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, positions)
+        if positions:
+            out_k, out_c, out_f, out_i, num = s.unique_positions(keys, n, counts=return_counts, first=return_index, inverse=return_inverse)
+        else:
+            out_k, out_c, num = s.unique(keys, n, counts=return_counts)
+            out_f = out_i = None
+    u = int(num.item())
+    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ()) + ((out_f[:u],) if return_index else ())
+    return out[0] if len(out) == 1 else out
+
+
+def unique_consecutive64(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False):
+    """``unique_consecutive`` for a 1-D contiguous tensor of 64-bit keys: one element per run of BITWISE-equal neighbours of the input as
+    it lies (no sort): returns ``output`` or ``(output[, inverse][, counts])`` with int32 ``inverse`` and ``counts``.  One wait on the
+    host, for the length.  ``keys`` is not written.  Other dtypes are a ``TypeError``: see ``unique_consecutive``."""
+    _require_unique64_keys(keys, "unique_consecutive64")
+    n = keys.numel()
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=keys.device)
+        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ())
+        return out[0] if len(out) == 1 else out
+    with torch.cuda.device(keys.device):
+        s = _unique64_handle(keys.device, n, KEY_UINT64, ORDER_ASCENDING, False)
+        out_k, out_c, out_i, num = s.unique_consecutive(keys, n, counts=return_counts, inverse=return_inverse)
+    u = int(num.item())
+    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ())
+    return out[0] if len(out) == 1 else out
+
+
+def _require_reduce64_args(keys: torch.Tensor, values: torch.Tensor, op: str, name: str):
+    if keys.dim() != 1 or values.dim() != 1 or keys.numel() != values.numel():
+        raise ValueError("keys and values must be contiguous 1-D device tensors of one length")
+    if keys.dtype not in _KEY64_TYPE:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: {name} takes 64-bit keys (int64, uint64, float64); 32-bit keys go to "
+                        f"{name[:-2]}")
+    vt = _torch_value_types().get(values.dtype)
+    if vt is None:
+        raise TypeError(f"unsupported value dtype {values.dtype}: {name} takes int32, uint32, float32, int64, uint64 or float64 values")
+    if op not in _REDUCE_OPS:
+        raise ValueError('op is "sum", "min" or "max"')
+    if not keys.is_contiguous() or not values.is_contiguous() or keys.device.type != "cuda" or values.device != keys.device:
+        raise ValueError("keys and values must be contiguous 1-D device tensors of one length")
+    return vt, _REDUCE_OPS[op]
+
+
+def reduce_by_key64(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", descending: bool = False, return_counts: bool = False,
+                    unsigned: bool = False):
+    """``reduce_by_key`` for 64-bit keys (int64, float64, uint64 where torch has it; ``unsigned=True`` reads int64 storage as uint64
+    keys): one ``op`` ("sum", "min", "max") of ``values`` per distinct element of ``keys``: ``(distinct, reduced[, counts])`` with
+    ``distinct`` as ``unique64(keys, descending=descending, unsigned=unsigned)`` delivers it, ``reduced`` in the values' dtype and
+    int32 ``counts``: ``unique(return_inverse=True)`` followed by ``index_add_`` / ``scatter_reduce`` in one call, with no inverse, no
+    gather and no atomics.  The operations are ``reduce_by_key``'s: integer sums wrap, "min" / "max" on floats use this library's total
+    order (UNLIKE ``torch.amin`` / ``amax`` and ``fmin`` / ``fmax``), a float "sum" is reproducible bit for bit but not the
+    left-to-right sum.  One wait on the host, for the length.  Neither input is written."""
+    vt, opc = _require_reduce64_args(keys, values, op, "reduce_by_key64")
+    kt = KEY_UINT64 if (unsigned and keys.dtype == torch.int64) else _KEY64_TYPE[keys.dtype]
+    n = keys.numel()
+    if n == 0:
+        return (keys.clone(), values.clone()) + ((torch.empty(0, dtype=torch.int32, device=keys.device),) if return_counts else ())
+    with torch.cuda.device(keys.device):
+        s = _reduce64_handle(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, values.element_size())
+        out_k, out_v, out_c, num = s.reduce_by_key(keys, values, opc, vt, n, counts=return_counts)
+    u = int(num.item())
+    return (out_k[:u], out_v[:u]) + ((out_c[:u],) if return_counts else ())
+
+
+def reduce_by_key_consecutive64(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", return_counts: bool = False):
+    """``reduce_by_key_consecutive`` for 64-bit keys: one ``op`` of ``values`` per run of BITWISE-equal neighbouring keys of the input as
+    it lies (no sort): ``(runs, reduced[, counts])``.  One wait on the host, for the length.  Neither input is written."""
+    vt, opc = _require_reduce64_args(keys, values, op, "reduce_by_key_consecutive64")
+    n = keys.numel()
+    if n == 0:
+        return (keys.clone(), values.clone()) + ((torch.empty(0, dtype=torch.int32, device=keys.device),) if return_counts else ())
+    with torch.cuda.device(keys.device):
+        s = _reduce64_handle(keys.device, n, KEY_UINT64, ORDER_ASCENDING, values.element_size())
+        out_k, out_v, out_c, num = s.reduce_by_key_consecutive(keys, values, opc, vt, n, counts=return_counts)
+    u = int(num.item())
+    return (out_k[:u], out_v[:u]) + ((out_c[:u],) if return_counts else ())

@@ -132,12 +132,21 @@ class ReduceByKey:
     "sum" / "min" / "max"; ``value_type`` defaults to the one of the values' dtype (pass ``VALUE_UINT32`` / ``VALUE_UINT64`` for unsigned
     values in int32 / int64 storage)."""
 
-    def __init__(self, max_keys: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT32, value_bytes: int = 4, device: int | None = None):
+    # the family of entries behind the class, its key width and key types (reduce64.ReduceByKey64 states its own)
+    _PREFIX, _KEY_BYTES, _KEY_TYPES = "gs_reduce_", 4, _KEY_TYPES
+    _KEYS_WANTED = "ReduceByKey takes 32-bit keys (KEY_UINT32, KEY_INT32, KEY_FLOAT32)"
+
+    def _entry(self, name: str):
+        return getattr(self._lib, self._PREFIX + name)
+
+    def __init__(self, max_keys: int, order: int = ORDER_ASCENDING, key_type: int | None = None, value_bytes: int = 4, device: int | None = None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type not in _KEY_TYPES:
-            raise ValueError("ReduceByKey takes 32-bit keys (KEY_UINT32, KEY_INT32, KEY_FLOAT32)")
+        if key_type is None:
+            key_type = self._KEY_TYPES[0]
+        if key_type not in self._KEY_TYPES:
+            raise ValueError(self._KEYS_WANTED)
         self._lib = _lib.load()
         if device is not None:
             torch.cuda.set_device(device)
@@ -145,12 +154,12 @@ class ReduceByKey:
         self.max_keys = int(max_keys)
         self.order, self.key_type, self.value_bytes = order, key_type, int(value_bytes)
         h = C.c_void_p()
-        check(self._lib.gs_reduce_create(C.byref(h), self.max_keys, self.value_bytes), "gs_reduce_create")
+        check(self._entry("create")(C.byref(h), self.max_keys, self.value_bytes), self._PREFIX + "create")
         self._h = h
 
     def close(self) -> None:
         if getattr(self, "_h", None):
-            self._lib.gs_reduce_destroy(self._h)
+            self._entry("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -161,12 +170,12 @@ class ReduceByKey:
 
     @property
     def temp_bytes(self) -> int:
-        return temp_bytes(self.max_keys, self.value_bytes)
+        return int(self._entry("temp_bytes")(self.max_keys, self.value_bytes))
 
     def _args(self, keys, values, n, op, value_type):
         from .onesweep import _require_room
-        if keys.element_size() != 4:
-            raise ValueError("keys must be 32-bit")
+        if keys.element_size() != self._KEY_BYTES:
+            raise ValueError("keys must be %d-bit" % (8 * self._KEY_BYTES))
         if value_type is None:
             value_type = _torch_value_types().get(values.dtype)
         if value_type not in VALUE_DTYPES:
@@ -193,9 +202,9 @@ class ReduceByKey:
         from .onesweep import _stream_ptr
         n, op, value_type = self._args(keys, values, n, op, value_type)
         out_k, out_v, out_c, num = self._outs(keys, values, n, counts)
-        check(self._lib.gs_reduce_by_key(self._h, keys.data_ptr(), values.data_ptr(), n, out_k.data_ptr(), out_v.data_ptr(),
+        check(self._entry("by_key")(self._h, keys.data_ptr(), values.data_ptr(), n, out_k.data_ptr(), out_v.data_ptr(),
                                          None if out_c is None else out_c.data_ptr(), num.data_ptr(), self.key_type, self.order, value_type, op,
-                                         _stream_ptr(stream)), "gs_reduce_by_key")
+                                         _stream_ptr(stream)), self._PREFIX + "by_key")
         return out_k, out_v, out_c, num
 
     def reduce_by_key_consecutive(self, keys, values, op=OP_SUM, value_type: int | None = None, n: int | None = None, counts: bool = True,
@@ -205,24 +214,24 @@ class ReduceByKey:
         from .onesweep import _stream_ptr
         n, op, value_type = self._args(keys, values, n, op, value_type)
         out_k, out_v, out_c, num = self._outs(keys, values, n, counts)
-        check(self._lib.gs_reduce_by_key_consecutive(self._h, keys.data_ptr(), values.data_ptr(), n, out_k.data_ptr(), out_v.data_ptr(),
+        check(self._entry("by_key_consecutive")(self._h, keys.data_ptr(), values.data_ptr(), n, out_k.data_ptr(), out_v.data_ptr(),
                                                      None if out_c is None else out_c.data_ptr(), num.data_ptr(), value_type, op,
-                                                     _stream_ptr(stream)), "gs_reduce_by_key_consecutive")
+                                                     _stream_ptr(stream)), self._PREFIX + "by_key_consecutive")
         return out_k, out_v, out_c, num
 
     def status(self, stream=None) -> int:
         """``gs_reduce_check`` as a status code (synchronises)."""
         from .onesweep import _stream_ptr
-        return int(self._lib.gs_reduce_check(self._h, _stream_ptr(stream)))
+        return int(self._entry("check")(self._h, _stream_ptr(stream)))
 
     def check(self, stream=None) -> None:
         """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
-        check(self.status(stream), "gs_reduce_check")
+        check(self.status(stream), self._PREFIX + "check")
 
     def last(self, stream=None) -> dict:
         """Diagnostics of the last call (synchronises): route, n, u, ranges, per_range, tile, status, rank (the sorter's rank mode),
         value_type, op."""
         from .onesweep import _stream_ptr
         buf = (C.c_uint32 * _lib.GS_REDUCE_REPORT_WORDS)()
-        check(self._lib.gs_reduce_last(self._h, buf, _lib.GS_REDUCE_REPORT_WORDS, _stream_ptr(stream)), "gs_reduce_last")
+        check(self._entry("last")(self._h, buf, _lib.GS_REDUCE_REPORT_WORDS, _stream_ptr(stream)), self._PREFIX + "last")
         return {name: int(buf[i]) for i, name in enumerate(_REPORT)}

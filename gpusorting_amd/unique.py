@@ -75,12 +75,21 @@ class Unique:
     (its sorter sorts (key, position) pairs).  Every call returns full-capacity tensors (``n`` elements; only the first ``u`` of keys,
     counts and first are written) plus the one-element count tensor ``num`` on the device, and does not wait on the host."""
 
-    def __init__(self, max_keys: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT32, positions: bool = False, device: int | None = None):
+    # the family of entries behind the class, its key width and key types (unique64.Unique64 states its own)
+    _PREFIX, _KEY_BYTES, _KEY_TYPES = "gs_unique_", 4, _KEY_TYPES
+    _KEYS_WANTED = "Unique takes 32-bit keys (KEY_UINT32, KEY_INT32, KEY_FLOAT32)"
+
+    def _entry(self, name: str):
+        return getattr(self._lib, self._PREFIX + name)
+
+    def __init__(self, max_keys: int, order: int = ORDER_ASCENDING, key_type: int | None = None, positions: bool = False, device: int | None = None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type not in _KEY_TYPES:
-            raise ValueError("Unique takes 32-bit keys (KEY_UINT32, KEY_INT32, KEY_FLOAT32)")
+        if key_type is None:
+            key_type = self._KEY_TYPES[0]
+        if key_type not in self._KEY_TYPES:
+            raise ValueError(self._KEYS_WANTED)
         self._lib = _lib.load()
         if device is not None:
             torch.cuda.set_device(device)
@@ -89,12 +98,12 @@ class Unique:
         self.order, self.key_type = order, key_type
         self.mode, self.value_bytes = (MODE_PAIRS, 4) if positions else (MODE_KEYS_ONLY, 0)
         h = C.c_void_p()
-        check(self._lib.gs_unique_create(C.byref(h), self.max_keys, self.mode, self.value_bytes), "gs_unique_create")
+        check(self._entry("create")(C.byref(h), self.max_keys, self.mode, self.value_bytes), self._PREFIX + "create")
         self._h = h
 
     def close(self) -> None:
         if getattr(self, "_h", None):
-            self._lib.gs_unique_destroy(self._h)
+            self._entry("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -105,12 +114,12 @@ class Unique:
 
     @property
     def temp_bytes(self) -> int:
-        return temp_bytes(self.max_keys, self.mode, self.value_bytes)
+        return int(self._entry("temp_bytes")(self.max_keys, self.mode, self.value_bytes))
 
     def _keys(self, keys, n):
         from .onesweep import _require_room
-        if keys.element_size() != 4:
-            raise ValueError("keys must be 32-bit")
+        if keys.element_size() != self._KEY_BYTES:
+            raise ValueError("keys must be %d-bit" % (8 * self._KEY_BYTES))
         n = keys.numel() if n is None else int(n)
         _require_room(keys, n, "keys")
         return n
@@ -130,8 +139,8 @@ class Unique:
         out_k = self._out(keys, n, True, keys.dtype)
         out_c = self._out(keys, n, counts)
         num = self._out(keys, 1, True)
-        check(self._lib.gs_unique_keys(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), num.data_ptr(), self.key_type, self.order,
-                                       _stream_ptr(stream)), "gs_unique_keys")
+        check(self._entry("keys")(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), num.data_ptr(), self.key_type, self.order,
+                                       _stream_ptr(stream)), self._PREFIX + "keys")
         return out_k, out_c, num
 
     def unique_positions(self, keys, n: int | None = None, counts: bool = True, first: bool = True, inverse: bool = True, stream=None):
@@ -142,8 +151,8 @@ class Unique:
         out_k = self._out(keys, n, True, keys.dtype)
         out_c, out_f, out_i = self._out(keys, n, counts), self._out(keys, n, first), self._out(keys, n, inverse)
         num = self._out(keys, 1, True)
-        check(self._lib.gs_unique_positions(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), self._ptr(out_f), self._ptr(out_i),
-                                            num.data_ptr(), self.key_type, self.order, _stream_ptr(stream)), "gs_unique_positions")
+        check(self._entry("positions")(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), self._ptr(out_f), self._ptr(out_i),
+                                            num.data_ptr(), self.key_type, self.order, _stream_ptr(stream)), self._PREFIX + "positions")
         return out_k, out_c, out_f, out_i, num
 
     def unique_consecutive(self, keys, n: int | None = None, counts: bool = True, inverse: bool = True, stream=None):
@@ -154,22 +163,22 @@ class Unique:
         out_k = self._out(keys, n, True, keys.dtype)
         out_c, out_i = self._out(keys, n, counts), self._out(keys, n, inverse)
         num = self._out(keys, 1, True)
-        check(self._lib.gs_unique_consecutive(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), self._ptr(out_i), num.data_ptr(),
-                                              _stream_ptr(stream)), "gs_unique_consecutive")
+        check(self._entry("consecutive")(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), self._ptr(out_i), num.data_ptr(),
+                                              _stream_ptr(stream)), self._PREFIX + "consecutive")
         return out_k, out_c, out_i, num
 
     def status(self, stream=None) -> int:
         """``gs_unique_check`` as a status code (synchronises)."""
         from .onesweep import _stream_ptr
-        return int(self._lib.gs_unique_check(self._h, _stream_ptr(stream)))
+        return int(self._entry("check")(self._h, _stream_ptr(stream)))
 
     def check(self, stream=None) -> None:
         """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
-        check(self.status(stream), "gs_unique_check")
+        check(self.status(stream), self._PREFIX + "check")
 
     def last(self, stream=None) -> dict:
         """Diagnostics of the last call (synchronises): route, n, u, ranges, per_range, tile, status, rank (the sorter's rank mode)."""
         from .onesweep import _stream_ptr
         buf = (C.c_uint32 * _lib.GS_UNIQUE_REPORT_WORDS)()
-        check(self._lib.gs_unique_last(self._h, buf, _lib.GS_UNIQUE_REPORT_WORDS, _stream_ptr(stream)), "gs_unique_last")
+        check(self._entry("last")(self._h, buf, _lib.GS_UNIQUE_REPORT_WORDS, _stream_ptr(stream)), self._PREFIX + "last")
         return {name: int(buf[i]) for i, name in enumerate(_REPORT)}

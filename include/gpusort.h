@@ -1536,6 +1536,137 @@ gs_status gs_reduce_check(gs_reduce* h, void* stream);
 /* No counterpart in the reference project.  Synchronous diagnostics of the last call: report[GS_REDUCE_R_*], words >= GS_REDUCE_REPORT_WORDS. */
 gs_status gs_reduce_last(gs_reduce* h, uint32_t* report, uint32_t words, void* stream);
 
+/* ---- unique / run-length encode on 64-bit keys: GS_KEY_UINT64 / INT64 / FLOAT64 ------------------------------------------------------------
+ * No counterpart in the reference project.  gs_unique_* restated for n keys of 8 bytes, as gs_unique16_* restates it for 2-byte keys:
+ * the outputs, what may be NULL, what is never written (NOTHING AT OR BEHIND ELEMENT u of out_keys, out_counts or out_first), the
+ * alignment, the asynchrony (every node a kernel, every grid fixed by n through gs_unique_plan, capturable and replayable with another
+ * u), one call in flight per handle, the three routes and the two handles ((GS_MODE_KEYS_ONLY, 0): keys and counts; (GS_MODE_PAIRS, 4):
+ * first and inverse as well) are those of gs_unique_*.  What differs:
+ *   - d_keys and d_out_keys hold 8-byte elements; out_keys are the distinct BIT PATTERNS in the order gs_onesweep_sort_keys leaves
+ *     64-bit keys (floats by the order-preserving flip), and equality is BITWISE on all 64 bits: -0.0 and +0.0 are two keys, every NaN
+ *     pattern is one of its own.  A head is a key that differs from its left neighbour in either word.
+ *   - key types are 3 .. 5; the 32-bit and the 16-bit key types return GS_ERR_ARG (gs_unique_*, gs_unique16_*).
+ *   - counts, first, inverse and *d_out_num stay uint32 (n <= GS_MAX_KEYS); out_first is the LOWEST input position in either order.
+ *   - the overlap check takes 8 n bytes for d_keys and d_out_keys and 4 n for the other outputs.
+ *   - both handles' embedded gs_onesweep keep their defaults: the engine's 64-bit route has no position-chain plan, so the caveat of
+ *     gs_unique_create does not arise.  The engine drops constant bytes of the keys in pairs on the device: keys below 2^32 (ids) cost
+ *     four passes, not eight.
+ * The run-length stage is the one of gs_unique_* on 8-byte loads (four 16-byte loads per thread and tile of 4096; the left neighbour
+ * of a thread's eight keys comes from the lane below as both words, lane 0 reads it from memory); the scan kernel between count and
+ * compact is the same kernel.
+ *
+ * Errors, in this order, as gs_unique_*.  GS_ERR_ARG: null handle (before anything else is looked at), null or misaligned d_keys /
+ * d_out_keys, a key type outside 3 .. 5, a bad order (gs_unique64_consecutive has neither).  GS_ERR_MODE: gs_unique64_positions on a
+ * keys-only handle.  GS_ERR_ARG: a misaligned d_out_counts / d_out_first / d_out_inverse / d_out_num.  GS_ERR_SIZE: n == 0 or
+ * n > max_keys.  GS_ERR_ARG: any two of the call's buffers overlapping (outputs at their capacity of n elements).  GS_ERR_MODE: every
+ * call on a build flavour without these kernels (the tuning and fault-injection libraries).  A refused call launches nothing and
+ * leaves route NONE.  Routes and report words are gs_unique's. */
+typedef struct gs_unique64 gs_unique64;
+#define GS_UNIQUE64_ROUTE_NONE 0
+#define GS_UNIQUE64_ROUTE_KEYS 1
+#define GS_UNIQUE64_ROUTE_POSITIONS 2
+#define GS_UNIQUE64_ROUTE_CONSECUTIVE 3
+/* gs_unique64_last report words: those of gs_unique_last */
+#define GS_UNIQUE64_R_ROUTE 0
+#define GS_UNIQUE64_R_N 1
+#define GS_UNIQUE64_R_U 2
+#define GS_UNIQUE64_R_RANGES 3
+#define GS_UNIQUE64_R_PER_RANGE 4
+#define GS_UNIQUE64_R_TILE 5
+#define GS_UNIQUE64_R_STATUS 6
+#define GS_UNIQUE64_R_RANK 7
+#define GS_UNIQUE64_REPORT_WORDS 8
+/* No counterpart in the reference project.  1 <= max_keys <= GS_MAX_KEYS (GS_ERR_SIZE), then (mode, value_bytes) as gs_unique_create
+ * (GS_ERR_MODE), both answered before a device is looked for.  Synchronous (allocates gs_unique64_temp_bytes of device memory). */
+gs_status gs_unique64_create(gs_unique64** out, uint32_t max_keys, gs_mode mode, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_unique64_destroy(gs_unique64* h);
+/* No counterpart in the reference project.  Host only.  With A(x) = (x + 255) & ~255:
+ *     A(64 * 4)                            the control block
+ *   + 4 * A(1024 * 4)                      per range: heads, last head, heads in front, last head in front
+ *   + 2 * A(8 * max_keys)                  the copy of the keys the engine sorts, and its alternate buffer
+ *   + 2 * A(4 * max_keys)  pairs only      the positions and their alternate buffer
+ *   + gs_onesweep_temp_bytes(max_keys)     the embedded engine
+ * 0 for invalid sizes, mode or value width. */
+size_t gs_unique64_temp_bytes(uint32_t max_keys, gs_mode mode, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_unique64_keys(gs_unique64* h, const void* d_keys, uint32_t n, void* d_out_keys, void* d_out_counts, void* d_out_num,
+                           gs_key_type key_type, gs_order order, void* stream);
+/* No counterpart in the reference project. */
+gs_status gs_unique64_positions(gs_unique64* h, const void* d_keys, uint32_t n, void* d_out_keys, void* d_out_counts, void* d_out_first,
+                                void* d_out_inverse, void* d_out_num, gs_key_type key_type, gs_order order, void* stream);
+/* No counterpart in the reference project. */
+gs_status gs_unique64_consecutive(gs_unique64* h, const void* d_keys, uint32_t n, void* d_out_keys, void* d_out_counts, void* d_out_inverse,
+                                  void* d_out_num, void* stream);
+/* No counterpart in the reference project.  As gs_unique_check. */
+gs_status gs_unique64_check(gs_unique64* h, void* stream);
+/* No counterpart in the reference project.  As gs_unique_last: report[GS_UNIQUE64_R_*], words >= GS_UNIQUE64_REPORT_WORDS. */
+gs_status gs_unique64_last(gs_unique64* h, uint32_t* report, uint32_t words, void* stream);
+
+/* ---- reduce by key on 64-bit keys: GS_KEY_UINT64 / INT64 / FLOAT64 -------------------------------------------------------------------------
+ * No counterpart in the reference project.  gs_reduce_* restated for n keys of 8 bytes: the outputs, the operations (integer sums wrap;
+ * MIN / MAX on floats follow the library's total order of floats and return one of the inputs bit for bit), what may be NULL, what is
+ * never written (NOTHING AT OR BEHIND ELEMENT u of out_keys, out_values or out_counts), the alignment, the seven buffers that must not
+ * overlap, the asynchrony (every node a kernel, every grid fixed by n through gs_unique_plan, capturable), one call in flight per
+ * handle, one value WIDTH (4 or 8 bytes) per handle and the two routes are those of gs_reduce_*.  What differs:
+ *   - d_keys and d_out_keys hold 8-byte elements; out_keys are exactly what gs_unique64_keys delivers; equality is BITWISE on 64 bits.
+ *   - key types are 3 .. 5; the 32-bit and the 16-bit key types return GS_ERR_ARG.
+ *   - counts and *d_out_num stay uint32; the overlap check takes 8 n bytes for d_keys and d_out_keys.
+ * GS_REDUCE_SUM on floats is THE SAME TREE as gs_reduce_*: eight values per thread left to right, the threads of a wave by a scan of
+ * distances 1 .. 32, then waves, tiles and ranges left to right, over gs_unique_plan's ranges; no identity element is combined in.  The
+ * tree depends on n and on where the runs lie, not on the width of the keys: ON KEYS THAT ARE ZERO-EXTENDED 32-BIT KEYS (of
+ * GS_KEY_UINT32, sorted as GS_KEY_UINT64) THE REDUCED VALUES ARE BIT FOR BIT THOSE OF gs_reduce_by_key, and two calls, or two handles,
+ * give bitwise identical output.
+ *
+ * Errors, in this order, as gs_reduce_*.  GS_ERR_ARG: null handle (before anything else is looked at); null or misaligned d_keys /
+ * d_values / d_out_keys / d_out_values; a key type outside 3 .. 5, a bad order (gs_reduce64_by_key_consecutive has neither); a value
+ * type outside 0 .. 5, an op outside 0 .. 2.  GS_ERR_MODE: a value type whose width is not the handle's.  GS_ERR_ARG: a misaligned
+ * d_out_counts / d_out_num.  GS_ERR_SIZE: n == 0 or n > max_keys.  GS_ERR_ARG: any two of the seven buffers overlapping (outputs at
+ * their capacity of n elements).  GS_ERR_MODE: every call on a build flavour without these kernels (the tuning and fault-injection
+ * libraries).  A refused call launches nothing and leaves route NONE.  Routes and report words are gs_reduce's. */
+typedef struct gs_reduce64 gs_reduce64;
+#define GS_REDUCE64_ROUTE_NONE 0
+#define GS_REDUCE64_ROUTE_SORTED 1
+#define GS_REDUCE64_ROUTE_CONSECUTIVE 2
+/* gs_reduce64_last report words: those of gs_reduce_last */
+#define GS_REDUCE64_R_ROUTE 0
+#define GS_REDUCE64_R_N 1
+#define GS_REDUCE64_R_U 2
+#define GS_REDUCE64_R_RANGES 3
+#define GS_REDUCE64_R_PER_RANGE 4
+#define GS_REDUCE64_R_TILE 5
+#define GS_REDUCE64_R_STATUS 6
+#define GS_REDUCE64_R_RANK 7
+#define GS_REDUCE64_R_VALUE_TYPE 8
+#define GS_REDUCE64_R_OP 9
+#define GS_REDUCE64_REPORT_WORDS 10
+/* No counterpart in the reference project.  1 <= max_keys <= GS_MAX_KEYS (GS_ERR_SIZE), then value_bytes 4 or 8 (GS_ERR_MODE), both
+ * answered before a device is looked for.  Synchronous (allocates gs_reduce64_temp_bytes of device memory). */
+gs_status gs_reduce64_create(gs_reduce64** out, uint32_t max_keys, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_reduce64_destroy(gs_reduce64* h);
+/* No counterpart in the reference project.  Host only.  With A(x) = (x + 255) & ~255:
+ *     A(64 * 4)                            the control block
+ *   + 4 * A(1024 * 4)                      per range: heads, last head, heads in front, last head in front
+ *   + 2 * A(1024 * 8)                      per range: the open partial and the carry (8 bytes each, whatever the width)
+ *   + 2 * A(8 * max_keys)                  the copy of the keys the engine sorts, and its alternate buffer
+ *   + 2 * A(value_bytes * max_keys)        the copy of the values, and its alternate buffer
+ *   + gs_onesweep_temp_bytes(max_keys)     the embedded engine
+ * 0 for invalid sizes or value width. */
+size_t gs_reduce64_temp_bytes(uint32_t max_keys, uint32_t value_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_reduce64_by_key(gs_reduce64* h, const void* d_keys, const void* d_values, uint32_t n, void* d_out_keys, void* d_out_values,
+                             void* d_out_counts, void* d_out_num, gs_key_type key_type, gs_order order, gs_value_type value_type,
+                             gs_reduce_op op, void* stream);
+/* No counterpart in the reference project. */
+gs_status gs_reduce64_by_key_consecutive(gs_reduce64* h, const void* d_keys, const void* d_values, uint32_t n, void* d_out_keys,
+                                         void* d_out_values, void* d_out_counts, void* d_out_num, gs_value_type value_type, gs_reduce_op op,
+                                         void* stream);
+/* No counterpart in the reference project.  As gs_reduce_check. */
+gs_status gs_reduce64_check(gs_reduce64* h, void* stream);
+/* No counterpart in the reference project.  As gs_reduce_last: report[GS_REDUCE64_R_*], words >= GS_REDUCE64_REPORT_WORDS. */
+gs_status gs_reduce64_last(gs_reduce64* h, uint32_t* report, uint32_t words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
