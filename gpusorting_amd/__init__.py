@@ -21,11 +21,13 @@ Only the hot path of b0nes164/GPUSorting named by BASELINE.json is here:
              on runs of equal neighbours) over gs_reduce_*, and its numpy reference
   unique64   unique on 64-bit keys (uint64, int64, float64) over gs_unique64_*, and its numpy reference
   reduce64   reduce by key on 64-bit keys over gs_reduce64_*, and its numpy reference
+  search     sorted search: the lower / upper bound of many queries in a sorted array, in the library's own order (both orders, floats
+             by the bit flip), over gs_search_*, and its numpy reference
   functional sort / sort_ / argsort / sort_rows / argsort_rows / segmented_sort / topk / topk16 / segmented_topk / segmented_topk16 /
              unique / unique_consecutive / unique16 / unique_consecutive16 / reduce_by_key / reduce_by_key_consecutive / unique64 /
-             unique_consecutive64 / reduce_by_key64 / reduce_by_key_consecutive64 on torch tensors (plumbing
+             unique_consecutive64 / reduce_by_key64 / reduce_by_key_consecutive64 / searchsorted / bucketize on torch tensors (plumbing
              over OneSweep / RowSort / RowSort16 / SegmentedSort / SegmentedSort16 / TopK / SegmentedTopK / SegmentedTopK16 / TopK16 /
-             Unique / Unique16 / ReduceByKey / Unique64 / ReduceByKey64)
+             Unique / Unique16 / ReduceByKey / Unique64 / ReduceByKey64 / SortedSearch)
 """
 from .onesweep import (  # noqa: F401
     ENTROPY_PRESET_1, ENTROPY_PRESET_2, ENTROPY_PRESET_3, ENTROPY_PRESET_4, ENTROPY_PRESET_5,
@@ -37,11 +39,13 @@ from .functional import (  # noqa: F401
     argsort, argsort_rows, reduce_by_key, reduce_by_key_consecutive, segmented_argsort, segmented_sort, segmented_sort_, segmented_topk, segmented_topk16, sort, sort_, sort_rows, sort_rows_, topk,
     topk16, unique, unique16, unique_consecutive, unique_consecutive16,
     reduce_by_key64, reduce_by_key_consecutive64, unique64, unique_consecutive64,
+    bucketize, searchsorted,
 )
 from .reduce import ReduceByKey, reduce_by_key_reference  # noqa: F401
 from .reduce64 import ReduceByKey64, reduce_by_key64_reference  # noqa: F401
 from .rowsort import RowSort, sort_rows_plan, sort_rows_reference  # noqa: F401
 from .rowsort16 import SORT_ROWS16_FORMS, RowSort16, sort_rows16_plan, sort_rows16_reference  # noqa: F401
+from .search import SortedSearch, search_plan, search_plan_reference, searchsorted_reference  # noqa: F401
 from .segsort import SegmentedSort, segmented_sort_reference, segsort_long_units  # noqa: F401
 from .segsort16 import SEGSORT16_FORMS, SegmentedSort16, segmented_sort16_reference, segsort16_units  # noqa: F401
 from .segtopk import SegmentedTopK, segmented_topk_reference  # noqa: F401

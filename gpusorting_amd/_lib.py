@@ -118,6 +118,18 @@ GS_REDUCE64_ROUTE_NONE, GS_REDUCE64_ROUTE_SORTED, GS_REDUCE64_ROUTE_CONSECUTIVE 
 (GS_REDUCE64_R_ROUTE, GS_REDUCE64_R_N, GS_REDUCE64_R_U, GS_REDUCE64_R_RANGES, GS_REDUCE64_R_PER_RANGE, GS_REDUCE64_R_TILE, GS_REDUCE64_R_STATUS,
  GS_REDUCE64_R_RANK, GS_REDUCE64_R_VALUE_TYPE, GS_REDUCE64_R_OP) = range(10)
 GS_REDUCE64_REPORT_WORDS = 10
+# gs_search_*: sides, routes, table forms, the AUTO rule's constants, plan and report words
+GS_SEARCH_LEFT, GS_SEARCH_RIGHT = 0, 1
+GS_SEARCH_ROUTE_AUTO = GS_SEARCH_ROUTE_NONE = 0
+GS_SEARCH_ROUTE_TILE, GS_SEARCH_ROUTE_SORT, GS_SEARCH_ROUTE_BINARY = 1, 2, 3
+GS_SEARCH_TABLE_AUTO, GS_SEARCH_TABLE_ON, GS_SEARCH_TABLE_OFF = 0, 1, 2
+GS_SEARCH_TABLE_MIN_QUERIES, GS_SEARCH_SORT_MIN_QUERIES, GS_SEARCH_SORT_MIN_KEYS = 1 << 18, 1 << 22, 1 << 22
+(GS_SEARCH_P_TILE, GS_SEARCH_P_WINDOW, GS_SEARCH_P_SAMPLES, GS_SEARCH_P_STRIDE, GS_SEARCH_P_TILE_GRID, GS_SEARCH_P_BINARY_GRID,
+ GS_SEARCH_P_SAMPLE_GRID, GS_SEARCH_P_TABLE, GS_SEARCH_P_ROUTE_SORTED, GS_SEARCH_P_ROUTE_UNSORTED, GS_SEARCH_P_ROUTE_NO_ENGINE) = range(11)
+GS_SEARCH_PLAN_WORDS = 12
+(GS_SEARCH_R_ROUTE, GS_SEARCH_R_N, GS_SEARCH_R_M, GS_SEARCH_R_TABLE, GS_SEARCH_R_LDS_TILES, GS_SEARCH_R_GLOBAL_TILES, GS_SEARCH_R_ENGINE) = range(7)
+GS_SEARCH_R_PLAN = 8
+GS_SEARCH_REPORT_WORDS = 20
 
 # gs_debug_sort_route / gs_debug_set_hy_class / gs_debug_pass_flags / gs_debug_registry_* (test hooks)
 GS_ROUTE_NONE = 0xFFFFFFFF
@@ -408,6 +420,14 @@ _PROTOS = [
     ("gs_reduce64_by_key_consecutive", _int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     ("gs_reduce64_check", _int, [_vp, _vp]),
     ("gs_reduce64_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_search_create", _int, [C.POINTER(_vp), _u32, _u32, _u32, _int]),
+    ("gs_search_destroy", _int, [_vp]),
+    ("gs_search_temp_bytes", C.c_size_t, [_u32, _u32, _u32, _int]),
+    ("gs_search_plan", _int, [_u32, _u32, _u32, _u32p]),
+    ("gs_search_sorted", _int, [_vp, _vp, _u32, _vp, _u32, _vp, _int, _int, _int, _int, _vp]),
+    ("gs_search_set_route", _int, [_vp, _u32]),
+    ("gs_search_set_table", _int, [_vp, _u32]),
+    ("gs_search_last", _int, [_vp, _u32p, _u32, _vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

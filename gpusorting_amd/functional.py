@@ -12,6 +12,7 @@ handle cache, buffers).  The reference has no such layer; it is what a torch use
     runs, counts = gpusorting_amd.unique_consecutive(keys, return_counts=True)                         # torch.unique_consecutive
     distinct, sums = gpusorting_amd.reduce_by_key(keys, values, op="sum")   # unique + index_add_ in one call, no atomics (ReduceByKey)
     distinct, index = gpusorting_amd.unique16(half_keys, return_index=True)  # float16 / bfloat16 / int16 / uint16: one histogram (Unique16)
+    positions = gpusorting_amd.searchsorted(sorted_keys, queries, right=True, descending=True)  # in THIS library's order (SortedSearch)
 
 Semantics are the library's: stable LSD radix sort; descending = exact reverse of the stable ascending result;
 float keys ordered by the order-preserving bit flip (-0 < +0, NaNs by bit pattern); values bit-copied.
@@ -35,6 +36,7 @@ from .unique import Unique, unique_reference  # noqa: F401
 from .unique16 import Unique16, unique16_reference  # noqa: F401
 from .unique64 import Unique64, unique64_reference  # noqa: F401
 from .reduce64 import ReduceByKey64, reduce_by_key64_reference  # noqa: F401
+from .search import ROUTE_SORT as _SEARCH_ROUTE_SORT, SortedSearch, search_plan, searchsorted_reference  # noqa: F401
 from .onesweep import (KEY_FLOAT32, KEY_FLOAT64, KEY_INT32, KEY_INT64, KEY_UINT32, KEY_UINT64, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING,
                        ORDER_DESCENDING, OneSweep)
 
@@ -950,3 +952,64 @@ def reduce_by_key_consecutive64(keys: torch.Tensor, values: torch.Tensor, op: st
         out_k, out_v, out_c, num = s.reduce_by_key_consecutive(keys, values, opc, vt, n, counts=return_counts)
     u = int(num.item())
     return (out_k[:u], out_v[:u]) + ((out_c[:u],) if return_counts else ())
+
+
+# ---- sorted search: the lower / upper bound of many queries ------------------------------------------------------------------------
+_search_cache: dict = {}
+
+
+def _search_handle(device: torch.device, n: int, m: int, key_type: int, order: int, sort_queries: bool) -> SortedSearch:
+    """One ``SortedSearch`` handle per (device, stream, type, order, with the query sorter); re-created when a size outgrows it."""
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, sort_queries)
+    s = _search_cache.get(key)
+    if s is None or s.max_keys < n or s.max_queries < m:
+        if s is not None:
+            n, m = max(n, s.max_keys), max(m, s.max_queries)
+            s.close()
+        cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
+        s = SortedSearch(cap(n), cap(m), key_type, order, sort_queries=sort_queries, device=device.index)
+        _search_cache[key] = s
+    return s
+
+
+def searchsorted(sorted_keys: torch.Tensor, queries: torch.Tensor, right: bool = False, descending: bool = False, queries_sorted: bool = False,
+                 unsigned: bool = False) -> torch.Tensor:
+    """``torch.searchsorted`` in THIS library's order: for every element of ``queries`` (any shape; contiguous) its insertion position in
+    the 1-D contiguous ``sorted_keys``, as int32 in the shape of ``queries``: the number of keys strictly in front of the query
+    (``right=False``) or in front of or equal to it (``right=True``).  ``sorted_keys`` is what this library's sort delivers, ascending
+    or ``descending``: int32, float32, int64, float64 (uint32 / uint64 where torch has them; ``unsigned=True`` reads signed storage as
+    unsigned keys); floats are ordered ``-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN`` and compared BITWISE (``-0.0`` and ``+0.0``
+    are two keys, every NaN pattern is its own), which is where the result differs from ``torch.searchsorted``; on integers, ascending,
+    it is the same.  The order of ``sorted_keys`` is not checked (unsorted: unspecified positions within ``[0, n]``).
+    ``queries_sorted=True`` declares the queries sorted in the same order and takes the fastest route.  No wait on the host.  16-bit
+    dtypes are a ``TypeError``."""
+    if sorted_keys.dim() != 1:
+        raise ValueError("sorted_keys must be a contiguous 1-D device tensor")
+    if sorted_keys.dtype != queries.dtype:
+        raise TypeError(f"queries are {queries.dtype}, sorted_keys {sorted_keys.dtype}: one dtype for both")
+    dt = sorted_keys.dtype
+    if dt in _KEY_TYPE:
+        kt = KEY_UINT32 if (unsigned and dt == torch.int32) else _KEY_TYPE[dt]
+    elif dt in _KEY64_TYPE:
+        kt = KEY_UINT64 if (unsigned and dt == torch.int64) else _KEY64_TYPE[dt]
+    else:
+        raise TypeError(f"unsupported key dtype {dt}: searchsorted takes 32- and 64-bit keys (int32, uint32, float32, int64, uint64, float64)")
+    if not sorted_keys.is_contiguous() or not queries.is_contiguous() or sorted_keys.device.type != "cuda" or queries.device != sorted_keys.device:
+        raise ValueError("sorted_keys and queries must be contiguous tensors on one GPU")
+    n, m = sorted_keys.numel(), queries.numel()
+    if m == 0 or n == 0:  # nothing in front of anything
+        return torch.zeros(queries.shape, dtype=torch.int32, device=queries.device)
+    order = ORDER_DESCENDING if descending else ORDER_ASCENDING
+    with torch.cuda.device(sorted_keys.device):
+        wants_sort = not queries_sorted and search_plan(n, m, sorted_keys.element_size())["route_unsorted"] == _SEARCH_ROUTE_SORT
+        s = _search_handle(sorted_keys.device, n, m, kt, order, wants_sort)
+        out = s.search(sorted_keys, queries.reshape(-1), n, m, right=right, queries_sorted=queries_sorted)
+    return out.reshape(queries.shape)
+
+
+def bucketize(input: torch.Tensor, boundaries: torch.Tensor, right: bool = False) -> torch.Tensor:  # noqa: A002
+    """``torch.bucketize`` in this library's order: ``searchsorted(boundaries, input, right=right)`` under torch's argument order
+    (ascending boundaries; int32 result).  Narrower than torch's: ``boundaries`` must be 1-D and contiguous, ``input`` contiguous, both
+    on one GPU and of ONE dtype (a mixed pair is a ``TypeError``: convert first; torch promotes), and there is no ``out_int32`` or
+    ``out`` argument."""
+    return searchsorted(boundaries, input, right=right)

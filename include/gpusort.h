@@ -1667,6 +1667,117 @@ gs_status gs_reduce64_check(gs_reduce64* h, void* stream);
 /* No counterpart in the reference project.  As gs_reduce_last: report[GS_REDUCE64_R_*], words >= GS_REDUCE64_REPORT_WORDS. */
 gs_status gs_reduce64_last(gs_reduce64* h, uint32_t* report, uint32_t words, void* stream);
 
+/* ---- sorted search: the lower / upper bound of many queries in a sorted array ------------------------------------------------------------
+ * No counterpart in the reference project.  What a caller of the sorts, of gs_unique_* or of gs_reduce_* does next: where does this key
+ * fall in the sorted keys I already have.
+ *
+ * hay[0 .. n) is sorted in `order` under the library's total order of key_type: GS_KEY_UINT32 / INT32 / FLOAT32 on a handle created
+ * with key_bytes 4, GS_KEY_UINT64 / INT64 / FLOAT64 on one created with key_bytes 8 (floats by the order-preserving flip:
+ * -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN).  The 16-bit key types are refused with GS_ERR_ARG.  q[0 .. m) holds keys of the
+ * same type.  out[j] is a uint32 in [0, n]:
+ *
+ *                        GS_SEARCH_LEFT                                  GS_SEARCH_RIGHT
+ *     ascending          number of hay keys strictly below q[j]          number of hay keys below or equal
+ *     descending         number of hay keys strictly above q[j]          number of hay keys above or equal
+ *
+ * the insertion position that keeps hay sorted, before (LEFT) or after (RIGHT) the keys equal to the query.  Equality is BITWISE in the
+ * flipped domain: -0.0 and +0.0 are two keys and every NaN pattern is a key of its own.  On integers, ascending, the result is
+ * torch.searchsorted(hay, q, right = ...)'s.
+ *
+ * THE ORDER OF hay IS NOT CHECKED.  If hay is not sorted as declared the positions are unspecified, and so they are if queries declared
+ * sorted are not.  Even then every out[j] lies in [0, n], no byte outside the call's buffers is read or written, and the call ends:
+ * every window is clamped to lo <= hi <= n and every loop is bounded by the sizes, not by the data.
+ *
+ * Three routes (gs_search_last reports the one taken, gs_search_set_route forces one; GS_SEARCH_ROUTE_AUTO is the default):
+ *   GS_SEARCH_ROUTE_TILE    queries in order.  One workgroup per tile of GS_SEARCH_P_TILE queries finds the tile's window of hay with
+ *                           two searches (LEFT of its first query, RIGHT of its last); a window of at most GS_SEARCH_P_WINDOW keys is
+ *                           staged into LDS and every query answered there; a wider one (sparse queries) is searched in global
+ *                           memory narrowed to the window.  The decision is made per tile on the device.
+ *   GS_SEARCH_ROUTE_SORT    queries in any order, through TILE: the queries are copied with their positions 0 .. m - 1, the embedded
+ *                           stable pairs engine sorts (query, position) in `order`, the tile kernel runs on the sorted copy and
+ *                           stores out[position].  Needs a handle created with sort_queries = 1.
+ *   GS_SEARCH_ROUTE_BINARY  queries in any order without a sort: one thread per query.  With the sample table (GS_SEARCH_R_TABLE = 1)
+ *                           every GS_SEARCH_P_STRIDE-th key of hay is written into a table of at most 64 KiB in the workspace, a
+ *                           workgroup stages it into LDS once and serves many queries: the samples in LDS, then the keys between two
+ *                           samples in global memory.  Without it every level is a global load.  gs_search_set_table forces the
+ *                           form; AUTO takes the table from GS_SEARCH_TABLE_MIN_QUERIES queries on.
+ * AUTO: queries_sorted != 0 -> TILE.  Otherwise, on a handle with the engine, SORT when m >= GS_SEARCH_SORT_MIN_QUERIES and
+ * n >= GS_SEARCH_SORT_MIN_KEYS, else BINARY; on a handle without it BINARY.
+ *
+ * Buffers: d_hay, d_queries and d_out 16-byte aligned; d_out holds m uint32 and nothing at or behind element m is written; hay and the
+ * queries are not written.  No host wait; every node is a kernel and every grid is a function of (n, m) alone (gs_search_plan), so a
+ * call can be captured in a graph and replayed on other contents of the same sizes.  One call in flight per handle.
+ *
+ * Errors of gs_search_sorted, in this order.  GS_ERR_ARG: null handle (before anything else is looked at); a null or misaligned
+ * d_hay / d_queries / d_out; a key type whose width is not the handle's (the 16-bit ones included), a bad order, a bad side.
+ * GS_ERR_MODE: route SORT forced on a handle created without sort_queries.  GS_ERR_SIZE: n == 0, m == 0, n > max_keys or
+ * m > max_queries.  GS_ERR_ARG: any two of the three buffers overlapping.  GS_ERR_MODE: every call on a build flavour without these
+ * kernels (the tuning and fault-injection libraries).  A refused call launches nothing and leaves route NONE. */
+typedef struct gs_search gs_search;
+typedef enum gs_search_side { GS_SEARCH_LEFT = 0, GS_SEARCH_RIGHT = 1 } gs_search_side;
+#define GS_SEARCH_ROUTE_AUTO 0   /* gs_search_set_route only */
+#define GS_SEARCH_ROUTE_NONE 0   /* gs_search_last: no call yet, or the last one was refused */
+#define GS_SEARCH_ROUTE_TILE 1
+#define GS_SEARCH_ROUTE_SORT 2
+#define GS_SEARCH_ROUTE_BINARY 3
+#define GS_SEARCH_TABLE_AUTO 0   /* gs_search_set_table */
+#define GS_SEARCH_TABLE_ON 1
+#define GS_SEARCH_TABLE_OFF 2
+/* the AUTO rule's constants (measured: DESIGN.md 3.25) */
+#define GS_SEARCH_TABLE_MIN_QUERIES 262144u  /* level with the plain form at 2^18 queries, ahead from 2^20 on, behind at 2^16 */
+#define GS_SEARCH_SORT_MIN_QUERIES 4194304u  /* SORT is ahead of BINARY at 2^22 queries in 2^22 keys and more, behind at 2^20 of either */
+#define GS_SEARCH_SORT_MIN_KEYS 4194304u
+/* gs_search_plan words */
+#define GS_SEARCH_P_TILE 0              /* T: queries per workgroup of the tile kernel */
+#define GS_SEARCH_P_WINDOW 1            /* W: the most keys of a window in LDS (32 KiB / key_bytes) */
+#define GS_SEARCH_P_SAMPLES 2           /* samples in the table: n / S */
+#define GS_SEARCH_P_STRIDE 3            /* S: the smallest power of two with ceil(n / S) <= 64 KiB / key_bytes; 1: the table is hay */
+#define GS_SEARCH_P_TILE_GRID 4         /* ceil(m / T) */
+#define GS_SEARCH_P_BINARY_GRID 5       /* the BINARY route's grid in the form AUTO takes */
+#define GS_SEARCH_P_SAMPLE_GRID 6       /* the sample kernel's grid */
+#define GS_SEARCH_P_TABLE 7             /* 1: AUTO's BINARY uses the sample table for this m */
+#define GS_SEARCH_P_ROUTE_SORTED 8      /* AUTO's route for queries_sorted != 0 */
+#define GS_SEARCH_P_ROUTE_UNSORTED 9    /* ... for queries in no order on a handle with the engine */
+#define GS_SEARCH_P_ROUTE_NO_ENGINE 10  /* ... on a handle without it */
+#define GS_SEARCH_PLAN_WORDS 12
+/* gs_search_last report words */
+#define GS_SEARCH_R_ROUTE 0
+#define GS_SEARCH_R_N 1
+#define GS_SEARCH_R_M 2
+#define GS_SEARCH_R_TABLE 3         /* BINARY: 1 with the sample table, 0 plain */
+#define GS_SEARCH_R_LDS_TILES 4     /* TILE / SORT: tiles answered in LDS ... */
+#define GS_SEARCH_R_GLOBAL_TILES 5  /* ... and tiles whose window was wider than W */
+#define GS_SEARCH_R_ENGINE 6        /* 1: the handle sorts queries */
+#define GS_SEARCH_R_PLAN 8          /* the GS_SEARCH_PLAN_WORDS words of gs_search_plan(n, m, key_bytes) */
+#define GS_SEARCH_REPORT_WORDS 20
+/* No counterpart in the reference project.  1 <= max_keys, max_queries <= GS_MAX_KEYS (GS_ERR_SIZE), then key_bytes 4 or 8 and
+ * sort_queries 0 or 1 (GS_ERR_ARG; 2-byte keys are a follow-up), both answered before a device is looked for.  sort_queries = 1 embeds
+ * a gs_onesweep pairs engine of capacity max_queries with 4-byte values and allocates the copy of the queries, its alternate and two
+ * position buffers; without it the handle allocates only the control block and the sample table.  Synchronous. */
+gs_status gs_search_create(gs_search** out, uint32_t max_keys, uint32_t max_queries, uint32_t key_bytes, int sort_queries);
+/* No counterpart in the reference project. */
+gs_status gs_search_destroy(gs_search* h);
+/* No counterpart in the reference project.  Host only.  With A(x) = (x + 255) & ~255:
+ *     A(64 * 4) + A(65536)                         the control block and the sample table
+ *   + 2 * A(key_bytes * max_queries)               sort_queries only: the copy of the queries and its alternate buffer
+ *   + 2 * A(4 * max_queries)                       sort_queries only: the positions and their alternate buffer
+ *   + gs_onesweep_temp_bytes(max_queries)          sort_queries only: the embedded engine
+ * 0 for invalid arguments. */
+size_t gs_search_temp_bytes(uint32_t max_keys, uint32_t max_queries, uint32_t key_bytes, int sort_queries);
+/* No counterpart in the reference project.  Host only: plan[GS_SEARCH_P_*] for n keys and m queries of key_bytes bytes.  In the order
+ * of gs_search_create: GS_ERR_ARG: null plan; GS_ERR_SIZE: n or m 0 or above GS_MAX_KEYS; GS_ERR_ARG: key_bytes not 4 or 8. */
+gs_status gs_search_plan(uint32_t n, uint32_t m, uint32_t key_bytes, uint32_t plan[GS_SEARCH_PLAN_WORDS]);
+/* No counterpart in the reference project.  See above.  queries_sorted != 0 declares q sorted in the same `order`. */
+gs_status gs_search_sorted(gs_search* h, const void* d_hay, uint32_t n, const void* d_queries, uint32_t m, void* d_out, gs_key_type key_type,
+                           gs_order order, gs_search_side side, int queries_sorted, void* stream);
+/* No counterpart in the reference project.  GS_SEARCH_ROUTE_AUTO / _TILE / _SORT / _BINARY for the calls that follow, whatever
+ * queries_sorted says (GS_ERR_ARG: null handle, another value).  SORT on a handle without the engine is refused by the call. */
+gs_status gs_search_set_route(gs_search* h, uint32_t route);
+/* No counterpart in the reference project.  The form of the BINARY route: GS_SEARCH_TABLE_AUTO / _ON / _OFF (GS_ERR_ARG otherwise). */
+gs_status gs_search_set_table(gs_search* h, uint32_t table);
+/* No counterpart in the reference project.  Synchronous diagnostics of the last call: report[GS_SEARCH_R_*], words >= GS_SEARCH_REPORT_WORDS. */
+gs_status gs_search_last(gs_search* h, uint32_t* report, uint32_t words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
