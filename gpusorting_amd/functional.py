@@ -45,60 +45,72 @@ _KEY_TYPE = {torch.int32: KEY_INT32, torch.float32: KEY_FLOAT32, torch.uint32: K
 _KEY16_TYPE = {torch.float16: KEY_FLOAT16, torch.bfloat16: KEY_BFLOAT16, torch.int16: KEY_INT16}
 if hasattr(torch, "uint16"):
     _KEY16_TYPE[torch.uint16] = KEY_UINT16
+_KEY64_TYPE = {torch.int64: KEY_INT64, torch.float64: KEY_FLOAT64}
+if hasattr(torch, "uint64"):
+    _KEY64_TYPE[torch.uint64] = KEY_UINT64
+_UNSIGNED = {torch.int16: KEY_UINT16, torch.int32: KEY_UINT32, torch.int64: KEY_UINT64}  # what ``unsigned=True`` makes of signed storage
+
+
+def _key_type(keys: torch.Tensor, unsigned: bool, table: dict) -> int:
+    return _UNSIGNED[keys.dtype] if (unsigned and keys.dtype in _UNSIGNED) else table[keys.dtype]
+
+
+def _order(descending: bool) -> int:
+    return ORDER_DESCENDING if descending else ORDER_ASCENDING
+
+
+def _mode(value_bytes: int) -> int:
+    return MODE_PAIRS if value_bytes else MODE_KEYS_ONLY
+
+
+# ---- the handle caches: one rule -------------------------------------------------------------------------------------------------
+def _cap(x: int, floor_bits: int = 16) -> int:
+    """The next power of two (few re-creations while sizes wander), at least ``2^floor_bits``, at most the library's 2^30 - 1."""
+    return min(1 << max(int(x - 1).bit_length(), floor_bits), (1 << 30) - 1)
+
+
+def _on(device: torch.device) -> tuple:
+    """(device, stream): the head of every cache key."""
+    return device.index, int(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _cached(cache: dict, key: tuple, asked: dict, factory):
+    """The cache rule of every family: the handle under ``key``, closed and re-created by ``factory(**asked)`` when one of the sizes
+    ``asked`` (``max_*`` attribute -> what the call needs) outgrows it.  The factory rounds the sizes up (``_cap``)."""
+    s = cache.get(key)
+    if s is None or any(getattr(s, name) < size for name, size in asked.items()):
+        if s is not None:
+            s.close()
+        s = cache[key] = factory(**asked)
+    return s
+
+
 _cache: dict = {}
+
+
+def _flat_sorter(cls, tag: tuple, device: torch.device, n: int, key_type: int, order: int, value_bytes: int):
+    return _cached(_cache, tag + _on(device) + (key_type, order, value_bytes), {"max_keys": n},
+                   lambda max_keys: cls(_cap(max_keys), order, key_type, _mode(value_bytes), value_bytes, device=device.index))
 
 
 def _sorter(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> OneSweep:
     """One cached handle per (device, stream, type, order, value width); re-created when the size outgrows it."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
-    s = _cache.get(key)
-    if s is None or s.max_keys < n:
-        if s is not None:
-            s.close()
-        cap = 1 << max(int(n - 1).bit_length(), 16)  # next power of two: few re-creations while sizes wander
-        s = OneSweep(min(cap, (1 << 30) - 1), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes,
-                     device=device.index)
-        _cache[key] = s
-    return s
+    return _flat_sorter(OneSweep, (), device, n, key_type, order, value_bytes)
 
 
 def _sorter16(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> Sort16:
     """The same cache rule for 16-bit keys: one ``Sort16`` handle per (device, stream, type, order, value width)."""
-    key = (16, device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
-    s = _cache.get(key)
-    if s is None or s.max_keys < n:
-        if s is not None:
-            s.close()
-        cap = 1 << max(int(n - 1).bit_length(), 16)
-        s = Sort16(min(cap, (1 << 30) - 1), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes, device=device.index)
-        _cache[key] = s
-    return s
+    return _flat_sorter(Sort16, (16,), device, n, key_type, order, value_bytes)
 
 
 def _row_sorter(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> RowSort:
     """The same cache rule for the row-wise sort: one ``RowSort`` handle per (device, stream, type, order, value width)."""
-    key = ("rows", device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
-    s = _cache.get(key)
-    if s is None or s.max_keys < n:
-        if s is not None:
-            s.close()
-        cap = 1 << max(int(n - 1).bit_length(), 16)
-        s = RowSort(min(cap, (1 << 30) - 1), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes, device=device.index)
-        _cache[key] = s
-    return s
+    return _flat_sorter(RowSort, ("rows",), device, n, key_type, order, value_bytes)
 
 
 def _row_sorter16(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> RowSort16:
     """The same cache rule for the row-wise sort of 16-bit keys: one ``RowSort16`` handle per (device, stream, type, order, value width)."""
-    key = ("rows16", device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
-    s = _cache.get(key)
-    if s is None or s.max_keys < n:
-        if s is not None:
-            s.close()
-        cap = 1 << max(int(n - 1).bit_length(), 16)
-        s = RowSort16(min(cap, (1 << 30) - 1), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes, device=device.index)
-        _cache[key] = s
-    return s
+    return _flat_sorter(RowSort16, ("rows16",), device, n, key_type, order, value_bytes)
 
 
 def _values_width(keys: torch.Tensor, values: torch.Tensor | None) -> int:
@@ -113,13 +125,13 @@ def _values_width(keys: torch.Tensor, values: torch.Tensor | None) -> int:
 
 def _sort16_(keys: torch.Tensor, values: torch.Tensor | None, descending: bool, unsigned: bool, positions: torch.Tensor | None = None) -> None:
     """``sort_`` / ``argsort`` on 2-byte keys: one ``gs_sort16_*`` call (``positions``: argsort's output, made by the kernels)."""
-    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    kt = _key_type(keys, unsigned, _KEY16_TYPE)
     vb = 4 if positions is not None else _values_width(keys, values)
     n = keys.numel()
     if n == 0:
         return
     with torch.cuda.device(keys.device):
-        s = _sorter16(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb)
+        s = _sorter16(keys.device, n, kt, _order(descending), vb)
         if positions is not None:
             s.argsort(keys, positions, n=n)
         else:
@@ -138,12 +150,12 @@ def _sort_rows_(keys: torch.Tensor, values: torch.Tensor | None, descending: boo
     if keys.dtype not in _KEY_TYPE:
         raise RowKeyTypeError(f"unsupported key dtype {keys.dtype} for a 2-D tensor: rows are sorted on 32-bit keys only (int32, uint32, float32); "
                               "sort_rows / argsort_rows take 16-bit keys")
-    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    kt = _key_type(keys, unsigned, _KEY_TYPE)
     vb = _values_width(keys, values)
     if keys.numel() == 0:
         return
     with torch.cuda.device(keys.device):
-        s = _row_sorter(keys.device, keys.numel(), kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb)
+        s = _row_sorter(keys.device, keys.numel(), kt, _order(descending), vb)
         s.sort(keys.view(torch.int32) if keys.dtype != torch.int32 else keys, values)
 
 
@@ -165,19 +177,13 @@ def sort_(keys: torch.Tensor, values: torch.Tensor | None = None, descending: bo
     if keys.dtype not in _KEY_TYPE:
         raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys (int32, uint32, float32) and 16-bit keys "
                         "(float16, bfloat16, int16, uint16)")
-    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
-    vb = 0
-    if values is not None:
-        if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:
-            raise ValueError("values must match keys in shape and device and be contiguous")
-        vb = values.element_size()
-        if vb not in (4, 8):
-            raise TypeError("values must be 4 or 8 bytes wide")
+    kt = _key_type(keys, unsigned, _KEY_TYPE)
+    vb = _values_width(keys, values)
     n = keys.numel()
     if n <= 1:
         return
     with torch.cuda.device(keys.device):
-        s = _sorter(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb)
+        s = _sorter(keys.device, n, kt, _order(descending), vb)
         s.sort(keys.view(torch.int32) if keys.dtype != torch.int32 else keys, values, n=n)
 
 
@@ -224,12 +230,12 @@ def sort_rows_(keys: torch.Tensor, values: torch.Tensor | None = None, descendin
     _require_rows(keys)
     if keys.dtype in _KEY_TYPE:
         return _sort_rows_(keys, values, descending, unsigned)
-    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    kt = _key_type(keys, unsigned, _KEY16_TYPE)
     vb = _values_width(keys, values)
     if keys.numel() == 0:
         return
     with torch.cuda.device(keys.device):
-        _row_sorter16(keys.device, keys.numel(), kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb).sort(keys, values)
+        _row_sorter16(keys.device, keys.numel(), kt, _order(descending), vb).sort(keys, values)
 
 
 def sort_rows(keys: torch.Tensor, values: torch.Tensor | None = None, descending: bool = False, unsigned: bool = False):
@@ -249,9 +255,9 @@ def argsort_rows(keys: torch.Tensor, descending: bool = False, unsigned: bool = 
     idx = torch.empty(keys.shape, dtype=torch.int32, device=keys.device)
     if keys.numel() == 0:
         return idx
-    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    kt = _key_type(keys, unsigned, _KEY16_TYPE)
     with torch.cuda.device(keys.device):
-        _row_sorter16(keys.device, keys.numel(), kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, 4).argsort(keys.clone(), idx)
+        _row_sorter16(keys.device, keys.numel(), kt, _order(descending), 4).argsort(keys.clone(), idx)
     return idx
 
 
@@ -262,30 +268,16 @@ _seg_cache: dict = {}
 def _seg_sorter(device: torch.device, n: int, num_segments: int, key_type: int, order: int, value_bytes: int,
                 long_route: str = "host") -> SegmentedSort:
     """One cached handle per (device, stream, type, order, value width, long route); re-created when keys or segments outgrow it."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes, long_route)
-    s = _seg_cache.get(key)
-    if s is None or s.max_keys < n or s.max_segments < num_segments:
-        if s is not None:
-            s.close()
-        cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
-        s = SegmentedSort(cap(n), cap(num_segments), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes,
-                          device=device.index, long_route=long_route)
-        _seg_cache[key] = s
-    return s
+    return _cached(_seg_cache, _on(device) + (key_type, order, value_bytes, long_route), {"max_keys": n, "max_segments": num_segments},
+                   lambda max_keys, max_segments: SegmentedSort(_cap(max_keys), _cap(max_segments), order, key_type, _mode(value_bytes),
+                                                                value_bytes, device=device.index, long_route=long_route))
 
 
 def _seg_sorter16(device: torch.device, n: int, num_segments: int, key_type: int, order: int, value_bytes: int) -> SegmentedSort16:
     """The same cache rule for 16-bit keys: one ``SegmentedSort16`` handle per (device, stream, type, order, value width)."""
-    key = (16, device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
-    s = _seg_cache.get(key)
-    if s is None or s.max_keys < n or s.max_segments < num_segments:
-        if s is not None:
-            s.close()
-        cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
-        s = SegmentedSort16(cap(n), cap(num_segments), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes,
-                            device=device.index)
-        _seg_cache[key] = s
-    return s
+    return _cached(_seg_cache, (16,) + _on(device) + (key_type, order, value_bytes), {"max_keys": n, "max_segments": num_segments},
+                   lambda max_keys, max_segments: SegmentedSort16(_cap(max_keys), _cap(max_segments), order, key_type, _mode(value_bytes),
+                                                                  value_bytes, device=device.index))
 
 
 def _require_offsets(keys: torch.Tensor, offsets: torch.Tensor) -> None:
@@ -299,13 +291,13 @@ def _segmented_sort16_(keys: torch.Tensor, offsets: torch.Tensor, values: torch.
     """``segmented_sort_`` / ``segmented_argsort`` on 2-byte keys: one ``gs_segsort16_*`` call (``positions``: the argsort's output, made
     by the kernels inside the segments)."""
     _require_offsets(keys, offsets)
-    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
+    kt = _key_type(keys, unsigned, _KEY16_TYPE)
     vb = 4 if positions is not None else _values_width(keys, values)
     n = keys.numel()
     if n == 0:
         return
     with torch.cuda.device(keys.device):
-        s = _seg_sorter16(keys.device, n, offsets.numel() - 1, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb)
+        s = _seg_sorter16(keys.device, n, offsets.numel() - 1, kt, _order(descending), vb)
         if positions is not None:
             s.argsort(keys, offsets, positions, n=n, max_segment_len=max_segment_len)
         else:
@@ -323,27 +315,20 @@ def segmented_sort_(keys: torch.Tensor, offsets: torch.Tensor, values: torch.Ten
     (``SegmentedSort16``); that call never waits on the host anyway and ignores ``long_route``."""
     if long_route not in ("host", "device"):
         raise ValueError('long_route must be "host" or "device"')
-    if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
-        raise ValueError("keys must be a contiguous 1-D device tensor")
+    _require_1d_keys(keys)
     if keys.dtype in _KEY16_TYPE:
         return _segmented_sort16_(keys, offsets, values, descending, unsigned, max_segment_len)
     if keys.dtype not in _KEY_TYPE:
         raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys (int32, uint32, float32) and 16-bit keys "
                         "(float16, bfloat16, int16, uint16)")
     _require_offsets(keys, offsets)
-    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
-    vb = 0
-    if values is not None:
-        if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:
-            raise ValueError("values must match keys in shape and device and be contiguous")
-        vb = values.element_size()
-        if vb not in (4, 8):
-            raise TypeError("values must be 4 or 8 bytes wide")
+    kt = _key_type(keys, unsigned, _KEY_TYPE)
+    vb = _values_width(keys, values)
     n = keys.numel()
     if n == 0:
         return
     with torch.cuda.device(keys.device):
-        s = _seg_sorter(keys.device, n, offsets.numel() - 1, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, vb, long_route)
+        s = _seg_sorter(keys.device, n, offsets.numel() - 1, kt, _order(descending), vb, long_route)
         s.sort(keys.view(torch.int32) if keys.dtype != torch.int32 else keys, offsets, values, n=n, max_segment_len=max_segment_len)
 
 
@@ -364,8 +349,7 @@ def segmented_argsort(keys: torch.Tensor, offsets: torch.Tensor, descending: boo
     idx = torch.arange(keys.numel(), dtype=torch.int32, device=keys.device)
     k = keys.clone()
     if keys.dtype in _KEY16_TYPE:
-        if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
-            raise ValueError("keys must be a contiguous 1-D device tensor")
+        _require_1d_keys(keys)
         _segmented_sort16_(k, offsets, None, descending, unsigned, max_segment_len, positions=idx)
         return idx
     segmented_sort_(k, offsets, idx, descending, unsigned, max_segment_len, long_route)
@@ -376,17 +360,35 @@ def segmented_argsort(keys: torch.Tensor, offsets: torch.Tensor, descending: boo
 _topk_cache: dict = {}
 
 
+def _topk_of(cls, tag: tuple, device: torch.device, n: int, k: int, key_type: int, order: int, value_bytes: int):
+    # (max_k is capped by the capacity: k <= n)
+    return _cached(_topk_cache, tag + _on(device) + (key_type, order, value_bytes), {"max_keys": n, "max_k": k},
+                   lambda max_keys, max_k: cls(_cap(max_keys), min(_cap(max_k), _cap(max_keys)), order, key_type, _mode(value_bytes),
+                                               value_bytes, device=device.index))
+
+
 def _topk_handle(device: torch.device, n: int, k: int, key_type: int, order: int, value_bytes: int) -> TopK:
     """One cached handle per (device, stream, type, order, value width); re-created when n or k outgrow it."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
-    s = _topk_cache.get(key)
-    if s is None or s.max_keys < n or s.max_k < k:
-        if s is not None:
-            s.close()
-        cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
-        s = TopK(cap(n), min(cap(k), cap(n)), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes, device=device.index)
-        _topk_cache[key] = s
-    return s
+    return _topk_of(TopK, (), device, n, k, key_type, order, value_bytes)
+
+
+def _topk16_handle(device: torch.device, n: int, k: int, key_type: int, order: int, value_bytes: int) -> TopK16:
+    """The cache rule of ``_topk_handle`` for the 1-D selection on 16-bit keys."""
+    return _topk_of(TopK16, (16,), device, n, k, key_type, order, value_bytes)
+
+
+def _topk_1d(keys: torch.Tensor, k: int, largest: bool, values: torch.Tensor | None, kt: int, handle_for):
+    """``topk`` / ``topk16`` on a 1-D tensor behind their checks of the keys: ``kt`` is the key type of ``keys.dtype``."""
+    n, k = keys.numel(), int(k)
+    if not 1 <= k <= n:
+        raise ValueError("1 <= k <= n")
+    vb = _values_width(keys, values) or 4
+    out_k = torch.empty(k, dtype=keys.dtype, device=keys.device)
+    out_v = torch.empty(k, dtype=torch.int32 if values is None else values.dtype, device=keys.device)
+    with torch.cuda.device(keys.device):
+        s = handle_for(keys.device, n, k, kt, _order(largest), vb)
+        s.select(keys, k, out_k, values, out_v, n=n)
+    return out_k, out_v
 
 
 def topk(keys: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor | None = None, unsigned: bool = False):
@@ -400,30 +402,13 @@ def topk(keys: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor 
     largest"), ties by position (smallest: lowest positions first; largest: highest positions first).  The inputs are not written."""
     if keys.dim() == 2:
         return _topk_rows(keys, int(k), largest, values, unsigned)
-    if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
-        raise ValueError("keys must be a contiguous 1-D device tensor")
+    _require_1d_keys(keys)
     if keys.dtype in _KEY16_TYPE:
         raise TypeError(f"a 1-D {keys.dtype} tensor is not taken: 16-bit keys are selected row-wise, pass the 2-D form x[None, :] "
                         "(or call topk16, the 1-D selection on 16-bit keys)")
     if keys.dtype not in _KEY_TYPE:
         raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32)")
-    n, k = keys.numel(), int(k)
-    if not 1 <= k <= n:
-        raise ValueError("1 <= k <= n")
-    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
-    vb = 4
-    if values is not None:
-        if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:
-            raise ValueError("values must match keys in shape and device and be contiguous")
-        vb = values.element_size()
-        if vb not in (4, 8):
-            raise TypeError("values must be 4 or 8 bytes wide")
-    out_k = torch.empty(k, dtype=keys.dtype, device=keys.device)
-    out_v = torch.empty(k, dtype=torch.int32 if values is None else values.dtype, device=keys.device)
-    with torch.cuda.device(keys.device):
-        s = _topk_handle(keys.device, n, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
-        s.select(keys, k, out_k, values, out_v, n=n)
-    return out_k, out_v
+    return _topk_1d(keys, k, largest, values, _key_type(keys, unsigned, _KEY_TYPE), _topk_handle)
 
 
 def _topk_rows(keys: torch.Tensor, k: int, largest: bool, values: torch.Tensor | None, unsigned: bool):
@@ -440,10 +425,7 @@ def _topk_rows(keys: torch.Tensor, k: int, largest: bool, values: torch.Tensor |
     if keys.data_ptr() % 16:
         raise ValueError("the first row must start on a 16-byte boundary")
     stride = keys.stride(0) if rows > 1 else row_len
-    if key16:
-        kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
-    else:
-        kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
+    kt = _key_type(keys, unsigned, _KEY16_TYPE if key16 else _KEY_TYPE)
     vb = 4
     if values is not None:
         # (the row stride of a single row is never used)
@@ -462,22 +444,9 @@ def _topk_rows(keys: torch.Tensor, k: int, largest: bool, values: torch.Tensor |
     out_k = torch.empty((rows, k), dtype=keys.dtype, device=keys.device)
     out_v = torch.empty((rows, k), dtype=torch.int32 if values is None else values.dtype, device=keys.device)
     with torch.cuda.device(keys.device):
-        s = _topk_handle(keys.device, (rows - 1) * stride + row_len, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
+        s = _topk_handle(keys.device, (rows - 1) * stride + row_len, k, kt, _order(largest), vb)
         s.select_rows(keys, rows, row_len, stride, k, out_k, values, out_v)
     return out_k, out_v
-
-
-def _topk16_handle(device: torch.device, n: int, k: int, key_type: int, order: int, value_bytes: int) -> TopK16:
-    """The cache rule of ``_topk_handle`` for the 1-D selection on 16-bit keys."""
-    key = (16, device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
-    s = _topk_cache.get(key)
-    if s is None or s.max_keys < n or s.max_k < k:
-        if s is not None:
-            s.close()
-        cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
-        s = TopK16(cap(n), min(cap(k), cap(n)), order, key_type, MODE_PAIRS if value_bytes else MODE_KEYS_ONLY, value_bytes, device=device.index)
-        _topk_cache[key] = s
-    return s
 
 
 def topk16(keys: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor | None = None, unsigned: bool = False):
@@ -490,25 +459,8 @@ def topk16(keys: torch.Tensor, k: int, largest: bool = True, values: torch.Tenso
         return _topk_rows(keys, int(k), largest, values, unsigned)
     if keys.dtype not in _KEY16_TYPE:
         raise TypeError(f"unsupported key dtype {keys.dtype}: topk16 takes 16-bit keys (float16, bfloat16, int16, uint16); 32-bit keys go to topk")
-    if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
-        raise ValueError("keys must be a contiguous 1-D device tensor")
-    n, k = keys.numel(), int(k)
-    if not 1 <= k <= n:
-        raise ValueError("1 <= k <= n")
-    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
-    vb = 4
-    if values is not None:
-        if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:
-            raise ValueError("values must match keys in shape and device and be contiguous")
-        vb = values.element_size()
-        if vb not in (4, 8):
-            raise TypeError("values must be 4 or 8 bytes wide")
-    out_k = torch.empty(k, dtype=keys.dtype, device=keys.device)
-    out_v = torch.empty(k, dtype=torch.int32 if values is None else values.dtype, device=keys.device)
-    with torch.cuda.device(keys.device):
-        s = _topk16_handle(keys.device, n, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
-        s.select(keys, k, out_k, values, out_v, n=n)
-    return out_k, out_v
+    _require_1d_keys(keys)
+    return _topk_1d(keys, k, largest, values, _key_type(keys, unsigned, _KEY16_TYPE), _topk16_handle)
 
 
 # ---- segmented top-k ----------------------------------------------------------------------------------------------------------
@@ -518,16 +470,10 @@ _segtopk_cache: dict = {}
 def _segtopk_handle(device: torch.device, n: int, num_segments: int, k: int, key_type: int, order: int, value_bytes: int) -> SegmentedTopK:
     """One cached handle per (device, stream, type, order, value width); re-created when n, the segments or k outgrow it.  A 16-bit
     key type gets a ``SegmentedTopK16``."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
-    s = _segtopk_cache.get(key)
-    if s is None or s.max_keys < n or s.max_segments < num_segments or s.max_k < k:
-        if s is not None:
-            s.close()
-        cap = lambda x, low: min(1 << max(int(x - 1).bit_length(), low), (1 << 30) - 1)  # noqa: E731
-        cls = SegmentedTopK16 if key_type in _KEY16_TYPE.values() else SegmentedTopK
-        s = cls(cap(n, 16), cap(num_segments, 16), cap(k, 6), order, key_type, MODE_PAIRS, value_bytes, device=device.index)
-        _segtopk_cache[key] = s
-    return s
+    cls = SegmentedTopK16 if key_type in _KEY16_TYPE.values() else SegmentedTopK
+    return _cached(_segtopk_cache, _on(device) + (key_type, order, value_bytes), {"max_keys": n, "max_segments": num_segments, "max_k": k},
+                   lambda max_keys, max_segments, max_k: cls(_cap(max_keys), _cap(max_segments), _cap(max_k, 6), order, key_type, MODE_PAIRS,
+                                                             value_bytes, device=device.index))
 
 
 def segmented_topk(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor | None = None,
@@ -540,13 +486,11 @@ def segmented_topk(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: b
     knows one, 0 = unknown; a segment longer than LDS holds takes ``k <= rows_max_k`` (4096), so a larger ``k`` needs a bound that
     fits LDS (``ValueError`` otherwise).  The result is the head of ``segmented_sort``: floats by the order-preserving bit flip, ties
     by position (smallest: lowest positions first; largest: highest positions first).  The inputs are not written."""
-    if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
-        raise ValueError("keys must be a contiguous 1-D device tensor")
+    _require_1d_keys(keys)
     if keys.dtype not in _KEY_TYPE:
         raise TypeError(f"unsupported key dtype {keys.dtype}: 32-bit keys only (int32, uint32, float32); "
                         "float16, bfloat16, int16 and uint16 keys: segmented_topk16")
-    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
-    return _segmented_topk(keys, offsets, k, largest, values, kt, max_segment_len)
+    return _segmented_topk(keys, offsets, k, largest, values, _key_type(keys, unsigned, _KEY_TYPE), max_segment_len)
 
 
 def segmented_topk16(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: bool = True, values: torch.Tensor | None = None,
@@ -558,10 +502,8 @@ def segmented_topk16(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest:
     if keys.dtype not in _KEY16_TYPE:
         raise TypeError(f"unsupported key dtype {keys.dtype}: 16-bit keys only (float16, bfloat16, int16, uint16); "
                         "int32, uint32 and float32 keys: segmented_topk")
-    if keys.dim() != 1 or not keys.is_contiguous() or keys.device.type != "cuda":
-        raise ValueError("keys must be a contiguous 1-D device tensor")
-    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
-    return _segmented_topk(keys, offsets, k, largest, values, kt, max_segment_len)
+    _require_1d_keys(keys)
+    return _segmented_topk(keys, offsets, k, largest, values, _key_type(keys, unsigned, _KEY16_TYPE), max_segment_len)
 
 
 def _segmented_topk(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: bool, values: torch.Tensor | None, kt: int, max_segment_len: int):
@@ -570,13 +512,7 @@ def _segmented_topk(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: 
     n, k, segs = keys.numel(), int(k), offsets.numel() - 1
     if k < 1:
         raise ValueError("k >= 1")
-    vb = 4
-    if values is not None:
-        if values.shape != keys.shape or not values.is_contiguous() or values.device != keys.device:
-            raise ValueError("values must match keys in shape and device and be contiguous")
-        vb = values.element_size()
-        if vb not in (4, 8):
-            raise TypeError("values must be 4 or 8 bytes wide")
+    vb = _values_width(keys, values) or 4
     max_segment_len = int(max_segment_len)
     lds_len, max_k = _lib.load().gs_segsort_max_lds_segment(MODE_PAIRS, vb), rows_max_k(MODE_PAIRS, vb)
     if k > max_k and not 0 < max_segment_len <= lds_len:
@@ -591,36 +527,101 @@ def _segmented_topk(keys: torch.Tensor, offsets: torch.Tensor, k: int, largest: 
     if n == 0:
         return out_k, out_v, counts
     with torch.cuda.device(keys.device):
-        s = _segtopk_handle(keys.device, n, segs, k, kt, ORDER_DESCENDING if largest else ORDER_ASCENDING, vb)
+        s = _segtopk_handle(keys.device, n, segs, k, kt, _order(largest), vb)
         s.select(keys, offsets, k, out_k, values, out_v, n=n, max_segment_len=max_segment_len)
     return out_k, out_v, counts
 
 
-# ---- unique / run-length encode -------------------------------------------------------------------------------------------------
+# ---- unique / run-length encode and reduce by key: 32-, 16- and 64-bit keys -------------------------------------------------------
 _unique_cache: dict = {}
+_unique16_cache: dict = {}
+_unique64_cache: dict = {}
+_reduce_cache: dict = {}
+_reduce64_cache: dict = {}
+_WIDE_KEYS = {"16": "16-bit keys (float16, bfloat16, int16, uint16)", "64": "64-bit keys (int64, uint64, float64)"}
+
+
+def _sized_by_keys(cache: dict, cls, device: torch.device, n: int, key_type: int, order: int, *rest, **named):
+    """The cache rule of ``_sorter`` for a family sized by ``max_keys`` alone: one handle per (device, stream, type, order, ``rest``
+    or ``named``: the family's own argument), built as ``cls(max_keys, order, key_type, *rest, **named, device=...)``."""
+    return _cached(cache, _on(device) + (key_type, order) + rest + tuple(named.values()), {"max_keys": n},
+                   lambda max_keys: cls(_cap(max_keys), order, key_type, *rest, **named, device=device.index))
 
 
 def _unique_handle(device: torch.device, n: int, key_type: int, order: int, positions: bool) -> Unique:
-    """The cache rule of ``_sorter``: one ``Unique`` handle per (device, stream, type, order, with positions); re-created when the
-    size outgrows it."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, positions)
-    s = _unique_cache.get(key)
-    if s is None or s.max_keys < n:
-        if s is not None:
-            s.close()
-        cap = 1 << max(int(n - 1).bit_length(), 16)
-        s = Unique(min(cap, (1 << 30) - 1), order, key_type, positions=positions, device=device.index)
-        _unique_cache[key] = s
-    return s
+    """One ``Unique`` handle per (device, stream, type, order, with positions); re-created when the size outgrows it."""
+    return _sized_by_keys(_unique_cache, Unique, device, n, key_type, order, positions=positions)
 
 
-def _require_unique_keys(keys: torch.Tensor) -> None:
+def _unique64_handle(device: torch.device, n: int, key_type: int, order: int, positions: bool) -> Unique64:
+    """The cache rule of ``_unique_handle`` for the 64-bit keys."""
+    return _sized_by_keys(_unique64_cache, Unique64, device, n, key_type, order, positions=positions)
+
+
+def _unique16_handle(device: torch.device, n: int, key_type: int, order: int) -> Unique16:
+    """The cache rule of ``_unique_handle`` for the 16-bit keys: one ``Unique16`` handle per (device, stream, type, order); re-created
+    when the size outgrows it (its scratch does not grow with the size)."""
+    return _sized_by_keys(_unique16_cache, Unique16, device, n, key_type, order)
+
+
+def _reduce_handle(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> ReduceByKey:
+    """One ``ReduceByKey`` handle per (device, stream, type, order, value width); re-created when the size outgrows it."""
+    return _sized_by_keys(_reduce_cache, ReduceByKey, device, n, key_type, order, value_bytes)
+
+
+def _reduce64_handle(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> ReduceByKey64:
+    """The cache rule of ``_reduce_handle`` for the 64-bit keys."""
+    return _sized_by_keys(_reduce64_cache, ReduceByKey64, device, n, key_type, order, value_bytes)
+
+
+def _takes(name: str) -> str:
+    """What a frontend of the 16- or 64-bit keys says it takes: ``name`` ends in the width, and without it names the 32-bit one."""
+    return f"{name} takes {_WIDE_KEYS[name[-2:]]}; 32-bit keys go to {name[:-2]}"
+
+
+def _require_unique_keys(keys: torch.Tensor, table: dict = _KEY_TYPE, takes: str = "unique takes 32-bit keys (int32, uint32, float32)") -> None:
     if keys.dim() != 1:
         raise ValueError("keys must be a contiguous 1-D device tensor")
-    if keys.dtype not in _KEY_TYPE:
-        raise TypeError(f"unsupported key dtype {keys.dtype}: unique takes 32-bit keys (int32, uint32, float32)")
+    if keys.dtype not in table:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: {takes}")
     if not keys.is_contiguous() or keys.device.type != "cuda":
         raise ValueError("keys must be a contiguous 1-D device tensor")
+
+
+def _unique_outputs(keys: torch.Tensor, run, return_inverse: bool, return_counts: bool, return_index: bool = False):
+    """What every ``unique*`` frontend returns: ``run(n)`` makes ``(out_keys, out_counts, out_first, out_inverse, num)`` (None where
+    not asked for) on the keys' device; the outputs are sliced to their length (the one wait on the host) and put in torch's order."""
+    n = keys.numel()
+    if n == 0:
+        empty = lambda: torch.empty(0, dtype=torch.int32, device=keys.device)  # noqa: E731
+        out = (keys.clone(),) + ((empty(),) if return_inverse else ()) + ((empty(),) if return_counts else ()) + ((empty(),) if return_index else ())
+        return out[0] if len(out) == 1 else out
+    with torch.cuda.device(keys.device):
+        out_k, out_c, out_f, out_i, num = run(n)
+    u = int(num.item())
+    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ()) + ((out_f[:u],) if return_index else ())
+    return out[0] if len(out) == 1 else out
+
+
+def _unique_sorted(keys: torch.Tensor, handle_for, kt: int, descending: bool, return_inverse: bool, return_counts: bool, return_index: bool):
+    """``unique`` / ``unique64`` behind their checks of the keys: a handle with positions only where the inverse or the index is asked for."""
+    positions = return_inverse or return_index
+
+    def run(n):
+        s = handle_for(keys.device, n, kt, _order(descending), positions)
+        if positions:
+            return s.unique_positions(keys, n, counts=return_counts, first=return_index, inverse=return_inverse)
+        out_k, out_c, num = s.unique(keys, n, counts=return_counts)
+        return out_k, out_c, None, None, num
+    return _unique_outputs(keys, run, return_inverse, return_counts, return_index)
+
+
+def _unique_runs(keys: torch.Tensor, handle, return_inverse: bool, return_counts: bool):
+    """``unique_consecutive*`` behind their checks of the keys: ``handle(n)`` is the family's handle (key type and order play no part)."""
+    def run(n):
+        out_k, out_c, out_i, num = handle(n).unique_consecutive(keys, n, counts=return_counts, inverse=return_inverse)
+        return out_k, out_c, None, out_i, num
+    return _unique_outputs(keys, run, return_inverse, return_counts)
 
 
 def unique(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False, return_index: bool = False, descending: bool = False,
@@ -634,23 +635,7 @@ def unique(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool
     values.  On integers the result equals ``torch.unique``'s.  Slicing the outputs to their length is the one wait on the host, as in
     ``torch.unique``.  ``keys`` is not written."""
     _require_unique_keys(keys)
-    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
-    n = keys.numel()
-    positions = return_inverse or return_index
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int32, device=keys.device)
-        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ()) + ((e.clone(),) if return_index else ())
-        return out[0] if len(out) == 1 else out
-    with torch.cuda.device(keys.device):
-        s = _unique_handle(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, positions)
-        if positions:
-            out_k, out_c, out_f, out_i, num = s.unique_positions(keys, n, counts=return_counts, first=return_index, inverse=return_inverse)
-        else:
-            out_k, out_c, num = s.unique(keys, n, counts=return_counts)
-            out_f = out_i = None
-    u = int(num.item())
-    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ()) + ((out_f[:u],) if return_index else ())
-    return out[0] if len(out) == 1 else out
+    return _unique_sorted(keys, _unique_handle, _key_type(keys, unsigned, _KEY_TYPE), descending, return_inverse, return_counts, return_index)
 
 
 def unique_consecutive(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False):
@@ -658,50 +643,35 @@ def unique_consecutive(keys: torch.Tensor, return_inverse: bool = False, return_
     the input as it lies (no sort): returns ``output`` or ``(output[, inverse][, counts])`` with int32 ``inverse`` (the run of every
     input) and ``counts`` (the runs' lengths).  One wait on the host, for the length.  ``keys`` is not written."""
     _require_unique_keys(keys)
-    n = keys.numel()
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int32, device=keys.device)
-        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ())
-        return out[0] if len(out) == 1 else out
-    with torch.cuda.device(keys.device):
-        s = _unique_handle(keys.device, n, KEY_UINT32, ORDER_ASCENDING, False)
-        out_k, out_c, out_i, num = s.unique_consecutive(keys, n, counts=return_counts, inverse=return_inverse)
-    u = int(num.item())
-    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ())
-    return out[0] if len(out) == 1 else out
+    return _unique_runs(keys, lambda n: _unique_handle(keys.device, n, KEY_UINT32, ORDER_ASCENDING, False), return_inverse, return_counts)
 
 
-# ---- reduce by key ------------------------------------------------------------------------------------------------------------------
-_reduce_cache: dict = {}
-
-
-def _reduce_handle(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> ReduceByKey:
-    """The cache rule of ``_unique_handle``: one ``ReduceByKey`` handle per (device, stream, type, order, value width); re-created when
-    the size outgrows it."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
-    s = _reduce_cache.get(key)
-    if s is None or s.max_keys < n:
-        if s is not None:
-            s.close()
-        cap = 1 << max(int(n - 1).bit_length(), 16)
-        s = ReduceByKey(min(cap, (1 << 30) - 1), order, key_type, value_bytes, device=device.index)
-        _reduce_cache[key] = s
-    return s
-
-
-def _require_reduce_args(keys: torch.Tensor, values: torch.Tensor, op: str):
+def _require_reduce_args(keys: torch.Tensor, values: torch.Tensor, op: str, table: dict = _KEY_TYPE, name: str = "reduce_by_key",
+                         takes: str = "reduce_by_key takes 32-bit keys (int32, uint32, float32)"):
     if keys.dim() != 1 or values.dim() != 1 or keys.numel() != values.numel():
         raise ValueError("keys and values must be contiguous 1-D device tensors of one length")
-    if keys.dtype not in _KEY_TYPE:
-        raise TypeError(f"unsupported key dtype {keys.dtype}: reduce_by_key takes 32-bit keys (int32, uint32, float32)")
+    if keys.dtype not in table:
+        raise TypeError(f"unsupported key dtype {keys.dtype}: {takes}")
     vt = _torch_value_types().get(values.dtype)
     if vt is None:
-        raise TypeError(f"unsupported value dtype {values.dtype}: reduce_by_key takes int32, uint32, float32, int64, uint64 or float64 values")
+        raise TypeError(f"unsupported value dtype {values.dtype}: {name} takes int32, uint32, float32, int64, uint64 or float64 values")
     if op not in _REDUCE_OPS:
         raise ValueError('op is "sum", "min" or "max"')
     if not keys.is_contiguous() or not values.is_contiguous() or keys.device.type != "cuda" or values.device != keys.device:
         raise ValueError("keys and values must be contiguous 1-D device tensors of one length")
     return vt, _REDUCE_OPS[op]
+
+
+def _reduce_outputs(keys: torch.Tensor, values: torch.Tensor, run, return_counts: bool):
+    """What every ``reduce_by_key*`` frontend returns: ``run(n)`` makes ``(out_keys, out_values, out_counts | None, num)`` on the keys'
+    device; the outputs are sliced to their length (the one wait on the host)."""
+    n = keys.numel()
+    if n == 0:
+        return (keys.clone(), values.clone()) + ((torch.empty(0, dtype=torch.int32, device=keys.device),) if return_counts else ())
+    with torch.cuda.device(keys.device):
+        out_k, out_v, out_c, num = run(n)
+    u = int(num.item())
+    return (out_k[:u], out_v[:u]) + ((out_c[:u],) if return_counts else ())
 
 
 def reduce_by_key(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", descending: bool = False, return_counts: bool = False,
@@ -716,58 +686,17 @@ def reduce_by_key(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", des
     them.  A float "sum" is combined in an order fixed by the data: two calls give bitwise identical results (``index_add_`` does not),
     but not the left-to-right sum.  One wait on the host, for the length.  Neither input is written."""
     vt, opc = _require_reduce_args(keys, values, op)
-    kt = KEY_UINT32 if (unsigned and keys.dtype == torch.int32) else _KEY_TYPE[keys.dtype]
-    n = keys.numel()
-    if n == 0:
-        out = (keys.clone(), values.clone()) + ((torch.empty(0, dtype=torch.int32, device=keys.device),) if return_counts else ())
-        return out
-    with torch.cuda.device(keys.device):
-        s = _reduce_handle(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, values.element_size())
-        out_k, out_v, out_c, num = s.reduce_by_key(keys, values, opc, vt, n, counts=return_counts)
-    u = int(num.item())
-    return (out_k[:u], out_v[:u]) + ((out_c[:u],) if return_counts else ())
+    kt = _key_type(keys, unsigned, _KEY_TYPE)
+    return _reduce_outputs(keys, values, lambda n: _reduce_handle(keys.device, n, kt, _order(descending), values.element_size())
+                           .reduce_by_key(keys, values, opc, vt, n, counts=return_counts), return_counts)
 
 
 def reduce_by_key_consecutive(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", return_counts: bool = False):
     """``reduce_by_key`` on the input as it lies (no sort): one ``op`` of ``values`` per run of BITWISE-equal neighbouring keys, as thrust's
     ``reduce_by_key``: ``(runs, reduced[, counts])``.  One wait on the host, for the length.  Neither input is written."""
     vt, opc = _require_reduce_args(keys, values, op)
-    n = keys.numel()
-    if n == 0:
-        return (keys.clone(), values.clone()) + ((torch.empty(0, dtype=torch.int32, device=keys.device),) if return_counts else ())
-    with torch.cuda.device(keys.device):
-        s = _reduce_handle(keys.device, n, KEY_UINT32, ORDER_ASCENDING, values.element_size())
-        out_k, out_v, out_c, num = s.reduce_by_key_consecutive(keys, values, opc, vt, n, counts=return_counts)
-    u = int(num.item())
-    return (out_k[:u], out_v[:u]) + ((out_c[:u],) if return_counts else ())
-
-
-# ---- unique / run-length encode on 16-bit keys -----------------------------------------------------------------------------------
-_unique16_cache: dict = {}
-
-
-def _unique16_handle(device: torch.device, n: int, key_type: int, order: int) -> Unique16:
-    """The cache rule of ``_unique_handle`` for the 16-bit keys: one ``Unique16`` handle per (device, stream, type, order); re-created
-    when the size outgrows it (its scratch does not grow with the size)."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order)
-    s = _unique16_cache.get(key)
-    if s is None or s.max_keys < n:
-        if s is not None:
-            s.close()
-        cap = 1 << max(int(n - 1).bit_length(), 16)
-        s = Unique16(min(cap, (1 << 30) - 1), order, key_type, device=device.index)
-        _unique16_cache[key] = s
-    return s
-
-
-def _require_unique16_keys(keys: torch.Tensor, name: str) -> None:
-    if keys.dim() != 1:
-        raise ValueError("keys must be a contiguous 1-D device tensor")
-    if keys.dtype not in _KEY16_TYPE:
-        raise TypeError(f"unsupported key dtype {keys.dtype}: {name} takes 16-bit keys (float16, bfloat16, int16, uint16); 32-bit keys go to "
-                        f"{'unique_consecutive' if 'consecutive' in name else 'unique'}")
-    if not keys.is_contiguous() or keys.device.type != "cuda":
-        raise ValueError("keys must be a contiguous 1-D device tensor")
+    return _reduce_outputs(keys, values, lambda n: _reduce_handle(keys.device, n, KEY_UINT32, ORDER_ASCENDING, values.element_size())
+                           .reduce_by_key_consecutive(keys, values, opc, vt, n, counts=return_counts), return_counts)
 
 
 def unique16(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False, return_index: bool = False, descending: bool = False,
@@ -778,82 +707,19 @@ def unique16(keys: torch.Tensor, return_inverse: bool = False, return_counts: bo
     element), as ``unique`` does.  Equality is BITWISE and the order is this library's 16-bit sort: ``-0.0`` and ``+0.0`` are two
     elements (``-0.0`` first) and every NaN bit pattern is an element of its own.  Slicing the outputs to their length is the one wait
     on the host.  ``keys`` is not written.  Other dtypes are a ``TypeError``: see ``unique``."""
-    _require_unique16_keys(keys, "unique16")
-    kt = KEY_UINT16 if (unsigned and keys.dtype == torch.int16) else _KEY16_TYPE[keys.dtype]
-    n = keys.numel()
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int32, device=keys.device)
-        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ()) + ((e.clone(),) if return_index else ())
-        return out[0] if len(out) == 1 else out
-    with torch.cuda.device(keys.device):
-        s = _unique16_handle(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING)
-        out_k, out_c, out_f, out_i, num = s.unique(keys, n, counts=return_counts, first=return_index, inverse=return_inverse)
-    u = int(num.item())
-    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ()) + ((out_f[:u],) if return_index else ())
-    return out[0] if len(out) == 1 else out
+    _require_unique_keys(keys, _KEY16_TYPE, _takes("unique16"))
+    kt = _key_type(keys, unsigned, _KEY16_TYPE)
+    return _unique_outputs(keys, lambda n: _unique16_handle(keys.device, n, kt, _order(descending))
+                           .unique(keys, n, counts=return_counts, first=return_index, inverse=return_inverse),
+                           return_inverse, return_counts, return_index)
 
 
 def unique_consecutive16(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False):
     """``unique_consecutive`` for a 1-D contiguous tensor of 16-bit keys: one element per run of BITWISE-equal neighbours of the input as
     it lies (no sort): returns ``output`` or ``(output[, inverse][, counts])`` with int32 ``inverse`` and ``counts``.  One wait on the
     host, for the length.  ``keys`` is not written.  Other dtypes are a ``TypeError``: see ``unique_consecutive``."""
-    _require_unique16_keys(keys, "unique_consecutive16")
-    n = keys.numel()
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int32, device=keys.device)
-        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ())
-        return out[0] if len(out) == 1 else out
-    with torch.cuda.device(keys.device):
-        s = _unique16_handle(keys.device, n, KEY_UINT16, ORDER_ASCENDING)
-        out_k, out_c, out_i, num = s.unique_consecutive(keys, n, counts=return_counts, inverse=return_inverse)
-    u = int(num.item())
-    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ())
-    return out[0] if len(out) == 1 else out
-
-
-# ---- unique / run-length encode and reduce by key on 64-bit keys ------------------------------------------------------------------
-_KEY64_TYPE = {torch.int64: KEY_INT64, torch.float64: KEY_FLOAT64}
-if hasattr(torch, "uint64"):
-    _KEY64_TYPE[torch.uint64] = KEY_UINT64
-_unique64_cache: dict = {}
-_reduce64_cache: dict = {}
-
-
-def _unique64_handle(device: torch.device, n: int, key_type: int, order: int, positions: bool) -> Unique64:
-    """The cache rule of ``_unique_handle`` for the 64-bit keys: one ``Unique64`` handle per (device, stream, type, order, with
-    positions); re-created when the size outgrows it."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, positions)
-    s = _unique64_cache.get(key)
-    if s is None or s.max_keys < n:
-        if s is not None:
-            s.close()
-        cap = 1 << max(int(n - 1).bit_length(), 16)
-        s = Unique64(min(cap, (1 << 30) - 1), order, key_type, positions=positions, device=device.index)
-        _unique64_cache[key] = s
-    return s
-
-
-def _reduce64_handle(device: torch.device, n: int, key_type: int, order: int, value_bytes: int) -> ReduceByKey64:
-    """The cache rule of ``_reduce_handle`` for the 64-bit keys."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, value_bytes)
-    s = _reduce64_cache.get(key)
-    if s is None or s.max_keys < n:
-        if s is not None:
-            s.close()
-        cap = 1 << max(int(n - 1).bit_length(), 16)
-        s = ReduceByKey64(min(cap, (1 << 30) - 1), order, key_type, value_bytes, device=device.index)
-        _reduce64_cache[key] = s
-    return s
-
-
-def _require_unique64_keys(keys: torch.Tensor, name: str) -> None:
-    if keys.dim() != 1:
-        raise ValueError("keys must be a contiguous 1-D device tensor")
-    if keys.dtype not in _KEY64_TYPE:
-        raise TypeError(f"unsupported key dtype {keys.dtype}: {name} takes 64-bit keys (int64, uint64, float64); 32-bit keys go to "
-                        f"{name[:-2]}")
-    if not keys.is_contiguous() or keys.device.type != "cuda":
-        raise ValueError("keys must be a contiguous 1-D device tensor")
+    _require_unique_keys(keys, _KEY16_TYPE, _takes("unique_consecutive16"))
+    return _unique_runs(keys, lambda n: _unique16_handle(keys.device, n, KEY_UINT16, ORDER_ASCENDING), return_inverse, return_counts)
 
 
 def unique64(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False, return_index: bool = False, descending: bool = False,
@@ -865,58 +731,16 @@ def unique64(keys: torch.Tensor, return_inverse: bool = False, return_counts: bo
     ``+0.0`` are two elements (``-0.0`` first) and every NaN bit pattern is an element of its own; on integers the result equals
     ``torch.unique``'s.  Keys below 2^32 (ids) cost the sort four passes, not eight.  Slicing the outputs to their length is the one wait
     on the host.  ``keys`` is not written.  Other dtypes are a ``TypeError``: see ``unique``."""
-    _require_unique64_keys(keys, "unique64")
-    kt = KEY_UINT64 if (unsigned and keys.dtype == torch.int64) else _KEY64_TYPE[keys.dtype]
-    n = keys.numel()
-    positions = return_inverse or return_index
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int32, device=keys.device)
-        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ()) + ((e.clone(),) if return_index else ())
-        return out[0] if len(out) == 1 else out
-    with torch.cuda.device(keys.device):
-        s = _unique64_handle(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, positions)
-        if positions:
-            out_k, out_c, out_f, out_i, num = s.unique_positions(keys, n, counts=return_counts, first=return_index, inverse=return_inverse)
-        else:
-            out_k, out_c, num = s.unique(keys, n, counts=return_counts)
-            out_f = out_i = None
-    u = int(num.item())
-    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ()) + ((out_f[:u],) if return_index else ())
-    return out[0] if len(out) == 1 else out
+    _require_unique_keys(keys, _KEY64_TYPE, _takes("unique64"))
+    return _unique_sorted(keys, _unique64_handle, _key_type(keys, unsigned, _KEY64_TYPE), descending, return_inverse, return_counts, return_index)
 
 
 def unique_consecutive64(keys: torch.Tensor, return_inverse: bool = False, return_counts: bool = False):
     """``unique_consecutive`` for a 1-D contiguous tensor of 64-bit keys: one element per run of BITWISE-equal neighbours of the input as
     it lies (no sort): returns ``output`` or ``(output[, inverse][, counts])`` with int32 ``inverse`` and ``counts``.  One wait on the
     host, for the length.  ``keys`` is not written.  Other dtypes are a ``TypeError``: see ``unique_consecutive``."""
-    _require_unique64_keys(keys, "unique_consecutive64")
-    n = keys.numel()
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int32, device=keys.device)
-        out = (keys.clone(),) + ((e,) if return_inverse else ()) + ((e.clone(),) if return_counts else ())
-        return out[0] if len(out) == 1 else out
-    with torch.cuda.device(keys.device):
-        s = _unique64_handle(keys.device, n, KEY_UINT64, ORDER_ASCENDING, False)
-        out_k, out_c, out_i, num = s.unique_consecutive(keys, n, counts=return_counts, inverse=return_inverse)
-    u = int(num.item())
-    out = (out_k[:u],) + ((out_i,) if return_inverse else ()) + ((out_c[:u],) if return_counts else ())
-    return out[0] if len(out) == 1 else out
-
-
-def _require_reduce64_args(keys: torch.Tensor, values: torch.Tensor, op: str, name: str):
-    if keys.dim() != 1 or values.dim() != 1 or keys.numel() != values.numel():
-        raise ValueError("keys and values must be contiguous 1-D device tensors of one length")
-    if keys.dtype not in _KEY64_TYPE:
-        raise TypeError(f"unsupported key dtype {keys.dtype}: {name} takes 64-bit keys (int64, uint64, float64); 32-bit keys go to "
-                        f"{name[:-2]}")
-    vt = _torch_value_types().get(values.dtype)
-    if vt is None:
-        raise TypeError(f"unsupported value dtype {values.dtype}: {name} takes int32, uint32, float32, int64, uint64 or float64 values")
-    if op not in _REDUCE_OPS:
-        raise ValueError('op is "sum", "min" or "max"')
-    if not keys.is_contiguous() or not values.is_contiguous() or keys.device.type != "cuda" or values.device != keys.device:
-        raise ValueError("keys and values must be contiguous 1-D device tensors of one length")
-    return vt, _REDUCE_OPS[op]
+    _require_unique_keys(keys, _KEY64_TYPE, _takes("unique_consecutive64"))
+    return _unique_runs(keys, lambda n: _unique64_handle(keys.device, n, KEY_UINT64, ORDER_ASCENDING, False), return_inverse, return_counts)
 
 
 def reduce_by_key64(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", descending: bool = False, return_counts: bool = False,
@@ -928,30 +752,18 @@ def reduce_by_key64(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", d
     gather and no atomics.  The operations are ``reduce_by_key``'s: integer sums wrap, "min" / "max" on floats use this library's total
     order (UNLIKE ``torch.amin`` / ``amax`` and ``fmin`` / ``fmax``), a float "sum" is reproducible bit for bit but not the
     left-to-right sum.  One wait on the host, for the length.  Neither input is written."""
-    vt, opc = _require_reduce64_args(keys, values, op, "reduce_by_key64")
-    kt = KEY_UINT64 if (unsigned and keys.dtype == torch.int64) else _KEY64_TYPE[keys.dtype]
-    n = keys.numel()
-    if n == 0:
-        return (keys.clone(), values.clone()) + ((torch.empty(0, dtype=torch.int32, device=keys.device),) if return_counts else ())
-    with torch.cuda.device(keys.device):
-        s = _reduce64_handle(keys.device, n, kt, ORDER_DESCENDING if descending else ORDER_ASCENDING, values.element_size())
-        out_k, out_v, out_c, num = s.reduce_by_key(keys, values, opc, vt, n, counts=return_counts)
-    u = int(num.item())
-    return (out_k[:u], out_v[:u]) + ((out_c[:u],) if return_counts else ())
+    vt, opc = _require_reduce_args(keys, values, op, _KEY64_TYPE, "reduce_by_key64", _takes("reduce_by_key64"))
+    kt = _key_type(keys, unsigned, _KEY64_TYPE)
+    return _reduce_outputs(keys, values, lambda n: _reduce64_handle(keys.device, n, kt, _order(descending), values.element_size())
+                           .reduce_by_key(keys, values, opc, vt, n, counts=return_counts), return_counts)
 
 
 def reduce_by_key_consecutive64(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", return_counts: bool = False):
     """``reduce_by_key_consecutive`` for 64-bit keys: one ``op`` of ``values`` per run of BITWISE-equal neighbouring keys of the input as
     it lies (no sort): ``(runs, reduced[, counts])``.  One wait on the host, for the length.  Neither input is written."""
-    vt, opc = _require_reduce64_args(keys, values, op, "reduce_by_key_consecutive64")
-    n = keys.numel()
-    if n == 0:
-        return (keys.clone(), values.clone()) + ((torch.empty(0, dtype=torch.int32, device=keys.device),) if return_counts else ())
-    with torch.cuda.device(keys.device):
-        s = _reduce64_handle(keys.device, n, KEY_UINT64, ORDER_ASCENDING, values.element_size())
-        out_k, out_v, out_c, num = s.reduce_by_key_consecutive(keys, values, opc, vt, n, counts=return_counts)
-    u = int(num.item())
-    return (out_k[:u], out_v[:u]) + ((out_c[:u],) if return_counts else ())
+    vt, opc = _require_reduce_args(keys, values, op, _KEY64_TYPE, "reduce_by_key_consecutive64", _takes("reduce_by_key_consecutive64"))
+    return _reduce_outputs(keys, values, lambda n: _reduce64_handle(keys.device, n, KEY_UINT64, ORDER_ASCENDING, values.element_size())
+                           .reduce_by_key_consecutive(keys, values, opc, vt, n, counts=return_counts), return_counts)
 
 
 # ---- sorted search: the lower / upper bound of many queries ------------------------------------------------------------------------
@@ -959,17 +771,15 @@ _search_cache: dict = {}
 
 
 def _search_handle(device: torch.device, n: int, m: int, key_type: int, order: int, sort_queries: bool) -> SortedSearch:
-    """One ``SortedSearch`` handle per (device, stream, type, order, with the query sorter); re-created when a size outgrows it."""
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream), key_type, order, sort_queries)
-    s = _search_cache.get(key)
-    if s is None or s.max_keys < n or s.max_queries < m:
-        if s is not None:
-            n, m = max(n, s.max_keys), max(m, s.max_queries)
-            s.close()
-        cap = lambda x: min(1 << max(int(x - 1).bit_length(), 16), (1 << 30) - 1)  # noqa: E731
-        s = SortedSearch(cap(n), cap(m), key_type, order, sort_queries=sort_queries, device=device.index)
-        _search_cache[key] = s
-    return s
+    """One ``SortedSearch`` handle per (device, stream, type, order, with the query sorter); re-created when a size outgrows it, and
+    then at no less than it had: a call with many keys and few queries and one the other way round share a handle."""
+    key = _on(device) + (key_type, order, sort_queries)
+    old = _search_cache.get(key)
+    if old is not None:
+        n, m = max(n, old.max_keys), max(m, old.max_queries)
+    return _cached(_search_cache, key, {"max_keys": n, "max_queries": m},
+                   lambda max_keys, max_queries: SortedSearch(_cap(max_keys), _cap(max_queries), key_type, order, sort_queries=sort_queries,
+                                                              device=device.index))
 
 
 def searchsorted(sorted_keys: torch.Tensor, queries: torch.Tensor, right: bool = False, descending: bool = False, queries_sorted: bool = False,
@@ -988,21 +798,17 @@ def searchsorted(sorted_keys: torch.Tensor, queries: torch.Tensor, right: bool =
     if sorted_keys.dtype != queries.dtype:
         raise TypeError(f"queries are {queries.dtype}, sorted_keys {sorted_keys.dtype}: one dtype for both")
     dt = sorted_keys.dtype
-    if dt in _KEY_TYPE:
-        kt = KEY_UINT32 if (unsigned and dt == torch.int32) else _KEY_TYPE[dt]
-    elif dt in _KEY64_TYPE:
-        kt = KEY_UINT64 if (unsigned and dt == torch.int64) else _KEY64_TYPE[dt]
-    else:
+    if dt not in _KEY_TYPE and dt not in _KEY64_TYPE:
         raise TypeError(f"unsupported key dtype {dt}: searchsorted takes 32- and 64-bit keys (int32, uint32, float32, int64, uint64, float64)")
+    kt = _key_type(sorted_keys, unsigned, _KEY_TYPE if dt in _KEY_TYPE else _KEY64_TYPE)
     if not sorted_keys.is_contiguous() or not queries.is_contiguous() or sorted_keys.device.type != "cuda" or queries.device != sorted_keys.device:
         raise ValueError("sorted_keys and queries must be contiguous tensors on one GPU")
     n, m = sorted_keys.numel(), queries.numel()
     if m == 0 or n == 0:  # nothing in front of anything
         return torch.zeros(queries.shape, dtype=torch.int32, device=queries.device)
-    order = ORDER_DESCENDING if descending else ORDER_ASCENDING
     with torch.cuda.device(sorted_keys.device):
         wants_sort = not queries_sorted and search_plan(n, m, sorted_keys.element_size())["route_unsorted"] == _SEARCH_ROUTE_SORT
-        s = _search_handle(sorted_keys.device, n, m, kt, order, wants_sort)
+        s = _search_handle(sorted_keys.device, n, m, kt, _order(descending), wants_sort)
         out = s.search(sorted_keys, queries.reshape(-1), n, m, right=right, queries_sorted=queries_sorted)
     return out.reshape(queries.shape)
 

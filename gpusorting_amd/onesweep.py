@@ -22,12 +22,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import (KEY_FLOAT32, KEY_FLOAT64, KEY_INT32, KEY_INT64, KEY_UINT32, KEY_UINT64, MODE_KEYS_ONLY, MODE_PAIRS,  # noqa: F401
+                      ORDER_ASCENDING, ORDER_DESCENDING, _require_cuda, _require_room, _stream_ptr)
 from ._lib import check
 
-MODE_KEYS_ONLY, MODE_PAIRS = 0, 1
-ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
-KEY_UINT32, KEY_INT32, KEY_FLOAT32 = 0, 1, 2
-KEY_UINT64, KEY_INT64, KEY_FLOAT64 = 3, 4, 5  # 8-byte keys: eight passes planned by one histogram sweep
 PAYLOAD_UINT32, PAYLOAD_INT32, PAYLOAD_FLOAT32 = 0, 1, 2
 ENTROPY_PRESET_1, ENTROPY_PRESET_2, ENTROPY_PRESET_3, ENTROPY_PRESET_4, ENTROPY_PRESET_5 = range(5)
 _ENT_LOOKUP = (1.0, 0.811, 0.544, 0.337, 0.201)  # OneSweepDispatcher.cuh:201
@@ -42,24 +40,6 @@ class GPUSortingConfig:
     sortingOrder: int = ORDER_ASCENDING
     sortingKeyType: int = KEY_UINT32
     sortingPayloadType: int = PAYLOAD_UINT32
-
-
-def _stream_ptr(stream=None) -> int:
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return int(s.cuda_stream)
-
-
-def _require_cuda(t: torch.Tensor, name: str) -> None:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous tensor on the GPU")
-
-
-def _require_room(t: torch.Tensor | None, n: int, name: str) -> None:
-    """The C-ABI takes raw pointers: every buffer handed over must hold at least n elements."""
-    if t is not None:
-        _require_cuda(t, name)
-        if n > t.numel():
-            raise ValueError(f"{name} holds {t.numel()} elements, n = {n}")
 
 
 def init_random(keys: torch.Tensor, seed: int, entropy_preset: int = ENTROPY_PRESET_1,

@@ -12,12 +12,11 @@ memory and the current HIP stream.  The numpy statement of the semantics is ``re
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
-from ._lib import check
+from . import _handle, _lib
+from ._handle import _ptr, _require_room, _stream_ptr
+from ._lib import check  # noqa: F401
 from .segsort import sortable_bits
 from .topk import KEY_FLOAT32, KEY_INT32, KEY_UINT32, ORDER_ASCENDING, ORDER_DESCENDING  # noqa: F401
 
@@ -26,7 +25,7 @@ OP_SUM, OP_MIN, OP_MAX = range(3)
 OPS = {"sum": OP_SUM, "min": OP_MIN, "max": OP_MAX}
 ROUTE_NONE, ROUTE_SORTED, ROUTE_CONSECUTIVE = 0, 1, 2
 _REPORT = ("route", "n", "u", "ranges", "per_range", "tile", "status", "rank", "value_type", "op")
-_KEY_TYPES = (KEY_UINT32, KEY_INT32, KEY_FLOAT32)
+_KEY_TYPES = _handle.KEY32_TYPES
 VALUE_DTYPES = {VALUE_INT32: np.int32, VALUE_UINT32: np.uint32, VALUE_FLOAT32: np.float32, VALUE_INT64: np.int64, VALUE_UINT64: np.uint64,
                 VALUE_FLOAT64: np.float64}
 
@@ -61,36 +60,20 @@ def value_from_order_bits(bits: np.ndarray, value_type: int) -> np.ndarray:
     return np.ascontiguousarray(b).view(VALUE_DTYPES[value_type])
 
 
-def reduce_by_key_reference(keys: np.ndarray, values: np.ndarray, key_type: int = KEY_UINT32, descending: bool = False,
-                            value_type: int = VALUE_INT32, op: int = OP_SUM, consecutive: bool = False):
-    """What ``gs_reduce_by_key`` (or, with ``consecutive=True``, ``gs_reduce_by_key_consecutive``) delivers for the 4-byte array ``keys``
-    and the array ``values`` of ``value_type``'s width: ``(out_keys, out_values, counts)`` — the distinct key bit patterns in the order
-    of the library's sort (uint32), the reduction of each key's values, the multiplicities (uint32).  Integer sums wrap and come in the
-    value's dtype; FLOAT SUMS ARE SUMMED IN float64 and returned as float64 for the comparison (the device's order of combination is
-    its own); MIN / MAX go through ``value_order_bits`` and return one of the inputs bit for bit, in the value's dtype."""
-    k = np.ascontiguousarray(keys)
-    if k.dtype.itemsize != 4 or k.ndim != 1:
-        raise ValueError("keys must be a 1-D array of 4-byte elements")
+def _reference_values(k: np.ndarray, values: np.ndarray, value_type: int, op: int) -> np.ndarray:
+    """The references' check of their values: one per key of ``k``, of ``value_type``'s width; returned in that type's dtype."""
     if value_type not in VALUE_DTYPES or op not in (OP_SUM, OP_MIN, OP_MAX):
         raise ValueError("value_type is one of VALUE_* and op one of OP_SUM, OP_MIN, OP_MAX")
     dtype = np.dtype(VALUE_DTYPES[value_type])
     v = np.ascontiguousarray(values)
     if v.ndim != 1 or v.dtype.itemsize != dtype.itemsize or v.size != k.size:
         raise ValueError("values must be a 1-D array of the value type's width, one per key")
-    v = v.view(dtype)
-    bits = k.view(np.uint32)
-    n = bits.size
-    is_float = value_type in (VALUE_FLOAT32, VALUE_FLOAT64)
-    if n == 0:
-        return np.zeros(0, np.uint32), np.zeros(0, np.float64 if is_float and op == OP_SUM else dtype), np.zeros(0, np.uint32)
-    if consecutive:
-        perm = np.arange(n, dtype=np.int64)
-    else:
-        if key_type not in _KEY_TYPES:
-            raise ValueError("reduce_by_key takes 32-bit keys (KEY_UINT32, KEY_INT32, KEY_FLOAT32)")
-        perm = np.argsort(sortable_bits(bits, key_type), kind="stable")
-        if descending:
-            perm = perm[::-1]
+    return v.view(dtype)
+
+
+def _reference_runs(bits: np.ndarray, v: np.ndarray, perm: np.ndarray, value_type: int, op: int):
+    """The references' reduction of every run of ``bits[perm]`` (at least one element): ``(out_keys, out_values, counts)``."""
+    n, dtype, is_float = bits.size, v.dtype, value_type in (VALUE_FLOAT32, VALUE_FLOAT64)
     s, sv = bits[perm], v[perm]
     head = np.ones(n, dtype=bool)
     head[1:] = s[1:] != s[:-1]
@@ -108,6 +91,34 @@ def reduce_by_key_reference(keys: np.ndarray, values: np.ndarray, key_type: int 
     return s[starts].copy(), out, counts
 
 
+def reduce_by_key_reference(keys: np.ndarray, values: np.ndarray, key_type: int = KEY_UINT32, descending: bool = False,
+                            value_type: int = VALUE_INT32, op: int = OP_SUM, consecutive: bool = False):
+    """What ``gs_reduce_by_key`` (or, with ``consecutive=True``, ``gs_reduce_by_key_consecutive``) delivers for the 4-byte array ``keys``
+    and the array ``values`` of ``value_type``'s width: ``(out_keys, out_values, counts)`` — the distinct key bit patterns in the order
+    of the library's sort (uint32), the reduction of each key's values, the multiplicities (uint32).  Integer sums wrap and come in the
+    value's dtype; FLOAT SUMS ARE SUMMED IN float64 and returned as float64 for the comparison (the device's order of combination is
+    its own); MIN / MAX go through ``value_order_bits`` and return one of the inputs bit for bit, in the value's dtype."""
+    k = np.ascontiguousarray(keys)
+    if k.dtype.itemsize != 4 or k.ndim != 1:
+        raise ValueError("keys must be a 1-D array of 4-byte elements")
+    v = _reference_values(k, values, value_type, op)
+    dtype = v.dtype
+    bits = k.view(np.uint32)
+    n = bits.size
+    is_float = value_type in (VALUE_FLOAT32, VALUE_FLOAT64)
+    if n == 0:
+        return np.zeros(0, np.uint32), np.zeros(0, np.float64 if is_float and op == OP_SUM else dtype), np.zeros(0, np.uint32)
+    if consecutive:
+        perm = np.arange(n, dtype=np.int64)
+    else:
+        if key_type not in _KEY_TYPES:
+            raise ValueError("reduce_by_key takes 32-bit keys (KEY_UINT32, KEY_INT32, KEY_FLOAT32)")
+        perm = np.argsort(sortable_bits(bits, key_type), kind="stable")
+        if descending:
+            perm = perm[::-1]
+    return _reference_runs(bits, v, perm, value_type, op)
+
+
 def temp_bytes(max_keys: int, value_bytes: int = 4) -> int:
     """``gs_reduce_temp_bytes`` (host only); 0 for invalid sizes or value width."""
     return int(_lib.load().gs_reduce_temp_bytes(max_keys, value_bytes))
@@ -123,7 +134,7 @@ def _torch_value_types():
     return m
 
 
-class ReduceByKey:
+class ReduceByKey(_handle.Checked, _handle.Handle):
     """One ``gs_reduce`` handle: an embedded pairs sorter of capacity ``max_keys`` for values of ``value_bytes`` (4 or 8) and the
     buffers it sorts in.
 
@@ -136,44 +147,18 @@ class ReduceByKey:
     _PREFIX, _KEY_BYTES, _KEY_TYPES = "gs_reduce_", 4, _KEY_TYPES
     _KEYS_WANTED = "ReduceByKey takes 32-bit keys (KEY_UINT32, KEY_INT32, KEY_FLOAT32)"
 
-    def _entry(self, name: str):
-        return getattr(self._lib, self._PREFIX + name)
-
     def __init__(self, max_keys: int, order: int = ORDER_ASCENDING, key_type: int | None = None, value_bytes: int = 4, device: int | None = None):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type is None:
-            key_type = self._KEY_TYPES[0]
-        if key_type not in self._KEY_TYPES:
-            raise ValueError(self._KEYS_WANTED)
-        self._lib = _lib.load()
-        if device is not None:
-            torch.cuda.set_device(device)
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self.max_keys = int(max_keys)
-        self.order, self.key_type, self.value_bytes = order, key_type, int(value_bytes)
-        h = C.c_void_p()
-        check(self._entry("create")(C.byref(h), self.max_keys, self.value_bytes), self._PREFIX + "create")
-        self._h = h
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._entry("destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.key_type = self._check_key_type(key_type)
+        self.max_keys, self.order, self.value_bytes = int(max_keys), order, int(value_bytes)
+        self._create(device, self.max_keys, self.value_bytes)
 
     @property
     def temp_bytes(self) -> int:
         return int(self._entry("temp_bytes")(self.max_keys, self.value_bytes))
 
-    def _args(self, keys, values, n, op, value_type):
-        from .onesweep import _require_room
+    def _reduce(self, entry: str, sorted_by: tuple, keys, values, op, value_type, n, counts, stream):
+        """One call of ``by_key`` (``sorted_by``: the key type and the order it takes) or ``by_key_consecutive`` (which takes neither)."""
+        import torch
         if keys.element_size() != self._KEY_BYTES:
             raise ValueError("keys must be %d-bit" % (8 * self._KEY_BYTES))
         if value_type is None:
@@ -188,50 +173,25 @@ class ReduceByKey:
         n = keys.numel() if n is None else int(n)
         _require_room(keys, n, "keys")
         _require_room(values, n, "values")
-        return n, op, value_type
-
-    def _outs(self, keys, values, n, counts):
-        import torch
         out_k = torch.empty(n, dtype=keys.dtype, device=keys.device)
         out_v = torch.empty(n, dtype=values.dtype, device=keys.device)
         out_c = torch.empty(n, dtype=torch.int32, device=keys.device) if counts else None
-        return out_k, out_v, out_c, torch.empty(1, dtype=torch.int32, device=keys.device)
+        num = torch.empty(1, dtype=torch.int32, device=keys.device)
+        self._call(entry, keys.data_ptr(), values.data_ptr(), n, out_k.data_ptr(), out_v.data_ptr(), _ptr(out_c), num.data_ptr(),
+                   *sorted_by, value_type, op, _stream_ptr(stream))
+        return out_k, out_v, out_c, num
 
     def reduce_by_key(self, keys, values, op=OP_SUM, value_type: int | None = None, n: int | None = None, counts: bool = True, stream=None):
         """``gs_reduce_by_key``: ``(out_keys, out_values, out_counts | None, num)``.  ``keys`` and ``values`` are not written."""
-        from .onesweep import _stream_ptr
-        n, op, value_type = self._args(keys, values, n, op, value_type)
-        out_k, out_v, out_c, num = self._outs(keys, values, n, counts)
-        check(self._entry("by_key")(self._h, keys.data_ptr(), values.data_ptr(), n, out_k.data_ptr(), out_v.data_ptr(),
-                                         None if out_c is None else out_c.data_ptr(), num.data_ptr(), self.key_type, self.order, value_type, op,
-                                         _stream_ptr(stream)), self._PREFIX + "by_key")
-        return out_k, out_v, out_c, num
+        return self._reduce("by_key", (self.key_type, self.order), keys, values, op, value_type, n, counts, stream)
 
     def reduce_by_key_consecutive(self, keys, values, op=OP_SUM, value_type: int | None = None, n: int | None = None, counts: bool = True,
                                   stream=None):
         """``gs_reduce_by_key_consecutive``: the reduction of every run of bitwise-equal neighbouring keys of the input as it lies:
         ``(out_keys, out_values, out_counts | None, num)``."""
-        from .onesweep import _stream_ptr
-        n, op, value_type = self._args(keys, values, n, op, value_type)
-        out_k, out_v, out_c, num = self._outs(keys, values, n, counts)
-        check(self._entry("by_key_consecutive")(self._h, keys.data_ptr(), values.data_ptr(), n, out_k.data_ptr(), out_v.data_ptr(),
-                                                     None if out_c is None else out_c.data_ptr(), num.data_ptr(), value_type, op,
-                                                     _stream_ptr(stream)), self._PREFIX + "by_key_consecutive")
-        return out_k, out_v, out_c, num
-
-    def status(self, stream=None) -> int:
-        """``gs_reduce_check`` as a status code (synchronises)."""
-        from .onesweep import _stream_ptr
-        return int(self._entry("check")(self._h, _stream_ptr(stream)))
-
-    def check(self, stream=None) -> None:
-        """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
-        check(self.status(stream), self._PREFIX + "check")
+        return self._reduce("by_key_consecutive", (), keys, values, op, value_type, n, counts, stream)
 
     def last(self, stream=None) -> dict:
         """Diagnostics of the last call (synchronises): route, n, u, ranges, per_range, tile, status, rank (the sorter's rank mode),
         value_type, op."""
-        from .onesweep import _stream_ptr
-        buf = (C.c_uint32 * _lib.GS_REDUCE_REPORT_WORDS)()
-        check(self._entry("last")(self._h, buf, _lib.GS_REDUCE_REPORT_WORDS, _stream_ptr(stream)), self._PREFIX + "last")
-        return {name: int(buf[i]) for i, name in enumerate(_REPORT)}
+        return self._report("last", _lib.GS_REDUCE_REPORT_WORDS, _handle._indexed(_REPORT), stream)

@@ -16,8 +16,8 @@ import numpy as np
 
 from . import _lib
 from .onesweep import KEY_FLOAT64, KEY_INT64, KEY_UINT64  # noqa: F401
-from .reduce import (OP_MAX, OP_MIN, OP_SUM, VALUE_DTYPES, VALUE_FLOAT32, VALUE_FLOAT64, VALUE_INT32, ReduceByKey, value_from_order_bits,
-                     value_order_bits)
+from .reduce import (OP_MAX, OP_MIN, OP_SUM, VALUE_DTYPES, VALUE_FLOAT32, VALUE_FLOAT64, VALUE_INT32, ReduceByKey,  # noqa: F401
+                     _reference_runs, _reference_values, value_from_order_bits, value_order_bits)
 from .unique64 import KEY64_TYPES, sorted_perm64
 
 
@@ -31,34 +31,15 @@ def reduce_by_key64_reference(keys: np.ndarray, values: np.ndarray, key_type: in
     k = np.ascontiguousarray(keys)
     if k.dtype.itemsize != 8 or k.ndim != 1:
         raise ValueError("keys must be a 1-D array of 8-byte elements")
-    if value_type not in VALUE_DTYPES or op not in (OP_SUM, OP_MIN, OP_MAX):
-        raise ValueError("value_type is one of VALUE_* and op one of OP_SUM, OP_MIN, OP_MAX")
-    dtype = np.dtype(VALUE_DTYPES[value_type])
-    v = np.ascontiguousarray(values)
-    if v.ndim != 1 or v.dtype.itemsize != dtype.itemsize or v.size != k.size:
-        raise ValueError("values must be a 1-D array of the value type's width, one per key")
-    v = v.view(dtype)
+    v = _reference_values(k, values, value_type, op)
+    dtype = v.dtype
     bits = k.view(np.uint64)
     n = bits.size
     is_float = value_type in (VALUE_FLOAT32, VALUE_FLOAT64)
     if n == 0:
         return np.zeros(0, np.uint64), np.zeros(0, np.float64 if is_float and op == OP_SUM else dtype), np.zeros(0, np.uint32)
     perm = sorted_perm64(bits, key_type, descending, consecutive)
-    s, sv = bits[perm], v[perm]
-    head = np.ones(n, dtype=bool)
-    head[1:] = s[1:] != s[:-1]
-    starts = np.flatnonzero(head)
-    counts = np.diff(np.append(starts, n)).astype(np.uint32)
-    if op == OP_SUM:
-        if is_float:
-            out = np.add.reduceat(sv.astype(np.float64), starts)
-        else:
-            u = np.dtype("u%d" % dtype.itemsize)
-            out = np.add.reduceat(sv.view(u), starts).astype(u).view(dtype)  # modulo 2^32 / 2^64
-    else:
-        ob = value_order_bits(sv, value_type)
-        out = value_from_order_bits((np.minimum if op == OP_MIN else np.maximum).reduceat(ob, starts), value_type)
-    return s[starts].copy(), out, counts
+    return _reference_runs(bits, v, perm, value_type, op)
 
 
 def temp_bytes(max_keys: int, value_bytes: int = 4) -> int:

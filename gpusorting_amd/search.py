@@ -15,9 +15,10 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _handle, _lib
+from ._handle import KEY32_TYPES, KEY64_TYPES, _require_room, _stream_ptr
 from ._lib import check
-from .onesweep import KEY_FLOAT32, KEY_FLOAT64, KEY_INT32, KEY_INT64, KEY_UINT32, KEY_UINT64
+from .onesweep import KEY_FLOAT32, KEY_FLOAT64, KEY_INT32, KEY_INT64, KEY_UINT32, KEY_UINT64  # noqa: F401
 from .segsort import sortable_bits
 from .topk import ORDER_ASCENDING, ORDER_DESCENDING  # noqa: F401
 from .unique64 import sortable_bits64
@@ -26,8 +27,6 @@ ROUTE_AUTO = ROUTE_NONE = 0
 ROUTE_TILE, ROUTE_SORT, ROUTE_BINARY = 1, 2, 3
 ROUTES = {"auto": ROUTE_AUTO, "tile": ROUTE_TILE, "sort": ROUTE_SORT, "binary": ROUTE_BINARY}
 TABLE_AUTO, TABLE_ON, TABLE_OFF = 0, 1, 2
-KEY32_TYPES = (KEY_UINT32, KEY_INT32, KEY_FLOAT32)
-KEY64_TYPES = (KEY_UINT64, KEY_INT64, KEY_FLOAT64)
 SAMPLE_BYTES, WINDOW_BYTES = 65536, 32768
 _PLAN = ("tile", "window", "samples", "stride", "tile_grid", "binary_grid", "sample_grid", "table", "route_sorted", "route_unsorted",
          "route_no_engine")  # GS_SEARCH_P_*
@@ -92,59 +91,40 @@ def search_plan(n: int, m: int, key_bytes: int = 4) -> dict:
     return {name: int(plan[i]) for i, name in enumerate(_PLAN)}
 
 
-class SortedSearch:
+class SortedSearch(_handle.Handle):
     """One ``gs_search`` handle for haystacks of up to ``max_keys`` keys and calls of up to ``max_queries`` queries of ``key_type``.
 
     ``sort_queries=True`` embeds the pairs sorter that route SORT needs (and its buffers: 2 x (key + 4) bytes per query); without it
     the handle holds 64 KiB and serves queries in order (TILE) and in any order one thread per query (BINARY).  ``search`` does not
     wait on the host."""
 
+    _PREFIX, _KEY_TYPES = "gs_search_", KEY32_TYPES + KEY64_TYPES
+    _KEYS_WANTED = "SortedSearch takes 32- and 64-bit keys (KEY_UINT32 .. KEY_FLOAT64)"
+
     def __init__(self, max_keys: int, max_queries: int, key_type: int = KEY_UINT32, order: int = ORDER_ASCENDING, sort_queries: bool = False,
                  device: int | None = None):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type not in KEY32_TYPES + KEY64_TYPES:
-            raise ValueError("SortedSearch takes 32- and 64-bit keys (KEY_UINT32 .. KEY_FLOAT64)")
-        self._lib = _lib.load()
-        if device is not None:
-            torch.cuda.set_device(device)
-        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.key_type = self._check_key_type(key_type)
         self.max_keys, self.max_queries = int(max_keys), int(max_queries)
-        self.key_type, self.order, self.sort_queries = key_type, order, bool(sort_queries)
+        self.order, self.sort_queries = order, bool(sort_queries)
         self.key_bytes = 8 if key_type in KEY64_TYPES else 4
-        h = C.c_void_p()
-        check(self._lib.gs_search_create(C.byref(h), self.max_keys, self.max_queries, self.key_bytes, 1 if sort_queries else 0), "gs_search_create")
-        self._h = h
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.gs_search_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(device, self.max_keys, self.max_queries, self.key_bytes, 1 if sort_queries else 0)
 
     @property
     def temp_bytes(self) -> int:
-        return int(self._lib.gs_search_temp_bytes(self.max_keys, self.max_queries, self.key_bytes, 1 if self.sort_queries else 0))
+        return int(self._entry("temp_bytes")(self.max_keys, self.max_queries, self.key_bytes, 1 if self.sort_queries else 0))
 
     def set_route(self, route) -> None:
         """``gs_search_set_route``: "auto", "tile", "sort", "binary" (or the ROUTE_* value) for the calls that follow."""
-        check(self._lib.gs_search_set_route(self._h, ROUTES.get(route, route)), "gs_search_set_route")
+        self._call("set_route", ROUTES.get(route, route))
 
     def set_table(self, table: int) -> None:
         """``gs_search_set_table``: TABLE_AUTO, TABLE_ON or TABLE_OFF: the form of route BINARY."""
-        check(self._lib.gs_search_set_table(self._h, int(table)), "gs_search_set_table")
+        self._call("set_table", int(table))
 
     def status(self, hay, queries, n: int | None = None, m: int | None = None, right: bool = False, queries_sorted: bool = False, out=None,
                stream=None, key_type: int | None = None, order: int | None = None):
         """``gs_search_sorted`` as ``(status code, out)``; ``search`` raises on a status other than GS_OK."""
         import torch
-        from .onesweep import _require_room, _stream_ptr
         if hay.element_size() != self.key_bytes or queries.element_size() != self.key_bytes:
             raise ValueError("hay and queries must hold %d-byte elements" % self.key_bytes)
         n = hay.numel() if n is None else int(n)
@@ -156,9 +136,9 @@ class SortedSearch:
         if out.element_size() != 4:
             raise ValueError("out must hold 4-byte elements")
         _require_room(out, m, "out")
-        st = self._lib.gs_search_sorted(self._h, hay.data_ptr(), n, queries.data_ptr(), m, out.data_ptr(),
-                                        self.key_type if key_type is None else key_type, self.order if order is None else order,
-                                        _lib.GS_SEARCH_RIGHT if right else _lib.GS_SEARCH_LEFT, 1 if queries_sorted else 0, _stream_ptr(stream))
+        st = self._entry("sorted")(self._h, hay.data_ptr(), n, queries.data_ptr(), m, out.data_ptr(),
+                                   self.key_type if key_type is None else key_type, self.order if order is None else order,
+                                   _lib.GS_SEARCH_RIGHT if right else _lib.GS_SEARCH_LEFT, 1 if queries_sorted else 0, _stream_ptr(stream))
         return int(st), out
 
     def search(self, hay, queries, n: int | None = None, m: int | None = None, right: bool = False, queries_sorted: bool = False, out=None,
@@ -173,9 +153,5 @@ class SortedSearch:
     def last(self, stream=None) -> dict:
         """Diagnostics of the last call (synchronises): route, n, m, table, lds_tiles, global_tiles, engine, and ``plan``: the words of
         ``search_plan(n, m, key_bytes)``."""
-        from .onesweep import _stream_ptr
-        buf = (C.c_uint32 * _lib.GS_SEARCH_REPORT_WORDS)()
-        check(self._lib.gs_search_last(self._h, buf, _lib.GS_SEARCH_REPORT_WORDS, _stream_ptr(stream)), "gs_search_last")
-        rep = {name: int(buf[i]) for i, name in enumerate(_REPORT)}
-        rep["plan"] = {name: int(buf[_lib.GS_SEARCH_R_PLAN + i]) for i, name in enumerate(_PLAN)}
-        return rep
+        w = self._words("last", _lib.GS_SEARCH_REPORT_WORDS, stream)
+        return {**{name: w[i] for i, name in enumerate(_REPORT)}, "plan": {name: w[_lib.GS_SEARCH_R_PLAN + i] for i, name in enumerate(_PLAN)}}

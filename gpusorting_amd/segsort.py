@@ -8,17 +8,13 @@ the semantics (tests and tools compare against it); it needs no torch and no GPU
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
-from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, check
+from . import _handle, _lib
+from ._handle import (KEY16_TYPES, KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING,  # noqa: F401
+                      ORDER_DESCENDING, _require_cuda, _require_room, _stream_ptr)
+from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, check  # noqa: F401
 
-MODE_KEYS_ONLY, MODE_PAIRS = 0, 1
-ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
-KEY_UINT32, KEY_INT32, KEY_FLOAT32 = 0, 1, 2
-KEY16_TYPES = (KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16)  # 2-byte keys: the row-wise top-k only (gs_topk_select_rows_*)
 SEGSORT_CLASSES = _lib.GS_SEGSORT_CLASSES
 LONG_ROUTES = {"host": _lib.GS_SEGSORT_LONG_HOST, "device": _lib.GS_SEGSORT_LONG_DEVICE}
 _REPORT = ("route", "units", "long", "unit_cap", "forms", "status", "rank", "n")  # GS_SEGSORT_R_*
@@ -81,49 +77,81 @@ def segmented_sort_reference(keys: np.ndarray, offsets: np.ndarray, values: np.n
     return out, np.ascontiguousarray(values)[perm]
 
 
-class SegmentedSort:
+class _SegmentedSortCalls(_handle.Checked, _handle.AltBuffers, _handle.Handle):
+    """What ``SegmentedSort`` and ``SegmentedSort16`` (segsort16.py) share: the constructor's frame, ``sort``, the class counts."""
+
+    _KEY_BYTES = 4
+
+    def _open(self, max_keys, max_segments, order, key_type, mode, value_bytes, device) -> None:
+        self.max_keys, self.max_segments = int(max_keys), int(max_segments)
+        self.key_type = key_type
+        self._pairs_mode(order, mode, value_bytes)
+        self._create(device, self.max_keys, self.max_segments, mode, self.value_bytes)
+
+    @property
+    def max_lds_segment(self) -> int:
+        """Longest segment sorted in LDS; a ``max_segment_len`` up to it needs no alt buffers and, on 32-bit keys, keeps ``sort`` free
+        of host waits."""
+        return int(self._lib.gs_segsort_max_lds_segment(self.mode, self.value_bytes))
+
+    def class_of(self, length: int) -> int:
+        return int(self._lib.gs_segsort_class_of(int(length), self.mode, self.value_bytes))
+
+    def _args(self, keys, offsets, n):
+        _require_cuda(keys, "keys")
+        _require_cuda(offsets, "offsets")
+        if keys.element_size() != self._KEY_BYTES or offsets.element_size() != 4 or offsets.dim() != 1 or offsets.numel() < 2:
+            raise ValueError(f"keys must be {8 * self._KEY_BYTES}-bit and offsets a 1-D tensor of num_segments + 1 32-bit words")
+        n = keys.numel() if n is None else int(n)
+        _require_room(keys, n, "keys")
+        return n, offsets.numel() - 1
+
+    def _alt_for(self, n: int, max_segment_len: int):
+        """The alternate buffers of a call, unless the promised segment length keeps every segment in LDS."""
+        if max_segment_len != 0 and max_segment_len <= self.max_lds_segment:
+            return None, None
+        return self._alt(n)
+
+    def sort(self, keys, offsets, values=None, n: int | None = None, max_segment_len: int = 0, stream=None) -> None:
+        """Sort every segment of ``keys[:n]`` (and ``values[:n]``) in place on the current stream.  ``offsets``: int32 device tensor of
+        ``num_segments + 1`` CSR offsets.  ``max_segment_len``: a promise (0 = unknown).  16-bit keys: the call never waits on the host.
+        32-bit keys: non-zero and at most ``max_lds_segment`` the call never waits on the host; otherwise it waits once for the list of
+        long segments on the ``"host"`` long route and never on the ``"device"`` one."""
+        if (values is not None) != (self.mode == MODE_PAIRS):
+            raise ValueError("values must be given exactly when the sorter was built with MODE_PAIRS")
+        n, num_segments = self._args(keys, offsets, n)
+        _require_room(values, n, "values")
+        if values is not None and values.element_size() != self.value_bytes:
+            raise ValueError(f"values must be {self.value_bytes} bytes wide for this sorter")
+        max_segment_len = int(max_segment_len)
+        alt_k, alt_v = self._alt_for(n, max_segment_len)
+        tail = (n, offsets.data_ptr(), num_segments, max_segment_len, self.key_type, self.order, _stream_ptr(stream))
+        if values is None:
+            self._call("sort_keys", keys.data_ptr(), alt_k, *tail, where="sort")
+        else:
+            self._call("sort_pairs", keys.data_ptr(), values.data_ptr(), alt_k, alt_v, *tail, where="sort")
+
+    def last_classes(self, stream=None) -> dict:
+        """Segments per length class in the last call and the longest segment seen (synchronises)."""
+        w = self._words("last_classes", SEGSORT_CLASSES + 1, stream)
+        return {"counts": w[:SEGSORT_CLASSES], "longest": w[SEGSORT_CLASSES]}
+
+
+class SegmentedSort(_SegmentedSortCalls):
     """One ``gs_segsort`` handle (class lists + an embedded OneSweep engine for long segments) + lazily sized alt buffers.
     ``long_route``: ``"host"`` (the default: one host wait for the list of long segments, the engine sorts them one by one) or
     ``"device"`` (four passes over all long segments at once, no host wait: ``gs_segsort_set_long_route``)."""
 
+    _PREFIX, _KEY_TYPES, _KEYS_WANTED = "gs_segsort_", _handle.KEY32_TYPES, "the segmented sort takes 32-bit keys only"
+
     def __init__(self, max_keys: int, max_segments: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT32,
                  mode: int = MODE_KEYS_ONLY, value_bytes: int = 0, device: int | None = None, long_route: str = "host"):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type not in (KEY_UINT32, KEY_INT32, KEY_FLOAT32):
-            raise ValueError("the segmented sort takes 32-bit keys only")
+        key_type = self._check_key_type(key_type)
         if long_route not in LONG_ROUTES:
             raise ValueError('long_route must be "host" or "device"')
-        self._lib = _lib.load()
-        if device is not None:
-            torch.cuda.set_device(device)
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self.max_keys, self.max_segments = int(max_keys), int(max_segments)
-        self.order, self.key_type, self.mode = order, key_type, mode
-        self.value_bytes = (value_bytes or 4) if mode == MODE_PAIRS else 0
-        h = C.c_void_p()
-        check(self._lib.gs_segsort_create(C.byref(h), self.max_keys, self.max_segments, mode, self.value_bytes), "gs_segsort_create")
-        self._h = h
-        self._alt_keys = self._alt_vals = None
+        self._open(max_keys, max_segments, order, key_type, mode, value_bytes, device)
         if long_route != "host":
             self.set_long_route(long_route)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.gs_segsort_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def max_lds_segment(self) -> int:
-        """Longest segment sorted in LDS; a ``max_segment_len`` up to it keeps ``sort`` free of host waits."""
-        return int(self._lib.gs_segsort_max_lds_segment(self.mode, self.value_bytes))
 
     @property
     def engine(self):
@@ -144,69 +172,9 @@ class SegmentedSort:
         that route's buffers (synchronously); they stay until ``close``."""
         if long_route not in LONG_ROUTES:
             raise ValueError('long_route must be "host" or "device"')
-        check(self._lib.gs_segsort_set_long_route(self._h, LONG_ROUTES[long_route]), "gs_segsort_set_long_route")
-
-    def class_of(self, length: int) -> int:
-        return int(self._lib.gs_segsort_class_of(int(length), self.mode, self.value_bytes))
-
-    def sort(self, keys, offsets, values=None, n: int | None = None, max_segment_len: int = 0, stream=None) -> None:
-        """Sort every segment of ``keys[:n]`` (and ``values[:n]``) in place on the current stream.  ``offsets``: int32 device tensor of
-        ``num_segments + 1`` CSR offsets.  ``max_segment_len``: a promise (0 = unknown); non-zero and at most ``max_lds_segment`` the
-        call never waits on the host; otherwise it waits once for the list of long segments on the ``"host"`` long route and never
-        on the ``"device"`` one."""
-        import torch
-        from .onesweep import _require_cuda, _require_room, _stream_ptr
-        _require_cuda(keys, "keys")
-        _require_cuda(offsets, "offsets")
-        if keys.element_size() != 4 or offsets.element_size() != 4 or offsets.dim() != 1 or offsets.numel() < 2:
-            raise ValueError("keys must be 32-bit and offsets a 1-D tensor of num_segments + 1 32-bit words")
-        if (values is not None) != (self.mode == MODE_PAIRS):
-            raise ValueError("values must be given exactly when the sorter was built with MODE_PAIRS")
-        n = keys.numel() if n is None else int(n)
-        _require_room(keys, n, "keys")
-        _require_room(values, n, "values")
-        if values is not None and values.element_size() != self.value_bytes:
-            raise ValueError(f"values must be {self.value_bytes} bytes wide for this sorter")
-        num_segments = offsets.numel() - 1
-        max_segment_len = int(max_segment_len)
-        alt_k = alt_v = None
-        if max_segment_len == 0 or max_segment_len > self.max_lds_segment:
-            if self._alt_keys is None or self._alt_keys.numel() < n:
-                self._alt_keys = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
-            alt_k = self._alt_keys.data_ptr()
-            if values is not None:
-                if self._alt_vals is None or self._alt_vals.numel() < n:
-                    self._alt_vals = torch.empty(max(n, 1), dtype=torch.int32 if self.value_bytes == 4 else torch.int64, device=self.device)
-                alt_v = self._alt_vals.data_ptr()
-        s = _stream_ptr(stream)
-        if values is None:
-            st = self._lib.gs_segsort_sort_keys(self._h, keys.data_ptr(), alt_k, n, offsets.data_ptr(), num_segments, max_segment_len,
-                                                self.key_type, self.order, s)
-        else:
-            st = self._lib.gs_segsort_sort_pairs(self._h, keys.data_ptr(), values.data_ptr(), alt_k, alt_v, n, offsets.data_ptr(),
-                                                 num_segments, max_segment_len, self.key_type, self.order, s)
-        check(st, "gs_segsort_sort")
-
-    def status(self, stream=None) -> int:
-        """``gs_segsort_check`` as a status code (synchronises): GS_OK, GS_ERR_ARG (bad offsets), GS_ERR_SIZE (promise broken) ..."""
-        from .onesweep import _stream_ptr
-        return int(self._lib.gs_segsort_check(self._h, _stream_ptr(stream)))
-
-    def check(self, stream=None) -> None:
-        """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
-        check(self.status(stream), "gs_segsort_check")
-
-    def last_classes(self, stream=None) -> dict:
-        """Segments per length class in the last call and the longest segment seen (synchronises)."""
-        from .onesweep import _stream_ptr
-        buf = (C.c_uint32 * (SEGSORT_CLASSES + 1))()
-        check(self._lib.gs_segsort_last_classes(self._h, buf, SEGSORT_CLASSES + 1, _stream_ptr(stream)), "gs_segsort_last_classes")
-        return {"counts": [int(x) for x in buf[:SEGSORT_CLASSES]], "longest": int(buf[SEGSORT_CLASSES])}
+        self._call("set_long_route", LONG_ROUTES[long_route])
 
     def last(self, stream=None) -> dict:
         """``gs_segsort_last`` (synchronises): the report words of the last call as a dict: ``route``, ``units``, ``long``,
         ``unit_cap``, ``forms`` (``GS_SEGSORT_LF_*``), ``status``, ``rank``, ``n``."""
-        from .onesweep import _stream_ptr
-        buf = (C.c_uint32 * _lib.GS_SEGSORT_REPORT_WORDS)()
-        check(self._lib.gs_segsort_last(self._h, buf, _lib.GS_SEGSORT_REPORT_WORDS, _stream_ptr(stream)), "gs_segsort_last")
-        return {name: int(buf[i]) for i, name in enumerate(_REPORT)}
+        return self._report("last", _lib.GS_SEGSORT_REPORT_WORDS, _handle._indexed(_REPORT), stream)

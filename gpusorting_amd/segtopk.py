@@ -7,17 +7,14 @@ and no GPU.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
-from ._lib import check
+from . import _handle, _lib
+from ._handle import (KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING,  # noqa: F401
+                      _ptr, _require_cuda, _require_room, _stream_ptr)
+from ._lib import check  # noqa: F401
 from .topk import topk_reference
 
-MODE_KEYS_ONLY, MODE_PAIRS = 0, 1
-ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
-KEY_UINT32, KEY_INT32, KEY_FLOAT32 = 0, 1, 2
 _SCALARS = ("longest", "status", "reads", "forms", "rank", "k", "packed")  # GS_SEGTOPK_R_LONGEST ..
 
 
@@ -58,65 +55,34 @@ def forms_tile(cls: int, rank: int) -> int:
     return _lib.GS_SEGTOPK_F_TILE(cls, rank)
 
 
-class SegmentedTopK:
+_REPORT = tuple((name, _lib.GS_SEGTOPK_R_LONGEST + i) for i, name in enumerate(_SCALARS))
+
+
+class SegmentedTopK(_handle.Checked, _handle.RankMode, _handle.Handle):
     """One ``gs_segtopk`` handle: the control block and the class lists (``temp_bytes``; nothing sized by ``max_keys``).
 
     ``value_bytes`` 0 selects keys only; 4 or 8 carries values; on a 4-byte handle ``select(keys, offsets, k, out_keys, None,
     out_values)`` delivers the positions in the whole array as values."""
 
-    # what the key width decides (SegmentedTopK16, segtopk16.py, overrides the three)
-    _ENTRY = "gs_segtopk"
-    _KEY_TYPES = (KEY_UINT32, KEY_INT32, KEY_FLOAT32)
-    _KEY_BYTES = 4
-
-    def _fn(self, name: str):
-        return getattr(self._lib, f"{self._ENTRY}_{name}")
+    # what the key width decides (SegmentedTopK16, segtopk16.py, states its own)
+    _PREFIX, _KEY_BYTES, _KEY_TYPES = "gs_segtopk_", 4, _handle.KEY32_TYPES
+    _KEYS_WANTED = "SegmentedTopK takes 32-bit keys only"
 
     def __init__(self, max_keys: int, max_segments: int, max_k: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT32,
                  mode: int = MODE_KEYS_ONLY, value_bytes: int = 0, device: int | None = None):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type not in self._KEY_TYPES:
-            raise ValueError(f"{type(self).__name__} takes {8 * self._KEY_BYTES}-bit keys only")
-        self._lib = _lib.load()
-        if device is not None:
-            torch.cuda.set_device(device)
-        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.key_type = self._check_key_type(key_type)
         self.max_keys, self.max_segments, self.max_k = int(max_keys), int(max_segments), int(max_k)
-        self.order, self.key_type, self.mode = order, key_type, mode
-        self.value_bytes = (value_bytes or 4) if mode == MODE_PAIRS else 0
-        h = C.c_void_p()
-        check(self._fn("create")(C.byref(h), self.max_keys, self.max_segments, self.max_k, mode, self.value_bytes), f"{self._ENTRY}_create")
-        self._h = h
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._fn("destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._pairs_mode(order, mode, value_bytes)
+        self._create(device, self.max_keys, self.max_segments, self.max_k, mode, self.value_bytes)
 
     @property
     def temp_bytes(self) -> int:
-        return int(self._fn("temp_bytes")(self.max_segments))
+        return int(self._entry("temp_bytes")(self.max_segments))
 
     @property
     def max_lds_segment(self) -> int:
         """Longest segment selected in LDS; longer ones take ``k <= rows_max_k``."""
         return int(self._lib.gs_segsort_max_lds_segment(self.mode, self.value_bytes))
-
-    @property
-    def rank_mode(self) -> int:
-        return int(self._fn("get_rank_mode")(self._h))
-
-    def set_rank_mode(self, mode: int) -> None:
-        """``gs_segtopk_set_rank_mode``: the ranking inside a tile (0 ballot multi-split, 1 returning LDS atomic), with no call in flight."""
-        check(self._fn("set_rank_mode")(self._h, int(mode)), f"{self._ENTRY}_set_rank_mode")
 
     def class_of(self, length: int) -> int:
         return int(self._lib.gs_segsort_class_of(int(length), self.mode, self.value_bytes))
@@ -128,7 +94,6 @@ class SegmentedTopK:
         device tensor of ``num_segments + 1`` CSR offsets.  ``values=None`` with ``out_values`` given (4-byte handle): the values are
         the positions in the whole array.  ``max_segment_len``: a promise (0 = unknown); ``k`` above ``rows_max_k`` needs one that
         fits LDS.  The call never waits on the host; the inputs are not written."""
-        from .onesweep import _require_cuda, _require_room, _stream_ptr
         _require_cuda(keys, "keys")
         _require_cuda(offsets, "offsets")
         _require_cuda(out_keys, "out_keys")
@@ -151,30 +116,15 @@ class SegmentedTopK:
                     raise ValueError(f"{name} must be {self.value_bytes} bytes wide for this handle")
         s = _stream_ptr(stream)
         if out_values is None:
-            st = self._fn("select_keys")(self._h, keys.data_ptr(), n, offsets.data_ptr(), num_segments, k, int(max_segment_len),
-                                         out_keys.data_ptr(), self.key_type, self.order, s)
+            self._call("select_keys", keys.data_ptr(), n, offsets.data_ptr(), num_segments, k, int(max_segment_len), out_keys.data_ptr(),
+                       self.key_type, self.order, s, where="select")
         else:
-            st = self._fn("select_pairs")(self._h, keys.data_ptr(), None if values is None else values.data_ptr(), n,
-                                          offsets.data_ptr(), num_segments, k, int(max_segment_len), out_keys.data_ptr(),
-                                          out_values.data_ptr(), self.key_type, self.order, s)
-        check(st, f"{self._ENTRY}_select")
-
-    def status(self, stream=None) -> int:
-        """``gs_segtopk_check`` as a status code (synchronises): GS_OK, GS_ERR_ARG (bad offsets), GS_ERR_HIP, GS_ERR_SIZE (promise broken)."""
-        from .onesweep import _stream_ptr
-        return int(self._fn("check")(self._h, _stream_ptr(stream)))
-
-    def check(self, stream=None) -> None:
-        """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
-        check(self.status(stream), f"{self._ENTRY}_check")
+            self._call("select_pairs", keys.data_ptr(), _ptr(values), n, offsets.data_ptr(), num_segments, k, int(max_segment_len),
+                       out_keys.data_ptr(), out_values.data_ptr(), self.key_type, self.order, s, where="select")
 
     def last(self, stream=None) -> dict:
         """``gs_segtopk_last`` (synchronises): ``counts`` (segments per class of ``class_of``), ``longest``, ``status``, ``reads`` (the
         most reads of its segment any long segment took), ``forms`` (``GS_SEGTOPK_F_*``), ``rank``, ``k``, ``packed`` (segments the
         packed kernel emitted: length 1 .. 32)."""
-        from .onesweep import _stream_ptr
-        buf = (C.c_uint32 * _lib.GS_SEGTOPK_REPORT_WORDS)()
-        check(self._fn("last")(self._h, buf, _lib.GS_SEGTOPK_REPORT_WORDS, _stream_ptr(stream)), f"{self._ENTRY}_last")
-        out = {"counts": [int(buf[_lib.GS_SEGTOPK_R_CLASSES + c]) for c in range(_lib.GS_SEGSORT_CLASSES)]}
-        out.update({name: int(buf[_lib.GS_SEGTOPK_R_LONGEST + i]) for i, name in enumerate(_SCALARS)})
-        return out
+        w = self._words("last", _lib.GS_SEGTOPK_REPORT_WORDS, stream)
+        return {"counts": w[_lib.GS_SEGTOPK_R_CLASSES:_lib.GS_SEGTOPK_R_CLASSES + _lib.GS_SEGSORT_CLASSES], **{name: w[i] for name, i in _REPORT}}

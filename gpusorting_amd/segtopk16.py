@@ -7,7 +7,8 @@ the semantics is ``segmented_topk_reference`` (segtopk.py) on ``uint16`` bit pat
 """
 from __future__ import annotations
 
-from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16
+from ._handle import KEY16_TYPES as _KEY16_TYPES
+from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16  # noqa: F401
 from .segtopk import MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, SegmentedTopK, forms_tile, segmented_topk_reference  # noqa: F401
 
 
@@ -16,9 +17,8 @@ class SegmentedTopK16(SegmentedTopK):
     ``max_lds_segment``, ``temp_bytes``) on 2-byte key tensors.  The report of ``last`` has the 32-bit call's layout; ``reads`` is 2 or
     3 here."""
 
-    _ENTRY = "gs_segtopk16"
-    _KEY_TYPES = (KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16)
-    _KEY_BYTES = 2
+    _PREFIX, _KEY_BYTES, _KEY_TYPES = "gs_segtopk16_", 2, _KEY16_TYPES
+    _KEYS_WANTED = "SegmentedTopK16 takes 16-bit keys only"
 
     def __init__(self, max_keys: int, max_segments: int, max_k: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT16,
                  mode: int = MODE_KEYS_ONLY, value_bytes: int = 0, device: int | None = None):

@@ -10,12 +10,11 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _handle, _lib
+from ._handle import KEY16_TYPES, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING, _require_cuda, _require_room, _stream_ptr  # noqa: F401
 from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, check  # noqa: F401
-from .segsort import KEY16_TYPES, sortable_bits
+from .segsort import sortable_bits
 
-MODE_KEYS_ONLY, MODE_PAIRS = 0, 1
-ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
 SORT16_FORMS = {"hist": _lib.GS_SORT16_F_HIST, "scan": _lib.GS_SORT16_F_SCAN, "fill": _lib.GS_SORT16_F_FILL, "count": _lib.GS_SORT16_F_COUNT,
                 "pscan": _lib.GS_SORT16_F_PSCAN}
 for _v, _name in enumerate(("pos", "v4", "v8")):
@@ -43,57 +42,26 @@ def sort16_plan(n: int, mode: int = MODE_KEYS_ONLY, value_bytes: int = 0) -> dic
     return {"ranges": int(p[0]), "per_range": int(p[1]), "tile": int(p[2]), "cap": int(p[3])}
 
 
-class Sort16:
+_REPORT = (("route", _lib.GS_SORT16_R_ROUTE), ("ranges", _lib.GS_SORT16_R_RANGES), ("per_range", _lib.GS_SORT16_R_PER_RANGE),
+           ("tile", _lib.GS_SORT16_R_TILE), ("forms", _lib.GS_SORT16_R_FORMS), ("status", _lib.GS_SORT16_R_STATUS), ("n", _lib.GS_SORT16_R_N),
+           ("rank_mode", _lib.GS_SORT16_R_RANK))
+
+
+class Sort16(_handle.Checked, _handle.RankMode, _handle.AltBuffers, _handle.Handle):
     """One ``gs_sort16`` handle + lazily sized alt buffers (pairs and argsort; keys only needs none)."""
+
+    _PREFIX, _KEY_TYPES, _ALT_DTYPE = "gs_sort16_", KEY16_TYPES, "int16"
+    _KEYS_WANTED = "Sort16 takes 16-bit key types only"
 
     def __init__(self, max_keys: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT16, mode: int = MODE_KEYS_ONLY,
                  value_bytes: int = 0, device: int | None = None):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type not in KEY16_TYPES:
-            raise ValueError("Sort16 takes 16-bit key types only")
-        self._lib = _lib.load()
-        if device is not None:
-            torch.cuda.set_device(device)
-        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.key_type = self._check_key_type(key_type)
         self.max_keys = int(max_keys)
-        self.order, self.key_type, self.mode = order, key_type, mode
-        self.value_bytes = (value_bytes or 4) if mode == MODE_PAIRS else 0
-        h = C.c_void_p()
-        check(self._lib.gs_sort16_create(C.byref(h), self.max_keys, mode, self.value_bytes), "gs_sort16_create")
-        self._h = h
-        self._alt_keys = self._alt_vals = None
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.gs_sort16_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def rank_mode(self) -> int:
-        return int(self._lib.gs_sort16_get_rank_mode(self._h))
-
-    def set_rank_mode(self, mode: int) -> None:
-        check(self._lib.gs_sort16_set_rank_mode(self._h, int(mode)), "gs_sort16_set_rank_mode")
-
-    def _alt(self, n: int):
-        import torch
-        if self._alt_keys is None or self._alt_keys.numel() < n:
-            self._alt_keys = torch.empty(max(n, 1), dtype=torch.int16, device=self.device)
-        if self._alt_vals is None or self._alt_vals.numel() < n:
-            self._alt_vals = torch.empty(max(n, 1), dtype=torch.int32 if self.value_bytes == 4 else torch.int64, device=self.device)
-        return self._alt_keys.data_ptr(), self._alt_vals.data_ptr()
+        self._pairs_mode(order, mode, value_bytes)
+        self._create(device, self.max_keys, mode, self.value_bytes)
 
     def sort(self, keys, values=None, n: int | None = None, stream=None) -> None:
         """Sort ``keys[:n]`` (2-byte elements; and carry ``values[:n]``) in place on the current stream."""
-        from .onesweep import _require_cuda, _require_room, _stream_ptr
         _require_cuda(keys, "keys")
         if keys.element_size() != 2:
             raise ValueError("keys must be 2 bytes wide")
@@ -104,18 +72,15 @@ class Sort16:
         _require_room(values, n, "values")
         s = _stream_ptr(stream)
         if values is None:
-            check(self._lib.gs_sort16_sort_keys(self._h, keys.data_ptr(), n, self.key_type, self.order, s), "gs_sort16_sort_keys")
-            return
+            return self._call("sort_keys", keys.data_ptr(), n, self.key_type, self.order, s)
         if values.element_size() != self.value_bytes:
             raise ValueError(f"values must be {self.value_bytes} bytes wide for this sorter")
         alt_k, alt_v = self._alt(n)
-        check(self._lib.gs_sort16_sort_pairs(self._h, keys.data_ptr(), values.data_ptr(), alt_k, alt_v, n, self.key_type, self.order, s),
-              "gs_sort16_sort_pairs")
+        self._call("sort_pairs", keys.data_ptr(), values.data_ptr(), alt_k, alt_v, n, self.key_type, self.order, s)
 
     def argsort(self, keys, positions, n: int | None = None, stream=None) -> None:
         """Sort ``keys[:n]`` in place and write the input positions of the sorted order to ``positions[:n]`` (4-byte elements, output
         only: never read).  Needs a handle with 4-byte values."""
-        from .onesweep import _require_cuda, _require_room, _stream_ptr
         _require_cuda(keys, "keys")
         if keys.element_size() != 2 or positions.element_size() != 4:
             raise ValueError("keys must be 2 and positions 4 bytes wide")
@@ -125,24 +90,8 @@ class Sort16:
         _require_room(keys, n, "keys")
         _require_room(positions, n, "positions")
         alt_k, alt_v = self._alt(n)
-        check(self._lib.gs_sort16_argsort(self._h, keys.data_ptr(), positions.data_ptr(), alt_k, alt_v, n, self.key_type, self.order,
-                                          _stream_ptr(stream)), "gs_sort16_argsort")
-
-    def status(self, stream=None) -> int:
-        """``gs_sort16_check`` as a status code (synchronises)."""
-        from .onesweep import _stream_ptr
-        return int(self._lib.gs_sort16_check(self._h, _stream_ptr(stream)))
-
-    def check(self, stream=None) -> None:
-        """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
-        check(self.status(stream), "gs_sort16_check")
+        self._call("argsort", keys.data_ptr(), positions.data_ptr(), alt_k, alt_v, n, self.key_type, self.order, _stream_ptr(stream))
 
     def last(self, stream=None) -> dict:
         """Diagnostics of the last call (synchronises): route, ranges, elements per range, tile, the kernel forms it launched."""
-        from .onesweep import _stream_ptr
-        buf = (C.c_uint32 * _lib.GS_SORT16_REPORT_WORDS)()
-        check(self._lib.gs_sort16_last(self._h, buf, _lib.GS_SORT16_REPORT_WORDS, _stream_ptr(stream)), "gs_sort16_last")
-        r = [int(x) for x in buf]
-        return {"route": r[_lib.GS_SORT16_R_ROUTE], "ranges": r[_lib.GS_SORT16_R_RANGES], "per_range": r[_lib.GS_SORT16_R_PER_RANGE],
-                "tile": r[_lib.GS_SORT16_R_TILE], "forms": r[_lib.GS_SORT16_R_FORMS], "status": r[_lib.GS_SORT16_R_STATUS],
-                "n": r[_lib.GS_SORT16_R_N], "rank_mode": r[_lib.GS_SORT16_R_RANK]}
+        return self._report("last", _lib.GS_SORT16_REPORT_WORDS, _REPORT, stream)

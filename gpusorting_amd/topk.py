@@ -6,18 +6,15 @@ No counterpart in the reference project.  PyTorch is used only for device memory
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
-from ._lib import check
+from . import _handle, _lib
+from ._handle import (KEY16_TYPES, KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING,  # noqa: F401
+                      _require_cuda, _require_room, _ptr, _stream_ptr)
+from ._lib import check  # noqa: F401
 from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16  # noqa: F401
-from .segsort import KEY16_TYPES, sortable_bits
+from .segsort import sortable_bits
 
-MODE_KEYS_ONLY, MODE_PAIRS = 0, 1
-ORDER_ASCENDING, ORDER_DESCENDING = 0, 1
-KEY_UINT32, KEY_INT32, KEY_FLOAT32 = 0, 1, 2
 ROUTE_NONE, ROUTE_SELECT, ROUTE_FULL_SORT, ROUTE_SINGLE_TILE = 0, 1, 2, 3
 _REPORT = ("route", "threshold", "in_front", "equal", "taken", "candidates", "level2", "ranges")
 ROWS_ROUTE_NONE, ROWS_ROUTE_WAVE, ROWS_ROUTE_TILE, ROWS_ROUTE_STREAM, ROWS_ROUTE_LOOP = 0, 1, 2, 3, 4
@@ -60,65 +57,24 @@ def rows_max_k(mode: int = MODE_KEYS_ONLY, value_bytes: int = 0) -> int:
     return int(_lib.load().gs_topk_rows_max_k(mode, value_bytes))
 
 
-class TopK:
-    """One ``gs_topk`` handle: the selection's scratch and an embedded OneSweep engine for the final sort of k elements.
+class _TopKCalls(_handle.Checked, _handle.Handle):
+    """What ``TopK`` and ``TopK16`` (topk16.py) share: the constructor's frame and the 1-D ``select``."""
 
-    ``value_bytes`` 0 selects keys only; 4 or 8 carries values; on a 4-byte handle ``select(keys, k, out_keys, None, out_vals)``
-    delivers the input positions as values."""
+    _KEY_BYTES = 4
 
-    def __init__(self, max_keys: int, max_k: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT32, mode: int = MODE_KEYS_ONLY,
-                 value_bytes: int = 0, device: int | None = None):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type not in (KEY_UINT32, KEY_INT32, KEY_FLOAT32) + KEY16_TYPES:
-            raise ValueError("the selection takes 32-bit keys, and 16-bit keys (KEY_UINT16 .. KEY_BFLOAT16) in select_rows")
-        self._lib = _lib.load()
-        if device is not None:
-            torch.cuda.set_device(device)
-        self.device = torch.device("cuda", torch.cuda.current_device())
+    def _open(self, max_keys, max_k, order, key_type, mode, value_bytes, device) -> None:
+        self.key_type = self._check_key_type(key_type)
         self.max_keys, self.max_k = int(max_keys), int(max_k)
-        self.order, self.key_type, self.mode = order, key_type, mode
-        self.value_bytes = (value_bytes or 4) if mode == MODE_PAIRS else 0
-        h = C.c_void_p()
-        check(self._lib.gs_topk_create(C.byref(h), self.max_keys, self.max_k, mode, self.value_bytes), "gs_topk_create")
-        self._h = h
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.gs_topk_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def temp_bytes(self) -> int:
-        return int(self._lib.gs_topk_temp_bytes(self.max_keys, self.max_k, self.value_bytes))
-
-    @property
-    def engine(self):
-        """The embedded OneSweep engine, borrowed (``gs_topk_engine``): it runs the single-tile route and the final sort of k, and its
-        rank mode is the one the row-wise tile kernels run with.  For ``set_rank_mode`` / ``rank_mode`` / ``check``, with no call in
-        flight; it lives as long as this handle."""
-        from .onesweep import OneSweep
-        cap = max(self.max_k, min(self.max_keys, 32768))
-        kt = self.key_type if self.key_type in (KEY_UINT32, KEY_INT32, KEY_FLOAT32) else KEY_UINT32
-        return OneSweep._borrow(self._lib.gs_topk_engine(self._h), cap, self.mode, self.value_bytes, kt)
+        self._pairs_mode(order, mode, value_bytes)
+        self._create(device, self.max_keys, self.max_k, mode, self.value_bytes)
 
     def select(self, keys, k: int, out_keys, values=None, out_values=None, n: int | None = None, stream=None) -> None:
         """The first ``k`` of ``keys[:n]`` in this handle's order into ``out_keys[:k]`` (and ``out_values[:k]``) on the current stream.
         ``values=None`` with ``out_values`` given (4-byte handle): the values are the input positions.  Inputs are not written."""
-        from .onesweep import _require_cuda, _require_room, _stream_ptr
-        if self.key_type in KEY16_TYPES:
-            raise ValueError("the 1-D selection takes 32-bit keys only: 16-bit keys go through select_rows (one row: rows=1)")
         _require_cuda(keys, "keys")
         _require_cuda(out_keys, "out_keys")
-        if keys.element_size() != 4 or out_keys.element_size() != 4:
-            raise ValueError("keys must be 32-bit")
+        if keys.element_size() != self._KEY_BYTES or out_keys.element_size() != self._KEY_BYTES:
+            raise ValueError(f"keys must be {8 * self._KEY_BYTES}-bit")
         if (out_values is not None) != (self.mode == MODE_PAIRS):
             raise ValueError("out_values must be given exactly when the handle was built with MODE_PAIRS")
         n = keys.numel() if n is None else int(n)
@@ -134,11 +90,45 @@ class TopK:
                     raise ValueError(f"{name} must be {self.value_bytes} bytes wide for this handle")
         s = _stream_ptr(stream)
         if out_values is None:
-            st = self._lib.gs_topk_select_keys(self._h, keys.data_ptr(), n, k, out_keys.data_ptr(), self.key_type, self.order, s)
+            self._call("select_keys", keys.data_ptr(), n, k, out_keys.data_ptr(), self.key_type, self.order, s, where="select")
         else:
-            st = self._lib.gs_topk_select_pairs(self._h, keys.data_ptr(), None if values is None else values.data_ptr(), n, k,
-                                                out_keys.data_ptr(), out_values.data_ptr(), self.key_type, self.order, s)
-        check(st, "gs_topk_select")
+            self._call("select_pairs", keys.data_ptr(), _ptr(values), n, k, out_keys.data_ptr(), out_values.data_ptr(), self.key_type,
+                       self.order, s, where="select")
+
+
+class TopK(_TopKCalls):
+    """One ``gs_topk`` handle: the selection's scratch and an embedded OneSweep engine for the final sort of k elements.
+
+    ``value_bytes`` 0 selects keys only; 4 or 8 carries values; on a 4-byte handle ``select(keys, k, out_keys, None, out_vals)``
+    delivers the input positions as values."""
+
+    _PREFIX, _KEY_TYPES = "gs_topk_", _handle.KEY32_TYPES + KEY16_TYPES
+    _KEYS_WANTED = "the selection takes 32-bit keys, and 16-bit keys (KEY_UINT16 .. KEY_BFLOAT16) in select_rows"
+
+    def __init__(self, max_keys: int, max_k: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT32, mode: int = MODE_KEYS_ONLY,
+                 value_bytes: int = 0, device: int | None = None):
+        self._open(max_keys, max_k, order, key_type, mode, value_bytes, device)
+
+    @property
+    def temp_bytes(self) -> int:
+        return int(self._entry("temp_bytes")(self.max_keys, self.max_k, self.value_bytes))
+
+    @property
+    def engine(self):
+        """The embedded OneSweep engine, borrowed (``gs_topk_engine``): it runs the single-tile route and the final sort of k, and its
+        rank mode is the one the row-wise tile kernels run with.  For ``set_rank_mode`` / ``rank_mode`` / ``check``, with no call in
+        flight; it lives as long as this handle."""
+        from .onesweep import OneSweep
+        cap = max(self.max_k, min(self.max_keys, 32768))
+        kt = self.key_type if self.key_type in _handle.KEY32_TYPES else KEY_UINT32
+        return OneSweep._borrow(self._entry("engine")(self._h), cap, self.mode, self.value_bytes, kt)
+
+    def select(self, keys, k: int, out_keys, values=None, out_values=None, n: int | None = None, stream=None) -> None:
+        """The first ``k`` of ``keys[:n]`` in this handle's order into ``out_keys[:k]`` (and ``out_values[:k]``) on the current stream.
+        ``values=None`` with ``out_values`` given (4-byte handle): the values are the input positions.  Inputs are not written."""
+        if self.key_type in KEY16_TYPES:
+            raise ValueError("the 1-D selection takes 32-bit keys only: 16-bit keys go through select_rows (one row: rows=1)")
+        super().select(keys, k, out_keys, values, out_values, n, stream)
 
     def select_rows(self, keys, rows: int, row_len: int, row_stride: int, k: int, out_keys, values=None, out_values=None, stream=None) -> None:
         """The first ``k`` of every row ``keys[r * row_stride : r * row_stride + row_len]`` (a 2-D or flat tensor; ``row_stride`` in
@@ -147,7 +137,6 @@ class TopK:
         key type takes 2-byte key tensors (float16, bfloat16, int16, uint16); a row longer than LDS holds with
         ``k > rows_max_k`` is ``GS_ERR_SIZE`` there (no LOOP route)."""
         import torch
-        from .onesweep import _require_cuda, _stream_ptr
 
         def strided(t, name):  # an input: 1-D, or 2-D with any row stride; the last dimension contiguous
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() not in (1, 2) or t.stride(-1) != 1:
@@ -177,34 +166,18 @@ class TopK:
                 raise ValueError(f"{name} must be {self.value_bytes} bytes wide for this handle")
         s = _stream_ptr(stream)
         if out_values is None:
-            st = self._lib.gs_topk_select_rows_keys(self._h, keys.data_ptr(), rows, row_len, row_stride, k, out_keys.data_ptr(),
-                                                    self.key_type, self.order, s)
+            self._call("select_rows_keys", keys.data_ptr(), rows, row_len, row_stride, k, out_keys.data_ptr(), self.key_type, self.order, s,
+                       where="select_rows")
         else:
-            st = self._lib.gs_topk_select_rows_pairs(self._h, keys.data_ptr(), None if values is None else values.data_ptr(), rows, row_len,
-                                                     row_stride, k, out_keys.data_ptr(), out_values.data_ptr(), self.key_type, self.order, s)
-        check(st, "gs_topk_select_rows")
+            self._call("select_rows_pairs", keys.data_ptr(), _ptr(values), rows, row_len, row_stride, k, out_keys.data_ptr(),
+                       out_values.data_ptr(), self.key_type, self.order, s, where="select_rows")
 
     def rows_last(self, stream=None) -> dict:
         """Diagnostics of the last row-wise call (synchronises): route, rows, row_len, k, status, reads (stream route: the most reads
         of its row any row took)."""
-        from .onesweep import _stream_ptr
-        buf = (C.c_uint32 * _lib.GS_TOPK_ROWS_REPORT_WORDS)()
-        check(self._lib.gs_topk_rows_last(self._h, buf, _lib.GS_TOPK_ROWS_REPORT_WORDS, _stream_ptr(stream)), "gs_topk_rows_last")
-        return {name: int(buf[i]) for i, name in enumerate(_ROWS_REPORT)}
-
-    def status(self, stream=None) -> int:
-        """``gs_topk_check`` as a status code (synchronises)."""
-        from .onesweep import _stream_ptr
-        return int(self._lib.gs_topk_check(self._h, _stream_ptr(stream)))
-
-    def check(self, stream=None) -> None:
-        """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
-        check(self.status(stream), "gs_topk_check")
+        return self._report("rows_last", _lib.GS_TOPK_ROWS_REPORT_WORDS, _handle._indexed(_ROWS_REPORT), stream)
 
     def last(self, stream=None) -> dict:
         """Diagnostics of the last call (synchronises): route, threshold (the k-th key as sortable bits), in_front, equal, taken,
         candidates (left after the first level), level2, ranges."""
-        from .onesweep import _stream_ptr
-        buf = (C.c_uint32 * _lib.GS_TOPK_REPORT_WORDS)()
-        check(self._lib.gs_topk_last(self._h, buf, _lib.GS_TOPK_REPORT_WORDS, _stream_ptr(stream)), "gs_topk_last")
-        return {name: int(buf[i]) for i, name in enumerate(_REPORT)}
+        return self._report("last", _lib.GS_TOPK_REPORT_WORDS, _handle._indexed(_REPORT), stream)

@@ -12,14 +12,15 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _handle, _lib
+from ._handle import _ptr, _require_room, _stream_ptr
 from ._lib import check
 from .segsort import sortable_bits
 from .topk import KEY_FLOAT32, KEY_INT32, KEY_UINT32, MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING  # noqa: F401
 
 ROUTE_NONE, ROUTE_KEYS, ROUTE_POSITIONS, ROUTE_CONSECUTIVE = 0, 1, 2, 3
 _REPORT = ("route", "n", "u", "ranges", "per_range", "tile", "status", "rank")
-_KEY_TYPES = (KEY_UINT32, KEY_INT32, KEY_FLOAT32)
+_KEY_TYPES = _handle.KEY32_TYPES
 
 
 def unique_reference(keys: np.ndarray, key_type: int = KEY_UINT32, descending: bool = False, consecutive: bool = False):
@@ -44,6 +45,12 @@ def unique_reference(keys: np.ndarray, key_type: int = KEY_UINT32, descending: b
         perm = np.argsort(sortable_bits(bits, key_type), kind="stable")
         if descending:
             perm = perm[::-1]
+    return _runs(bits, perm)
+
+
+def _runs(bits: np.ndarray, perm: np.ndarray):
+    """The references' run-length stage on ``bits[perm]`` (at least one element): ``(out_keys, counts, first, inverse)``."""
+    n = bits.size
     s = bits[perm]
     head = np.ones(n, dtype=bool)
     head[1:] = s[1:] != s[:-1]
@@ -68,7 +75,13 @@ def unique_plan(n: int) -> tuple:
     return int(plan[0]), int(plan[1]), int(plan[2])
 
 
-class Unique:
+def _out(keys, count: int, want: bool = True, dtype=None):
+    """An output tensor of ``count`` elements (int32 unless ``dtype``) on the device of ``keys``, or None for one not wanted."""
+    import torch
+    return torch.empty(count, dtype=dtype or torch.int32, device=keys.device) if want else None
+
+
+class Unique(_handle.Checked, _handle.Handle):
     """One ``gs_unique`` handle: an embedded sorter of capacity ``max_keys`` and the buffers it sorts in.
 
     ``positions=False`` makes a handle for keys and counts; ``positions=True`` one that also delivers first positions and the inverse
@@ -79,106 +92,48 @@ class Unique:
     _PREFIX, _KEY_BYTES, _KEY_TYPES = "gs_unique_", 4, _KEY_TYPES
     _KEYS_WANTED = "Unique takes 32-bit keys (KEY_UINT32, KEY_INT32, KEY_FLOAT32)"
 
-    def _entry(self, name: str):
-        return getattr(self._lib, self._PREFIX + name)
-
     def __init__(self, max_keys: int, order: int = ORDER_ASCENDING, key_type: int | None = None, positions: bool = False, device: int | None = None):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type is None:
-            key_type = self._KEY_TYPES[0]
-        if key_type not in self._KEY_TYPES:
-            raise ValueError(self._KEYS_WANTED)
-        self._lib = _lib.load()
-        if device is not None:
-            torch.cuda.set_device(device)
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self.max_keys = int(max_keys)
-        self.order, self.key_type = order, key_type
+        self.key_type = self._check_key_type(key_type)
+        self.max_keys, self.order = int(max_keys), order
         self.mode, self.value_bytes = (MODE_PAIRS, 4) if positions else (MODE_KEYS_ONLY, 0)
-        h = C.c_void_p()
-        check(self._entry("create")(C.byref(h), self.max_keys, self.mode, self.value_bytes), self._PREFIX + "create")
-        self._h = h
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._entry("destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(device, self.max_keys, self.mode, self.value_bytes)
 
     @property
     def temp_bytes(self) -> int:
         return int(self._entry("temp_bytes")(self.max_keys, self.mode, self.value_bytes))
 
     def _keys(self, keys, n):
-        from .onesweep import _require_room
         if keys.element_size() != self._KEY_BYTES:
             raise ValueError("keys must be %d-bit" % (8 * self._KEY_BYTES))
         n = keys.numel() if n is None else int(n)
         _require_room(keys, n, "keys")
         return n
 
-    def _out(self, keys, n, want: bool, dtype=None):
-        import torch
-        return torch.empty(n, dtype=dtype or torch.int32, device=keys.device) if want else None
-
-    @staticmethod
-    def _ptr(t):
-        return None if t is None else t.data_ptr()
-
     def unique(self, keys, n: int | None = None, counts: bool = True, stream=None):
         """``gs_unique_keys``: ``(out_keys, out_counts | None, num)``.  ``keys`` is not written."""
-        from .onesweep import _stream_ptr
         n = self._keys(keys, n)
-        out_k = self._out(keys, n, True, keys.dtype)
-        out_c = self._out(keys, n, counts)
-        num = self._out(keys, 1, True)
-        check(self._entry("keys")(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), num.data_ptr(), self.key_type, self.order,
-                                       _stream_ptr(stream)), self._PREFIX + "keys")
+        out_k, out_c, num = _out(keys, n, dtype=keys.dtype), _out(keys, n, counts), _out(keys, 1)
+        self._call("keys", keys.data_ptr(), n, out_k.data_ptr(), _ptr(out_c), num.data_ptr(), self.key_type, self.order, _stream_ptr(stream))
         return out_k, out_c, num
 
     def unique_positions(self, keys, n: int | None = None, counts: bool = True, first: bool = True, inverse: bool = True, stream=None):
         """``gs_unique_positions`` (a handle with ``positions=True``): ``(out_keys, out_counts | None, out_first | None, out_inverse | None,
         num)``; positions and the inverse are int32 tensors holding uint32 values."""
-        from .onesweep import _stream_ptr
         n = self._keys(keys, n)
-        out_k = self._out(keys, n, True, keys.dtype)
-        out_c, out_f, out_i = self._out(keys, n, counts), self._out(keys, n, first), self._out(keys, n, inverse)
-        num = self._out(keys, 1, True)
-        check(self._entry("positions")(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), self._ptr(out_f), self._ptr(out_i),
-                                            num.data_ptr(), self.key_type, self.order, _stream_ptr(stream)), self._PREFIX + "positions")
+        out_k = _out(keys, n, dtype=keys.dtype)
+        out_c, out_f, out_i, num = _out(keys, n, counts), _out(keys, n, first), _out(keys, n, inverse), _out(keys, 1)
+        self._call("positions", keys.data_ptr(), n, out_k.data_ptr(), _ptr(out_c), _ptr(out_f), _ptr(out_i), num.data_ptr(), self.key_type,
+                   self.order, _stream_ptr(stream))
         return out_k, out_c, out_f, out_i, num
 
     def unique_consecutive(self, keys, n: int | None = None, counts: bool = True, inverse: bool = True, stream=None):
         """``gs_unique_consecutive``: the run-length encode of ``keys`` as it lies: ``(out_keys, out_counts | None, out_inverse | None,
         num)``."""
-        from .onesweep import _stream_ptr
         n = self._keys(keys, n)
-        out_k = self._out(keys, n, True, keys.dtype)
-        out_c, out_i = self._out(keys, n, counts), self._out(keys, n, inverse)
-        num = self._out(keys, 1, True)
-        check(self._entry("consecutive")(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), self._ptr(out_i), num.data_ptr(),
-                                              _stream_ptr(stream)), self._PREFIX + "consecutive")
+        out_k, out_c, out_i, num = _out(keys, n, dtype=keys.dtype), _out(keys, n, counts), _out(keys, n, inverse), _out(keys, 1)
+        self._call("consecutive", keys.data_ptr(), n, out_k.data_ptr(), _ptr(out_c), _ptr(out_i), num.data_ptr(), _stream_ptr(stream))
         return out_k, out_c, out_i, num
-
-    def status(self, stream=None) -> int:
-        """``gs_unique_check`` as a status code (synchronises)."""
-        from .onesweep import _stream_ptr
-        return int(self._entry("check")(self._h, _stream_ptr(stream)))
-
-    def check(self, stream=None) -> None:
-        """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
-        check(self.status(stream), self._PREFIX + "check")
 
     def last(self, stream=None) -> dict:
         """Diagnostics of the last call (synchronises): route, n, u, ranges, per_range, tile, status, rank (the sorter's rank mode)."""
-        from .onesweep import _stream_ptr
-        buf = (C.c_uint32 * _lib.GS_UNIQUE_REPORT_WORDS)()
-        check(self._entry("last")(self._h, buf, _lib.GS_UNIQUE_REPORT_WORDS, _stream_ptr(stream)), self._PREFIX + "last")
-        return {name: int(buf[i]) for i, name in enumerate(_REPORT)}
+        return self._report("last", _lib.GS_UNIQUE_REPORT_WORDS, _handle._indexed(_REPORT), stream)

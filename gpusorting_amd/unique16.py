@@ -9,14 +9,14 @@ current HIP stream.  The numpy statement of the semantics is ``unique16_referenc
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
-from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, check
+from . import _handle, _lib
+from ._handle import _ptr, _require_cuda, _require_room, _stream_ptr
+from ._lib import KEY_BFLOAT16, KEY_FLOAT16, KEY_INT16, KEY_UINT16, check  # noqa: F401
 from .segsort import sortable_bits
 from .topk import ORDER_ASCENDING, ORDER_DESCENDING  # noqa: F401
+from .unique import _out, _runs
 
 ROUTE_NONE, ROUTE_HISTOGRAM, ROUTE_CONSECUTIVE = 0, 1, 2
 RAN_FIRST, RAN_INVERSE_LDS, RAN_INVERSE_GATHER = _lib.GS_UNIQUE16_K_FIRST, _lib.GS_UNIQUE16_K_INVERSE_LDS, _lib.GS_UNIQUE16_K_INVERSE_GATHER
@@ -24,7 +24,7 @@ INVERSE_AUTO, INVERSE_LDS, INVERSE_GATHER = 0, 1, 2  # the inverse lookup's form
 INVERSE_LDS_MIN = _lib.GS_UNIQUE16_INVERSE_LDS_MIN
 BINS = 1 << 16  # a call of ``unique`` never delivers more distinct keys
 _REPORT = ("route", "n", "u", "status", "ran", "ranges", "per_range", "tile", "first_ranges", "inverse_ranges")
-_KEY_TYPES = (KEY_UINT16, KEY_INT16, KEY_FLOAT16, KEY_BFLOAT16)
+_KEY_TYPES = _handle.KEY16_TYPES
 
 
 def unique16_reference(keys: np.ndarray, key_type: int = KEY_UINT16, descending: bool = False, consecutive: bool = False):
@@ -50,16 +50,7 @@ def unique16_reference(keys: np.ndarray, key_type: int = KEY_UINT16, descending:
         perm = np.argsort(sortable_bits(bits, key_type), kind="stable")
         if descending:
             perm = perm[::-1]
-    s = bits[perm]
-    head = np.ones(n, dtype=bool)
-    head[1:] = s[1:] != s[:-1]
-    starts = np.flatnonzero(head)
-    rank = np.cumsum(head) - 1  # the run of every sorted element
-    counts = np.diff(np.append(starts, n))
-    first = np.minimum.reduceat(perm, starts)  # ascending: the run's head; descending: its tail
-    inverse = np.empty(n, dtype=np.int64)
-    inverse[perm] = rank
-    return s[starts].copy(), counts.astype(np.uint32), first.astype(np.uint32), inverse.astype(np.uint32)
+    return _runs(bits, perm)
 
 
 def temp_bytes(max_keys: int) -> int:
@@ -67,46 +58,26 @@ def temp_bytes(max_keys: int) -> int:
     return int(_lib.load().gs_unique16_temp_bytes(int(max_keys)))
 
 
-class Unique16:
+class Unique16(_handle.Checked, _handle.Handle):
     """One ``gs_unique16`` handle: the histogram, the first-position and rank tables and the run-length stage's per-range words.
 
     ``unique`` returns tensors of ``min(n, 65 536)`` elements for keys, counts and first (only the first ``u`` are written) and ``n``
     for the inverse, ``unique_consecutive`` ``n`` elements each, plus the one-element count tensor ``num`` on the device; neither waits
     on the host.  Counts, positions and the inverse are int32 tensors holding uint32 values."""
 
+    _PREFIX, _KEY_TYPES = "gs_unique16_", _KEY_TYPES
+    _KEYS_WANTED = "Unique16 takes 16-bit keys (KEY_UINT16 .. KEY_BFLOAT16); 32-bit keys go to Unique"
+
     def __init__(self, max_keys: int, order: int = ORDER_ASCENDING, key_type: int = KEY_UINT16, device: int | None = None):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("gpusorting_amd needs a GPU: the product path has no CPU fallback")
-        if key_type not in _KEY_TYPES:
-            raise ValueError("Unique16 takes 16-bit keys (KEY_UINT16 .. KEY_BFLOAT16); 32-bit keys go to Unique")
-        self._lib = _lib.load()
-        if device is not None:
-            torch.cuda.set_device(device)
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self.max_keys = int(max_keys)
-        self.order, self.key_type = order, key_type
-        h = C.c_void_p()
-        check(self._lib.gs_unique16_create(C.byref(h), self.max_keys), "gs_unique16_create")
-        self._h = h
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.gs_unique16_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.key_type = self._check_key_type(key_type)
+        self.max_keys, self.order = int(max_keys), order
+        self._create(device, self.max_keys)
 
     @property
     def temp_bytes(self) -> int:
         return temp_bytes(self.max_keys)
 
     def _keys(self, keys, n):
-        from .onesweep import _require_cuda, _require_room
         _require_cuda(keys, "keys")
         if keys.element_size() != 2:
             raise ValueError("keys must be 16-bit")
@@ -114,58 +85,31 @@ class Unique16:
         _require_room(keys, n, "keys")
         return n
 
-    @staticmethod
-    def _out(keys, count, want: bool, dtype=None):
-        import torch
-        return torch.empty(count, dtype=dtype or torch.int32, device=keys.device) if want else None
-
-    @staticmethod
-    def _ptr(t):
-        return None if t is None else t.data_ptr()
-
     def unique(self, keys, n: int | None = None, counts: bool = True, first: bool = True, inverse: bool = True, stream=None):
         """``gs_unique16_unique``: ``(out_keys, out_counts | None, out_first | None, out_inverse | None, num)``.  ``keys`` is not
         written."""
-        from .onesweep import _stream_ptr
         n = self._keys(keys, n)
         cap = min(n, BINS)
-        out_k = self._out(keys, cap, True, keys.dtype)
-        out_c, out_f, out_i = self._out(keys, cap, counts), self._out(keys, cap, first), self._out(keys, n, inverse)
-        num = self._out(keys, 1, True)
-        check(self._lib.gs_unique16_unique(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), self._ptr(out_f), self._ptr(out_i),
-                                           num.data_ptr(), self.key_type, self.order, _stream_ptr(stream)), "gs_unique16_unique")
+        out_k = _out(keys, cap, dtype=keys.dtype)
+        out_c, out_f, out_i, num = _out(keys, cap, counts), _out(keys, cap, first), _out(keys, n, inverse), _out(keys, 1)
+        self._call("unique", keys.data_ptr(), n, out_k.data_ptr(), _ptr(out_c), _ptr(out_f), _ptr(out_i), num.data_ptr(), self.key_type,
+                   self.order, _stream_ptr(stream))
         return out_k, out_c, out_f, out_i, num
 
     def unique_consecutive(self, keys, n: int | None = None, counts: bool = True, inverse: bool = True, stream=None):
         """``gs_unique16_consecutive``: the run-length encode of ``keys`` as it lies: ``(out_keys, out_counts | None, out_inverse | None,
         num)``."""
-        from .onesweep import _stream_ptr
         n = self._keys(keys, n)
-        out_k = self._out(keys, n, True, keys.dtype)
-        out_c, out_i = self._out(keys, n, counts), self._out(keys, n, inverse)
-        num = self._out(keys, 1, True)
-        check(self._lib.gs_unique16_consecutive(self._h, keys.data_ptr(), n, out_k.data_ptr(), self._ptr(out_c), self._ptr(out_i), num.data_ptr(),
-                                                _stream_ptr(stream)), "gs_unique16_consecutive")
+        out_k, out_c, out_i, num = _out(keys, n, dtype=keys.dtype), _out(keys, n, counts), _out(keys, n, inverse), _out(keys, 1)
+        self._call("consecutive", keys.data_ptr(), n, out_k.data_ptr(), _ptr(out_c), _ptr(out_i), num.data_ptr(), _stream_ptr(stream))
         return out_k, out_c, out_i, num
 
     def set_inverse_form(self, which: int) -> None:
         """Which form of the inverse lookup ``unique`` runs from the next call on: ``INVERSE_AUTO`` (by n, the default), ``INVERSE_LDS``
         or ``INVERSE_GATHER``; the result is the same bit for bit."""
-        check(self._lib.gs_unique16_set_inverse_form(self._h, which), "gs_unique16_set_inverse_form")
-
-    def status(self, stream=None) -> int:
-        """``gs_unique16_check`` as a status code (synchronises)."""
-        from .onesweep import _stream_ptr
-        return int(self._lib.gs_unique16_check(self._h, _stream_ptr(stream)))
-
-    def check(self, stream=None) -> None:
-        """Raises ``GpuSortError`` unless the last call went through (synchronises)."""
-        check(self.status(stream), "gs_unique16_check")
+        self._call("set_inverse_form", which)
 
     def last(self, stream=None) -> dict:
         """Diagnostics of the last call (synchronises): route, n, u, status, ran (``RAN_*`` bits: the optional kernels launched), ranges,
         per_range, tile, first_ranges and inverse_ranges (the workgroups of the first-position and the inverse kernel)."""
-        from .onesweep import _stream_ptr
-        buf = (C.c_uint32 * _lib.GS_UNIQUE16_REPORT_WORDS)()
-        check(self._lib.gs_unique16_last(self._h, buf, _lib.GS_UNIQUE16_REPORT_WORDS, _stream_ptr(stream)), "gs_unique16_last")
-        return {name: int(buf[i]) for i, name in enumerate(_REPORT)}
+        return self._report("last", _lib.GS_UNIQUE16_REPORT_WORDS, _handle._indexed(_REPORT), stream)

@@ -14,9 +14,8 @@ import numpy as np
 from . import _lib
 from .onesweep import KEY_FLOAT64, KEY_INT64, KEY_UINT64
 from .topk import MODE_KEYS_ONLY, MODE_PAIRS, ORDER_ASCENDING, ORDER_DESCENDING  # noqa: F401
-from .unique import Unique
-
-KEY64_TYPES = (KEY_UINT64, KEY_INT64, KEY_FLOAT64)
+from ._handle import KEY64_TYPES
+from .unique import Unique, _runs
 
 
 def sortable_bits64(keys: np.ndarray, key_type: int = KEY_UINT64) -> np.ndarray:
@@ -59,16 +58,7 @@ def unique64_reference(keys: np.ndarray, key_type: int = KEY_UINT64, descending:
     if n == 0:
         return np.zeros(0, np.uint64), empty, empty.copy(), empty.copy()
     perm = sorted_perm64(bits, key_type, descending, consecutive)
-    s = bits[perm]
-    head = np.ones(n, dtype=bool)
-    head[1:] = s[1:] != s[:-1]
-    starts = np.flatnonzero(head)
-    rank = np.cumsum(head) - 1  # the run of every sorted element
-    counts = np.diff(np.append(starts, n))
-    first = np.minimum.reduceat(perm, starts)  # ascending: the run's head; descending: its tail
-    inverse = np.empty(n, dtype=np.int64)
-    inverse[perm] = rank
-    return s[starts].copy(), counts.astype(np.uint32), first.astype(np.uint32), inverse.astype(np.uint32)
+    return _runs(bits, perm)
 
 
 def temp_bytes(max_keys: int, mode: int = MODE_KEYS_ONLY, value_bytes: int = 0) -> int:
