@@ -428,6 +428,14 @@ _PROTOS = [
     ("gs_search_set_route", _int, [_vp, _u32]),
     ("gs_search_set_table", _int, [_vp, _u32]),
     ("gs_search_last", _int, [_vp, _u32p, _u32, _vp]),
+    ("gs_merge_create", _int, [C.POINTER(_vp), _u32, _u32]),
+    ("gs_merge_destroy", _int, [_vp]),
+    ("gs_merge_temp_bytes", C.c_size_t, [_u32, _u32]),
+    ("gs_merge_plan", _int, [_u32, _u32, _u32, _u32p]),
+    ("gs_merge_keys", _int, [_vp, _vp, _u32, _vp, _u32, _vp, _int, _int, _vp]),
+    ("gs_merge_pairs", _int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _int, _int, _vp]),
+    ("gs_merge_positions", _int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _int, _int, _vp]),
+    ("gs_merge_last", _int, [_vp, _u32p, _u32, _vp]),
 ]
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 

@@ -27,6 +27,7 @@
 #include "unique16_kernels.hpp"
 #include "reduce_kernels.hpp"
 #include "search_kernels.hpp"
+#include "merge_kernels.hpp"
 #include "sortrows_kernels.hpp"
 #include "sortrows16_kernels.hpp"
 #include "segsort16_kernels.hpp"
@@ -48,6 +49,7 @@
 #include "unique64_host.hpp"    // gs_unique64: gs_unique on 8-byte keys (behind unique_host)
 #include "reduce64_host.hpp"    // gs_reduce64: gs_reduce on 8-byte keys (behind reduce_host)
 #include "search_host.hpp"      // gs_search: lower / upper bound of many queries in a sorted array (behind onesweep_host and unique_host)
+#include "merge_host.hpp"       // gs_merge: two sorted arrays into one: keys, pairs or positions (behind search_kernels.hpp: its word and staging helpers)
 #include "sortrows_host.hpp"    // gs_sort_rows: every row of a matrix sorted in one call
 #include "sortrows16_host.hpp"  // gs_sort_rows16: the same on 16-bit keys
 #include "segsort16_host.hpp"   // gs_segsort16: the segmented sort on 16-bit keys

@@ -1778,6 +1778,83 @@ gs_status gs_search_set_table(gs_search* h, uint32_t table);
 /* No counterpart in the reference project.  Synchronous diagnostics of the last call: report[GS_SEARCH_R_*], words >= GS_SEARCH_REPORT_WORDS. */
 gs_status gs_search_last(gs_search* h, uint32_t* report, uint32_t words, void* stream);
 
+/* ---- merge: two sorted arrays into one: keys, pairs or positions --------------------------------------------------------------------------
+ * No counterpart in the reference project.  What a caller who holds keys sorted by this library does with new ones: gs_search_sorted says
+ * where each belongs, this moves the data, reading every element once and writing it once.
+ *
+ * A[0 .. na) and B[0 .. nb) are sorted in `order` under the library's total order of key_type: GS_KEY_UINT32 / INT32 / FLOAT32 on a handle
+ * created with key_bytes 4, GS_KEY_UINT64 / INT64 / FLOAT64 on one created with key_bytes 8 (floats by the order-preserving flip:
+ * -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN).  The 16-bit key types are refused with GS_ERR_ARG.  out[0 .. na + nb) is the
+ * STABLE merge: sorted in the same order, and among keys with the same word all of A's come before all of B's, each side in its input
+ * order: A[i] lands at i + #{B in front of A[i]}, B[j] at j + #{A in front of or equal to B[j]}.  Equality is BITWISE in the flipped
+ * domain: -0.0 and +0.0 are two keys and every NaN pattern is a key of its own.  The result is that of a stable pairs sort of the
+ * concatenation [A; B].  Three forms:
+ *
+ *     gs_merge_keys        out_keys
+ *     gs_merge_pairs       out_keys, out_vals: the values follow their keys; value_bytes 4 or 8, given per call, the same for A and B
+ *     gs_merge_positions   out_keys, out_src: uint32, i for A[i] and na + j for B[j]: the "argmerge"; a caller gathers any payload through it
+ *
+ * THE ORDER OF THE INPUTS IS NOT CHECKED.  If A or B is not sorted as declared the output is unspecified.  Even then the call ends (every
+ * kernel loop is bounded by the sizes, not by the data), every output slot [0, na + nb) is written exactly once, every out_src value is
+ * below na + nb, and no byte outside the call's buffers is read or written.
+ *
+ * One kernel: a workgroup per tile of GS_MERGE_P_TILE consecutive outputs finds its two merge-path diagonals with 64-way searches,
+ * stages its piece of A and of B into LDS and merges there, GS_MERGE_P_VT outputs per thread; a tile that lies wholly in one input is a
+ * copy (gs_merge_last counts them).
+ *
+ * Buffers: either side may be empty, but not both, and a side of length 0 may be passed as null pointers; 1 <= na + nb <= max_keys;
+ * every base pointer 16-byte aligned; the inputs are not written; nothing at or behind element na + nb of an output is written; no buffer
+ * of the call may overlap another.  No host wait; every node is a kernel and the grid is a function of na + nb alone (gs_merge_plan), so
+ * a call can be captured in a graph and replayed on other contents of the same sizes.  One call in flight per handle.
+ *
+ * Errors of gs_merge_keys / _pairs / _positions, in this order.  GS_ERR_ARG: null handle (before anything else is looked at).
+ * GS_ERR_ARG: a null or misaligned pointer of a non-empty side or of an output; a key type whose width is not the handle's (the 16-bit
+ * ones included); a bad order.  GS_ERR_MODE: value_bytes not 4 or 8.  GS_ERR_SIZE: na + nb == 0 or na + nb > max_keys (the sum in 64
+ * bits).  GS_ERR_ARG: any two buffers of the call overlapping.  GS_ERR_MODE: every call on a build flavour without these kernels (the
+ * tuning and fault-injection libraries).  A refused call launches nothing and leaves form NONE. */
+typedef struct gs_merge gs_merge;
+#define GS_MERGE_FORM_NONE 0 /* gs_merge_last: no call yet, or the last one was refused */
+#define GS_MERGE_FORM_KEYS 1
+#define GS_MERGE_FORM_PAIRS 2
+#define GS_MERGE_FORM_POSITIONS 3
+/* gs_merge_plan words */
+#define GS_MERGE_P_TILE 0      /* T: outputs per workgroup */
+#define GS_MERGE_P_VT 1        /* VT: outputs per thread, T / threads */
+#define GS_MERGE_P_THREADS 2   /* threads per workgroup */
+#define GS_MERGE_P_GRID 3      /* ceil((na + nb) / T) */
+#define GS_MERGE_P_LDS_BYTES 4 /* LDS of the pairs and positions forms: T * (key_bytes + 2) + 8; the keys form has no indices: T * key_bytes + 8 */
+#define GS_MERGE_PLAN_WORDS 8
+/* gs_merge_last report words */
+#define GS_MERGE_R_FORM 0
+#define GS_MERGE_R_NA 1
+#define GS_MERGE_R_NB 2
+#define GS_MERGE_R_TILES 3      /* tiles run: the plan's grid */
+#define GS_MERGE_R_COPY_TILES 4 /* ... of which lay wholly in one input and were copied */
+#define GS_MERGE_R_PLAN 8       /* the GS_MERGE_PLAN_WORDS words of gs_merge_plan(na, nb, key_bytes) */
+#define GS_MERGE_REPORT_WORDS 16
+/* No counterpart in the reference project.  1 <= max_keys <= GS_MAX_KEYS (GS_ERR_SIZE), then key_bytes 4 or 8 (GS_ERR_ARG; 2-byte keys
+ * are a follow-up), both answered before a device is looked for.  The handle allocates the control block only.  Synchronous. */
+gs_status gs_merge_create(gs_merge** out, uint32_t max_keys, uint32_t key_bytes);
+/* No counterpart in the reference project. */
+gs_status gs_merge_destroy(gs_merge* h);
+/* No counterpart in the reference project.  Host only.  4096: the control block (32 pairs of counters, each pair on a 128-byte line of its own);
+ * nothing grows with max_keys.  0 for invalid arguments. */
+size_t gs_merge_temp_bytes(uint32_t max_keys, uint32_t key_bytes);
+/* No counterpart in the reference project.  Host only: plan[GS_MERGE_P_*] for na + nb outputs of key_bytes bytes.  GS_ERR_ARG: null plan;
+ * GS_ERR_SIZE: na + nb 0 or above GS_MAX_KEYS (the sum in 64 bits); GS_ERR_ARG: key_bytes not 4 or 8. */
+gs_status gs_merge_plan(uint32_t na, uint32_t nb, uint32_t key_bytes, uint32_t plan[GS_MERGE_PLAN_WORDS]);
+/* No counterpart in the reference project.  See above. */
+gs_status gs_merge_keys(gs_merge* h, const void* d_a, uint32_t na, const void* d_b, uint32_t nb, void* d_out, gs_key_type key_type, gs_order order,
+                        void* stream);
+/* No counterpart in the reference project.  See above. */
+gs_status gs_merge_pairs(gs_merge* h, const void* d_a_keys, const void* d_a_vals, uint32_t na, const void* d_b_keys, const void* d_b_vals, uint32_t nb,
+                         void* d_out_keys, void* d_out_vals, uint32_t value_bytes, gs_key_type key_type, gs_order order, void* stream);
+/* No counterpart in the reference project.  See above. */
+gs_status gs_merge_positions(gs_merge* h, const void* d_a, uint32_t na, const void* d_b, uint32_t nb, void* d_out_keys, void* d_out_src,
+                             gs_key_type key_type, gs_order order, void* stream);
+/* No counterpart in the reference project.  Synchronous diagnostics of the last call: report[GS_MERGE_R_*], words >= GS_MERGE_REPORT_WORDS. */
+gs_status gs_merge_last(gs_merge* h, uint32_t* report, uint32_t words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
