@@ -471,14 +471,19 @@ static_assert(CHMAX == RADIX, "pass B: one chain per top-byte value");
 // (PF_HALF16, hy_half_slot); the top 16 bits are the bucket's number, blockIdx.x, in radix-sortable form already.  Descending: the
 // bucket's range is the mirrored one, [n - start - count, n - start), and the sorted keys are written back in reverse (keys only:
 // equal keys are indistinguishable, the reverse of the stable ascending order is any descending order).
+// HALF: the kernel keeps what varies inside a bucket, the low halves, alone — two per register as they were loaded, one uint16 per
+// stage slot — and puts `top` back in the final store.  The same eight LDS instructions per key on the same slots (the stage is
+// written and read per halfword); what shrinks is what a workgroup occupies: registers and LDS decide how many buckets a CU holds
+// at once, and buckets in flight are what keeps the LDS pipe busy (profiles/local_sort_residency_ab.txt).
 // ---------------------------------------------------------------------------
-template <int KT, int THREADS_, int KPT_>
-__global__ __launch_bounds__(THREADS_) void hy_local_sort_kernel(uint32_t* keys, const uint32_t* __restrict__ tab, uint32_t* __restrict__ slab,
+template <int KT, int THREADS_, int KPT_, bool HALF = false>
+__global__ __launch_bounds__(THREADS_, HALF ? 8 : 1) void hy_local_sort_kernel(uint32_t* keys, const uint32_t* __restrict__ tab, uint32_t* __restrict__ slab,
                                                                  uint32_t n, uint32_t descending) {
     constexpr int KPT = KPT_, WAVES = THREADS_ / 64;
     constexpr uint32_t THREADS = THREADS_, TILE = THREADS_ * KPT_;
     static_assert(THREADS >= RADIX && KPT % 2 == 0 && WAVES % 2 == 0 && TILE < 65536, "one digit per thread in the scans; ranks and counters are packed two per word");
-    __shared__ __attribute__((aligned(16))) uint32_t s_stage[TILE];
+    using Staged = std::conditional_t<HALF, uint16_t, uint32_t>;
+    __shared__ __attribute__((aligned(16))) Staged s_stage[TILE];
     __shared__ uint32_t s_cnt[WAVES / 2 * RADIX];  // pass 1: [0 .. 255] one table for the workgroup; pass 2: per-wave counters, waves 2k and 2k + 1 in one word
     __shared__ uint32_t s_wtot[4];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -502,22 +507,49 @@ __global__ __launch_bounds__(THREADS_) void hy_local_sort_kernel(uint32_t* keys,
     const uint32_t kp2 = (kpt + 1u) >> 1, ndw = (count + 1u) >> 1;  // uniform
     const uint32_t my_half = 2u * (wave * (64u * kp2) + lane);     // halfword index of key[0]; key[i]: my_half + (i >> 1) * 128 + (i & 1)
     const uint32_t top = blockIdx.x << 16;
-    uint32_t key[KPT];
+    constexpr int LD = HALF ? 1 : 2;  // HALF: key i is half i & 1 of key[i >> 1], as loaded
+    uint32_t key[KPT / 2 * LD];
+    if constexpr (HALF) {
+#pragma unroll
+        for (int j = 0; j < KPT / 2; ++j) key[j] = 0;
+    }
+    auto digit = [&](int i, int byte) -> uint32_t {
+        if constexpr (HALF) return (key[i >> 1] >> (16 * (i & 1) + 8 * byte)) & 255u;
+        else return (key[i] >> (8 * byte)) & 255u;
+    };
+    auto put = [&](uint32_t slot, int i) {  // key i -> the stage
+        if constexpr (HALF) s_stage[slot] = (uint16_t)(key[i >> 1] >> (16 * (i & 1)));
+        else s_stage[slot] = key[i];
+    };
+    auto take = [&](int i, uint32_t slot) {  // the stage -> key i (HALF: the even key of a register is taken first and clears its neighbour)
+        if constexpr (HALF) key[i >> 1] = (i & 1) ? key[i >> 1] | ((uint32_t)s_stage[slot] << 16) : (uint32_t)s_stage[slot];
+        else key[i] = s_stage[slot];
+    };
+    // HALF: between the ranking and the scattering of a pass the compiler would keep every key's counter address in a register of its
+    // own, 24 beside the 24 of keys and ranks; behind this empty statement it computes them again (two VALU instructions per key)
+    auto forget_addresses = [&]() {
+        if constexpr (HALF) {
+#pragma unroll
+            for (int j = 0; j < KPT / 2; ++j) asm volatile("" : "+v"(key[j]));
+        }
+    };
     // (all loads are issued before the first is consumed: split in the loop that loads, every load waited for its own round trip —
     //  0.65 ms for the kernel instead of 0.51, profiles/half16_headline_ab.txt)
 #pragma unroll
     for (int j = 0; j < KPT / 2; ++j) {
         if ((uint32_t)j >= kp2) continue;  // uniform
         const uint32_t q = (my_half >> 1) + j * 64u;
-        key[2 * j] = keys[at + (q < ndw ? q : ndw - 1u)];
+        key[LD * j] = keys[at + (q < ndw ? q : ndw - 1u)];
     }
     if (tid < RADIX) s_cnt[tid] = 0;
+    if constexpr (!HALF) {
 #pragma unroll
-    for (int j = 0; j < KPT / 2; ++j) {
-        if ((uint32_t)j >= kp2) continue;
-        const uint32_t w = key[2 * j];
-        key[2 * j] = top | (w & 0xffffu);
-        key[2 * j + 1] = top | (w >> 16);
+        for (int j = 0; j < KPT / 2; ++j) {
+            if ((uint32_t)j >= kp2) continue;
+            const uint32_t w = key[2 * j];
+            key[2 * j] = top | (w & 0xffffu);
+            key[2 * j + 1] = top | (w >> 16);
+        }
     }
     __syncthreads();
     // The kernel is bound by its LDS instructions (two passes x rank / base / stage / read back, profiles/r05_*): whatever is not
@@ -531,8 +563,9 @@ __global__ __launch_bounds__(THREADS_) void hy_local_sort_kernel(uint32_t* keys,
     for (int i = 0; i < KPT; ++i) {
         if ((uint32_t)(i >> 1) >= kp2) continue;  // uniform
         if (my_half + (i >> 1) * 128u + (i & 1) < count)
-            off[i >> 1] |= __hip_atomic_fetch_add(&s_cnt[key[i] & 255u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) << (16 * (i & 1));
+            off[i >> 1] |= __hip_atomic_fetch_add(&s_cnt[digit(i, 0)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) << (16 * (i & 1));
     }
+    forget_addresses();
     __syncthreads();
     uint32_t c = 0, scan_incl = 0;
     if (tid < RADIX) {
@@ -550,13 +583,13 @@ __global__ __launch_bounds__(THREADS_) void hy_local_sort_kernel(uint32_t* keys,
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
         if ((uint32_t)(i >> 1) >= kp2) continue;
-        if (my_half + (i >> 1) * 128u + (i & 1) < count) s_stage[((off[i >> 1] >> (16 * (i & 1))) & 0xffffu) + s_cnt[key[i] & 255u]] = key[i];
+        if (my_half + (i >> 1) * 128u + (i & 1) < count) put(((off[i >> 1] >> (16 * (i & 1))) & 0xffffu) + s_cnt[digit(i, 0)], i);
     }
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
         if ((uint32_t)i >= kpt) continue;
-        key[i] = s_stage[my_base + i * 64u];  // (slots >= count hold nothing: masked wherever they are used)
+        take(i, my_base + i * 64u);  // (slots >= count hold nothing: masked wherever they are used)
     }
     // ---- pass 2, byte 1: stable (it must keep pass 1's order).  Per-wave counters, two waves per word (a wave counts at most
     // 64 x KPT, a stage slot is < TILE < 65 536: a half never carries into its neighbour)
@@ -570,10 +603,11 @@ __global__ __launch_bounds__(THREADS_) void hy_local_sort_kernel(uint32_t* keys,
     for (int i = 0; i < KPT; ++i) {
         if ((uint32_t)i >= kpt) continue;
         if (my_base + i * 64u < count) {
-            const uint32_t r = __hip_atomic_fetch_add(&wh[(key[i] >> 8) & 255u], 1u << wsh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const uint32_t r = __hip_atomic_fetch_add(&wh[digit(i, 1)], 1u << wsh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             off[i >> 1] |= ((r >> wsh) & 0xffffu) << (16 * (i & 1));
         }
     }
+    forget_addresses();
     __syncthreads();
     uint32_t run = 0;
     if (tid < RADIX) {
@@ -599,13 +633,13 @@ __global__ __launch_bounds__(THREADS_) void hy_local_sort_kernel(uint32_t* keys,
     for (int i = 0; i < KPT; ++i) {
         if ((uint32_t)i >= kpt) continue;
         if (my_base + i * 64u < count)
-            s_stage[((off[i >> 1] >> (16 * (i & 1))) & 0xffffu) + ((wh[(key[i] >> 8) & 255u] >> wsh) & 0xffffu)] = key[i];
+            put(((off[i >> 1] >> (16 * (i & 1))) & 0xffffu) + ((wh[digit(i, 1)] >> wsh) & 0xffffu), i);
     }
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
         const uint32_t slot = my_base + i * 64u;
-        if ((uint32_t)i < kpt && slot < count) keys[at + (descending ? count - 1u - slot : slot)] = from_bits<KT>(s_stage[slot]);
+        if ((uint32_t)i < kpt && slot < count) keys[at + (descending ? count - 1u - slot : slot)] = from_bits<KT>(HALF ? top | s_stage[slot] : s_stage[slot]);
     }
 }
 

@@ -71,9 +71,9 @@ void launch_hy_hist(hipStream_t s, uint32_t grid, const uint32_t* keys, uint32_t
                        wg_per_seg, slices, cap);
 }
 using HyLocalLauncher = void (*)(hipStream_t, uint32_t grid, uint32_t* keys, const uint32_t* tab, uint32_t* slab, uint32_t n, uint32_t descending);
-template <int KT, int T, int K>
+template <int KT, int T, int K, bool HALF>
 void launch_hy_local(hipStream_t s, uint32_t grid, uint32_t* keys, const uint32_t* tab, uint32_t* slab, uint32_t n, uint32_t descending) {
-    hipLaunchKernelGGL((gs::hy_local_sort_kernel<KT, T, K>), dim3(grid), dim3(T), 0, s, keys, tab, slab, n, descending);
+    hipLaunchKernelGGL((gs::hy_local_sort_kernel<KT, T, K, HALF>), dim3(grid), dim3(T), 0, s, keys, tab, slab, n, descending);
 }
 using HyLocalPairsLauncher = void (*)(hipStream_t, uint32_t* keys, void* vals, const uint32_t* tab, const uint32_t* slab, uint32_t n, uint32_t descending);
 template <int KT, int VB, int T, int K>
@@ -89,6 +89,20 @@ struct HyLocalClass {
     constexpr uint32_t cap() const { return (uint32_t)threads * kpt; }
 };
 constexpr HyLocalClass g_hy_class[4] = {{1u << 27, 256, 12}, {1u << 28, 512, 12}, {1u << 29, 1024, 12}, {GS_MAX_KEYS, 1024, 24}};
+// the keys-only kernel's own workgroup per class: the same cap on a shape of its own.  Class 1 sorts 256 x 24 on 16-bit halves (HALF of
+// hy_local_sort_kernel): half the waves per bucket, 64 registers and 14 KiB of LDS, so that eight buckets are resident per CU
+// instead of four (profiles/local_sort_residency_ab.txt)
+struct HyKeysShape {
+    int threads, kpt;
+    bool half;
+};
+constexpr HyKeysShape g_hy_keys_shape[4] = {{256, 12, false}, {256, 24, true}, {1024, 12, false}, {1024, 24, false}};
+constexpr bool hy_keys_shapes_hold_cap() {
+    for (int c = 0; c < 4; ++c)
+        if ((uint32_t)g_hy_keys_shape[c].threads * g_hy_keys_shape[c].kpt != g_hy_class[c].cap()) return false;
+    return true;
+}
+static_assert(hy_keys_shapes_hold_cap(), "the histogram's cap and the plan's validity are decided on g_hy_class");
 inline int hy_class(uint32_t n) { return n <= g_hy_class[0].max_n ? 0 : n <= g_hy_class[1].max_n ? 1 : n <= g_hy_class[2].max_n ? 2 : 3; }
 constexpr uint32_t HY_MIN_PAIRS_DEFAULT = (1u << 25) + 1u;  // pairs: from where the position-chain plan (its fall-back) starts — at 2^25 pairs the two-level plan already wins (61.6 against 58.8, 44.6 against 40.4 GKeys/s with 4- / 8-byte values), at 2^24 it loses
 constexpr uint32_t HY_MIN_KEYS_DEFAULT = 3u << 24;  // 50 M keys: measured, the LSD passes win at 2^25 (121 against 102 GKeys/s), the two-level plan at 2^26 (139 against 122): below, its 65 536 buckets are a few hundred keys each and a workgroup per bucket is mostly launch (profiles/r05_two_level_threshold.txt)
@@ -318,7 +332,7 @@ constexpr auto g_hy_hist = Table<NKT>::make([](auto kt) -> HyHistLauncher {
 });
 using HyTable = Table<4, NKT>;  // [class][key type]
 constexpr auto g_hy_local = HyTable::make([](auto c, auto kt) -> HyLocalLauncher {
-    if constexpr (key32(kt)) return launch_hy_local<kt, g_hy_class[c].threads, g_hy_class[c].kpt>;
+    if constexpr (key32(kt)) return launch_hy_local<kt, g_hy_keys_shape[c].threads, g_hy_keys_shape[c].kpt, g_hy_keys_shape[c].half>;
     else return nullptr;
 });
 using HyPairsTable = Table<2, 4, NKT>;  // [8-byte values][class][key type]

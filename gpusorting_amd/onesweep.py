@@ -238,8 +238,8 @@ class OneSweep:
 
     def set_hy_class(self, cls: int) -> None:
         """Test hook (gs_debug_set_hy_class; host only): force size class ``cls`` (0 .. 3: workgroups of 256 x 12, 512 x 12, 1024 x 12,
-        1024 x 24 keys) of the two-level plan's bucket-local sort for every later sort of this handle, whatever its size; -1 (the
-        default): the class follows ``n``.  Call it with no sort of the handle in flight."""
+        1024 x 24 keys; keys only, class 1 holds its 6144 keys on 256 x 24) of the two-level plan's bucket-local sort for every later
+        sort of this handle, whatever its size; -1 (the default): the class follows ``n``.  Call it with no sort of the handle in flight."""
         check(self._lib.gs_debug_set_hy_class(self._h, int(cls)), "gs_debug_set_hy_class")
 
     def pass_flags(self, stream=None) -> list:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/r07_pmc_traffic.json from the summaries tools/rocprof_collect.sh wrote: HBM bytes per working launch of the DigitBinningPass and of the
+"""profiles/r08_pmc_traffic.json from the summaries tools/rocprof_collect.sh wrote: HBM bytes per working launch of the DigitBinningPass and of the
 histogram sweep = FETCH_SIZE x 2 (gfx950 tallies 128-byte requests at 64 B: MI355X_MICROARCH.md, HBM section) + WRITE_SIZE, in KiB per dispatch, with the
 calibration of the same runs (init_random writes 2^30 B; the histogram sweep reads 2^30 B) and the hash of the kernel sources they were measured on
 (bench.py hands the numbers on only for that source state).  Keys only, pass B hands the bucket-local sort 16-bit halves (PF_HALF16): the pass
@@ -13,6 +13,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
+
+ROUND = 8  # the file bench.py picks up is the newest profiles/rNN_pmc_traffic.json
 
 
 def counters(path):
@@ -57,10 +59,10 @@ def config_entry(d, cfg, vb, half16):
 def main():
     d, commit = sys.argv[1], sys.argv[2]
     parent = sys.argv[3] if len(sys.argv) > 3 else None
-    res = {"round": 7, "commit": commit, "kernel_sources_sha256": bench.kernel_sources_sha256(), "kernel_sources": list(bench.KERNEL_SOURCES),
+    res = {"round": ROUND, "commit": commit, "kernel_sources_sha256": bench.kernel_sources_sha256(), "kernel_sources": list(bench.KERNEL_SOURCES),
            "collected_by": "the three commands of tools/rocprof_collect.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE in separate passes of "
                            "`python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-more [--pairs N]`, 2^28 elements, summaries under "
-                           "profiles/r07_rocprof/",
+                           f"profiles/r{ROUND:02d}_rocprof/",
            "correction": "FETCH_SIZE x 2 on gfx950 (128-byte requests tallied at 64 B); KiB per dispatch; mean over the WORKING dispatches of a kernel "
                          "(a sort also enqueues launches that exit on their flag word); keys: the pass kernel's mean covers pass A (8 B/key) and "
                          "pass B (6 B/key)"}
@@ -69,7 +71,7 @@ def main():
             res[cfg] = config_entry(d, cfg, vb, half16=vb == 0)
     if parent:
         res["keys_parent"] = config_entry(parent, "keys", 0, half16=False)
-    json.dump(res, open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r07_pmc_traffic.json"), "w"), indent=1)
+    json.dump(res, open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", f"r{ROUND:02d}_pmc_traffic.json"), "w"), indent=1)
     print(json.dumps({k: {kk: vv.get("ratio") for kk, vv in v.items() if isinstance(vv, dict) and "ratio" in vv} for k, v in res.items() if isinstance(v, dict)}))
 
 
