@@ -846,6 +846,28 @@ struct ValT { using type = uint32_t; };
 template <>
 struct ValT<8> { using type = uint64_t; };
 
+// Words of the `misc` region of a pass's LDS (BinCfg::OFF_MISC) ...
+constexpr uint32_t M_CHAIN = 0;       // bin_steal_tile: the chain it took a tile of
+constexpr uint32_t M_TICKET = 1;      // the ticket drawn: the tile's index in its chain (NO_TICKET: every chain is fully claimed)
+constexpr uint32_t M_GAVE_UP = 2;     // set by the look-back if it has to give up: the tile must not scatter
+constexpr uint32_t M_STATUS = 3;      // copy of the sort's status word, read beside the ticket
+constexpr uint32_t M_WAVE_TOTAL = 4;  // [4..7] wave totals of the digit scan (256 digit threads: four waves)
+constexpr uint32_t M_FB_ROW = 8;      // row a stuck look-back asks the workgroup to recount (GS_FALLBACK), 0: none
+constexpr uint32_t M_PLAN = 9;        // [9..15] the pass's flag/plan words, info[PASS_FLAGS ..]: flags, nch, next_shift, seglog, shift, dstride, mode
+constexpr uint32_t M_WORDS = 16;
+constexpr uint32_t m_plan(uint32_t info_word) { return M_PLAN + (info_word - PASS_FLAGS); }  // the LDS copy of info[info_word]
+static_assert(m_plan(I_MODE) == M_WORDS - 1, "the plan words end the misc region");
+// ... and of the `pos` region of the position-chain forms (BinCfg::OFF_POS; POS == 2 has the first P_WORDS_LAST only)
+constexpr uint32_t P_SKEW = 0;        // some digit holds > n/16 keys
+constexpr uint32_t P_MAX = 2;         // [2..3] 64-bit maximum of (count << 8 | 255 - digit): the most frequent digit
+constexpr uint32_t P_LEFT_OUT = 4;    // POS == 1: the next digit this workgroup does NOT count (DIGIT_UNDECIDED until it is elected) ...
+constexpr uint32_t P_ELECTION = 5;    // ... and its election: (popcount << 8) | digit
+constexpr uint32_t P_WRITTEN = 8;     // [8..8 + NCH) keys this workgroup wrote to each output position segment
+constexpr uint32_t P_WORDS = 32, P_WORDS_LAST = 8;
+static_assert(P_WRITTEN + NCH <= P_WORDS && P_MAX + 2 <= P_WORDS_LAST, "pos words");
+constexpr uint32_t NO_TICKET = 0xffffffffu, NO_CHAIN = 0xffffffffu, NO_SHIFT = 0xffffffffu, NO_DIGIT = 0xffffffffu;  // "none" of a ticket, an open chain, a digit position, a digit
+constexpr uint32_t DIGIT_UNDECIDED = 0xfffffffeu;                                            // P_LEFT_OUT: not chosen yet
+
 template <int THREADS, int KPT, int VB, int KW = 1, int VR = 1, int POS = 0>
 struct BinCfg {
     static constexpr int WAVES = THREADS / 64;
@@ -872,8 +894,25 @@ struct BinCfg {
     //  Only where the 32-bit counters do not fit beside a second workgroup: the packed form costs ~2 vector instructions per key.)
     static constexpr bool PACKED = POS == 1 && STAGE_BYTES + WAVES * RADIX * 4 + 2 * RADIX * 4 + 64 + NCH * RADIX * 4 + RADIX * 4 + 128 > 80 * 1024;
     static constexpr int WHIST_BYTES = WAVES * RADIX * (PACKED ? 2 : 4);
-    static constexpr int POS_BYTES = POS == 1 ? (NCH * RADIX * (PACKED ? 2 : 4) + RADIX * 4 + 128) : POS == 2 ? (RADIX * 4 + 32) : 0;
-    static constexpr int LDS_BYTES = STAGE_BYTES + WHIST_BYTES + 2 * RADIX * 4 + 64 + POS_BYTES;
+    // The workgroup's LDS: the regions in their order, each starting where the one before ends (BinLds hands out the pointers) —
+    // stage, per-wave counters, tile-local digit prefix, global digit bases, the M_* words, and for the position-chain forms the
+    // next-digit table (POS == 1), this pass's digit starts and the P_* words.
+    static constexpr int CNT_BYTES = POS == 1 ? NCH * RADIX * (PACKED ? 2 : 4) : 0;
+    static constexpr int DSTART_BYTES = POS ? RADIX * 4 : 0;
+    static constexpr int POSW_BYTES = POS == 1 ? P_WORDS * 4 : POS == 2 ? P_WORDS_LAST * 4 : 0;
+    static constexpr int OFF_WHIST = STAGE_BYTES;  // (the stage is first)
+    static constexpr int OFF_DPRE = OFF_WHIST + WHIST_BYTES;
+    static constexpr int OFF_GBASE = OFF_DPRE + RADIX * 4;
+    static constexpr int OFF_MISC = OFF_GBASE + RADIX * 4;
+    static constexpr int OFF_CNT = OFF_MISC + M_WORDS * 4;
+    static constexpr int OFF_DSTART = OFF_CNT + CNT_BYTES;
+    static constexpr int OFF_POS = OFF_DSTART + DSTART_BYTES;
+    static constexpr int POS_BYTES = CNT_BYTES + DSTART_BYTES + POSW_BYTES;
+    static constexpr int LDS_BYTES = OFF_POS + POSW_BYTES;
+    static_assert(OFF_POS + POSW_BYTES == LDS_BYTES, "the last region ends at LDS_BYTES");  // (definitional: the statement; the guard is the next one)
+    static_assert(LDS_BYTES == STAGE_BYTES + WHIST_BYTES + 2 * RADIX * 4 + 64 +
+                                   (POS == 1 ? (NCH * RADIX * (PACKED ? 2 : 4) + RADIX * 4 + 128) : POS == 2 ? (RADIX * 4 + 32) : 0),
+                  "the regions add up to the closed form every instantiation has always asked for");
     // residency we ask the register allocator for: as many workgroups per CU as
     // LDS (160 KiB) and the 2048-thread limit admit, so that one workgroup's
     // look-back wait is covered by its neighbours' work
@@ -888,9 +927,11 @@ struct BinCfg {
     static constexpr int WAVES_PER_SIMD =
         WAVES_PER_SIMD_RAW < WAVES_PER_SIMD_CAP ? WAVES_PER_SIMD_RAW : WAVES_PER_SIMD_CAP;
 };
+// (the sizes of the headline kernels' forms, as they have always been)
+static_assert(BinCfg<512, 32, 0, 1, 1, 0>::LDS_BYTES == 75840 && BinCfg<512, 32, 0, 1, 1, 1>::LDS_BYTES == 81088 && BinCfg<512, 32, 0, 1, 1, 2>::LDS_BYTES == 76896 &&
+                  BinCfg<1024, 16, 4>::LDS_BYTES == 149568 && BinCfg<512, 32, 8>::LDS_BYTES == 141376 && BinCfg<512, 24, 8, 1, 2, 1>::LDS_BYTES == 76992,
+              "LDS of the binning passes");
 
-// The pass as a device function: one tile (PERSIST = false: one workgroup per tile, the grid covers the tiles) or tile after
-// tile until every chain is claimed (PERSIST = true).  s_raw: Cfg::LDS_BYTES of LDS.
 // Mode word of a DigitBinningPass launch: what the HOST knows about the launch (everything the DEVICE decided is in the pass's flag
 // word PF_* of its info block).  One launch carries at most the bits of its family: plain passes BM_REVERSE / BM_PLANNED /
 // BM_ZERO_HIST (+ BM_IF_SKEW / BM_IF_EVEN for the two forms of the 8-byte-value pass); launches of a sort that may run on position
@@ -904,6 +945,9 @@ constexpr uint32_t BM_FORMS = 64;         // the pass is also launched in its po
 constexpr uint32_t BM_INFO_SHIFT = 128;   // the digit's bit position comes from the info block (I_SHIFT), not from shift_full
 constexpr uint32_t BM_INFO_CHAINS = 256;  // the chain count comes from the info block BEFORE the first ticket (I_NCH may be CHMAX: the two-level plan's second pass)
 constexpr uint32_t BM_ZERO_DESC23 = 512;  // LSD pass 1 of a sort that was offered the two-level plan: zeroes the descriptor regions of passes 2 and 3 if the LSD plan runs
+
+// A value that is the same in every lane of the wave, as a scalar (values read from LDS or through a VGPR index are vector registers to the compiler).
+__device__ __forceinline__ uint32_t uni(const uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // ---------------------------------------------------------------------------
 // binning_body, phase "load": the tile's keys, wave-striped (lane l of wave w holds keys tile_base + 64 KPT w + 64 i + l: coalesced
@@ -1101,14 +1145,13 @@ __device__ __forceinline__ void bin_rank_keys(const uint32_t (&key)[KPT], uint32
 
 // ---------------------------------------------------------------------------
 // binning_body, phase "claim", second half: the workgroup's own chain is fully claimed — take a tile of ANOTHER chain that still has
-// unclaimed tiles.  Leaves the chain in s_misc[0] and the ticket in s_misc[1] (~0: every chain is fully claimed); the caller reads
+// unclaimed tiles.  Leaves the chain in M_CHAIN and the ticket in M_TICKET (NO_TICKET: every chain is fully claimed); the caller reads
 // them behind a barrier.  `chain` = the chain just found exhausted (the linear search starts behind it).
 // ---------------------------------------------------------------------------
 template <uint32_t THREADS, uint32_t TILE>
 __device__ __forceinline__ void bin_steal_tile(const uint32_t nch, const uint32_t chain, const uint32_t* __restrict__ info, uint32_t* __restrict__ counters,
                                                 uint32_t* __restrict__ s_misc) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     // Steal: wave 0 looks at ALL chains in one parallel round trip (lane x = chain x); a serial
     // scan with dependent sc1 loads cost ~22 us per exhausted workgroup and stretched every pass's tail.
     __syncthreads();
@@ -1118,26 +1161,26 @@ __device__ __forceinline__ void bin_steal_tile(const uint32_t nch, const uint32_
         // spread over the open chains) is tried with one ticket, until a ticket holds or no chain is open.
         const uint32_t start = ((blockIdx.x * 0x9E3779B1u) >> 16) & (nch - 1u);
         for (;;) {
-            if (tid == 0) s_misc[0] = 0xffffffffu;
+            if (tid == 0) s_misc[M_CHAIN] = NO_CHAIN;
             __syncthreads();
             if (tid < nch) {
                 const uint32_t tx = chain_tiles(info[I_START + tid], info[I_END + tid], TILE);
-                if (ld_agent(&counters[tid * COUNTER_STRIDE]) < tx) atomicMin(&s_misc[0], (((tid - start) & (nch - 1u)) << 16) | tid);
+                if (ld_agent(&counters[tid * COUNTER_STRIDE]) < tx) atomicMin(&s_misc[M_CHAIN], (((tid - start) & (nch - 1u)) << 16) | tid);
             }
             __syncthreads();
-            const uint32_t cand = uni(s_misc[0]);
-            if (cand == 0xffffffffu) {  // every chain is fully claimed
-                if (tid == 0) s_misc[1] = 0xffffffffu;
+            const uint32_t cand = uni(s_misc[M_CHAIN]);
+            if (cand == NO_CHAIN) {  // every chain is fully claimed
+                if (tid == 0) s_misc[M_TICKET] = NO_TICKET;
                 break;
             }
             const uint32_t x = cand & 0xffffu;
             if (tid == 0) {
                 const uint32_t t = atomicAdd(&counters[x * COUNTER_STRIDE], 1u);
-                s_misc[1] = t < chain_tiles(info[I_START + x], info[I_END + x], TILE) ? t : 0xffffffffu;
+                s_misc[M_TICKET] = t < chain_tiles(info[I_START + x], info[I_END + x], TILE) ? t : NO_TICKET;
             }
             __syncthreads();
-            if (uni(s_misc[1]) != 0xffffffffu) {
-                if (tid == 0) s_misc[0] = x;
+            if (uni(s_misc[M_TICKET]) != NO_TICKET) {
+                if (tid == 0) s_misc[M_CHAIN] = x;
                 break;
             }
         }
@@ -1149,7 +1192,7 @@ __device__ __forceinline__ void bin_steal_tile(const uint32_t nch, const uint32_
             open = ld_agent(&counters[lane * COUNTER_STRIDE]) < tiles_x;
         }
         unsigned long long m = __builtin_amdgcn_ballot_w64(open);
-        uint32_t got_x = 0, got_t = 0xffffffffu;
+        uint32_t got_x = 0, got_t = NO_TICKET;
         // First try: a chain drawn in proportion to the chains' tile counts (Fibonacci hashing of the
         // workgroup id: consecutive ids spread evenly over the cumulative tile range).  With skewed
         // digit groups most workgroups land here — their own chain is tiny — and the big chains still
@@ -1178,7 +1221,7 @@ __device__ __forceinline__ void bin_steal_tile(const uint32_t nch, const uint32_
             if (t < tx) { got_x = x; got_t = t; break; }
             m &= ~(1ull << x);
         }
-        if (lane == 0) { s_misc[0] = got_x; s_misc[1] = got_t; }
+        if (lane == 0) { s_misc[M_CHAIN] = got_x; s_misc[M_TICKET] = got_t; }
     }
 }
 
@@ -1206,11 +1249,11 @@ __device__ __forceinline__ void bin_load_values(const V* __restrict__ vals_in, c
 // binning_body, phase "count-next" (POS == 1), once per workgroup: the next-pass digit this workgroup does NOT count while it scatters
 // (its counts are recovered at the flush from the keys written per segment).  Every wave looks at 64 staged keys of its own (`mine` =
 // this lane's), eight candidate lanes each; a digit that at least 8 of the 64 share is a find, the most frequent find wins
-// (s_pos[5] = (popcount << 8) | digit) and becomes s_pos[4]; without a find the choice is left to the next tile.
+// (P_ELECTION = (popcount << 8) | digit) and becomes P_LEFT_OUT; without a find the choice is left to the next tile.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void bin_elect_left_out_digit(const uint32_t* __restrict__ mine, const uint32_t next_shift, uint32_t* __restrict__ s_pos) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    __syncthreads();  // (everybody has read s_pos[4])
+    __syncthreads();  // (everybody has read P_LEFT_OUT)
     {
         const uint32_t d0 = (*mine >> next_shift) & 255u;
         uint32_t best = 0;  // (popcount << 8) | digit
@@ -1220,10 +1263,10 @@ __device__ __forceinline__ void bin_elect_left_out_digit(const uint32_t* __restr
             const uint32_t pc = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(d0 == cand));
             best = ((pc << 8) | cand) > best ? ((pc << 8) | cand) : best;
         }
-        if (lane == 0 && (best >> 8) >= 8u) atomicMax(&s_pos[5], best);
+        if (lane == 0 && (best >> 8) >= 8u) atomicMax(&s_pos[P_ELECTION], best);
     }
     __syncthreads();
-    if (tid == 0 && s_pos[5] != 0u) s_pos[4] = s_pos[5] & 255u;
+    if (tid == 0 && s_pos[P_ELECTION] != 0u) s_pos[P_LEFT_OUT] = s_pos[P_ELECTION] & 255u;
     __syncthreads();
 }
 
@@ -1263,23 +1306,225 @@ __device__ __forceinline__ bool bin_entry(const uint32_t mode, const uint32_t* _
     return true;
 }
 
-// MAP of binning_body.  The phases with a narrow interface are functions of their own above (bin_entry, bin_steal_tile, bin_load_keys,
-// bin_load_values, bin_rank_keys, bin_elect_left_out_digit: round 6); what is left in the body works on the tile's state all at once —
-// key[KPT], the packed ranks offp[], the per-digit prefixes and bases in LDS, the chain's descriptor rows — and would pass ~30 of them
-// by reference.  The compile-time switches prune each instantiation to the phases its kernel needs.  Phases, in order:
+// ---------------------------------------------------------------------------
+// The LDS of a DigitBinningPass workgroup: one pointer per region of BinCfg's layout, from the block's first byte (the words of `misc`
+// and `pos`: M_* and P_* above).  Functions of the base pointer, not an object holding pointers: see DESIGN.md, "binning_body in phases".
+// ---------------------------------------------------------------------------
+template <class Cfg>
+struct BinLds {
+    using B = unsigned char*;
+    static __device__ __forceinline__ uint32_t* at(B raw, const int off) { return reinterpret_cast<uint32_t*>(raw + off); }
+    static __device__ __forceinline__ uint32_t* stage(B raw) { return reinterpret_cast<uint32_t*>(raw); }  // keys in digit order (stable)
+    static __device__ __forceinline__ uint32_t* whist(B raw) { return at(raw, Cfg::OFF_WHIST); }    // per-wave digit counters (PACKED: two waves per word), later each wave's stage offsets
+    static __device__ __forceinline__ uint32_t* dpre(B raw) { return at(raw, Cfg::OFF_DPRE); }      // tile-local exclusive digit prefix
+    static __device__ __forceinline__ uint32_t* gbase(B raw) { return at(raw, Cfg::OFF_GBASE); }    // global base of digit run minus dpre
+    static __device__ __forceinline__ uint32_t* misc(B raw) { return at(raw, Cfg::OFF_MISC); }      // M_*
+    static __device__ __forceinline__ uint32_t* cnt(B raw) { return at(raw, Cfg::OFF_CNT); }        // POS == 1: [NCH][256] keys written to position segment x whose next digit is d (PACKED: 16 bits each)
+    static __device__ __forceinline__ uint32_t* dstart(B raw) { return at(raw, Cfg::OFF_DSTART); }  // POS: digit starts of this pass (from the counts of the pass before)
+    static __device__ __forceinline__ uint32_t* pos(B raw) { return at(raw, Cfg::OFF_POS); }        // POS: P_*
+};
+
+// Packed registers: two 16-bit ranks (later: stage positions) per word of offp[], four 8-bit digits per word of digs[].
+template <int N>
+__device__ __forceinline__ uint32_t rank16(const uint32_t (&offp)[N], const int i) { return (offp[i >> 1] >> (16 * (i & 1))) & 0xffffu; }
+template <int N>
+__device__ __forceinline__ void set_rank16(uint32_t (&offp)[N], const int i, const uint32_t v) {
+    if ((i & 1) == 0) offp[i >> 1] = (offp[i >> 1] & 0xffff0000u) | v;
+    else offp[i >> 1] = (offp[i >> 1] & 0x0000ffffu) | (v << 16);
+}
+template <int N>
+__device__ __forceinline__ uint32_t digit8(const uint32_t (&digs)[N], const int j) { return (digs[j >> 2] >> (8 * (j & 3))) & 255u; }
+template <int N>
+__device__ __forceinline__ void add_digit8(uint32_t (&digs)[N], const int j, const uint32_t d) { digs[j >> 2] |= d << (8 * (j & 3)); }
+
+// Output index under the descending rule (last pass): n-1-o == (o ^ ~0) + n, folded into two uniform operands (rev_xor, rev_add:
+// ~0 and n, or 0 and 0) so that the straight-line scatter of a full tile serves both orders.
+__device__ __forceinline__ uint32_t out_index(const uint32_t o, const uint32_t rev_xor, const uint32_t rev_add) { return (o ^ rev_xor) + rev_add; }
+// ... and as a branch, in the loops of partial tiles, which branch per slot anyway
+__device__ __forceinline__ uint32_t out_index_branch(const uint32_t o, const bool reverse, const uint32_t n) { return reverse ? n - 1u - o : o; }
+
+// Stage slot i holds a key of the segment (not a dummy in front of or behind it).
+__device__ __forceinline__ bool bin_slot_valid(const bool full, const uint32_t head, const uint32_t count, const uint32_t i) {
+    return full || (i >= head && i < head + count);
+}
+
+// ---------------------------------------------------------------------------
+// binning_body, phase "POS setup": what a workgroup of a position-chain pass sets up once.  Behind the first pass nobody knows the pass's
+// digit counts upfront: CNEXT[this pass][segment][digit] (cn_in), gathered by the pass that wrote this pass's input, is all there
+// is — every workgroup derives the digit starts (s_dstart), whether the pass is skewed and its most frequent digit
+// from it (16 coalesced loads per digit thread); tile 0 of each chain turns it into the chain's row 0.  POS == 1: clears the next-digit
+// table and the P_* words.  Returns (uniform): derived — anything was derived at all; skew — some digit holds > n/16 keys; mode — that digit.
+// ---------------------------------------------------------------------------
+struct BinPosPlan {
+    bool derived, skew;
+    uint32_t mode;
+};
+template <uint32_t THREADS, int POS, bool PK>
+__device__ __forceinline__ BinPosPlan bin_pos_setup(uint32_t* s_cnt, uint32_t* s_pos, uint32_t* s_misc, uint32_t* s_dstart, const uint32_t* cn_in, const uint32_t n,
+                                                     const uint32_t shift_full) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    bool pos_derived = false, pos_skew = false;
+    uint32_t pos_mode = NO_DIGIT;
+    if constexpr (POS != 0) {
+        if constexpr (POS == 1) {
+            for (uint32_t i = tid; i < NCH * RADIX / (PK ? 2 : 1); i += THREADS) s_cnt[i] = 0;
+            if (tid < P_WORDS && tid >= P_LEFT_OUT) s_pos[tid] = tid == P_LEFT_OUT ? DIGIT_UNDECIDED : 0u;
+        }
+        pos_derived = shift_full != 0u;  // (the first pass of a PF_POS sort is never dropped: its chains come from the Scan kernel)
+        if (pos_derived) {
+            uint32_t G = 0, incl = 0;
+            if (tid < P_LEFT_OUT) s_pos[tid] = 0;
+            if (tid < RADIX) {
+#pragma unroll
+                for (uint32_t x = 0; x < NCH; ++x) G += cn_in[x * RADIX + tid];
+                incl = wave_inclusive_scan_dpp(G);
+                if (lane == 63) s_misc[M_WAVE_TOTAL + wave] = incl;
+            }
+            __syncthreads();
+            if (tid < RADIX) {
+                uint32_t wbase = 0;
+                for (uint32_t w = 0; w < wave; ++w) wbase += s_misc[M_WAVE_TOTAL + w];
+                s_dstart[tid] = wbase + incl - G;
+                if (G >= (n >> SKEW_SHIFT) + 1u) {
+                    s_pos[P_SKEW] = 1u;
+                    atomicMax(reinterpret_cast<unsigned long long*>(s_pos + P_MAX), ((unsigned long long)G << 8) | (255u - tid));
+                }
+            }
+            __syncthreads();
+            pos_skew = uni(s_pos[P_SKEW]) != 0u;
+            pos_mode = pos_skew ? 255u - (uni(s_pos[P_MAX]) & 255u) : NO_DIGIT;
+        }
+    }
+    return BinPosPlan{pos_derived, pos_skew, pos_mode};
+}
+
+// ---------------------------------------------------------------------------
+// binning_body, phase "table guard" (POS == 1, packed table), before every tile: a tile adds at most TILE = 16 384 to a counter, so a
+// counter at or above 0xC000 goes to CNEXT now (and out of the segment's written-keys total, which the left-out digit is recovered
+// from).  Nobody adds to the table between the barrier that opens the tile and this tile's scatter.  Rare: a workgroup sees ~32
+// tiles, and its most frequent next digit is not counted at all.  guard_ns: the digit position this workgroup counts for (NO_SHIFT: none).
+// ---------------------------------------------------------------------------
+template <uint32_t THREADS>
+__device__ __forceinline__ void bin_guard_packed_table(uint32_t* s_cnt, uint32_t* s_pos, uint32_t* hsub, const uint32_t guard_ns) {
+    const uint32_t tid = threadIdx.x;
+    if (guard_ns != NO_SHIFT) {  // uniform
+        for (uint32_t i = tid; i < NCH * RADIX / 2; i += THREADS) {
+            uint32_t w = s_cnt[i];
+            if (GS_UNLIKELY((w & (w << 1) & 0x80008000u) != 0u)) {
+                uint32_t* cn_out = hsub + (guard_ns >> 3) * HSUB_STRIDE;
+#pragma unroll
+                for (uint32_t h = 0; h < 2; ++h) {
+                    const uint32_t v = (w >> (16u * h)) & 0xffffu;
+                    if (v >= 0xC000u) {
+                        atomicAdd(&cn_out[2u * i + h], v);
+                        atomicSub(&s_pos[P_WRITTEN + (i >> 7)], v);
+                        w &= ~(0xffffu << (16u * h));
+                    }
+                }
+                s_cnt[i] = w;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// binning_body, phase "written keys" (POS == 1), per digit thread with keys in this tile: the keys this tile writes per output position
+// segment, from the run's geometry [prev, prev + tile_total) (ONE LDS add per run, two for the rare run across a segment boundary): what
+// count_next leaves out — the workgroup's hot next digit — is recovered from these totals when the table is flushed.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void bin_note_written_keys(uint32_t* s_pos, const uint32_t seglog, const uint32_t prev, const uint32_t tile_total) {
+    const uint32_t x0 = prev >> seglog, x1 = (prev + tile_total - 1u) >> seglog;
+    if (x0 == x1) {
+        atomicAdd(&s_pos[P_WRITTEN + x0], tile_total);
+    } else {  // (a run is shorter than a segment: two segments at most)
+        const uint32_t first = ((x0 + 1u) << seglog) - prev;
+        atomicAdd(&s_pos[P_WRITTEN + x0], first);
+        atomicAdd(&s_pos[P_WRITTEN + x1], tile_total - first);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// binning_body, phase "exit" (POS == 1), when the workgroup has run out of tiles: hand the counts to the next pass that runs —
+// CNEXT[that pass][segment][digit] += this workgroup's table, the left-out digit's counts first recovered per segment as the keys
+// written to it (P_WRITTEN) minus everything that was counted.
+// ---------------------------------------------------------------------------
+template <uint32_t THREADS, uint32_t WAVES, bool PK>
+__device__ __forceinline__ void bin_flush_cnext(uint32_t* s_cnt, uint32_t* s_pos, const uint32_t* info, uint32_t* hsub,
+                                                 const uint32_t mode) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t ns = uni(info[I_NEXT_SHIFT]);
+    if ((mode & BM_PLANNED) && ns != NO_SHIFT && !(uni(info[PASS_FLAGS]) & PF_SKIP)) {
+        __syncthreads();
+        const uint32_t left_out = uni(s_pos[P_LEFT_OUT]);
+        uint32_t* cn_out = hsub + (ns >> 3) * HSUB_STRIDE;
+        if constexpr (PK) {
+            if (left_out < RADIX) {  // the digit count_next skipped: keys written to the segment minus everything that was counted
+                const uint32_t lo_word = left_out >> 1, lo_keep = 0xffff0000u >> ((left_out & 1u) * 16u);  // its word in a row, the OTHER half
+                for (uint32_t x = wave; x < NCH; x += WAVES) {
+                    uint32_t sum = 0;
+                    for (uint32_t c = lane; c < RADIX / 2; c += 64u) {
+                        uint32_t w = s_cnt[x * (RADIX / 2) + c];
+                        if (c == lo_word) w &= lo_keep;  // (what the tiles in front of the choice counted for it is part of the total)
+                        sum += (w & 0xffffu) + (w >> 16);
+                    }
+                    sum = wave_reduce_sum(sum);
+                    if (lane == 0) {
+                        const uint32_t v = s_pos[P_WRITTEN + x] - sum;
+                        if (v != 0u) atomicAdd(&cn_out[x * RADIX + left_out], v);
+                        s_cnt[x * (RADIX / 2) + lo_word] &= lo_keep;
+                    }
+                }
+                __syncthreads();
+            }
+            // (Round 4, measured and not kept: one copy of the table per XCD — workgroup b adds to copy b % 8, the last workgroup of the
+            //  pass to arrive sums the copies — against the same-address contention of these atomics: the counting passes got SLOWER,
+            //  0.566 -> 0.588 ms at entropy preset 3, profiles/r04_pos_flush_copies.txt: non-returning atomics do not hold the
+            //  workgroups up, the closing sum by one workgroup does.)
+            for (uint32_t i = tid; i < NCH * RADIX / 2; i += THREADS) {
+                const uint32_t w = s_cnt[i];
+                if ((w & 0xffffu) != 0u) atomicAdd(&cn_out[2u * i], w & 0xffffu);
+                if ((w >> 16) != 0u) atomicAdd(&cn_out[2u * i + 1u], w >> 16);
+            }
+        } else {
+            if (left_out < RADIX) {  // the digit count_next skipped: keys written to the segment minus everything that was counted
+                for (uint32_t x = wave; x < NCH; x += WAVES) {
+                    uint32_t sum = 0;
+                    for (uint32_t d = lane; d < RADIX; d += 64u) sum += d == left_out ? 0u : s_cnt[x * RADIX + d];
+                    sum = wave_reduce_sum(sum);
+                    if (lane == 0) s_cnt[x * RADIX + left_out] = s_pos[P_WRITTEN + x] - sum;
+                }
+                __syncthreads();
+            }
+            for (uint32_t i = tid; i < NCH * RADIX; i += THREADS) {
+                const uint32_t v = s_cnt[i];
+                if (v != 0u) atomicAdd(&cn_out[i], v);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// The pass as a device function: one tile (PERSIST = false: one workgroup per tile, the grid covers the tiles) or tile after
+// tile until every chain is claimed (PERSIST = true).  s_raw: Cfg::LDS_BYTES of LDS.  MAP of binning_body: the phases in order; a name
+// is a function above (scalars by value, register arrays by reference), "inline" a phase that stays in the body under its `----` heading,
+// because as a function — or on a tile-state struct handed to the phases by reference — it compiled to other registers and spills in
+// most instantiations ("binning_body in phases").  The compile-time switches prune each instantiation to the phases its kernel needs.
 //   entry      bin_entry: BM_ZERO_HIST / BM_ZERO_DESC23 zeroing; BM_IF_* / BM_FORMS: does THIS form of the pass work?
-//   POS setup  (POS != 0) digit starts / skew / mode digit from CNEXT of the pass before; the workgroup's next-digit table
+//   POS setup  bin_pos_setup (POS != 0): digit starts / skew / mode digit from CNEXT of the pass before; the workgroup's next-digit table
 //   [tile loop, PERSIST: until every chain is claimed]
-//   claim      ticket on the workgroup's chain (BM_INFO_CHAINS: chain groups of a CHMAX-chain pass), else bin_steal_tile
+//   guard      bin_guard_packed_table (POS == 1, packed): next-digit counters near overflow go to CNEXT early
+//   claim      inline: ticket on the workgroup's chain (BM_INFO_CHAINS: chain groups of a CHMAX-chain pass), else bin_steal_tile
 //   load       bin_load_keys (KW == 2: 64-bit keys carry their other word along); partial tiles masked; fused forms: bin_load_values
 //   rank       bin_rank_keys — RANK 0: eight-ballot multi-split; RANK 1: one returning LDS add per key (crowded waves, partial tiles, skew)
-//   reduce     per-digit exclusive prefix over waves, tile total, REDUCTION row published, digit scan
-//   stage      keys to LDS in digit order (VR == 2: 8-byte values in two staging rounds)
-//   look-back  one digit per thread walks the chain's rows back to an INCLUSIVE one; GS_FALLBACK: recount a row nobody published
+//   reduce     inline: per-digit exclusive prefix over waves, tile total, REDUCTION row published, digit scan
+//   stage      inline: keys to LDS in digit order (VR == 2: 8-byte values in two staging rounds)
+//   look-back  inline: one digit per thread walks the chain's rows back to an INCLUSIVE one; GS_FALLBACK: recount a row nobody published
+//   written    bin_note_written_keys (POS == 1): keys written per output position segment
 //   values     (VB != 0, not fused) bin_load_values: fetched late, staged behind the keys
 //   count-next (POS == 1) bin_elect_left_out_digit once; the next pass's digit counted per output position segment while scattering
-//   scatter    stage slot i -> global base of its digit + i (reverse: the descending rule on the plan's last pass), coalesced runs
-//   exit       (POS == 1) CNEXT flush; trace / fault hooks of experiment builds
+//   scatter    inline: stage slot i -> global base of its digit + i (out_index: the descending rule on the plan's last pass), coalesced runs
+//   exit       bin_flush_cnext (POS == 1); trace / fault hooks of experiment builds
+// ---------------------------------------------------------------------------
 template <int THREADS, int KPT, int VB, int KT, int RANK, int VR, int POS, bool PERSIST>
 __device__ __forceinline__ void binning_body(
     unsigned char* s_raw,
@@ -1313,66 +1558,26 @@ __device__ __forceinline__ void binning_body(
     const bool hi_word = KW == 2 && shift_full >= 32u;
     static_assert(THREADS >= 256 && THREADS % 64 == 0, "need >= 256 threads");
     static_assert(KPT % 4 == 0 && TILE <= 65536, "offsets are packed 2 x 16 bit, digits 4 x 8 bit");
-    auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
 
     static_assert(POS == 0 || PERSIST, "the position-chain forms keep state across their tiles");
     // packed counters: two waves share a counter word and only the returning-atomic ranking adds to its own half (the ballot
     // ranking stores whole words); the overflow guard of the packed next-digit table (0xC000 + TILE <= 0xFFFF) holds up to 16 384 keys
     static_assert(!(Cfg::PACKED && RANK == 0), "packed per-wave counters need the LDS-atomic ranking");
     static_assert(!Cfg::PACKED || Cfg::TILE <= 16384, "packed next-digit counters: a tile adds at most 16 384 to a 16-bit counter flushed at 0xC000");
-    uint32_t* s_stage = reinterpret_cast<uint32_t*>(s_raw);
-    uint32_t* s_whist = reinterpret_cast<uint32_t*>(s_raw + Cfg::STAGE_BYTES);
-    constexpr bool PK = Cfg::PACKED;             // two 16-bit counters per word: per-wave rank counters and next-digit table
-    uint32_t* s_dpre = s_whist + Cfg::WHIST_BYTES / 4;  // tile-local exclusive digit prefix
-    uint32_t* s_gbase = s_dpre + RADIX;          // global base of digit run minus s_dpre
-    uint32_t* s_misc = s_gbase + RADIX;          // [0] chain, [1] ticket (~0 = none), [4..7] wave totals of the digit scan,
-                                                 // [9..14] the pass's flag/plan words
-    uint32_t* s_cnt = s_misc + 16;               // POS: [NCH][256] keys written to position segment x whose next digit is d, 16 bits each
-    uint32_t* s_dstart = s_cnt + (POS == 1 ? NCH * RADIX / (PK ? 2 : 1) : 0);  // POS: digit starts of this pass (from the counts of the pass before)
-    uint32_t* s_pos = s_dstart + (POS ? RADIX : 0);        // POS: [0] some digit holds > n/16 keys, [2..3] (count << 8 | 255 - digit) max;
-                                                           // POS == 1: [4] the next digit this workgroup does NOT count (see count_next), [5] its election, [8..23] keys written per output segment
+    constexpr bool PK = Cfg::PACKED;  // two 16-bit counters per word: per-wave rank counters and next-digit table
+    using Lds = BinLds<Cfg>;
+    uint32_t *s_stage = Lds::stage(s_raw), *s_whist = Lds::whist(s_raw), *s_dpre = Lds::dpre(s_raw), *s_gbase = Lds::gbase(s_raw);
+    uint32_t *s_misc = Lds::misc(s_raw), *s_cnt = Lds::cnt(s_raw), *s_dstart = Lds::dstart(s_raw), *s_pos = Lds::pos(s_raw);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
 
     if (!bin_entry<(uint32_t)THREADS, POS>(mode, info, desc, hsub)) return;  // launch-level duties; is this form of the pass the one that works?
-    // ---- POS: what a workgroup of a position-chain pass sets up once.  Behind the first pass nobody knows the pass's digit
-    // counts upfront: CNEXT[this pass][segment][digit], gathered by the pass that wrote this pass's input, is all there
-    // is — every workgroup derives the digit starts (s_dstart), whether the pass is skewed and its most frequent digit
-    // from it (16 coalesced loads per digit thread); tile 0 of each chain turns it into the chain's row 0.
-    bool pos_derived = false, pos_skew = false;  // uniform
-    uint32_t pos_mode = 0xffffffffu, cnt_guess = 0xffffffffu;
-    const uint32_t* cn_in = hsub + (shift_full >> 3) * HSUB_STRIDE;
-    if constexpr (POS != 0) {
-        if constexpr (POS == 1) {
-            for (uint32_t i = tid; i < NCH * RADIX / (PK ? 2 : 1); i += THREADS) s_cnt[i] = 0;
-            if (tid < 32u && tid >= 4u) s_pos[tid] = tid == 4u ? 0xfffffffeu : 0u;  // [4]: not chosen yet
-        }
-        pos_derived = shift_full != 0u;  // (the first pass of a PF_POS sort is never dropped: its chains come from the Scan kernel)
-        if (pos_derived) {
-            uint32_t G = 0, incl = 0;
-            if (tid < 4) s_pos[tid] = 0;
-            if (tid < RADIX) {
-#pragma unroll
-                for (uint32_t x = 0; x < NCH; ++x) G += cn_in[x * RADIX + tid];
-                incl = wave_inclusive_scan_dpp(G);
-                if (lane == 63) s_misc[4 + wave] = incl;
-            }
-            __syncthreads();
-            if (tid < RADIX) {
-                uint32_t wbase = 0;
-                for (uint32_t w = 0; w < wave; ++w) wbase += s_misc[4 + w];
-                s_dstart[tid] = wbase + incl - G;
-                if (G >= (n >> SKEW_SHIFT) + 1u) {
-                    s_pos[0] = 1u;
-                    atomicMax(reinterpret_cast<unsigned long long*>(s_pos + 2), ((unsigned long long)G << 8) | (255u - tid));
-                }
-            }
-            __syncthreads();
-            pos_skew = uni(s_pos[0]) != 0u;
-            pos_mode = pos_skew ? 255u - (uni(s_pos[2]) & 255u) : 0xffffffffu;
-        }
-    }
-    // (POS == 1) the digit position this workgroup counts for, ~0: none — the same word every tile reads below as next_shift
-    const uint32_t guard_ns = (POS == 1 && (mode & BM_PLANNED)) ? uni(info[I_NEXT_SHIFT]) : 0xffffffffu;
+    uint32_t cnt_guess = NO_DIGIT;
+    const uint32_t* cn_in = hsub + (shift_full >> 3) * HSUB_STRIDE;  // CNEXT[this pass]
+    const BinPosPlan pos_plan = bin_pos_setup<(uint32_t)THREADS, POS, PK>(s_cnt, s_pos, s_misc, s_dstart, cn_in, n, shift_full);
+    const bool pos_derived = pos_plan.derived, pos_skew = pos_plan.skew;  // uniform
+    const uint32_t pos_mode = pos_plan.mode;
+    // (POS == 1) the digit position this workgroup counts for, NO_SHIFT: none — the same word every tile reads below as next_shift
+    const uint32_t guard_ns = (POS == 1 && (mode & BM_PLANNED)) ? uni(info[I_NEXT_SHIFT]) : NO_SHIFT;
     GS_TRACE_SETUP();
     // (measured and not kept, PERSIST: the next tile's ticket drawn while this tile is scattered — +0.5 .. 1 %: a tile claimed
     //  4 us before its workgroup starts on it publishes its counts 4 us late for the tiles behind it,
@@ -1380,30 +1585,7 @@ __device__ __forceinline__ void binning_body(
 #pragma unroll 1
     for (;;) {  // PERSIST: one tile after the other until every chain is claimed; otherwise ONE tile per workgroup
     if constexpr (PERSIST) __syncthreads();  // the last tile's readers of the stage and of s_misc are through
-    if constexpr (POS == 1 && PK) {
-        // Overflow guard of the packed next-digit table: a tile adds at most TILE = 16 384 to a counter, so a counter at or above
-        // 0xC000 goes to CNEXT now (and out of the segment's written-keys total, which the left-out digit is recovered from).
-        // Nobody adds to the table between the barrier above and this tile's scatter.  Rare: a workgroup sees ~32 tiles, and its
-        // most frequent next digit is not counted at all.
-        if (guard_ns != 0xffffffffu) {  // uniform
-            for (uint32_t i = tid; i < NCH * RADIX / 2; i += THREADS) {
-                uint32_t w = s_cnt[i];
-                if (GS_UNLIKELY((w & (w << 1) & 0x80008000u) != 0u)) {
-                    uint32_t* cn_out = hsub + (guard_ns >> 3) * HSUB_STRIDE;
-#pragma unroll
-                    for (uint32_t h = 0; h < 2; ++h) {
-                        const uint32_t v = (w >> (16u * h)) & 0xffffu;
-                        if (v >= 0xC000u) {
-                            atomicAdd(&cn_out[2u * i + h], v);
-                            atomicSub(&s_pos[8u + (i >> 7)], v);
-                            w &= ~(0xffffu << (16u * h));
-                        }
-                    }
-                    s_cnt[i] = w;
-                }
-            }
-        }
-    }
+    if constexpr (POS == 1 && PK) bin_guard_packed_table<(uint32_t)THREADS>(s_cnt, s_pos, hsub, guard_ns);  // next-digit counters near overflow go to CNEXT now
     for (uint32_t i = tid; i < Cfg::WHIST_BYTES / 4; i += THREADS) s_whist[i] = 0;
     GS_TRACE(0);
     // ---- claim a tile.  Fast path: ONE returning atomic on the ticket counter of
@@ -1415,21 +1597,21 @@ __device__ __forceinline__ void binning_body(
     // their round trip runs beside the ticket atomic's instead of after the barrier
     const uint32_t seg_start_f = info[I_START + chain], seg_end_f = info[I_END + chain], row_f = info[I_ROW + chain];
     if (tid == 0) {
-        s_misc[2] = 0u;  // set by the look-back if it has to give up
-        s_misc[8] = 0u;  // row a stuck look-back asks the workgroup to recount (GS_FALLBACK)
-        s_misc[1] = atomicAdd(&counters[chain * COUNTER_STRIDE], 1u);
+        s_misc[M_GAVE_UP] = 0u;  // set by the look-back if it has to give up
+        s_misc[M_FB_ROW] = 0u;  // row a stuck look-back asks the workgroup to recount (GS_FALLBACK)
+        s_misc[M_TICKET] = atomicAdd(&counters[chain * COUNTER_STRIDE], 1u);
     }
     // An earlier pass of this sort gave up (status word set): its output is incomplete, so positions derived
     // from the upfront histograms no longer bound this pass's writes — do nothing.  Read by another wave, in
     // flight together with the ticket atomic, so it adds no latency.  Same for the pass's flag and plan words.
-    if (tid == 64) s_misc[3] = ld_agent(status);
-    if (tid >= 128 && tid < 135) s_misc[9 + (tid - 128)] = info[PASS_FLAGS + (tid - 128)];  // flags, nch, next_shift, seglog, -, -, mode
+    if (tid == 64) s_misc[M_STATUS] = ld_agent(status);
+    if (tid >= 128 && tid < 135) s_misc[M_PLAN + (tid - 128)] = info[PASS_FLAGS + (tid - 128)];  // flags, nch, next_shift, seglog, shift, dstride, mode
     __syncthreads();
     // Everything below that is the same for the whole workgroup is made SCALAR explicitly (values read from LDS
     // or through a VGPR index are vector registers to the compiler: pointers selected by them cost two VGPRs
     // each and a 64-bit vector add per access, and every branch on them is an exec-mask branch).
-    if (uni(s_misc[3]) != STATUS_OK) break;
-    const uint32_t pflags = uni(s_misc[9]) | (pos_skew ? PF_SKEW : 0u);
+    if (uni(s_misc[M_STATUS]) != STATUS_OK) break;
+    const uint32_t pflags = uni(s_misc[m_plan(PASS_FLAGS)]) | (pos_skew ? PF_SKEW : 0u);
     if ((mode & BM_PLANNED) && (pflags & PF_SKIP)) break;  // identity pass of a full sort
     const bool swapped = (mode & BM_PLANNED) && (pflags & PF_SRC_ALT);
     const uint32_t* keys_in = swapped ? keys_b : keys_a;
@@ -1441,10 +1623,10 @@ __device__ __forceinline__ void binning_body(
     // stores halfwords, and hy_half_slot's addend — folded into s_gbase below — carries the order: no index reversal
     const bool half16 = HALF16_FORM && (pflags & PF_HALF16) != 0u;
     const bool reverse = descending && !half16;
-    const uint32_t nch = uni(s_misc[10]);                                 // chains of this pass
+    const uint32_t nch = uni(s_misc[m_plan(I_NCH)]);                                 // chains of this pass
     // POS: bit position of the next running pass's digit (~0: nothing to count) and log2 of its position segments
-    const uint32_t next_shift = (POS == 1 && (mode & BM_PLANNED)) ? uni(s_misc[11]) : 0xffffffffu, seglog = uni(s_misc[12]);
-    uint32_t tile = uni(s_misc[1]);
+    const uint32_t next_shift = (POS == 1 && (mode & BM_PLANNED)) ? uni(s_misc[m_plan(I_NEXT_SHIFT)]) : NO_SHIFT, seglog = uni(s_misc[m_plan(I_SEGLOG)]);
+    uint32_t tile = uni(s_misc[M_TICKET]);
     // A chain's tile grid starts at its segment start rounded DOWN to 64 keys, so every
     // wave-load is 256-byte aligned; keys in front of the segment are masked like the tail.
     uint32_t seg_start = uni(seg_start_f), seg_end = uni(seg_end_f), row0 = uni(row_f);
@@ -1457,9 +1639,9 @@ __device__ __forceinline__ void binning_body(
         }
         bin_steal_tile<(uint32_t)THREADS, TILE>(nch, chain, info, counters, s_misc);
         __syncthreads();
-        chain = uni(s_misc[0]);
-        tile = uni(s_misc[1]);
-        if (tile == 0xffffffffu) break;  // every chain is fully claimed
+        chain = uni(s_misc[M_CHAIN]);
+        tile = uni(s_misc[M_TICKET]);
+        if (tile == NO_TICKET) break;  // every chain is fully claimed
         seg_start = uni(info[I_START + chain]);
         seg_end = uni(info[I_END + chain]);
         row0 = uni(info[I_ROW + chain]);
@@ -1504,7 +1686,7 @@ __device__ __forceinline__ void binning_body(
 #pragma unroll
     for (int i = 0; i < KPT / 2; ++i) offp[i] = 0;
     bin_rank_keys<KPT, RANK, PK>(key, offp, shift, whist, wsh, pflags, full, my_base, hi,
-                                 ((pflags & PF_SKEW) != 0u) ? (pos_derived ? pos_mode : uni(s_misc[15])) : 0u, lane);
+                                 ((pflags & PF_SKEW) != 0u) ? (pos_derived ? pos_mode : uni(s_misc[m_plan(I_MODE)])) : 0u, lane);
     GS_TRACE(2);
     __syncthreads();
 
@@ -1537,12 +1719,12 @@ __device__ __forceinline__ void binning_body(
         if (!GS_FAULT_TILE(chain, tile))
             st_agent(&cdesc[(size_t)(tile + 1u) * RADIX + tid], (tile_total << 2) | FLAG_REDUCTION);
         scan_incl = wave_inclusive_scan_dpp(run);
-        if (lane == 63) s_misc[4 + wave] = scan_incl;
+        if (lane == 63) s_misc[M_WAVE_TOTAL + wave] = scan_incl;
     }
     __syncthreads();
     if (tid < RADIX) {
         uint32_t wbase = 0;
-        for (uint32_t w = 0; w < wave; ++w) wbase += s_misc[4 + w];
+        for (uint32_t w = 0; w < wave; ++w) wbase += s_misc[M_WAVE_TOTAL + w];
         dpre = wbase + scan_incl - (tile_total + dummies);  // stage offset of the run (dummies included)
         s_dpre[tid] = dpre;
 #pragma unroll
@@ -1570,15 +1752,14 @@ __device__ __forceinline__ void binning_body(
 #pragma unroll
         for (int i = 0; i < KPT; ++i) {
             const uint32_t d = (key[i] >> shift) & 255u;
-            const uint32_t lpos = ((offp[i >> 1] >> (16 * (i & 1))) & 0xffffu) + (PK ? (whist[d] >> wsh) & 0xffffu : whist[d]);
+            const uint32_t lpos = rank16(offp, i) + (PK ? (whist[d] >> wsh) & 0xffffu : whist[d]);
             if constexpr (Cfg::FUSED) {
                 stage_pair(lpos, key[i], val[i]);
             } else {
                 if constexpr (KW == 2) reinterpret_cast<uint2*>(s_raw)[lpos] = uint2{key[i], key2[i]};  // (digit word, other word)
                 else s_stage[lpos] = key[i];
                 if constexpr (VB != 0) {  // values follow the same positions later
-                    if ((i & 1) == 0) offp[i >> 1] = (offp[i >> 1] & 0xffff0000u) | lpos;
-                    else offp[i >> 1] = (offp[i >> 1] & 0x0000ffffu) | (lpos << 16);
+                    set_rank16(offp, i, lpos);
                 }
             }
         }
@@ -1586,7 +1767,7 @@ __device__ __forceinline__ void binning_body(
 #pragma unroll
         for (int i = 0; i < KPT; ++i) {
             const uint32_t d = (key[i] >> shift) & 255u;
-            const uint32_t lpos = ((offp[i >> 1] >> (16 * (i & 1))) & 0xffffu) + (PK ? (whist[d] >> wsh) & 0xffffu : whist[d]);
+            const uint32_t lpos = rank16(offp, i) + (PK ? (whist[d] >> wsh) & 0xffffu : whist[d]);
             if constexpr (Cfg::FUSED) {
                 if (my_base + i * 64u < hi) stage_pair(lpos, key[i], val[i]);
             } else {
@@ -1595,8 +1776,7 @@ __device__ __forceinline__ void binning_body(
                     else s_stage[lpos] = key[i];
                 }
                 if constexpr (VB != 0) {
-                    if ((i & 1) == 0) offp[i >> 1] = (offp[i >> 1] & 0xffff0000u) | lpos;
-                    else offp[i >> 1] = (offp[i >> 1] & 0x0000ffffu) | (lpos << 16);
+                    set_rank16(offp, i, lpos);
                 }
             }
         }
@@ -1645,7 +1825,7 @@ __device__ __forceinline__ void binning_body(
                 __builtin_amdgcn_s_sleep(1);
                 ++spins;
                 if (GS_FALLBACK && k > 0 && spins > FALLBACK_SPINS) {  // (row 0 of a PF_POS chain behind the first pass is seeded by its tile 0)
-                    atomicMax(&s_misc[8], (uint32_t)k);  // ask the workgroup to recount tile k-1
+                    atomicMax(&s_misc[M_FB_ROW], (uint32_t)k);  // ask the workgroup to recount tile k-1
                     return;
                 }
                 if (spins > SPIN_LIMIT || ((spins & 1023u) == 0 && ld_agent(status) != STATUS_OK)) {
@@ -1665,7 +1845,7 @@ __device__ __forceinline__ void binning_body(
                 finished = true;
                 if (poisoned) {
                     st_agent(status, STATUS_TIMEOUT);
-                    s_misc[2] = 1u;  // this tile must not scatter
+                    s_misc[M_GAVE_UP] = 1u;  // this tile must not scatter
                 }
                 if (!GS_FAULT_TILE(chain, tile))
                     st_agent(&cdesc[(size_t)(tile + 1u) * RADIX + tid],
@@ -1675,7 +1855,7 @@ __device__ __forceinline__ void binning_body(
         }
         __syncthreads();
         if (!GS_FALLBACK) break;
-        const uint32_t fb_row = uni(s_misc[8]);  // uniform
+        const uint32_t fb_row = uni(s_misc[M_FB_ROW]);  // uniform
         if (GS_LIKELY(fb_row == 0u)) break;
         // ---- fallback: some digit's walk waited FALLBACK_SPINS polls on row fb_row.  The whole workgroup
         // recounts that tile's digits from the pass input (which nobody writes during the pass), offers the
@@ -1691,7 +1871,7 @@ __device__ __forceinline__ void binning_body(
             __syncthreads();
             // every thread has read the request (fb_row above) before it is withdrawn; the next request can only
             // be posted after the barrier that ends this block
-            if (tid == 0) s_misc[8] = 0u;
+            if (tid == 0) s_misc[M_FB_ROW] = 0u;
             for (uint32_t idx = flo + tid; idx < fhi; idx += THREADS) {
                 uint32_t w;
                 if constexpr (KW == 2) {
@@ -1717,21 +1897,9 @@ __device__ __forceinline__ void binning_body(
     }
     GS_TRACE(5);
     GS_TRACE_END(chain);
-    if (uni(s_misc[2]) != 0u) break;  // look-back gave up (timeout or poisoned predecessor): write nothing
-    if constexpr (POS == 1) {
-        // keys this tile writes per output position segment, from the digit threads' run geometry (ONE LDS add per run, two for the
-        // rare run across a segment boundary): what count_next leaves out — the workgroup's hot next digit — is recovered from these
-        // totals when the table is flushed
-        if (next_shift != 0xffffffffu && tid < RADIX && tile_total != 0u) {
-            const uint32_t x0 = prev >> seglog, x1 = (prev + tile_total - 1u) >> seglog;
-            if (x0 == x1) {
-                atomicAdd(&s_pos[8u + x0], tile_total);
-            } else {  // (a run is shorter than a segment: two segments at most)
-                const uint32_t first = ((x0 + 1u) << seglog) - prev;
-                atomicAdd(&s_pos[8u + x0], first);
-                atomicAdd(&s_pos[8u + x1], tile_total - first);
-            }
-        }
+    if (uni(s_misc[M_GAVE_UP]) != 0u) break;  // look-back gave up (timeout or poisoned predecessor): write nothing
+    if constexpr (POS == 1) {  // keys this tile writes per output position segment (for the flush: the left-out digit is recovered from them)
+        if (next_shift != NO_SHIFT && tid < RADIX && tile_total != 0u) bin_note_written_keys(s_pos, seglog, prev, tile_total);
     }
 
     // ---- (pairs) fetch this tile's values now: the key registers are dead, and the loads fly
@@ -1743,7 +1911,7 @@ __device__ __forceinline__ void binning_body(
     // THIS digit, so the lanes of one scatter instruction write one or two runs — one segment, with few exceptions — and
     // their next digits are what collides.  The workgroup therefore leaves ONE next digit out — its guess of the most frequent
     // one, fixed at its first tile — and recovers that digit's counts at the flush from the number of keys it wrote to each segment
-    // (known per run from the digit threads: s_pos[8..]).  (Round 3, first form: the lanes holding a per-wave guess counted with ONE
+    // (known per run from the digit threads: P_WRITTEN).  (Round 3, first form: the lanes holding a per-wave guess counted with ONE
     // add of a ballot's popcount — exact, but two ballots, a readlane and a popcount per key: 153 M VALU + 97 M SALU instructions per
     // counting pass against 59 M + 29 M for the plain pass, profiles/r03_rocprofv3_pmc_sq_insts.txt.  Plain adds cost 0.23 / 0.57 ms per pass
     // at entropy presets 3 / 5 against 0.01 ms for uniform keys, profiles/r03_next_digit_count_cost.txt).
@@ -1752,14 +1920,14 @@ __device__ __forceinline__ void binning_body(
         if constexpr (PK) { if (valid && dn != cnt_guess) atomicAdd(&s_cnt[((o >> seglog) << 7) + (dn >> 1)], 1u << ((dn & 1u) * 16u)); }
         else { if (valid && dn != cnt_guess) atomicAdd(&s_cnt[((o >> seglog) << 8) + dn], 1u); }
     };
-    const bool counting = POS == 1 && next_shift != 0xffffffffu;  // uniform
+    const bool counting = POS == 1 && next_shift != NO_SHIFT;  // uniform
     if constexpr (POS == 1) {
         if (counting) {
             // the digit this workgroup leaves out, chosen ONCE: a next digit that at least 8 of 64 staged keys share (every wave looks at 64
             // of its own, eight candidate lanes each; the most frequent find wins); a tile without such a digit leaves the choice to the next one
-            if (uni(s_pos[4]) == 0xfffffffeu) bin_elect_left_out_digit(s_stage + wave * (TILE / WAVES) + lane, next_shift & 31u, s_pos);
-            cnt_guess = uni(s_pos[4]);
-            if (cnt_guess == 0xfffffffeu) cnt_guess = 0xffffffffu;  // (no digit left out in this tile: nothing to recover for it)
+            if (uni(s_pos[P_LEFT_OUT]) == DIGIT_UNDECIDED) bin_elect_left_out_digit(s_stage + wave * (TILE / WAVES) + lane, next_shift & 31u, s_pos);
+            cnt_guess = uni(s_pos[P_LEFT_OUT]);
+            if (cnt_guess == DIGIT_UNDECIDED) cnt_guess = NO_DIGIT;  // (no digit left out in this tile: nothing to recover for it)
         }
     }
 
@@ -1791,7 +1959,7 @@ __device__ __forceinline__ void binning_body(
             for (int j = 0; j < KPT; ++j) load_pair(tid + j * THREADS, kk[j], vv[j]);
 #pragma unroll
             for (int j = 0; j < KPT; ++j) {
-                const uint32_t o = ((s_gbase[(kk[j] >> shift) & 255u] + tid + j * THREADS) ^ rev_xor) + rev_add;
+                const uint32_t o = out_index(s_gbase[(kk[j] >> shift) & 255u] + tid + j * THREADS, rev_xor, rev_add);
                 st_stream(keys_out + o, from_bits<KT>(kk[j]));
                 st_stream(vals_out + o, vv[j]);
             }
@@ -1803,8 +1971,8 @@ __device__ __forceinline__ void binning_body(
                 V v;
                 load_pair(i, k, v);
                 uint32_t o = s_gbase[(k >> shift) & 255u] + i;
-                if (reverse) o = n - 1u - o;
-                if (full || (i >= head && i < head + count)) {
+                o = out_index_branch(o, reverse, n);
+                if (bin_slot_valid(full, head, count, i)) {
                     st_stream(keys_out + o, from_bits<KT>(k));
                     st_stream(vals_out + o, v);
                 }
@@ -1826,8 +1994,8 @@ __device__ __forceinline__ void binning_body(
             for (int j = 0; j < KPT; ++j) {
                 const uint32_t d = (kb[j].x >> shift) & 255u;
                 const uint2 nat = from_bits2<KT>(hi_word ? uint2{kb[j].y, kb[j].x} : kb[j]);
-                st_stream(reinterpret_cast<uint2*>(keys_out) + (((s_gbase[d] + tid + j * THREADS) ^ rev_xor) + rev_add), nat);
-                if constexpr (VB != 0) digs[j >> 2] |= d << (8 * (j & 3));
+                st_stream(reinterpret_cast<uint2*>(keys_out) + out_index(s_gbase[d] + tid + j * THREADS, rev_xor, rev_add), nat);
+                if constexpr (VB != 0) add_digit8(digs, j, d);
             }
         } else {
             uint32_t kb[KPT];
@@ -1843,9 +2011,9 @@ __device__ __forceinline__ void binning_body(
                 for (int j = 0; j < KPT; ++j) {
                     const uint32_t d = (kb[j] >> shift) & 255u;
                     const uint32_t opos = s_gbase[d] + tid + j * THREADS;
-                    st_stream(keys_out + ((opos ^ rev_xor) + rev_add), from_bits<KT>(kb[j]));
+                    st_stream(keys_out + out_index(opos, rev_xor, rev_add), from_bits<KT>(kb[j]));
                     if constexpr (POS == 1) { if (counting) count_next(kb[j], opos, true); }
-                    if constexpr (VB != 0) digs[j >> 2] |= d << (8 * (j & 3));
+                    if constexpr (VB != 0) add_digit8(digs, j, d);
                 }
             }
         }
@@ -1858,9 +2026,9 @@ __device__ __forceinline__ void binning_body(
             const uint32_t kb = KW == 2 ? kb2.x : s_stage[i];
             const uint32_t d = (kb >> shift) & 255u;
             uint32_t o = s_gbase[d] + i;
-            if constexpr (POS == 1) { if (counting) count_next(kb, o, full || (i >= head && i < head + count)); }
-            if (reverse) o = n - 1u - o;
-            if (full || (i >= head && i < head + count)) {
+            if constexpr (POS == 1) { if (counting) count_next(kb, o, bin_slot_valid(full, head, count, i)); }
+            o = out_index_branch(o, reverse, n);
+            if (bin_slot_valid(full, head, count, i)) {
                 if constexpr (KW == 2)
                     st_stream(reinterpret_cast<uint2*>(keys_out) + o, from_bits2<KT>(hi_word ? uint2{kb2.y, kb2.x} : kb2));
                 else if (half16)  // (o is the halfword slot: `reverse` is off)
@@ -1868,7 +2036,7 @@ __device__ __forceinline__ void binning_body(
                 else
                     st_stream(keys_out + o, from_bits<KT>(kb));
             }
-            if constexpr (VB != 0) digs[j >> 2] |= d << (8 * (j & 3));
+            if constexpr (VB != 0) add_digit8(digs, j, d);
         }
     }
     GS_TRACE(6);
@@ -1884,13 +2052,13 @@ __device__ __forceinline__ void binning_body(
             if (GS_LIKELY(!mask_tail)) {
 #pragma unroll
                 for (int i = 0; i < KPT; ++i) {
-                    const uint32_t pos = (offp[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+                    const uint32_t pos = rank16(offp, i);
                     if (VRN == 1 || pos / HALF == (uint32_t)h) s_vstage[pos - h * HALF] = val[i];
                 }
             } else {
 #pragma unroll
                 for (int i = 0; i < KPT; ++i) {
-                    const uint32_t pos = (offp[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+                    const uint32_t pos = rank16(offp, i);
                     if (my_base + i * 64u < hi && (VRN == 1 || pos / HALF == (uint32_t)h)) s_vstage[pos - h * HALF] = val[i];
                 }
             }
@@ -1908,7 +2076,7 @@ __device__ __forceinline__ void binning_body(
 #pragma unroll
                     for (int j = 0; j < VBATCH; ++j) {
                         const int jj = h * JN + j0 + j;
-                        st_stream(vals_out + (((s_gbase[(digs[jj >> 2] >> (8 * (jj & 3))) & 255u] + tid + jj * THREADS) ^ rev_xor) + rev_add), vv[j]);
+                        st_stream(vals_out + out_index(s_gbase[digit8(digs, jj)] + tid + jj * THREADS, rev_xor, rev_add), vv[j]);
                     }
                 }
             } else {
@@ -1916,67 +2084,16 @@ __device__ __forceinline__ void binning_body(
                 for (int j = J0; j < JN; ++j) {
                     const int jj = h * JN + j;
                     const uint32_t i = tid + jj * THREADS;
-                    uint32_t o = s_gbase[(digs[jj >> 2] >> (8 * (jj & 3))) & 255u] + i;
-                    if (reverse) o = n - 1u - o;
-                    if (full || (i >= head && i < head + count)) st_stream(vals_out + o, s_vstage[tid + j * THREADS]);
+                    uint32_t o = s_gbase[digit8(digs, jj)] + i;
+                    o = out_index_branch(o, reverse, n);
+                    if (bin_slot_valid(full, head, count, i)) st_stream(vals_out + o, s_vstage[tid + j * THREADS]);
                 }
             }
         }
     }
     if constexpr (!PERSIST) break;
     }  // tiles
-    if constexpr (POS == 1) {
-        // hand the counts to the next pass that runs: CNEXT[that pass][segment][digit] += this workgroup's table
-        const uint32_t ns = uni(info[I_NEXT_SHIFT]);
-        if ((mode & BM_PLANNED) && ns != 0xffffffffu && !(uni(info[PASS_FLAGS]) & PF_SKIP)) {
-            __syncthreads();
-            const uint32_t left_out = uni(s_pos[4]);
-            uint32_t* cn_out = hsub + (ns >> 3) * HSUB_STRIDE;
-          if constexpr (PK) {
-            if (left_out < RADIX) {  // the digit count_next skipped: keys written to the segment minus everything that was counted
-                const uint32_t lo_word = left_out >> 1, lo_keep = 0xffff0000u >> ((left_out & 1u) * 16u);  // its word in a row, the OTHER half
-                for (uint32_t x = wave; x < NCH; x += WAVES) {
-                    uint32_t sum = 0;
-                    for (uint32_t c = lane; c < RADIX / 2; c += 64u) {
-                        uint32_t w = s_cnt[x * (RADIX / 2) + c];
-                        if (c == lo_word) w &= lo_keep;  // (what the tiles in front of the choice counted for it is part of the total)
-                        sum += (w & 0xffffu) + (w >> 16);
-                    }
-                    sum = wave_reduce_sum(sum);
-                    if (lane == 0) {
-                        const uint32_t v = s_pos[8u + x] - sum;
-                        if (v != 0u) atomicAdd(&cn_out[x * RADIX + left_out], v);
-                        s_cnt[x * (RADIX / 2) + lo_word] &= lo_keep;
-                    }
-                }
-                __syncthreads();
-            }
-            // (Round 4, measured and not kept: one copy of the table per XCD — workgroup b adds to copy b % 8, the last workgroup of the
-            //  pass to arrive sums the copies — against the same-address contention of these atomics: the counting passes got SLOWER,
-            //  0.566 -> 0.588 ms at entropy preset 3, profiles/r04_pos_flush_copies.txt: non-returning atomics do not hold the
-            //  workgroups up, the closing sum by one workgroup does.)
-            for (uint32_t i = tid; i < NCH * RADIX / 2; i += THREADS) {
-                const uint32_t w = s_cnt[i];
-                if ((w & 0xffffu) != 0u) atomicAdd(&cn_out[2u * i], w & 0xffffu);
-                if ((w >> 16) != 0u) atomicAdd(&cn_out[2u * i + 1u], w >> 16);
-            }
-          } else {
-            if (left_out < RADIX) {  // the digit count_next skipped: keys written to the segment minus everything that was counted
-                for (uint32_t x = wave; x < NCH; x += WAVES) {
-                    uint32_t sum = 0;
-                    for (uint32_t d = lane; d < RADIX; d += 64u) sum += d == left_out ? 0u : s_cnt[x * RADIX + d];
-                    sum = wave_reduce_sum(sum);
-                    if (lane == 0) s_cnt[x * RADIX + left_out] = s_pos[8u + x] - sum;
-                }
-                __syncthreads();
-            }
-            for (uint32_t i = tid; i < NCH * RADIX; i += THREADS) {
-                const uint32_t v = s_cnt[i];
-                if (v != 0u) atomicAdd(&cn_out[i], v);
-            }
-          }
-        }
-    }
+    if constexpr (POS == 1) bin_flush_cnext<(uint32_t)THREADS, (uint32_t)WAVES, PK>(s_cnt, s_pos, info, hsub, mode);  // CNEXT[the next pass that runs] += this workgroup's table
 }
 
 // One workgroup per tile: every key / value type, every compiled shape.

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A/B of library builds on one box: best-of-N whole-sort time per (library, value bytes), libraries interleaved.
-Usage: ab.py lib1.so lib2.so ... [--log2 28] [--rounds 4] [--vb 0,4,8] [--preset 0]"""
+Usage: ab.py lib1.so lib2.so ... [--log2 28] [--rounds 4] [--vb 0,4,8] [--preset 0]
+Stops with exit status 1 at the first child process that fails."""
 import os
 import subprocess
 import sys
@@ -42,7 +43,8 @@ for rnd in range(int(opt["--rounds"])):
                 vals = [float(x) for x in f[1:]]
                 if key not in res or vals[0] < res[key][0]:
                     res[key] = vals
-        if out.returncode:
-            print(lib, "FAILED", out.stderr[-300:])
+        if out.returncode:  # stop here: after a fault nothing more is started on the device
+            print(lib, "FAILED", f"(exit status {out.returncode}); stopping", out.stderr[-300:])
+            sys.exit(1)
 for (lib, vb), v in sorted(res.items(), key=lambda kv: (kv[0][1], kv[0][0])):
     print(f"vb={vb} {os.path.basename(lib):32s} total={v[0]:.3f} ms passes=[{v[1]:.3f} {v[2]:.3f} {v[3]:.3f} {v[4]:.3f}] hist={v[5]:.3f}")
