@@ -248,6 +248,7 @@ _PROTOS = [
     ("gs_debug_read_slab", _int, [_vp, _u32, _u32, _u32p, _vp]),
     ("gs_debug_sort_route", _int, [_vp, _u32, _int, _u32p]),
     ("gs_debug_set_hy_class", _int, [_vp, _int]),
+    ("gs_debug_set_pos_grid", _int, [_vp, _u32]),
     ("gs_debug_pass_flags", _int, [_vp, _u32p, _vp]),
     ("gs_debug_hy_half_slot", _u32, [_u32, _u32, _u32, _u32, _u32]),
     ("gs_debug_registry_dims", _int, [_u32, C.POINTER(C.c_int32)]),

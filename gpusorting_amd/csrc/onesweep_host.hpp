@@ -61,6 +61,7 @@ struct gs_onesweep {
     uint32_t* hy_tab = nullptr;  // the two-level plan's tables (gs::HYT_WORDS), nullptr: the handle cannot run it (pairs, 64-bit keys only ...)
     uint32_t hy_grid;      // workgroups of its histogram kernel (a multiple of NCH)
     int last_hy = 0;       // the last sort was enqueued with the two-level plan's launches (whether it RAN on it is the device's decision: gs_onesweep_last_plan)
+    uint32_t pos_grid_forced = 0;  // gs_debug_set_pos_grid: 0 the position-chain launches run on pos_grid() workgroups, else on this many (>= NCH)
     int hy_class_forced = -1;  // gs_debug_set_hy_class: -1 the size class of the bucket-local sort follows n (hy_class), 0 .. 3 that class whatever n is
 };
 
@@ -122,6 +123,10 @@ uint32_t hist_blocks(uint32_t n, uint32_t forced = 0) {
 
 // persistent workgroups of the position-chain pass: two per CU (76 KiB of LDS each)
 uint32_t pos_grid() { return 2u * cu_count(); }
+// ... of this handle's position-chain launches (pos_launcher): a test may have set another grid (gs_debug_set_pos_grid).  Any grid of
+// NCH workgroups or more is correct: a workgroup draws tickets on chain blockIdx % NCH (group by group on a CHMAX-chain pass), then
+// takes tiles of the chains that still have some, and no tile waits for a workgroup that has not started.
+uint32_t pos_grid_of(const gs_onesweep* h) { return h->pos_grid_forced ? h->pos_grid_forced : pos_grid(); }
 
 // workgroups of the two-level plan's histogram kernel: one per CU, a multiple of NCH (position segments get equal numbers of them)
 uint32_t hy_grid_for_device() {
@@ -420,7 +425,7 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
                 // (1) keys-only sorts that may run on position chains: ONE launch per pass serves every plan (persistent workgroups, two per
                 // CU).  Offered the two-level plan, the first two launches are pass A / pass B or LSD passes 0 / 1 — digit and chain count come
                 // from the info block — the bucket-local sort follows them, and LSD passes 2 and 3 exit on PF_SKIP if it ran.
-                launch(pos_launcher(vb, p == 3, kt), pos_grid(), p, a, p * 8,
+                launch(pos_launcher(vb, p == 3, kt), pos_grid_of(h), p, a, p * 8,
                        mode | ((hy && p < 2) ? gs::BM_INFO_SHIFT | gs::BM_INFO_CHAINS : 0u) | ((hy && p == 1) ? gs::BM_ZERO_DESC23 : 0u));
                 if (hy && p == 1) {
                     if (h->profiling) GS_HIP(hipEventRecord(h->ev[5], s));  // slot 4 = pass B; slot 5: the local sort (+ LSD pass 2's launch); slot 6: LSD pass 3's
@@ -432,7 +437,7 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
                 // form, which also serves LSD passes 2 and 3); the bucket-local sort sits between them.  The non-persistent plain forms
                 // are not launched at all: whichever plan the device picks, one of these two forms is the one that works.
                 if (p < 2) launch(persist_launcher(vb, kt), pos_grid() / 2u, p, a, p * 8, mode | gs::BM_FORMS | gs::BM_INFO_SHIFT | gs::BM_INFO_CHAINS);
-                launch(pos_launcher(vb, p == 3, kt), pos_grid(), p, a, p * 8, (mode & ~gs::BM_ZERO_HIST) | gs::BM_FORMS | (p == 1 ? gs::BM_ZERO_DESC23 : 0u));
+                launch(pos_launcher(vb, p == 3, kt), pos_grid_of(h), p, a, p * 8, (mode & ~gs::BM_ZERO_HIST) | gs::BM_FORMS | (p == 1 ? gs::BM_ZERO_DESC23 : 0u));
                 if (p == 1) {
                     if (h->profiling) GS_HIP(hipEventRecord(h->ev[5], s));
                     if (!skip_local) hy_pairs_launcher(vb, hy_class_of(h, n), kt)(s, k[0], v[0], h->hy_tab, h->slab, n, desc_bit);
@@ -444,7 +449,7 @@ gs_status sort_impl(gs_onesweep* h, void* d_keys, void* d_vals, void* d_alt_keys
                 launch(p == 0 ? fn0 : fn, p == 0 ? plan.grid0 : plan.grid, p, a, word * 32 + p * 8,
                        mode | (two_forms ? gs::BM_IF_EVEN : 0u) | ((pos && vb != 0) ? gs::BM_FORMS : 0u));
                 if (two_forms) launch(bin_launcher(shape, h->rank_mode, vb, kt, 2), plan.grid, p, a, word * 32 + p * 8, mode | gs::BM_IF_SKEW | ((pos && vb == 8) ? gs::BM_FORMS : 0u));
-                if (pos && vb != 0) launch(pos_launcher(vb, p == 3, kt), pos_grid(), p, a, p * 8, (mode & ~gs::BM_ZERO_HIST) | gs::BM_FORMS);
+                if (pos && vb != 0) launch(pos_launcher(vb, p == 3, kt), pos_grid_of(h), p, a, p * 8, (mode & ~gs::BM_ZERO_HIST) | gs::BM_FORMS);
             }
             if (h->profiling && word == 0 && p < 4 && !(hy && p == 1)) GS_HIP(hipEventRecord(h->ev[4 + p], s));
         }
@@ -648,6 +653,8 @@ gs_status gs_debug_sort_route(gs_onesweep* h, uint32_t n, gs_key_type kt, uint32
 
 static_assert(GS_PF_SKEW == gs::PF_SKEW && GS_PF_SKIP == gs::PF_SKIP && GS_PF_SRC_ALT == gs::PF_SRC_ALT && GS_PF_LAST == gs::PF_LAST &&
               GS_PF_POS == gs::PF_POS && GS_PF_HALF16 == gs::PF_HALF16, "header and kernels agree on the pass flags");
+static_assert(GS_SLAB_STATUS_WORD == gs::SLAB_STATUS && GS_ST_GUARD_HANDOVERS == gs::ST_GUARD_HANDOVERS && GS_ST_STOLEN_TILES == gs::ST_STOLEN_TILES,
+              "header and kernels agree on the status block");
 uint32_t gs_debug_hy_half_slot(uint32_t base_p, uint32_t base_p1, uint32_t n, uint32_t descending, uint32_t rank) {
     return gs::hy_half_slot(base_p, base_p1, n, descending, rank);
 }
@@ -691,6 +698,12 @@ gs_status gs_onesweep_set_plan(gs_onesweep* h, int plan) {
 gs_status gs_debug_set_hy_class(gs_onesweep* h, int cls) {
     if (!h || cls < -1 || cls > 3) return GS_ERR_ARG;
     h->hy_class_forced = cls;
+    return GS_OK;
+}
+
+gs_status gs_debug_set_pos_grid(gs_onesweep* h, uint32_t workgroups) {
+    if (!h || (workgroups != 0u && (workgroups < gs::NCH || workgroups > 65535u))) return GS_ERR_ARG;
+    h->pos_grid_forced = workgroups;
     return GS_OK;
 }
 

@@ -865,6 +865,10 @@ constexpr uint32_t P_ELECTION = 5;    // ... and its election: (popcount << 8) |
 constexpr uint32_t P_WRITTEN = 8;     // [8..8 + NCH) keys this workgroup wrote to each output position segment
 constexpr uint32_t P_WORDS = 32, P_WORDS_LAST = 8;
 static_assert(P_WRITTEN + NCH <= P_WORDS && P_MAX + 2 <= P_WORDS_LAST, "pos words");
+// Words of the sort's status block behind the status word itself (zeroed with it, by the histogram kernel, at the start of every sort):
+// what only the workgroups of a counting position-chain pass (POS == 1) know, counted on their rare paths for the tests.
+constexpr uint32_t ST_GUARD_HANDOVERS = 4;  // counters of packed next-digit tables that bin_guard_packed_table handed to CNEXT early
+constexpr uint32_t ST_STOLEN_TILES = 5;     // tiles bin_steal_tile took from another chain
 constexpr uint32_t NO_TICKET = 0xffffffffu, NO_CHAIN = 0xffffffffu, NO_SHIFT = 0xffffffffu, NO_DIGIT = 0xffffffffu;  // "none" of a ticket, an open chain, a digit position, a digit
 constexpr uint32_t DIGIT_UNDECIDED = 0xfffffffeu;                                            // P_LEFT_OUT: not chosen yet
 
@@ -1147,10 +1151,11 @@ __device__ __forceinline__ void bin_rank_keys(const uint32_t (&key)[KPT], uint32
 // binning_body, phase "claim", second half: the workgroup's own chain is fully claimed — take a tile of ANOTHER chain that still has
 // unclaimed tiles.  Leaves the chain in M_CHAIN and the ticket in M_TICKET (NO_TICKET: every chain is fully claimed); the caller reads
 // them behind a barrier.  `chain` = the chain just found exhausted (the linear search starts behind it).
+// COUNT (the counting position-chain form): a tile taken adds one to status[ST_STOLEN_TILES].
 // ---------------------------------------------------------------------------
-template <uint32_t THREADS, uint32_t TILE>
+template <uint32_t THREADS, uint32_t TILE, bool COUNT>
 __device__ __forceinline__ void bin_steal_tile(const uint32_t nch, const uint32_t chain, const uint32_t* __restrict__ info, uint32_t* __restrict__ counters,
-                                                uint32_t* __restrict__ s_misc) {
+                                                uint32_t* __restrict__ s_misc, uint32_t* status) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     // Steal: wave 0 looks at ALL chains in one parallel round trip (lane x = chain x); a serial
     // scan with dependent sc1 loads cost ~22 us per exhausted workgroup and stretched every pass's tail.
@@ -1180,7 +1185,10 @@ __device__ __forceinline__ void bin_steal_tile(const uint32_t nch, const uint32_
             }
             __syncthreads();
             if (uni(s_misc[M_TICKET]) != NO_TICKET) {
-                if (tid == 0) s_misc[M_CHAIN] = x;
+                if (tid == 0) {
+                    s_misc[M_CHAIN] = x;
+                    if constexpr (COUNT) atomicAdd(&status[ST_STOLEN_TILES], 1u);
+                }
                 break;
             }
         }
@@ -1221,7 +1229,11 @@ __device__ __forceinline__ void bin_steal_tile(const uint32_t nch, const uint32_
             if (t < tx) { got_x = x; got_t = t; break; }
             m &= ~(1ull << x);
         }
-        if (lane == 0) { s_misc[M_CHAIN] = got_x; s_misc[M_TICKET] = got_t; }
+        if (lane == 0) {
+            s_misc[M_CHAIN] = got_x;
+            s_misc[M_TICKET] = got_t;
+            if constexpr (COUNT) { if (got_t != NO_TICKET) atomicAdd(&status[ST_STOLEN_TILES], 1u); }
+        }
     }
 }
 
@@ -1405,23 +1417,25 @@ __device__ __forceinline__ BinPosPlan bin_pos_setup(uint32_t* s_cnt, uint32_t* s
 // tiles, and its most frequent next digit is not counted at all.  guard_ns: the digit position this workgroup counts for (NO_SHIFT: none).
 // ---------------------------------------------------------------------------
 template <uint32_t THREADS>
-__device__ __forceinline__ void bin_guard_packed_table(uint32_t* s_cnt, uint32_t* s_pos, uint32_t* hsub, const uint32_t guard_ns) {
+__device__ __forceinline__ void bin_guard_packed_table(uint32_t* s_cnt, uint32_t* s_pos, uint32_t* hsub, uint32_t* status, const uint32_t guard_ns) {
     const uint32_t tid = threadIdx.x;
     if (guard_ns != NO_SHIFT) {  // uniform
         for (uint32_t i = tid; i < NCH * RADIX / 2; i += THREADS) {
-            uint32_t w = s_cnt[i];
+            const uint32_t w = s_cnt[i];
             if (GS_UNLIKELY((w & (w << 1) & 0x80008000u) != 0u)) {
                 uint32_t* cn_out = hsub + (guard_ns >> 3) * HSUB_STRIDE;
+                uint32_t taken = 0;  // what goes to CNEXT, in the word's own halves
 #pragma unroll
                 for (uint32_t h = 0; h < 2; ++h) {
                     const uint32_t v = (w >> (16u * h)) & 0xffffu;
                     if (v >= 0xC000u) {
                         atomicAdd(&cn_out[2u * i + h], v);
                         atomicSub(&s_pos[P_WRITTEN + (i >> 7)], v);
-                        w &= ~(0xffffu << (16u * h));
+                        atomicAdd(&status[ST_GUARD_HANDOVERS], 1u);  // (for the tests: that this path ran)
+                        taken |= v << (16u * h);
                     }
                 }
-                s_cnt[i] = w;
+                atomicSub(&s_cnt[i], taken);  // (exactly what was handed over leaves the word: no store of a value read earlier)
             }
         }
     }
@@ -1584,8 +1598,13 @@ __device__ __forceinline__ void binning_body(
     //  profiles/r03_ab_ticket_ahead.txt)
 #pragma unroll 1
     for (;;) {  // PERSIST: one tile after the other until every chain is claimed; otherwise ONE tile per workgroup
+    // (POS == 1: count_next's adds to the next-digit table have no result anybody waits for, and a barrier orders the ISSUE of LDS
+    //  instructions, not their completion — every wave sees its own adds LAND before it enters the barrier behind which the guard reads
+    //  the table.  Without the wait a counter the guard saw below 0xC000 received the tail of the last tile and then a whole tile more:
+    //  the 16-bit half wrapped)
+    if constexpr (POS == 1) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
     if constexpr (PERSIST) __syncthreads();  // the last tile's readers of the stage and of s_misc are through
-    if constexpr (POS == 1 && PK) bin_guard_packed_table<(uint32_t)THREADS>(s_cnt, s_pos, hsub, guard_ns);  // next-digit counters near overflow go to CNEXT now
+    if constexpr (POS == 1 && PK) bin_guard_packed_table<(uint32_t)THREADS>(s_cnt, s_pos, hsub, status, guard_ns);  // next-digit counters near overflow go to CNEXT now
     for (uint32_t i = tid; i < Cfg::WHIST_BYTES / 4; i += THREADS) s_whist[i] = 0;
     GS_TRACE(0);
     // ---- claim a tile.  Fast path: ONE returning atomic on the ticket counter of
@@ -1637,7 +1656,7 @@ __device__ __forceinline__ void binning_body(
                 continue;
             }
         }
-        bin_steal_tile<(uint32_t)THREADS, TILE>(nch, chain, info, counters, s_misc);
+        bin_steal_tile<(uint32_t)THREADS, TILE, POS == 1>(nch, chain, info, counters, s_misc, status);
         __syncthreads();
         chain = uni(s_misc[M_CHAIN]);
         tile = uni(s_misc[M_TICKET]);

@@ -167,13 +167,7 @@ gs_status gs_unique_create(gs_unique** out, uint32_t max_keys, gs_mode mode, uin
     if (!unique_mode_ok(mode, value_bytes)) return GS_ERR_MODE;  // (8-byte values: before anything looks for a device)
     return handle_create(out, true, mode, value_bytes, [&](gs_unique* h) {
         h->max_keys = max_keys;
-        // The keys-only sorter never takes its position-chain plan here: on heavily skewed keys (2 .. 16 distinct values among 2^27 and
-        // more) that plan was measured to leave a few keys out of order now and then, and the run-length stage
-        // turns every misplaced key into a run of its own.  The pairs sorter showed nothing of the kind and keeps its defaults.
-        gs_onesweep_options o;
-        gs_onesweep_options_default(&o);
-        if (mode == GS_MODE_KEYS_ONLY) o.position_chains = 0;
-        const gs_status st = gs_onesweep_create_ex(&h->engine, max_keys, mode, value_bytes, &o);
+        const gs_status st = gs_onesweep_create(&h->engine, max_keys, mode, value_bytes);  // (either engine at the library's defaults)
         if (st != GS_OK) return st;
         const UniqueLayout l = unique_layout(max_keys, mode == GS_MODE_PAIRS);
         return h->ws.alloc(l.total, l.ctl, gs::UQC_WORDS, gs::UQC_WORDS);

@@ -248,6 +248,22 @@ gs_status gs_debug_sort_route(gs_onesweep* h, uint32_t n, gs_key_type key_type, 
  * is not offered the plan (GS_ROUTE_R_HY 0) and runs on the LSD passes.  GS_ERR_ARG for a null handle or any other cls.  Call it with no
  * sort of the handle in flight. */
 gs_status gs_debug_set_hy_class(gs_onesweep* h, int cls);
+/* Test hook, host only (no device work): the grid of the handle's position-chain launches — the persistent workgroups that run a
+ * keys-only sort's passes on either plan, and the position-chain form of a pairs sort's passes — is two workgroups per CU.  At
+ * 2^20 .. 2^23 keys each of them sees one tile, so what a workgroup keeps ACROSS its tiles (the packed next-digit table and its
+ * overflow guard, the next digit it leaves out, tiles taken from other chains) is only reached at full size.  workgroups >= 16 (the
+ * chains of a pass) sets that grid for every later sort of the handle; 0 restores the default.  Any such grid is correct: a workgroup
+ * draws tickets on chain blockIdx % 16 — group by group on the 256 chains of the two-level plan's second pass — and then takes tiles of
+ * whichever chain still has some, and no tile waits for a workgroup that has not started.  (The plain persistent form of a pairs sort
+ * on the two-level plan and the bucket-local sorts keep their grids.)  GS_ERR_ARG for a null handle, 1 .. 15, or more than 65 535.
+ * Call it with no sort of the handle in flight.
+ * What such a sort leaves in its status block, readable until the next sort of the handle (gs_debug_read_slab, first_word =
+ * GS_SLAB_STATUS_WORD + ...): word GS_ST_GUARD_HANDOVERS = counters of the packed next-digit tables that went to the next pass's
+ * counts early (at 0xC000), word GS_ST_STOLEN_TILES = tiles a counting position-chain workgroup took from another chain than its own. */
+#define GS_SLAB_STATUS_WORD 67584u
+#define GS_ST_GUARD_HANDOVERS 4u
+#define GS_ST_STOLEN_TILES 5u
+gs_status gs_debug_set_pos_grid(gs_onesweep* h, uint32_t workgroups);
 /* Test hook: flags[q] = the flag word the Scan kernel and the passes left in the info block of the last sort's q-th pass (32-bit keys
  * use the first four, 64-bit keys planned by one sweep all eight) — which passes ran, from which buffer, in which form.  All zero
  * after a sort that left no scan state (the single-tile and mid-size routes).  Synchronous. */
@@ -1284,8 +1300,8 @@ int gs_segtopk16_get_rank_mode(gs_segtopk16* h);
  *   gs_unique_consecutive  either handle: the run-length encode of the input AS IT LIES, no sort, no key type: runs of bitwise-equal
  *                          neighbours (torch.unique_consecutive); out_inverse[i] is the index of the run that holds i.  It is the second
  *                          half of the two calls above.
- * The result does not depend on the route the engine takes (single tile, mid, two-level, LSD passes).  The keys-only handle's engine
- * is created with position_chains = 0 (gs_onesweep_options): DESIGN.md 3.21 says why.
+ * The result does not depend on the route the engine takes (single tile, mid, two-level, LSD passes).  Both engines are created
+ * with the library's defaults (gs_onesweep_create).
  * The run-length stage: the array is cut into gs_unique_plan's ranges of whole tiles; count (one workgroup per range: the heads of the
  * range — element i is a head when i == 0 or key[i] != key[i - 1] — and its last head's position), scan (one workgroup: heads and last
  * head in front of every range, u), compact (the head of rank r writes out_keys[r] and closes run r - 1: out_counts[r - 1] = its

@@ -135,6 +135,7 @@ def test_null_handle_is_an_argument_error_in_every_handle_entry():
         "gs_topk_last": (None, u32p, 4096, None),
         "gs_debug_sort_route": (None, 1024, 0, u32p),
         "gs_debug_set_hy_class": (None, 0),
+        "gs_debug_set_pos_grid": (None, 0),
         "gs_debug_pass_flags": (None, u32p, None),
     }
     for name, args in calls.items():
