@@ -66,17 +66,16 @@ __host__ __device__ inline uint32_t hy_half_slot(uint32_t base_p, uint32_t base_
 }
 
 constexpr int HY_HIST_THREADS = 1024;
-constexpr uint32_t HY_FOLD_CHUNKS = 256;  // the digit-0 replicas are folded at least this often (see global_histogram_kernel)
+static_assert(HY_HIST_THREADS == GHIST_THREADS, "HIST_CHUNK, and with it the replicas' fold cadence, is four keys of each of this many threads");
 
 // ---------------------------------------------------------------------------
 // Histogram sweep.  Workgroup w counts ONE contiguous range of keys inside one position segment of the first pass:
 // segment x = w / wg_per_seg, range j = w % wg_per_seg of per_wg keys (a multiple of HIST_CHUNK).
-//   s_j   the 16-bit-prefix table, 2 x 16 bit per word.  Random prefixes: one add per key, bank = 6 address bits of the prefix.
-//         A counter that wraps loses 65 536 (high half) or 65 535 (low half carries into its neighbour) from the table's SUM, never
-//         adds to it — so "sum of the decoded table == keys counted" is an EXACT test for "no counter wrapped", made when the
-//         table is written out.  Dominant prefixes (sorted input, constant top bytes, skew) are counted with one add of a ballot's
-//         popcount per wave, as in global_histogram_kernel.
-//   s_r   digit 0 on 32 lane-private 16-bit replicas (never a bank conflict), folded into s_b0.
+//   s_j   the 16-bit-prefix table on packed counters (pk16_*): one add per key on random prefixes, bank = 6 address bits of the
+//         prefix; the exact overflow test is made when the table is written out.  Dominant prefixes (sorted input, constant top bytes,
+//         skew) are counted as StickyBins counts them, in a copy of its own: see `skew` below.
+//   s_r   digit 0 on the lane-private replicas (replica_add / replica_fold), folded into s_b0.
+// The kernel is also the sort's clear (clear_scan_state).
 // ---------------------------------------------------------------------------
 template <int KT>
 __global__ __launch_bounds__(HY_HIST_THREADS, HY_HIST_THREADS / 256) void hy_histogram_kernel(
@@ -85,91 +84,53 @@ __global__ __launch_bounds__(HY_HIST_THREADS, HY_HIST_THREADS / 256) void hy_his
     static_assert(KeyWords<KT>::value == 1, "32-bit keys");
     constexpr uint32_t T = HY_HIST_THREADS;
     __shared__ __attribute__((aligned(16))) uint32_t s_j[HY_JOINT_WORDS];
-    __shared__ __attribute__((aligned(16))) uint32_t s_r[RADIX / 2 * 32];
+    __shared__ __attribute__((aligned(16))) uint32_t s_r[HIST_REPLICA_WORDS];
     __shared__ uint32_t s_b0[RADIX];
-    __shared__ uint32_t s_red[4];
+    __shared__ uint32_t s_red[4];  // 0 table sum, 1-2 KeyBits::publish's scratch, 3 a bucket above cap
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     uint32_t* hist = slab + SLAB_HIST;
-    // the sort's clear (see global_histogram_kernel): everything nobody reads before this kernel ends
-    {
-        uint4* a = reinterpret_cast<uint4*>(slab);
-        const size_t na = SLAB_HIST / 4, b0 = SLAB_HSUB / 4, nb = slab_used_words / 4;
-        const size_t stride = (size_t)gridDim.x * T;
-        const uint4 z = {0u, 0u, 0u, 0u};
-        for (size_t i = (size_t)blockIdx.x * T + tid; i < na; i += stride) a[i] = z;
-        for (size_t i = b0 + (size_t)blockIdx.x * T + tid; i < nb; i += stride) a[i] = z;
-    }
+    clear_scan_state<T>(slab, slab_used_words, tid);
     for (uint32_t i = tid; i < HY_JOINT_WORDS / 4; i += T) reinterpret_cast<uint4*>(s_j)[i] = uint4{0u, 0u, 0u, 0u};
-    for (uint32_t i = tid; i < RADIX / 2 * 32 / 4; i += T) reinterpret_cast<uint4*>(s_r)[i] = uint4{0u, 0u, 0u, 0u};
+    for (uint32_t i = tid; i < HIST_REPLICA_WORDS / 4; i += T) reinterpret_cast<uint4*>(s_r)[i] = uint4{0u, 0u, 0u, 0u};
     if (tid < RADIX) s_b0[tid] = 0;
     if (tid < 4) s_red[tid] = 0;
-    // eight threads share the 32 replicas of a counter pair (see global_histogram_kernel's fold)
-    auto fold = [&]() {
-        __syncthreads();
-        for (uint32_t i = tid; i < RADIX / 2 * 8; i += T) {
-            const uint4 v = reinterpret_cast<const uint4*>(s_r)[i];
-            reinterpret_cast<uint4*>(s_r)[i] = uint4{0u, 0u, 0u, 0u};
-            uint32_t lo = (v.x & 0xffffu) + (v.y & 0xffffu) + (v.z & 0xffffu) + (v.w & 0xffffu);
-            uint32_t hi = (v.x >> 16) + (v.y >> 16) + (v.z >> 16) + (v.w >> 16);
-#pragma unroll
-            for (int m = 1; m < 8; m <<= 1) {
-                lo += __shfl_xor(lo, m, 64);
-                hi += __shfl_xor(hi, m, 64);
-            }
-            if ((i & 7u) == 0u) {
-                s_b0[(i >> 3) * 2u] += lo;
-                s_b0[(i >> 3) * 2u + 1u] += hi;
-            }
-        }
-        __syncthreads();
-    };
     __syncthreads();
-
     const uint32_t x = blockIdx.x / wg_per_seg, jr = blockIdx.x % wg_per_seg;
     const unsigned long long sb = (unsigned long long)x * seg_len0, se = sb + seg_len0;
     const uint32_t seg_begin = sb < n ? (uint32_t)sb : n, seg_end = se < n ? (uint32_t)se : n;
     const unsigned long long rb = (unsigned long long)seg_begin + (unsigned long long)jr * per_wg;
     const uint32_t begin = rb < seg_end ? (uint32_t)rb : seg_end;
     const uint32_t end = (unsigned long long)begin + per_wg < seg_end ? begin + per_wg : seg_end;
-
-    uint32_t k_or = 0, k_nand = 0;
-    bool skew = false;               // wave-uniform: a dominant prefix was seen; cleared when it fades
-    uint32_t sticky = 0xffffffffu;   // wave-uniform guess of it
+    KeyBits bits;
+    // The dominant prefix: StickyBins' rules (onesweep_kernels.hpp) written out, with this kernel's fast path between the relearn step
+    // and the adds.  Kept as a copy: on StickyBins<1> the flag is a mask word in an SGPR and not a branch condition, which changed the
+    // whole loop's code; that form measured the valid plan's sweep at 0.214 against 0.208 / 0.205 ms (profiles/hist_sweep_ab.txt).
+    bool skew = false;              // wave-uniform: a dominant prefix was seen; cleared when it fades
+    uint32_t sticky = 0xffffffffu;  // wave-uniform guess of it
     uint32_t since_fold = 0;
     // joint_off (workgroup-uniform, re-read once per work item): THIS workgroup alone has counted more than `cap` keys under one
     // prefix — that bucket cannot be sorted by one workgroup, the plan is void whatever the other workgroups see (an exact
     // verdict, not a sample: those keys exist).  It says so (HX_HY_BAD) and stops counting prefixes: skewed keys (presets 3-5 of the
     // entropy sweep: 12 % .. 60 % under prefix 0) then cost this kernel one add per key, like the LSD plan's histogram kernel.
     bool joint_off = false;
-    typedef uint32_t hv4 __attribute__((ext_vector_type(4)));
-    auto ld16 = [](const uint32_t* q) -> uint4 {
-        const hv4 v = __builtin_nontemporal_load(reinterpret_cast<const hv4*>(q));
-        return uint4{v.x, v.y, v.z, v.w};
-    };
-    auto add_joint = [&](uint32_t p, uint32_t c) { atomicAdd(&s_j[p >> 1], c << ((p & 1u) << 4)); };
+    auto add_joint = [&](uint32_t p, uint32_t c) { pk16_add(s_j, p, c); };
     // four keys of this thread (radix-sortable form); probe: look for a dominant prefix first (once per work item)
     auto process = [&](const uint4 t, const bool probe) {
         const uint32_t b[4] = {t.x, t.y, t.z, t.w};
-        k_or |= t.x | t.y | t.z | t.w;
-        k_nand |= ~(t.x & t.y & t.z & t.w);
-        if (since_fold >= HY_FOLD_CHUNKS) {  // uniform
-            fold();
+        bits.add4(t);
+        if (since_fold >= HIST_FOLD_CHUNKS) {  // uniform
+            replica_fold<T>(s_r, s_b0, tid);
             since_fold = 0;
         }
         ++since_fold;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t d = b[j] & 255u;
-            atomicAdd(&s_r[(d >> 1) * 32u + (lane & 31u)], 1u << ((d & 1u) * 16u));
-        }
+        for (int j = 0; j < 4; ++j) replica_add(s_r, b[j] & 255u, lane);
         if (joint_off) return;  // uniform
         if (probe) {
-            const uint32_t p0 = b[0] >> 16;
-            const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)p0);
-            const uint32_t pc = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(p0 == f));
-            if (pc >= HIST_SKEW_LANES) {
+            const WaveFirst w = wave_first(b[0] >> 16);
+            if (w.lanes >= HIST_SKEW_LANES) {
                 skew = true;
-                if (pc >= 24 || sticky == 0xffffffffu) sticky = f;
+                if (w.lanes >= HIST_RELEARN_LANES || sticky == 0xffffffffu) sticky = w.bin;
             }
         }
         if (!skew) {  // uniform
@@ -177,12 +138,8 @@ __global__ __launch_bounds__(HY_HIST_THREADS, HY_HIST_THREADS / 256) void hy_his
             for (int j = 0; j < 4; ++j) add_joint(b[j] >> 16, 1u);
             return;
         }
-        const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)(b[0] >> 16));
-        const uint32_t pc = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((b[0] >> 16) == f));
-        // Relearn BEFORE the adds: on sorted input every chunk of 4096 keys lies under a new prefix — relearning behind the adds put
-        // each chunk's 64 lanes x 4 keys on ONE counter individually first (0.71 ms for the sweep on sorted keys, profiles/
-        // r05_sorted_inputs.txt).
-        if (pc >= 24 && f != sticky) sticky = f;
+        const WaveFirst w = wave_first(b[0] >> 16);
+        if (w.lanes >= HIST_RELEARN_LANES && w.bin != sticky) sticky = w.bin;  // relearn BEFORE the adds (see StickyBins::add4)
         // every lane's four keys under the remembered prefix (sorted / constant input): one add of 256 and done
         if (__builtin_amdgcn_ballot_w64((b[0] >> 16) == sticky && (b[1] >> 16) == sticky && (b[2] >> 16) == sticky && (b[3] >> 16) == sticky) == ~0ull) {
             if (lane == 0) add_joint(sticky, 256u);
@@ -198,74 +155,57 @@ __global__ __launch_bounds__(HY_HIST_THREADS, HY_HIST_THREADS / 256) void hy_his
             else if (__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) == 0u)
                 add_joint(sticky, (uint32_t)__popcll(m));
         }
-        if (hit < 32) {  // the guess covers < 1/8 of the lanes: relearn, or leave skew mode
-            sticky = f;
-            if (pc < 8) skew = false;
+        if (hit < HIST_STICKY_HITS) {  // the guess covers < 1/8 of the lanes: relearn, or leave skew mode
+            sticky = w.bin;
+            if (w.lanes < HIST_SKEW_LANES) skew = false;
         }
     };
-    // One work item = HY_HIST_UNROLL consecutive chunks; all their 16-byte loads are issued before the first is consumed.
-    constexpr uint32_t UNROLL = HY_HIST_UNROLL;
-    for (uint32_t c0 = begin; c0 < end; c0 += UNROLL * HIST_CHUNK) {
-        if ((unsigned long long)c0 + UNROLL * HIST_CHUNK <= end) {
-            uint4 t[UNROLL];
+    // One work item = HIST_UNROLL consecutive chunks; all their 16-byte loads are issued before the first is consumed.
+    for (uint32_t c0 = begin; c0 < end; c0 += HIST_UNROLL * HIST_CHUNK) {
+        if ((unsigned long long)c0 + HIST_UNROLL * HIST_CHUNK <= end) {
+            uint4 t[HIST_UNROLL];
 #pragma unroll
-            for (uint32_t u = 0; u < UNROLL; ++u) t[u] = ld16(keys + c0 + u * HIST_CHUNK + tid * 4u);
+            for (uint32_t u = 0; u < HIST_UNROLL; ++u) t[u] = ld_stream<true>(reinterpret_cast<const uint4*>(keys + c0 + u * HIST_CHUNK + tid * 4u));
             if (!joint_off) {
                 // the wave's dominant prefix against the bucket limit (one LDS read per wave and work item; a 16-bit counter is
                 // read long before it could wrap: cap < 2^15)
                 const uint32_t pf = to_bits<KT>((uint32_t)__builtin_amdgcn_readfirstlane((int)t[0].x)) >> 16;  // the prefix of the wave's first key: a hot prefix is drawn often
-                if (lane == 0 && (((s_j[pf >> 1] >> ((pf & 1u) << 4)) & 0xffffu) > cap ||
-                                  (skew && ((s_j[sticky >> 1] >> ((sticky & 1u) << 4)) & 0xffffu) > cap))) s_red[3] = 1u;
+                if (lane == 0 && (pk16_read(s_j, pf) > cap || (skew && pk16_read(s_j, sticky) > cap))) s_red[3] = 1u;
                 joint_off = __builtin_amdgcn_readfirstlane((int)s_red[3]) != 0;  // (a benign race: a wave that misses the flag this time sees it next time)
             }
 #pragma unroll
-            for (uint32_t u = 0; u < UNROLL; ++u)
+            for (uint32_t u = 0; u < HIST_UNROLL; ++u)
                 process(uint4{to_bits<KT>(t[u].x), to_bits<KT>(t[u].y), to_bits<KT>(t[u].z), to_bits<KT>(t[u].w)}, u == 0);
             continue;
         }
         for (uint32_t c = c0; c < end; c += HIST_CHUNK) {  // the range's last, partial work item
             if ((unsigned long long)c + HIST_CHUNK <= end) {
-                const uint4 t = ld16(keys + c + tid * 4u);
+                const uint4 t = ld_stream<true>(reinterpret_cast<const uint4*>(keys + c + tid * 4u));
                 process(uint4{to_bits<KT>(t.x), to_bits<KT>(t.y), to_bits<KT>(t.z), to_bits<KT>(t.w)}, true);
             } else {
                 for (uint32_t i = c + tid; i < end; i += T) {
                     const uint32_t kb = to_bits<KT>(keys[i]);
-                    k_or |= kb;
-                    k_nand |= ~kb;
+                    bits.add(kb);
                     add_joint(kb >> 16, 1u);
                     atomicAdd(&s_b0[kb & 255u], 1u);
                 }
             }
         }
     }
-    fold();
+    replica_fold<T>(s_r, s_b0, tid);
     // the workgroup's slice: the packed table as it is (coalesced 16-byte stores) + the digit-0 counts; the overflow test on the way
     uint32_t* mine = slices + (size_t)blockIdx.x * HY_SLICE_WORDS;
     uint32_t sum = 0;
     for (uint32_t i = tid; i < HY_JOINT_WORDS / 4; i += T) {
         const uint4 v = reinterpret_cast<const uint4*>(s_j)[i];
         reinterpret_cast<uint4*>(mine)[i] = v;
-        sum += (v.x & 0xffffu) + (v.x >> 16) + (v.y & 0xffffu) + (v.y >> 16) + (v.z & 0xffffu) + (v.z >> 16) + (v.w & 0xffffu) + (v.w >> 16);
+        sum += pk16_sum(v);
     }
     if (tid < RADIX) mine[HY_JOINT_WORDS + tid] = s_b0[tid];
     sum = wave_reduce_sum(sum);
-#pragma unroll
-    for (int dd = 32; dd > 0; dd >>= 1) {
-        k_or |= __shfl_xor(k_or, dd, 64);
-        k_nand |= __shfl_xor(k_nand, dd, 64);
-    }
-    if (lane == 0) {
-        atomicAdd(&s_red[0], sum);
-        atomicOr(&s_red[1], k_or);
-        atomicOr(&s_red[2], k_nand);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        if (s_red[0] != end - begin || s_red[3] != 0u) atomicOr(&hist[HIST_TABLE_WORDS + HX_HY_BAD], 1u);
-        // the OR / AND of all keys: how a sort planned on position chains finds its constant bytes (one atomic pair per workgroup)
-        atomicOr(&hist[HIST_TABLE_WORDS + HX_OR], s_red[1]);
-        atomicOr(&hist[HIST_TABLE_WORDS + HX_NAND], s_red[2]);
-    }
+    if (lane == 0) atomicAdd(&s_red[0], sum);
+    bits.publish(s_red + 1, hist, tid);  // (zero since the set-up; its barrier puts the sum in place too)
+    if (tid == 0 && (s_red[0] != end - begin || s_red[3] != 0u)) atomicOr(&hist[HIST_TABLE_WORDS + HX_HY_BAD], 1u);
 }
 
 // ---------------------------------------------------------------------------
@@ -308,7 +248,8 @@ __global__ __launch_bounds__(256) void hy_reduce_kernel(const uint32_t* __restri
                     cur_x = xs;
                     acc_x = 0;
                 }
-                const uint32_t h[8] = {v[k].x & 0xffffu, v[k].x >> 16, v[k].y & 0xffffu, v[k].y >> 16, v[k].z & 0xffffu, v[k].z >> 16, v[k].w & 0xffffu, v[k].w >> 16};
+                uint32_t h[8];
+                pk16_unpack(v[k], h);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { a[j] += h[j]; acc_x += h[j]; }
             }

@@ -91,9 +91,10 @@ constexpr uint32_t NCH = 16;  // independent chained scans per pass (power of tw
 static_assert(NCH >= 1 && NCH <= 32 && (NCH & (NCH - 1)) == 0, "NCH must be a power of two <= 32");
 constexpr int GHIST_THREADS = 1024;                        // threads of a global_histogram_kernel workgroup
 constexpr int GHIST_WAVES_PER_SIMD = GHIST_THREADS / 256;  // one workgroup per CU
-constexpr uint32_t HIST_UNROLL = 4;     // chunks per work item of global_histogram_kernel ...
-constexpr uint32_t HY_HIST_UNROLL = 4;  // ... and of the two-level plan's histogram kernel (hybrid_kernels.hpp)
-constexpr uint32_t HIST_SKEW_LANES = 8;  // lanes sharing the first lane's bin that switch a byte's counting to wave-aggregated adds
+constexpr uint32_t HIST_UNROLL = 4;  // chunks per work item of both histogram sweeps (global_histogram_kernel, hy_histogram_kernel)
+constexpr uint32_t HIST_SKEW_LANES = 8;      // lanes sharing the first lane's bin that switch a table's counting to wave-aggregated adds (StickyBins) ...
+constexpr uint32_t HIST_RELEARN_LANES = 24;  // ... that replace the remembered bin by the first lane's ...
+constexpr uint32_t HIST_STICKY_HITS = 32;    // ... and keys of a wave's chunk (of 256) the remembered bin must cover to be kept
 constexpr uint32_t SKEW_SHIFT = 4;  // a pass is ranked with wave-aggregated adds (PF_SKEW, mode digit) when some digit holds more than n >> SKEW_SHIFT keys.
                                     // Rounds 1-2: 3.  Entropy preset 2 (two ANDs: digit 0 holds 10 %) fell between — plain LDS adds with a 10 % digit:
                                     // 4 takes 3 % off its keys-only sort and 6 % off its (u32, u64) pairs, nothing changes elsewhere
@@ -250,6 +251,12 @@ __device__ __forceinline__ uint2 ld_stream(const uint2* p) {
     const u32x2_t v = ld_stream<NT>(reinterpret_cast<const u32x2_t*>(p));
     return uint2{v.x, v.y};
 }
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ uint4 ld_stream(const uint4* p) {
+    const u32x4_t v = ld_stream<NT>(reinterpret_cast<const u32x4_t*>(p));
+    return uint4{v.x, v.y, v.z, v.w};
+}
 __device__ __forceinline__ void st_stream(uint2* p, uint2 v) {
     st_stream(reinterpret_cast<u32x2_t*>(p), u32x2_t{v.x, v.y});
 }
@@ -312,81 +319,203 @@ __host__ __device__ constexpr uint32_t hist_index(uint32_t q, uint32_t d, uint32
     return q == 0 ? x * RADIX + d : (q * RADIX + d) * NCH + x;
 }
 
+// ---- Building blocks of the two histogram sweeps — global_histogram_kernel below, hy_histogram_kernel (hybrid_kernels.hpp) — and of the
+// other kernels that count on packed 16-bit counters.  Each contract: what must be uniform, the barriers inside, the LDS owned.
+// ---- packed counters: bin d is the 16-bit field d & 1 of word d >> 1 of its table.
+// A field that wraps loses 65 536 (high field) or 65 535 (low field: it carries into its neighbour) from the table's decoded SUM and
+// never adds to it — so "decoded sum == keys counted" is an EXACT test for "no counter wrapped", made when a table is written out.
+__host__ __device__ constexpr uint32_t pk16_addend(uint32_t d, uint32_t c) { return c << ((d & 1u) << 4); }              // what adds c to bin d's word
+__host__ __device__ constexpr uint32_t pk16_field(uint32_t word, uint32_t d) { return (word >> ((d & 1u) << 4)) & 0xffffu; }  // bin d's count
+__host__ __device__ constexpr uint32_t pk16_sum(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {  // the eight counts of four words
+    return (x & 0xffffu) + (x >> 16) + (y & 0xffffu) + (y >> 16) + (z & 0xffffu) + (z >> 16) + (w & 0xffffu) + (w >> 16);
+}
+static_assert(pk16_addend(6, 3) == 3u && pk16_addend(7, 3) == 0x30000u && pk16_field(0x00050003u, 6) == 3u && pk16_field(0x00050003u, 7) == 5u, "low field, high field");
+static_assert(pk16_sum(0x0002ffffu + pk16_addend(0, 1), 0, 0, 0) == 65537u + 1u - 65535u, "a low field that carries loses 65 535");
+static_assert(pk16_sum(0xffff0001u + pk16_addend(1, 1), 0, 0, 0) == 65536u + 1u - 65536u, "a high field that wraps loses 65 536");
+__device__ __forceinline__ uint32_t pk16_sum(const uint4 v) { return pk16_sum(v.x, v.y, v.z, v.w); }
+__device__ __forceinline__ uint32_t pk16_read(const uint32_t* table, uint32_t d) { return pk16_field(table[d >> 1], d); }  // bin d's count
+// LDS add of c to bin d of `table` (any lanes, no barrier)
+__device__ __forceinline__ void pk16_add(uint32_t* table, uint32_t d, uint32_t c) { atomicAdd(&table[d >> 1], pk16_addend(d, c)); }
+// the eight counts of four words, in bin order
+__device__ __forceinline__ void pk16_unpack(const uint4 v, uint32_t (&h)[8]) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) h[j] = pk16_field(w[j >> 1], j);
+}
+
+// ---- the sort's CLEAR (reference: ClearMemory, OneSweepDispatcher.cuh:301-309).  The histogram sweep — whichever runs — zeroes the
+// scan state nobody reads before it ends — ticket counters, status, info, slice counts, descriptors — as 16-byte grid-stride stores
+// next to its read stream; a separate memset was one more launch (5 us of a 50 us sort at mid sizes).  The HIST region is zero whenever no
+// call is in flight: the first DigitBinningPass behind the Scan re-zeroes it (mode bit 2).  Called by every thread of every workgroup (T threads); no barrier, no LDS.
+template <uint32_t T>
+__device__ __forceinline__ void clear_scan_state(uint32_t* slab, size_t slab_used_words, uint32_t tid) {
+    uint4* a = reinterpret_cast<uint4*>(slab);
+    const size_t na = SLAB_HIST / 4, b0 = SLAB_HSUB / 4, nb = slab_used_words / 4;  // all multiples of 4 words
+    const size_t stride = (size_t)gridDim.x * T;
+    const uint4 z = {0u, 0u, 0u, 0u};
+    for (size_t i = (size_t)blockIdx.x * T + tid; i < na; i += stride) a[i] = z;
+    for (size_t i = b0 + (size_t)blockIdx.x * T + tid; i < nb; i += stride) a[i] = z;
+}
+
+// ---- digit 0 of a sweep: 32 lane-private replicas of the 256 counters, packed two per dword.  Dword (d >> 1) * 32 + (lane & 31) lies
+// in bank lane & 31, so a wave's add never meets a bank conflict — whatever the keys are: the 256-bin table of one position segment
+// was the most expensive of the four (9.7 clk per wave-add against 7.5 for the 4096-bin joint tables and 4.2 conflict-free,
+// profiles/r02_lds_microbench.txt: 64 random lanes on 256 bins collide on ADDRESSES, which serialises atomics), and a constant low
+// byte — every lane on one counter, 128 clk — costs nothing here.  The sweep folds them when the table they count for changes, every
+// HIST_FOLD_CHUNKS chunks and at the end: between two folds a replica sees at most HIST_CHUNK / 32 keys per chunk — a chunk being four
+// keys of each of GHIST_THREADS threads in both sweeps (hybrid_kernels.hpp asserts its workgroup size against it).
+constexpr uint32_t HIST_REPLICA_WORDS = RADIX / 2 * 32;  // the LDS a sweep gives them (16-byte aligned, zero before the first add)
+static_assert(HIST_FOLD_CHUNKS * (HIST_CHUNK / 32) <= 0xffff, "a replica must not wrap between two folds");
+// counts digit d (< 256) for this lane; no barrier
+__device__ __forceinline__ void replica_add(uint32_t* s_r, uint32_t d, uint32_t lane) {
+    atomicAdd(&s_r[(d >> 1) * 32u + (lane & 31u)], pk16_addend(d, 1u));
+}
+// Adds the replicas' sums to dst[0 .. 255] (LDS) and zeroes them.  Uniform call by all T threads; `live` uniform: false — nothing
+// counted yet, no dst — passes the two barriers only.  Barriers: one in front (the adds are in), one behind (dst and the zeroes are).
+// Eight threads share the 32 replicas of a counter pair (one 16-byte read each, conflict-free), sum them with three butterfly steps,
+// and the first of them owns the two bins they go to.  (One LDS add per non-empty replica word had the 32 replicas of a pair meet on
+// ONE address: 128 wave-adds of 32 serial steps each, 9 us per fold — half of global_histogram_kernel's fixed cost at mid sizes and
+// 3 % of it at 2^28, profiles/r03_mid_route_v3_and_hist_fold.txt.)
+template <uint32_t T>
+__device__ __forceinline__ void replica_fold(uint32_t* s_r, uint32_t* dst, uint32_t tid, bool live = true) {
+    __syncthreads();
+    if (live) {
+        for (uint32_t i = tid; i < RADIX / 2 * 8; i += T) {  // (one round with 1024 threads)
+            const uint4 v = reinterpret_cast<const uint4*>(s_r)[i];
+            reinterpret_cast<uint4*>(s_r)[i] = uint4{0u, 0u, 0u, 0u};
+            uint32_t lo = (v.x & 0xffffu) + (v.y & 0xffffu) + (v.z & 0xffffu) + (v.w & 0xffffu);
+            uint32_t hi = (v.x >> 16) + (v.y >> 16) + (v.z >> 16) + (v.w >> 16);
+#pragma unroll
+            for (int m = 1; m < 8; m <<= 1) {
+                lo += __shfl_xor(lo, m, 64);
+                hi += __shfl_xor(hi, m, 64);
+            }
+            if ((i & 7u) == 0u) {
+                dst[(i >> 3) * 2u] += lo;
+                dst[(i >> 3) * 2u + 1u] += hi;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// ---- dominant-bin ("sticky") counting of N tables by one wave, table by table.  Same-address LDS atomics serialise per lane (Thearling-Smith
+// presets, constant bytes, sorted input); lanes holding the remembered dominant bin are counted with ONE add of their popcount (by
+// their first lane), all other lanes add individually.  All state is wave-uniform, every call is made by the whole wave; no barrier,
+// no LDS of its own.  `add(bin, count)` is how the table counts: a plain LDS add (joint tables), pk16_add (the prefix table).
+// hy_histogram_kernel keeps a written-out copy for its one table (see there).
+// (Measured and not kept: counting those lanes on the scalar unit only — a running popcount, added when the guess changes — skewed
+//  presets -2 %, uniform +4 %: the cost under skew is the conflicts among the OTHER hot bins, profiles/r02_skew_rank_fixed_mode.txt)
+struct WaveFirst { uint32_t bin, lanes; };  // the first active lane's bin, the lanes that share it
+__device__ __forceinline__ WaveFirst wave_first(uint32_t bin0) {
+    const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)bin0);
+    return WaveFirst{f, (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(bin0 == f))};
+}
+template <uint32_t N>
+struct StickyBins {
+    uint32_t skew = 0;  // bit q: a dominant bin was seen in table q; cleared when it fades (0: no table is in skew mode)
+    uint32_t bin[N];    // table q's guess of it
+    __device__ __forceinline__ StickyBins() {
+#pragma unroll
+        for (uint32_t q = 0; q < N; ++q) bin[q] = 0xffffffffu;
+    }
+    // Cheap probe on the first key of a work item's first chunk: do >= HIST_SKEW_LANES lanes share the first lane's bin?  (On every
+    // chunk the probe cost the uniform case 10 % of the kernel, profiles/r02_ab_hist_variants.txt; skew does not come and go chunk by
+    // chunk.)  A sweep probes ALL its tables BEFORE the adds, so that a wave that has seen no dominant bin does every add of the chunk
+    // in one basic block: the address arithmetic of one table overlaps the LDS adds of the previous one (with uniform branches between
+    // the tables they could not: profiles/r04_hist_kernel_variants.txt).
+    __device__ __forceinline__ void probe(uint32_t q, uint32_t bin0) {
+        const WaveFirst s = wave_first(bin0);
+        if (s.lanes >= HIST_SKEW_LANES) {
+            skew |= 1u << q;
+            if (s.lanes >= HIST_RELEARN_LANES || bin[q] == 0xffffffffu) bin[q] = s.bin;  // (re)learn the dominant bin
+        }
+    }
+    // Skew mode: the chunk's four bins of every lane.  Relearn BEFORE the adds: on sorted input every chunk lies under a new dominant
+    // bin, and relearning behind the adds put 64 lanes x 4 keys on one counter one by one first (0.88 ms for global_histogram_kernel,
+    // 0.71 ms for hy_histogram_kernel on sorted keys, profiles/r05_sorted_inputs.txt).
+    template <class Add>
+    __device__ __forceinline__ void add4(uint32_t q, const uint32_t (&b)[4], Add add) {
+        const WaveFirst s = wave_first(b[0]);
+        if (s.lanes >= HIST_RELEARN_LANES && s.bin != bin[q]) bin[q] = s.bin;
+        uint32_t hit = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(b[j] == bin[q]);
+            hit += (uint32_t)__popcll(m);
+            if (b[j] != bin[q]) add(b[j], 1u);
+            else if (__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) == 0u)
+                add(bin[q], (uint32_t)__popcll(m));
+        }
+        if (hit < HIST_STICKY_HITS) {  // the guess covers < 1/8 of the lanes: relearn, or leave skew mode
+            bin[q] = s.bin;
+            if (s.lanes < HIST_SKEW_LANES) skew &= ~(1u << q);
+        }
+    }
+};
+
+// ---- OR of all keys (radix-sortable digit words) and of their complements: a bit set in both varies; a byte clear in their AND is
+// constant — how a sort planned on position chains (its joint tables are incomplete) still finds its identity passes.  The
+// accumulation is free: the sweeps wait for their LDS adds.
+struct KeyBits {
+    uint32_t k_or = 0, k_nand = 0;  // per thread
+    __device__ __forceinline__ void add(uint32_t k) {
+        k_or |= k;
+        k_nand |= ~k;
+    }
+    __device__ __forceinline__ void add4(const uint4 t) {
+        k_or |= t.x | t.y | t.z | t.w;
+        k_nand |= ~(t.x & t.y & t.z & t.w);
+    }
+    // HX_OR / HX_NAND of `hist` |= every thread's.  Uniform call by the whole workgroup.  scratch: two LDS words that are ZERO, as every
+    // thread sees them (a barrier behind their zeroing), and that nobody else touches from the call on.  One barrier, behind the waves' ORs.
+    // ONE pair of global atomics per workgroup: same-address device atomics run at ~100 per microsecond — a pair per wave, 8192 of
+    // them, cost global_histogram_kernel 0.075 ms, profiles/r04_hist_orand_atomics.txt.
+    __device__ __forceinline__ void publish(uint32_t* scratch, uint32_t* hist, uint32_t tid) {
+#pragma unroll
+        for (int dd = 32; dd > 0; dd >>= 1) {
+            k_or |= __shfl_xor(k_or, dd, 64);
+            k_nand |= __shfl_xor(k_nand, dd, 64);
+        }
+        if ((tid & 63u) == 0) {
+            atomicOr(&scratch[0], k_or);
+            atomicOr(&scratch[1], k_nand);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            atomicOr(&hist[HIST_TABLE_WORDS + HX_OR], scratch[0]);
+            atomicOr(&hist[HIST_TABLE_WORDS + HX_NAND], scratch[1]);
+        }
+    }
+};
+
 // 64-bit keys: np <= 4: `word` selects the 32-bit word the np digits are taken from (stand-alone passes, the multi-GPU split);
 // np == 8 (the sort): ONE sweep counts all eight tables — the digits of the low word as above, byte 4's table joint with the
 // low word's top bits (the bin is the 12-bit field at bit 28 of the 64-bit key), bytes 5..7 inside the high word — so
 // the sort reads its keys once for the histogram instead of once per word (8 x 4096 bins: 128 KiB of LDS).  A work item is
 // still HIST_CHUNK keys — two 16-byte loads per thread instead of one.
 template <int KT>
-__global__ __launch_bounds__(GHIST_THREADS, GHIST_WAVES_PER_SIMD) void global_histogram_kernel(const uint32_t* __restrict__ keys,
-                                                                         uint32_t* slab, size_t slab_used_words,
-                                                                         uint32_t n, uint32_t seg_len0, uint32_t p0,
-                                                                         uint32_t np, uint32_t word,
-                                                                         uint32_t allow_pos /*1: the sort may run on position
-                                                                         chains (scan_kernel, PF_POS) — uneven digit groups end the
-                                                                         counting of the joint tables*/,
-                                                                         uint32_t* partials /*[gridDim][HIST_TABLE_WORDS]: every
-                                                                         workgroup's tables, summed by hist_reduce_kernel*/) {
+__global__ __launch_bounds__(GHIST_THREADS, GHIST_WAVES_PER_SIMD) void global_histogram_kernel(
+    const uint32_t* __restrict__ keys, uint32_t* slab, size_t slab_used_words, uint32_t n, uint32_t seg_len0, uint32_t p0, uint32_t np, uint32_t word,
+    uint32_t allow_pos /*1: the sort may run on position chains (scan_kernel, PF_POS) — uneven digit groups end the counting of the joint tables*/,
+    uint32_t* partials /*[gridDim][HIST_TABLE_WORDS]: every workgroup's tables, summed by hist_reduce_kernel*/) {
+    // ---- set-up
     constexpr int KW = KeyWords<KT>::value;
     constexpr uint32_t NQ = KW == 2 ? MAX_PASSES : 4;  // tables a workgroup can count
     __shared__ __attribute__((aligned(16))) uint32_t s_h[NQ * NCH * RADIX];  // (read as uint4 for the slice store)
     __shared__ uint32_t s_uneven;  // a digit group of this workgroup's first work item holds more than POS_SHARE / 16 of its keys
-    // Pass-0 digit counts on 32 lane-private replicas, 16-bit counters packed two per dword: dword (d >> 1) * 32 +
-    // (lane & 31) lies in bank lane & 31, so a wave's add never meets a bank conflict — whatever the keys are: the
-    // 256-bin table of one position segment was the most expensive of the four (9.7 clk per wave-add against 7.5
-    // for the 4096-bin joint tables and 4.2 conflict-free, profiles/r02_lds_microbench.txt: 64 random lanes on
-    // 256 bins collide on ADDRESSES, which serialises atomics), and a constant low byte — every lane on one
-    // counter, 128 clk — costs nothing here.  Folded into s_h when the workgroup's segment changes, every
-    // HIST_FOLD_CHUNKS chunks (a replica sees 128 keys per chunk: 16-bit counters hold 511 chunks), and at the end.
-    __shared__ __attribute__((aligned(16))) uint32_t s_r[RADIX / 2 * 32];
+    __shared__ __attribute__((aligned(16))) uint32_t s_r[HIST_REPLICA_WORDS];  // pass-0 digit counts of the current position segment
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     uint32_t* hist = slab + SLAB_HIST;
-    // This kernel is also the sort's CLEAR (reference: ClearMemory, OneSweepDispatcher.cuh:301-309): it zeroes the
-    // scan state nobody reads before it ends — ticket counters, status, info, slice counts, descriptors — as
-    // 16-byte grid-stride stores next to its read stream; a separate memset was one more launch (5 us of a 50 us
-    // sort at mid sizes).  The HIST region is zero whenever no call is in flight: the first DigitBinningPass
-    // launched after the Scan re-zeroes it (mode bit 2).
-    {
-        uint4* a = reinterpret_cast<uint4*>(slab);
-        const size_t na = SLAB_HIST / 4, b0 = SLAB_HSUB / 4, nb = slab_used_words / 4;  // all multiples of 4 words
-        const size_t stride = (size_t)gridDim.x * GHIST_THREADS;
-        const uint4 z = {0u, 0u, 0u, 0u};
-        for (size_t i = (size_t)blockIdx.x * GHIST_THREADS + tid; i < na; i += stride) a[i] = z;
-        for (size_t i = b0 + (size_t)blockIdx.x * GHIST_THREADS + tid; i < nb; i += stride) a[i] = z;
-    }
+    clear_scan_state<GHIST_THREADS>(slab, slab_used_words, tid);
     const uint32_t bins = np * NCH * RADIX;
     for (uint32_t i = tid; i < bins; i += GHIST_THREADS) s_h[i] = 0;
     if (tid == 0) s_uneven = 0;
     bool joint_off = (allow_pos & 2u) != 0u;  // uniform: the joint tables are given up (see the probe behind the first work item; bit 1: from the start)
-    for (uint32_t i = tid; i < RADIX / 2 * 32; i += GHIST_THREADS) s_r[i] = 0;
-    uint32_t cur_x0 = 0xffffffffu, since_fold = 0;  // uniform: segment the replicas are counting for, chunks since the last fold
-    // Eight threads share the 32 replicas of a counter pair (one 16-byte read each, conflict-free), sum them with three
-    // butterfly steps, and the first of them owns the two bins they go to.  (One LDS add per non-empty replica word had the
-    // 32 replicas of a pair meet on ONE address: 128 wave-adds of 32 serial steps each, 9 us per fold — half of this
-    // kernel's fixed cost at mid sizes and 3 % of it at 2^28, profiles/r03_mid_route_v3_and_hist_fold.txt.)
-    auto fold = [&](uint32_t x) {
-        __syncthreads();
-        if (x != 0xffffffffu) {
-            for (uint32_t i = tid; i < RADIX / 2 * 8; i += GHIST_THREADS) {  // (one round with 1024 threads)
-                const uint4 v = reinterpret_cast<const uint4*>(s_r)[i];
-                reinterpret_cast<uint4*>(s_r)[i] = uint4{0u, 0u, 0u, 0u};
-                uint32_t lo = (v.x & 0xffffu) + (v.y & 0xffffu) + (v.z & 0xffffu) + (v.w & 0xffffu);
-                uint32_t hi = (v.x >> 16) + (v.y >> 16) + (v.z >> 16) + (v.w >> 16);
-#pragma unroll
-                for (int m = 1; m < 8; m <<= 1) {
-                    lo += __shfl_xor(lo, m, 64);
-                    hi += __shfl_xor(hi, m, 64);
-                }
-                if ((i & 7u) == 0u) {
-                    s_h[hist_index(0, (i >> 3) * 2u, x)] += lo;
-                    s_h[hist_index(0, (i >> 3) * 2u + 1u, x)] += hi;
-                }
-            }
-        }
-        __syncthreads();
-    };
+    for (uint32_t i = tid; i < HIST_REPLICA_WORDS; i += GHIST_THREADS) s_r[i] = 0;
+    uint32_t cur_x0 = 0xffffffffu, since_fold = 0;  // uniform: segment the replicas are counting for (none yet), chunks since the last fold
+    auto fold = [&]() { replica_fold<GHIST_THREADS>(s_r, s_h + hist_index(0, 0, cur_x0 != 0xffffffffu ? cur_x0 : 0u), tid, cur_x0 != 0xffffffffu); };
     __syncthreads();
-
     const uint32_t shift0 = p0 * 8u;
     const bool both = KW == 2 && np > 4u;  // uniform: all eight tables of a 64-bit key in this sweep (p0 = 0)
     // b: the word the first four digits come from, hi: the key's high word (both only)
@@ -396,118 +525,70 @@ __global__ __launch_bounds__(GHIST_THREADS, GHIST_WAVES_PER_SIMD) void global_hi
         if (q == 4) return 4u * (RADIX * NCH) + (((hi & 255u) << LOG_NCH) | (b >> (32u - LOG_NCH)));
         return q * (RADIX * NCH) + __builtin_amdgcn_ubfe(hi, 8u * (q - 4u) - LOG_NCH, 8u + LOG_NCH);
     };
-
-    uint32_t k_or = 0, k_nand = 0;  // OR of this thread's digit words / of their complements (free: the kernel waits for its LDS adds)
-    uint32_t skew_mode = 0;  // bit q (wave-uniform): a dominant bin was seen for byte q; cleared when it fades
-    uint32_t sticky[NQ];     // wave-uniform guess of that bin
-#pragma unroll
-    for (uint32_t q = 0; q < NQ; ++q) sticky[q] = 0xffffffffu;
+    auto add = [&](uint32_t bin, uint32_t c) { atomicAdd(&s_h[bin], c); };
+    KeyBits bits;
+    StickyBins<NQ> sticky;  // one state per joint table (q >= 1)
     // One work item = HIST_UNROLL consecutive chunks; all their 16-byte loads are issued before the
     // first is consumed (one load per thread in flight left the kernel latency-bound at 3.1 TB/s).
     // JOINT = 0: the joint tables are given up (joint_off) — only the first digit is counted
     // t: four keys' digit words, sortable form; th: their high words (both)
     auto process = [&](auto joint_tag, const uint4 t, const uint4 th, const uint32_t x0, const bool probe) {
-            constexpr bool JOINT = decltype(joint_tag)::value != 0;
-            const uint32_t b[4] = {t.x, t.y, t.z, t.w};
-            k_or |= t.x | t.y | t.z | t.w;
-            k_nand |= ~(t.x & t.y & t.z & t.w);
-            const uint32_t bh[4] = {th.x, th.y, th.z, th.w};
-            // the first digit goes to the replicas; the joint tables (q >= 1) below
-            if (x0 != cur_x0 || since_fold >= HIST_FOLD_CHUNKS) {  // uniform
-                fold(cur_x0);
-                cur_x0 = x0;
-                since_fold = 0;
-            }
-            ++since_fold;
+        constexpr bool JOINT = decltype(joint_tag)::value != 0;
+        const uint32_t b[4] = {t.x, t.y, t.z, t.w};
+        const uint32_t bh[4] = {th.x, th.y, th.z, th.w};
+        bits.add4(t);
+        // the first digit goes to the replicas; the joint tables (q >= 1) below
+        if (x0 != cur_x0 || since_fold >= HIST_FOLD_CHUNKS) {  // uniform
+            fold();
+            cur_x0 = x0;
+            since_fold = 0;
+        }
+        ++since_fold;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t d = (b[j] >> shift0) & 255u;
-                atomicAdd(&s_r[(d >> 1) * 32u + (lane & 31u)], 1u << ((d & 1u) * 16u));
-            }
-            if constexpr (!JOINT) return;
-            // Skew (Thearling-Smith presets, constant bytes): same-address LDS atomics serialise per lane.  Cheap probe on
-            // the first key of a work item's first chunk: do >= 8 lanes share the first lane's bin?  (On every chunk the
-            // probe cost the uniform case 10 % of the kernel, profiles/r02_ab_hist_variants.txt; skew does not come and go
-            // chunk by chunk.)  The probe runs BEFORE the adds so that a wave that has seen no dominant bin does every add of
-            // the chunk in one basic block: the address arithmetic of one table overlaps the LDS adds of the previous one
-            // (with uniform branches between the tables they could not: profiles/r04_hist_kernel_variants.txt).
-            if (probe) {
+        for (int j = 0; j < 4; ++j) replica_add(s_r, (b[j] >> shift0) & 255u, lane);
+        if constexpr (!JOINT) return;
+        if (probe) {
 #pragma unroll
-                for (uint32_t q = 1; q < NQ; ++q)
-                    if (q < np) {
-                        const uint32_t bin0 = bin_of(b[0], bh[0], q, x0);
-                        const uint32_t b0 = __builtin_amdgcn_readfirstlane(bin0);
-                        const uint32_t pc = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(bin0 == b0));
-                        if (pc >= HIST_SKEW_LANES) {
-                            skew_mode |= 1u << q;
-                            if (pc >= 24 || sticky[q] == 0xffffffffu) sticky[q] = b0;  // (re)learn the dominant bin
-                        }
-                    }
-            }
-            if (skew_mode == 0u) {  // uniform
+            for (uint32_t q = 1; q < NQ; ++q)
+                if (q < np) sticky.probe(q, bin_of(b[0], bh[0], q, x0));
+        }
+        if (sticky.skew == 0u) {  // uniform: every add of the chunk in one basic block (see StickyBins::probe)
 #pragma unroll
-                for (uint32_t q = 1; q < NQ; ++q)
-                    if (q < np) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) atomicAdd(&s_h[bin_of(b[j], bh[j], q, x0)], 1u);
-                    }
-                return;
-            }
-#pragma unroll
-            for (uint32_t q = 1; q < NQ; ++q) {
+            for (uint32_t q = 1; q < NQ; ++q)
                 if (q < np) {
-                    uint32_t bin[4];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) bin[j] = bin_of(b[j], bh[j], q, x0);
-                    if (skew_mode & (1u << q)) {
-                        // lanes holding the remembered dominant bin are counted with ONE add of their
-                        // popcount (by their first lane); all other lanes add individually
-                        // (measured and not kept: counting those lanes on the scalar unit only — a running popcount,
-                        //  added when the guess changes — skewed presets -2 %, uniform +4 %: the cost under skew is the
-                        //  conflicts among the OTHER hot bins, profiles/r02_skew_rank_fixed_mode.txt)
-                        const uint32_t b0 = __builtin_amdgcn_readfirstlane(bin[0]);
-                        const uint32_t pc = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(bin[0] == b0));
-                        // (round 5: relearn BEFORE the adds — on sorted input every chunk lies under a new dominant bin, and relearning
-                        //  behind the adds put 64 lanes x 4 keys on one counter one by one first: 0.88 ms for this kernel on sorted keys)
-                        if (pc >= 24 && b0 != sticky[q]) sticky[q] = b0;
-                        uint32_t hit = 0;
+                    for (int j = 0; j < 4; ++j) add(bin_of(b[j], bh[j], q, x0), 1u);
+                }
+            return;
+        }
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const unsigned long long m = __builtin_amdgcn_ballot_w64(bin[j] == sticky[q]);
-                            hit += (uint32_t)__popcll(m);
-                            if (bin[j] != sticky[q]) atomicAdd(&s_h[bin[j]], 1u);
-                            else if (__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) == 0u)
-                                atomicAdd(&s_h[sticky[q]], (uint32_t)__popcll(m));
-                        }
-                        if (hit < 32) {  // the guess covers < 1/8 of the lanes: relearn, or leave skew mode
-                            sticky[q] = b0;
-                            if (pc < 8) skew_mode &= ~(1u << q);
-                        }
-                    } else {
+        for (uint32_t q = 1; q < NQ; ++q) {
+            if (q < np) {
+                uint32_t bin[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) atomicAdd(&s_h[bin[j]], 1u);
-                    }
+                for (int j = 0; j < 4; ++j) bin[j] = bin_of(b[j], bh[j], q, x0);
+                if (sticky.skew & (1u << q)) {
+                    sticky.add4(q, bin, add);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) add(bin[j], 1u);
                 }
             }
+        }
     };
     // the four keys of thread tid in chunk c, reduced to their digit words (radix-sortable form)
     auto word_of = [&](uint32_t lo, uint32_t hi) {
         const uint2 b = to_bits2<KT>(uint2{lo, hi});
         return word ? b.y : b.x;
     };
-    typedef uint32_t hv4 __attribute__((ext_vector_type(4)));
     // non-temporal key loads: 0.296 -> 0.250 ms at 2^28 (the pass that follows pays 0.008 ms of it back: fewer of its first reads
     // hit the memory-side cache), profiles/r03_ab_hist_nt_loads.txt.  Measured with it and not kept: the next work item's loads in
     // flight while this one is counted (no change: the kernel does not wait for its loads)
-    auto ld16 = [](const uint4* q) -> uint4 {
-        const hv4 v = __builtin_nontemporal_load(reinterpret_cast<const hv4*>(q));
-        return uint4{v.x, v.y, v.z, v.w};
-    };
     struct Chunk { uint4 w, hi; };  // the digit words of a thread's four keys (and, 64-bit keys counted in one sweep, their high words)
     auto load_chunk = [&](uint32_t c) -> Chunk {
         if constexpr (KW == 2) {
             const uint4* p = reinterpret_cast<const uint4*>(keys) + (size_t)c * (HIST_CHUNK / 2);
-            const uint4 a = ld16(p + tid), b2 = ld16(p + tid + GHIST_THREADS);
+            const uint4 a = ld_stream<true>(p + tid), b2 = ld_stream<true>(p + tid + GHIST_THREADS);
             if (both) {
                 const uint2 k0 = to_bits2<KT>(uint2{a.x, a.y}), k1 = to_bits2<KT>(uint2{a.z, a.w});
                 const uint2 k2 = to_bits2<KT>(uint2{b2.x, b2.y}), k3 = to_bits2<KT>(uint2{b2.z, b2.w});
@@ -515,7 +596,7 @@ __global__ __launch_bounds__(GHIST_THREADS, GHIST_WAVES_PER_SIMD) void global_hi
             }
             return Chunk{uint4{word_of(a.x, a.y), word_of(a.z, a.w), word_of(b2.x, b2.y), word_of(b2.z, b2.w)}, uint4{0u, 0u, 0u, 0u}};
         } else {
-            const uint4 a = ld16(reinterpret_cast<const uint4*>(keys + (size_t)c * HIST_CHUNK) + tid);
+            const uint4 a = ld_stream<true>(reinterpret_cast<const uint4*>(keys + (size_t)c * HIST_CHUNK) + tid);
             return Chunk{uint4{to_bits<KT>(a.x), to_bits<KT>(a.y), to_bits<KT>(a.z), to_bits<KT>(a.w)}, uint4{0u, 0u, 0u, 0u}};
         }
     };
@@ -525,6 +606,7 @@ __global__ __launch_bounds__(GHIST_THREADS, GHIST_WAVES_PER_SIMD) void global_hi
     const uint32_t per_wg = (nchunks_all + gridDim.x - 1) / gridDim.x;
     const uint32_t c_first = blockIdx.x * per_wg;
     const uint32_t nchunks = c_first + per_wg < nchunks_all ? c_first + per_wg : nchunks_all;
+    // ---- work-item loop
     uint32_t c0 = c_first;
     for (; c0 < nchunks; c0 += HIST_UNROLL) {
         if (c0 + HIST_UNROLL <= nchunks && (unsigned long long)(c0 + HIST_UNROLL) * HIST_CHUNK <= n) {
@@ -560,6 +642,7 @@ __global__ __launch_bounds__(GHIST_THREADS, GHIST_WAVES_PER_SIMD) void global_hi
             }
             continue;
         }
+        // ---- tail: the range's last, partial work item
         Chunk t[HIST_UNROLL];
 #pragma unroll
         for (uint32_t u = 0; u < HIST_UNROLL; ++u) {
@@ -584,16 +667,16 @@ __global__ __launch_bounds__(GHIST_THREADS, GHIST_WAVES_PER_SIMD) void global_hi
                         } else {
                             kb = to_bits<KT>(keys[i]);
                         }
-                        k_or |= kb;
-                        k_nand |= ~kb;
+                        bits.add(kb);
                         for (uint32_t q = 0; q < np; ++q)
-                            if (!(joint_off && q >= 1)) atomicAdd(&s_h[bin_of(kb, kh, q, x0)], 1u);
+                            if (!(joint_off && q >= 1)) add(bin_of(kb, kh, q, x0), 1u);
                     }
                 }
             }
         }
     }
-    fold(cur_x0);
+    // ---- close
+    fold();
     // The workgroup's tables go out as they are — coalesced plain stores into its own slice — and hist_reduce_kernel sums the
     // slices.  (One global atomic per non-empty bin cost 256 workgroups x ~14 000 device-scope atomics on the same 16 384 words:
     // 20-40 us of every sort from 2^23 keys up, half of this kernel at 2^23, profiles/r03_mid_size_routes.txt.)
@@ -603,27 +686,7 @@ __global__ __launch_bounds__(GHIST_THREADS, GHIST_WAVES_PER_SIMD) void global_hi
             reinterpret_cast<uint4*>(mine)[i] = reinterpret_cast<const uint4*>(s_h)[i];
     }
     if (tid == 0 && joint_off) atomicOr(&hist[HIST_TABLE_WORDS + HX_SKEW], 1u);
-    if (allow_pos) {
-        // (only a sort that may end up on position chains needs them.  ONE pair of atomics per workgroup: same-address device atomics
-        //  run at ~100 per microsecond — a pair per wave, 8192 of them, cost this kernel 0.075 ms, profiles/r04_hist_orand_atomics.txt)
-#pragma unroll
-        for (int dd = 32; dd > 0; dd >>= 1) {
-            k_or |= __shfl_xor(k_or, dd, 64);
-            k_nand |= __shfl_xor(k_nand, dd, 64);
-        }
-        __syncthreads();  // (s_h is stored: its first words serve as scratch)
-        if (tid < 2) s_h[tid] = 0;
-        __syncthreads();
-        if (lane == 0) {
-            atomicOr(&s_h[0], k_or);
-            atomicOr(&s_h[1], k_nand);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            atomicOr(&hist[HIST_TABLE_WORDS + HX_OR], s_h[0]);
-            atomicOr(&hist[HIST_TABLE_WORDS + HX_NAND], s_h[1]);
-        }
-    }
+    if (allow_pos) bits.publish(s_r, hist, tid);  // (only a sort that may end up on position chains needs them; the last fold left the replicas zero: the scratch)
 }
 
 // Sum of the histogram workgroups' tables: hist[i] = sum over workgroups of partials[w][i].  A workgroup of 256 threads owns

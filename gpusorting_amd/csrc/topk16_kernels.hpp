@@ -55,7 +55,7 @@ __device__ __forceinline__ uint4 tk16_load_chunk(const uint16_t* src, uint32_t c
     const uint32_t i = c + tid * 8u;
     if (GS_LIKELY(c + TK16_CHUNK <= end)) {
         mask = 255u;
-        return tk_ld16(reinterpret_cast<const uint32_t*>(src + i));
+        return ld_stream<true>(reinterpret_cast<const uint4*>(src + i));
     }
     uint32_t e[4] = {0u, 0u, 0u, 0u};
     mask = 0u;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(TK_THREADS) void tk16_hist_kernel(const uint16_t* _
     __syncthreads();
     const uint32_t hot = (s_red[0] >> 16) >= TK_HOT_VOTES ? (s_red[0] & 0xffffu) : TK_NO_BIN;
     uint32_t hot_count = 0;
-    auto add = [&](uint32_t d, uint32_t c) { atomicAdd(&s_j[(d & 0xffffu) >> 1], c << ((d & 1u) << 4)); };
+    auto add = [&](uint32_t d, uint32_t c) { atomicAdd(&s_j[(d & 0xffffu) >> 1], pk16_addend(d, c)); };  // pk16_add's add with the word index masked to the table
     auto process = [&](const uint4 t, const uint32_t mask) {
         const uint32_t w4[4] = {t.x, t.y, t.z, t.w};
         uint32_t d[8];
@@ -138,11 +138,11 @@ __global__ __launch_bounds__(TK_THREADS) void tk16_hist_kernel(const uint16_t* _
             if (c0 + u * TK16_CHUNK < end) process(t[u], mask[u]);  // uniform
     }
     __syncthreads();
-    // the exact overflow test
+    // the exact overflow test (see pk16_sum)
     uint32_t sum = 0;
     for (uint32_t i = tid; i < TK_TABLE_WORDS / 4; i += T) {
         const uint4 v = reinterpret_cast<const uint4*>(s_j)[i];
-        sum += (v.x & 0xffffu) + (v.x >> 16) + (v.y & 0xffffu) + (v.y >> 16) + (v.z & 0xffffu) + (v.z >> 16) + (v.w & 0xffffu) + (v.w >> 16);
+        sum += pk16_sum(v);
     }
     sum = wave_reduce_sum(sum);
     const uint32_t hsum = wave_reduce_sum(hot_count);

@@ -80,17 +80,12 @@ __global__ __launch_bounds__(256) void tk_init_kernel(uint32_t* ctl, uint32_t* e
     }
 }
 
-__device__ __forceinline__ uint4 tk_ld16(const uint32_t* q) {
-    typedef uint32_t hv4 __attribute__((ext_vector_type(4)));
-    const hv4 v = __builtin_nontemporal_load(reinterpret_cast<const hv4*>(q));
-    return uint4{v.x, v.y, v.z, v.w};
-}
 // four elements of thread `tid` in the chunk at c (indices stay below 2^30 + TK_TILE: no wrap); `valid`: how many lie in front of `end`
 __device__ __forceinline__ uint4 tk_load_chunk(const uint32_t* src, uint32_t c, uint32_t end, uint32_t tid, uint32_t& valid) {
     const uint32_t i = c + tid * 4u;
     if (GS_LIKELY(c + TK_CHUNK <= end)) {
         valid = 4u;
-        return tk_ld16(src + i);
+        return ld_stream<true>(reinterpret_cast<const uint4*>(src + i));
     }
     valid = i >= end ? 0u : (end - i < 4u ? end - i : 4u);
     uint4 t{0u, 0u, 0u, 0u};
@@ -133,7 +128,7 @@ __global__ __launch_bounds__(TK_THREADS) void tk_hist_kernel(const uint32_t* __r
     __syncthreads();
     const uint32_t hot = (s_red[0] >> 16) >= TK_HOT_VOTES ? (s_red[0] & 0xffffu) : TK_NO_BIN;
     uint32_t hot_count = 0;
-    auto add = [&](uint32_t d, uint32_t c) { atomicAdd(&s_j[d >> 1], c << ((d & 1u) << 4)); };
+    auto add = [&](uint32_t d, uint32_t c) { pk16_add(s_j, d, c); };
     auto process = [&](const uint4 t, const uint32_t valid) {
         const uint32_t d[4] = {tk_digit(tk_sel(t.x, kt, flip), level), tk_digit(tk_sel(t.y, kt, flip), level),
                                tk_digit(tk_sel(t.z, kt, flip), level), tk_digit(tk_sel(t.w, kt, flip), level)};
@@ -165,11 +160,11 @@ __global__ __launch_bounds__(TK_THREADS) void tk_hist_kernel(const uint32_t* __r
             if (c0 + u * TK_CHUNK < end) process(t[u], valid[u]);  // uniform
     }
     __syncthreads();
-    // the exact overflow test
+    // the exact overflow test (see pk16_sum)
     uint32_t sum = 0;
     for (uint32_t i = tid; i < TK_TABLE_WORDS / 4; i += T) {
         const uint4 v = reinterpret_cast<const uint4*>(s_j)[i];
-        sum += (v.x & 0xffffu) + (v.x >> 16) + (v.y & 0xffffu) + (v.y >> 16) + (v.z & 0xffffu) + (v.z >> 16) + (v.w & 0xffffu) + (v.w >> 16);
+        sum += pk16_sum(v);
     }
     sum = wave_reduce_sum(sum);
     const uint32_t hsum = wave_reduce_sum(hot_count);
